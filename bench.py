@@ -1,8 +1,13 @@
 #!/usr/bin/env python3
-"""Headline benchmark: numeric LU + lsolve/usolve on the 50k power-grid Jacobian, plus the two sharding
-configurations of BASELINE.json on the same JSON line.
+"""Headline benchmark: numeric LU + lsolve/usolve on the 50k power-grid Jacobian, plus (with --full) the two
+sharding configurations of BASELINE.json on the same JSON line.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times exactly K steps and prints the headline.  --full adds everything else on the
+same line: the phase pass (factor and solve as two calls, the roofline), the residual check of the solution, the
+sharding configurations (`configs`) and the CPU baselines.  --dump-outputs DIR writes the solution of the last timed
+step as DIR/x.npy (float64, rank 0); the inputs are seeded, so the same arguments give the same inputs every run.
 
 `value` (the driver's number) = BASELINE.json configs[2]: one step = one pass of the hot path over one matrix
 already resident in HBM -- numeric refactorisation (assembly + multifrontal LU, symbolic analysis reused) and
@@ -36,6 +41,22 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
 HBM_MEASURED_GBS = 6290.0      # same guide: float4 copy
+DUMP_BUDGET_BYTES = 64 * 10**6
+
+
+def dump_outputs(path, arrays):
+    """Write every array as path/<name>.npy in float64.  An array larger than what is left of the 64 MB budget is
+    replaced by a fixed sample of its entries (sorted flat positions drawn with seed 0), the same on every run."""
+    os.makedirs(path, exist_ok=True)
+    left = DUMP_BUDGET_BYTES
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        left -= 128                                               # the .npy header
+        if a.nbytes > left:
+            pick = np.random.default_rng(0).choice(a.size, size=max(left, 0) // a.itemsize, replace=False)
+            a = a.reshape(-1)[np.sort(pick)]
+        np.save(os.path.join(path, name + ".npy"), a)
+        left -= a.nbytes
 
 
 def csc_matvec_np(n, Ap, Ai, Ax, x):
@@ -351,8 +372,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--n", type=int, default=50000)
     ap.add_argument("--rhs", type=int, default=1)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--configs", default="4,5", help="sharding legs to run beside the headline ('' = none)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the phase pass / roofline, the residual check, the sharding legs and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the solution of the last timed step to DIR/x.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
+    ap.add_argument("--configs", default="4,5", help="sharding legs to run beside the headline with --full ('' = none)")
     ap.add_argument("--c4-rhs", type=int, default=1024)
     ap.add_argument("--c4-reps", type=int, default=10)
     ap.add_argument("--c5-mats", type=int, default=512)
@@ -361,6 +385,8 @@ def main():
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (gloo only to rehearse N > 1 on one GPU)")
     ap.add_argument("--one-device", action="store_true", help="rehearsal: every rank uses cuda:0")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     import torch.distributed as dist
@@ -419,7 +445,8 @@ def main():
         F.solve_dev(d_x.data_ptr(), args.rhs, sh)
         if events: events[2].record(stream)
 
-    split_step()                                 # captures the two stand-alone graphs
+    if args.full:
+        split_step()                             # captures the two stand-alone graphs of the phase pass
     for _ in range(max(args.warmup, 1)):
         step()
     F.factor_status(sh)
@@ -439,40 +466,43 @@ def main():
     elapsed = time.perf_counter() - t0
     F.factor_status(sh)
     x_fused = d_x.clone()
-
-    # ---- phase pass (not part of `value`): the same kernels as two graphs, bracketed by events on the
-    # launch stream -- the factorisation's duration for the roofline, and the sequential step time
-    nphase = args.steps
-    ev = [[torch.cuda.Event(enable_timing=True) for _ in range(3)] for _ in range(nphase)]
-    torch.cuda.synchronize()
-    for s in range(nphase):
-        split_step(ev[s])
-    torch.cuda.synchronize()
-    F.factor_status(sh)
-    if not torch.equal(d_x, x_fused):
-        raise SystemExit("bench: fused and two-call steps differ")
-    t_factor_ms = float(np.mean([e[0].elapsed_time(e[1]) for e in ev]))
-    t_solve_ms = float(np.mean([e[1].elapsed_time(e[2]) for e in ev]))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"x": x_fused.cpu().numpy()})
 
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=comm_dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
-    # ---- sanity (not timed): the solution solves the system
-    x = d_x.cpu().numpy()
-    x1 = x if args.rhs == 1 else x[:, 0]
-    b1 = b if args.rhs == 1 else b[:, 0]
-    res = csc_matvec_np(n, Ap, Ai, Ax, x1) - b1
-    rel_res = float(np.abs(res).max() / (np.abs(b1).max() + 1e-300))
-    if not rel_res < 1e-9:
-        raise SystemExit("bench: solution check failed, relative residual %.3e" % rel_res)
-    q_order = F.ordering()["q"]
+    if args.full:
+        # ---- phase pass (not part of `value`): the same kernels as two graphs, bracketed by events on the
+        # launch stream -- the factorisation's duration for the roofline, and the sequential step time
+        nphase = args.steps
+        ev = [[torch.cuda.Event(enable_timing=True) for _ in range(3)] for _ in range(nphase)]
+        torch.cuda.synchronize()
+        for s in range(nphase):
+            split_step(ev[s])
+        torch.cuda.synchronize()
+        F.factor_status(sh)
+        if not torch.equal(d_x, x_fused):
+            raise SystemExit("bench: fused and two-call steps differ")
+        t_factor_ms = float(np.mean([e[0].elapsed_time(e[1]) for e in ev]))
+        t_solve_ms = float(np.mean([e[1].elapsed_time(e[2]) for e in ev]))
+
+        # ---- sanity (not timed): the solution solves the system
+        x = d_x.cpu().numpy()
+        x1 = x if args.rhs == 1 else x[:, 0]
+        b1 = b if args.rhs == 1 else b[:, 0]
+        res = csc_matvec_np(n, Ap, Ai, Ax, x1) - b1
+        rel_res = float(np.abs(res).max() / (np.abs(b1).max() + 1e-300))
+        if not rel_res < 1e-9:
+            raise SystemExit("bench: solution check failed, relative residual %.3e" % rel_res)
+        q_order = F.ordering()["q"]
     F.close()
 
     # ---- the two sharding configurations (every rank takes part; failures are reported, never fatal to `value`)
     legs = {}
-    want = [c for c in args.configs.split(",") if c]
+    want = [c for c in args.configs.split(",") if c] if args.full else []
     host_bl = (not args.no_cpu_baseline) and world == 1
     for name, fn in (("4", leg_config4), ("5", leg_config5)):
         if name not in want:
@@ -485,22 +515,7 @@ def main():
                 raise                                            # a rank that left a collective would hang the others
 
     if rank == 0:
-        # algorithmic bytes: int32 index + f64 value per entry, each array once
         nnz_l, nnz_u = int(info.nnz_l), int(info.nnz_u)
-        bytes_factor = 12 * nnz_a + 4 * (n + 1) + 12 * nnz_lu + 8 * (n + 1)
-        bytes_solve = (12 * nnz_l + 4 * (n + 1) + 16 * n * args.rhs) + \
-                      (12 * nnz_u + 4 * (n + 1) + 16 * n * args.rhs) + 2 * 8 * n * args.rhs
-        achieved = bytes_factor / (t_factor_ms * 1e-3) / 1e9
-        traffic, traffic_src = None, None            # PMC bytes per factorisation: NOT measured by this run (rocprofv3
-        try:                                         # collects them in separate passes); read from the committed profile
-            import glob
-            tf = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_traffic.json")))[-1]
-            if args.n == 50000:
-                traffic = json.load(open(tf))["factor"]["hbm_bytes_corrected"]
-                traffic_src = "profiles/" + os.path.basename(tf) + " (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command, " \
-                              "FETCH doubled as the guide prescribes); not collected by this run"
-        except Exception:
-            traffic = None
         out = {
             "metric": "numeric-LU + lsolve/usolve nnz/s on 50k power-grid Jacobian",
             "value": world * units * args.steps / elapsed,
@@ -520,34 +535,50 @@ def main():
                        "supernodes": int(info.nsuper), "levels": int(info.nlevels),
                        "max_front": int(info.max_front), "ordering": "amd(A+A')",
                        "parallelism": "independent matrices per rank, no collective (a single factorisation stays on "
-                                      "one GPU); the sharding configurations are under `configs`"},
-            "roofline": {"bound": "hbm",
-                         "kernel": "numeric factorisation = one hipGraph: k_sub_factor (the bottom forest: subtrees of fronts of "
-                                   "order <= 32, one workgroup per task, one launch), then per tree level k_front_mix / "
-                                   "k_front_block / k_big_gather + k_big_step (one launch per 32-pivot block step of a big front)",
-                         "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS,
-                         "frac_of_measured_peak": achieved / HBM_MEASURED_GBS,
-                         "traffic": traffic, "traffic_source": traffic_src,
-                         "algorithmic_bytes": bytes_factor,
-                         "avg_launch_ms": t_factor_ms,
-                         "measured": "HIP events around the stand-alone factorisation graph, %d launches right after "
-                                     "the timed region (inside the fused step the forward sweep overlaps it)" % nphase,
-                         "note": "dependency-depth bound: %d tree levels per factorisation (the lowest of them inside the "
-                                 "forest launch)" % int(info.nlevels)},
-            "phases": {"factor_ms": t_factor_ms, "solve_ms": t_solve_ms,
-                       "two_call_step_ms": t_factor_ms + t_solve_ms,
-                       "factor_nnz_per_s": nnz_lu / (t_factor_ms * 1e-3),
-                       "solve_nnz_per_s": nnz_lu * args.rhs / (t_solve_ms * 1e-3),
-                       "solve_hbm_GBs": bytes_solve / (t_solve_ms * 1e-3) / 1e9,
-                       "symbolic_s": float(info.t_order_s + info.t_symbolic_s),
-                       "rel_residual": rel_res},
-            "configs": legs,
+                                      "one GPU); the sharding configurations are under `configs` (--full)"},
         }
-        if not args.no_cpu_baseline and world == 1:
-            out["cpu_baseline"] = cpu_baseline(n, Ap, Ai, Ax, q_order, b1, nnz_lu, args.rhs)
-        else:
-            out["cpu_baseline"] = None
+        if args.full:
+            # algorithmic bytes: int32 index + f64 value per entry, each array once
+            bytes_factor = 12 * nnz_a + 4 * (n + 1) + 12 * nnz_lu + 8 * (n + 1)
+            bytes_solve = (12 * nnz_l + 4 * (n + 1) + 16 * n * args.rhs) + \
+                          (12 * nnz_u + 4 * (n + 1) + 16 * n * args.rhs) + 2 * 8 * n * args.rhs
+            achieved = bytes_factor / (t_factor_ms * 1e-3) / 1e9
+            traffic, traffic_src = None, None            # PMC bytes per factorisation: NOT measured by this run (rocprofv3
+            try:                                         # collects them in separate passes); read from the committed profile
+                import glob
+                tf = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_traffic.json")))[-1]
+                if args.n == 50000:
+                    traffic = json.load(open(tf))["factor"]["hbm_bytes_corrected"]
+                    traffic_src = "profiles/" + os.path.basename(tf) + " (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this " \
+                                  "command, FETCH doubled as the guide prescribes); not collected by this run"
+            except Exception:
+                traffic = None
+            out["roofline"] = {"bound": "hbm",
+                               "kernel": "numeric factorisation = one hipGraph: k_sub_factor (the bottom forest: subtrees of fronts of "
+                                         "order <= 32, one workgroup per task, one launch), then per tree level k_front_mix / "
+                                         "k_front_block / k_big_gather + k_big_step (one launch per 32-pivot block step of a big front)",
+                               "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                               "frac": achieved / HBM_PEAK_GBS,
+                               "frac_of_measured_peak": achieved / HBM_MEASURED_GBS,
+                               "traffic": traffic, "traffic_source": traffic_src,
+                               "algorithmic_bytes": bytes_factor,
+                               "avg_launch_ms": t_factor_ms,
+                               "measured": "HIP events around the stand-alone factorisation graph, %d launches right after "
+                                           "the timed region (inside the fused step the forward sweep overlaps it)" % nphase,
+                               "note": "dependency-depth bound: %d tree levels per factorisation (the lowest of them inside the "
+                                       "forest launch)" % int(info.nlevels)}
+            out["phases"] = {"factor_ms": t_factor_ms, "solve_ms": t_solve_ms,
+                             "two_call_step_ms": t_factor_ms + t_solve_ms,
+                             "factor_nnz_per_s": nnz_lu / (t_factor_ms * 1e-3),
+                             "solve_nnz_per_s": nnz_lu * args.rhs / (t_solve_ms * 1e-3),
+                             "solve_hbm_GBs": bytes_solve / (t_solve_ms * 1e-3) / 1e9,
+                             "symbolic_s": float(info.t_order_s + info.t_symbolic_s),
+                             "rel_residual": rel_res}
+            out["configs"] = legs
+            if not args.no_cpu_baseline and world == 1:
+                out["cpu_baseline"] = cpu_baseline(n, Ap, Ai, Ax, q_order, b1, nnz_lu, args.rhs)
+            else:
+                out["cpu_baseline"] = None
         print(json.dumps(out))
     if world > 1:
         dist.destroy_process_group()
