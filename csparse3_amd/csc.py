@@ -189,9 +189,9 @@ class CscMat:
         F.factor(self.data)
         return F
 
-    def solve(self, b, tol=0.0):
-        """x = A \\ b by LU (factorises if needed)."""
-        return self.lu(tol).solve(b)
+    def solve(self, b, tol=0.0, trans=False):
+        """x = A \\ b by LU (factorises if needed); trans: A' x = b on the same factors."""
+        return self.lu(tol).solve(b, trans=trans)
 
 
 def _sub_matrix_cols(Ap, Ai, Ax, cols):
@@ -232,6 +232,18 @@ def lsolve(L, x):
 def usolve(U, x):
     """x = U \\ x in place, U an upper-triangular CscMat with the diagonal last in each column."""
     _k.csc_usolve_f(U.n, U.indptr, U.indices, U.data, x)
+    return x
+
+
+def ltsolve(L, x):
+    """x = L' \\ x in place, L a lower-triangular CscMat with the diagonal first in each column (cs_ltsolve)."""
+    _k.csc_ltsolve_f(L.n, L.indptr, L.indices, L.data, x)
+    return x
+
+
+def utsolve(U, x):
+    """x = U' \\ x in place, U an upper-triangular CscMat with the diagonal last in each column (cs_utsolve)."""
+    _k.csc_utsolve_f(U.n, U.indptr, U.indices, U.data, x)
     return x
 
 

@@ -104,13 +104,16 @@ def lib():
         L.cs3_factor_status.argtypes = [vp, vp]
         L.cs3_factor_solve_dev.argtypes = [vp, vp, C.c_double, vp, I64, vp]
         L.cs3_factor_solve_bx_dev.argtypes = [vp, vp, C.c_double, vp, vp, I64, vp]
-        for f in (L.cs3_solve, L.cs3_lsolve, L.cs3_usolve):
+        for f in (L.cs3_solve, L.cs3_lsolve, L.cs3_usolve, L.cs3_solve_t, L.cs3_ltsolve, L.cs3_utsolve):
             f.argtypes = [vp, _f64p, I64]
-        for f in (L.cs3_solve_dev, L.cs3_lsolve_dev, L.cs3_usolve_dev):
+        for f in (L.cs3_solve_dev, L.cs3_lsolve_dev, L.cs3_usolve_dev, L.cs3_solve_t_dev, L.cs3_ltsolve_dev, L.cs3_utsolve_dev):
             f.argtypes = [vp, vp, I64, vp]
-        L.cs3_residual_dev.argtypes = [vp, vp, vp, vp, vp, I64, vp]
-        L.cs3_matvec_dev.argtypes = [vp, vp, vp, vp, I64, vp]
-        L.cs3_refine_dev.argtypes = [vp, vp, vp, vp, I64, I64, C.POINTER(C.c_double), vp]
+        for f in (L.cs3_residual_dev, L.cs3_residual_t_dev):
+            f.argtypes = [vp, vp, vp, vp, vp, I64, vp]
+        for f in (L.cs3_matvec_dev, L.cs3_matvec_t_dev):
+            f.argtypes = [vp, vp, vp, vp, I64, vp]
+        for f in (L.cs3_refine_dev, L.cs3_refine_t_dev):
+            f.argtypes = [vp, vp, vp, vp, I64, I64, C.POINTER(C.c_double), vp]
         L.cs3_export_factor_dev.argtypes = [vp, vp, vp]
         L.cs3_import_factor_dev.argtypes = [vp, vp, vp]
         L.cs3_get_factors.argtypes = [vp, I64, _i32p, _i32p, _f64p, _i32p, _i32p, _f64p]
@@ -120,6 +123,8 @@ def lib():
         L.cs3_counts.argtypes = [I64, _i32p, _i32p, _i32p, _i32p, _i32p]
         L.cs3_csc_lsolve.argtypes = [I64, _i32p, _i32p, _f64p, _f64p, I64]
         L.cs3_csc_usolve.argtypes = [I64, _i32p, _i32p, _f64p, _f64p, I64]
+        L.cs3_csc_ltsolve.argtypes = [I64, _i32p, _i32p, _f64p, _f64p, I64]
+        L.cs3_csc_utsolve.argtypes = [I64, _i32p, _i32p, _f64p, _f64p, I64]
         L.cs3_csc_matvec.argtypes = [I64, I64, _i32p, _i32p, _f64p, _f64p, _f64p, I64]
         L.cs3_csc_stack_4_by_4.argtypes = [I64, I64, _i32p, _i32p, _f64p] * 4 + [_i32p, _i32p, _f64p]
         L.cs3_csc_stack_4_by_4_dev.argtypes = [I64, I64, I64, vp, vp, vp] * 4 + [vp, vp, vp, vp, vp]
@@ -265,12 +270,12 @@ class Factorization:
         _check(lib().cs3_factor(self._h, _pf(Ax), tol))
         return self
 
-    def solve(self, b):
-        """Solve A x = b.  b: [n], [n, k] or [batch, n, k]; returns a new array."""
+    def solve(self, b, trans=False):
+        """Solve A x = b (trans: A' x = b, on the same factors).  b: [n], [n, k] or [batch, n, k]; returns a new array."""
         x = np.array(b, dtype=np.float64, order="C", copy=True)
         per = self.batch * self.n
         assert x.size % per == 0, "right-hand side does not match [batch,] n [, k]"
-        _check(lib().cs3_solve(self._h, _pf(x), x.size // per))
+        _check((lib().cs3_solve_t if trans else lib().cs3_solve)(self._h, _pf(x), x.size // per))
         return x
 
     def _sweep(self, fn, x):
@@ -288,6 +293,14 @@ class Factorization:
         """x = U \\ x in pivot order (cs_usolve; L' for Cholesky, i.e. cs_ltsolve)."""
         return self._sweep(lib().cs3_usolve, x)
 
+    def ltsolve(self, x):
+        """x = L' \\ x in pivot order (cs_ltsolve; unit diagonal for LU, the same as usolve for Cholesky)."""
+        return self._sweep(lib().cs3_ltsolve, x)
+
+    def utsolve(self, x):
+        """x = U' \\ x in pivot order (cs_utsolve; Cs3Error on a Cholesky handle)."""
+        return self._sweep(lib().cs3_utsolve, x)
+
     # -- numeric, device pointers (e.g. torch.Tensor.data_ptr()) on a HIP stream
     def factor_dev(self, ax_ptr, tol=0.0, stream=0):
         _check(lib().cs3_factor_dev(self._h, C.c_void_p(ax_ptr), tol, C.c_void_p(stream)))
@@ -303,8 +316,9 @@ class Factorization:
     def factor_status(self, stream=0):
         _check(lib().cs3_factor_status(self._h, C.c_void_p(stream)))
 
-    def solve_dev(self, x_ptr, k=1, stream=0):
-        _check(lib().cs3_solve_dev(self._h, C.c_void_p(x_ptr), k, C.c_void_p(stream)))
+    def solve_dev(self, x_ptr, k=1, stream=0, trans=False):
+        fn = lib().cs3_solve_t_dev if trans else lib().cs3_solve_dev
+        _check(fn(self._h, C.c_void_p(x_ptr), k, C.c_void_p(stream)))
 
     def lsolve_dev(self, x_ptr, k=1, stream=0):
         _check(lib().cs3_lsolve_dev(self._h, C.c_void_p(x_ptr), k, C.c_void_p(stream)))
@@ -312,20 +326,30 @@ class Factorization:
     def usolve_dev(self, x_ptr, k=1, stream=0):
         _check(lib().cs3_usolve_dev(self._h, C.c_void_p(x_ptr), k, C.c_void_p(stream)))
 
-    def residual_dev(self, ax_ptr, b_ptr, x_ptr, r_ptr, k=1, stream=0):
-        """R = B - A X on resident data (A's values at ax_ptr, the analysed pattern); csc_mat_vec_ff's summation order."""
-        _check(lib().cs3_residual_dev(self._h, C.c_void_p(ax_ptr), C.c_void_p(b_ptr), C.c_void_p(x_ptr), C.c_void_p(r_ptr), k,
-                                      C.c_void_p(stream)))
+    def ltsolve_dev(self, x_ptr, k=1, stream=0):
+        _check(lib().cs3_ltsolve_dev(self._h, C.c_void_p(x_ptr), k, C.c_void_p(stream)))
 
-    def matvec_dev(self, ax_ptr, x_ptr, y_ptr, k=1, stream=0):
-        """Y = A X on resident data (the analysed pattern, values at ax_ptr), summed as csc_mat_vec_ff sums."""
-        _check(lib().cs3_matvec_dev(self._h, C.c_void_p(ax_ptr), C.c_void_p(x_ptr), C.c_void_p(y_ptr), k, C.c_void_p(stream)))
+    def utsolve_dev(self, x_ptr, k=1, stream=0):
+        _check(lib().cs3_utsolve_dev(self._h, C.c_void_p(x_ptr), k, C.c_void_p(stream)))
 
-    def refine_dev(self, ax_ptr, b_ptr, x_ptr, k=1, steps=1, stream=0, want_correction=True):
-        """`steps` rounds of x += A \\ (b - A x) with the factors at hand; returns max |dx| of the last round."""
+    def residual_dev(self, ax_ptr, b_ptr, x_ptr, r_ptr, k=1, stream=0, trans=False):
+        """R = B - A X (trans: B - A' X) on resident data (A's values at ax_ptr, the analysed pattern); csc_mat_vec_ff's
+        summation order."""
+        fn = lib().cs3_residual_t_dev if trans else lib().cs3_residual_dev
+        _check(fn(self._h, C.c_void_p(ax_ptr), C.c_void_p(b_ptr), C.c_void_p(x_ptr), C.c_void_p(r_ptr), k, C.c_void_p(stream)))
+
+    def matvec_dev(self, ax_ptr, x_ptr, y_ptr, k=1, stream=0, trans=False):
+        """Y = A X (trans: A' X) on resident data (the analysed pattern, values at ax_ptr), summed as csc_mat_vec_ff sums."""
+        fn = lib().cs3_matvec_t_dev if trans else lib().cs3_matvec_dev
+        _check(fn(self._h, C.c_void_p(ax_ptr), C.c_void_p(x_ptr), C.c_void_p(y_ptr), k, C.c_void_p(stream)))
+
+    def refine_dev(self, ax_ptr, b_ptr, x_ptr, k=1, steps=1, stream=0, want_correction=True, trans=False):
+        """`steps` rounds of x += A \\ (b - A x) (trans: x += A^-T (b - A' x)) with the factors at hand; returns max |dx|
+        of the last round."""
         out = C.c_double(0.0)
-        _check(lib().cs3_refine_dev(self._h, C.c_void_p(ax_ptr), C.c_void_p(b_ptr), C.c_void_p(x_ptr), k, steps,
-                                    C.byref(out) if want_correction else None, C.c_void_p(stream)))
+        fn = lib().cs3_refine_t_dev if trans else lib().cs3_refine_dev
+        _check(fn(self._h, C.c_void_p(ax_ptr), C.c_void_p(b_ptr), C.c_void_p(x_ptr), k, steps,
+                  C.byref(out) if want_correction else None, C.c_void_p(stream)))
         return float(out.value)
 
     def export_factor_dev(self, dst_ptr, stream=0):
@@ -393,6 +417,16 @@ def csc_lsolve_f(n, Lp, Li, Lx, x):
 def csc_usolve_f(n, Up, Ui, Ux, x):
     """x = U \\ x in place; U upper triangular CSC, diagonal last per column."""
     _tri(lib().cs3_csc_usolve, n, Up, Ui, Ux, x)
+
+
+def csc_ltsolve_f(n, Lp, Li, Lx, x):
+    """x = L' \\ x in place; L lower triangular CSC, diagonal first per column (cs_ltsolve)."""
+    _tri(lib().cs3_csc_ltsolve, n, Lp, Li, Lx, x)
+
+
+def csc_utsolve_f(n, Up, Ui, Ux, x):
+    """x = U' \\ x in place; U upper triangular CSC, diagonal last per column (cs_utsolve)."""
+    _tri(lib().cs3_csc_utsolve, n, Up, Ui, Ux, x)
 
 
 def csc_lusol_f(order, m, n, Ap, Ai, Ax, b, tol=0.0):

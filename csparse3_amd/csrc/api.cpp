@@ -43,6 +43,9 @@ struct cs3_handle_s {
     double factor_graph_inv_tol = 0.0;
     std::map<int, hipGraphExec_t> solve_graphs;   // keyed by nrhs
     std::map<std::pair<int, const void *>, hipGraphExec_t> solve_graphs_px;   // fused permutations: keyed by (nrhs, caller's X)
+    // transposed solves (LU: A' X = B) keep graphs of their own, with the same keys and bounds
+    std::map<int, hipGraphExec_t> solve_graphs_t;
+    std::map<std::pair<int, const void *>, hipGraphExec_t> solve_graphs_px_t;
     std::map<int, hipGraphExec_t> fused_graphs;   // factor + overlapped forward + backward, keyed by nrhs
     // the same with the closing permutation inside the graph (no eager launch behind it: 5 us): X's address is baked in, so
     // these are kept per (nrhs, X) and only for a caller that keeps handing in the same X
@@ -57,6 +60,7 @@ struct cs3_handle_s {
     // residual / refinement: the analysed pattern in row view (built on first use), a work array, a result word
     std::vector<i32> Ap_host, Ai_host;
     int *d_rp = nullptr, *d_rj = nullptr, *d_rmap = nullptr;
+    int *d_cp = nullptr, *d_ci = nullptr, *d_cmap = nullptr;       // the same pattern in column view (transposed products)
     double *d_res = nullptr;
     long long res_cap = 0;
     unsigned long long *d_maxbits = nullptr;
@@ -79,6 +83,10 @@ void drop_solve_graphs(cs3_handle h)
     h->solve_graphs.clear();
     for (auto &kv : h->solve_graphs_px) (void) hipGraphExecDestroy(kv.second);
     h->solve_graphs_px.clear();
+    for (auto &kv : h->solve_graphs_t) (void) hipGraphExecDestroy(kv.second);
+    h->solve_graphs_t.clear();
+    for (auto &kv : h->solve_graphs_px_t) (void) hipGraphExecDestroy(kv.second);
+    h->solve_graphs_px_t.clear();
     for (auto &kv : h->fused_graphs) (void) hipGraphExecDestroy(kv.second);
     h->fused_graphs.clear();
     for (auto &kv : h->fused_graphs_px) (void) hipGraphExecDestroy(kv.second);
@@ -101,7 +109,7 @@ void release_device(cs3_handle h)
                      (void **) &D.ax, (void **) &D.pool, (void **) &D.dbuf, (void **) &D.tbuf, (void **) &D.bigv,
                      (void **) &D.cv, (void **) &D.xp, (void **) &D.status, (void **) &h->d_lmap, (void **) &h->d_umap,
                      (void **) &h->d_lx, (void **) &h->d_ux, (void **) &h->d_rp, (void **) &h->d_rj, (void **) &h->d_rmap,
-                     (void **) &h->d_res, (void **) &h->d_maxbits};
+                     (void **) &h->d_cp, (void **) &h->d_ci, (void **) &h->d_cmap, (void **) &h->d_res, (void **) &h->d_maxbits};
     h->res_cap = 0;
     for (void **p : ptrs) if (*p) { (void) hipFree(*p); *p = nullptr; }
     D.nrhs_cap = 0;
@@ -279,9 +287,10 @@ int capture(cs3_handle h, hipGraphExec_t *exec, Body body)
 
 // One right-hand side on a handle with a bottom forest: the sweeps follow the factor schedule (tiers, then the levels
 // above them) with their own descriptor array.  Sets what the launchers read; returns the launch groups to pass.
-const std::vector<LaunchGroup> &select_sweep_schedule(cs3_handle h, int nrhs)
+// (The forest's sweeps have no transposed form: a transposed solve takes the level schedule whatever nrhs is.)
+const std::vector<LaunchGroup> &select_sweep_schedule(cs3_handle h, int nrhs, bool trans = false)
 {
-    const bool forest = nrhs == 1 && !h->S.sub_tiers.empty();
+    const bool forest = nrhs == 1 && !trans && !h->S.sub_tiers.empty();
     h->D.sd_active = forest ? h->D.sdesc1 : nullptr;
     return forest ? h->S.sgroups1 : h->S.sgroups;
 }
@@ -341,8 +350,10 @@ int read_status(cs3_handle h, hipStream_t st)
     return CS3_ERR_NOT_SPD;
 }
 
-// mode 0: full solve with permutations; 1: lsolve only; 2: usolve only (in pivot order, on X itself)
-int run_solve(cs3_handle h, double *x_dev, long long k, int mode, hipStream_t st)
+// mode 0: full solve with permutations; 1: lsolve only; 2: usolve only (in pivot order, on X itself).
+// trans (LU): A' X = B; the forward sweep solves with U', the backward sweep with L' (mode 1: utsolve, 2: ltsolve).
+// On a Cholesky handle A' = A and trans changes nothing.
+int run_solve(cs3_handle h, double *x_dev, long long k, int mode, hipStream_t st, bool trans = false)
 {
     if (!h->factored) { set_error("solve before a successful factorisation"); return CS3_ERR_STATE; }
     if (k < 1 || k > INT_MAX) { set_error("solve: bad number of right-hand sides"); return CS3_ERR_ARG; }
@@ -352,7 +363,12 @@ int run_solve(cs3_handle h, double *x_dev, long long k, int mode, hipStream_t st
     const int nrhs = (int) k;
     D.inverses_in_sweep = false;
     D.fwd_in_factor = false;
-    const std::vector<LaunchGroup> &sg = select_sweep_schedule(h, nrhs);
+    trans = trans && D.kind == CS3_LU;
+    const std::vector<LaunchGroup> &sg = select_sweep_schedule(h, nrhs, trans);
+    std::map<int, hipGraphExec_t> &graphs = trans ? h->solve_graphs_t : h->solve_graphs;
+    std::map<std::pair<int, const void *>, hipGraphExec_t> &graphs_px = trans ? h->solve_graphs_px_t : h->solve_graphs_px;
+    D.trans = trans;
+    struct TransReset { DeviceFactor &D; ~TransReset() { D.trans = false; } } trans_reset{D};
     if (nrhs >= 16 && D.n_inv_tasks > 0 && !h->inverses_valid) {      // many right-hand sides: GEMM sweeps need the inverted blocks
         CS3_HIP(launch_diag_inverses(D, st));
         h->inverses_valid = true;
@@ -365,12 +381,12 @@ int run_solve(cs3_handle h, double *x_dev, long long k, int mode, hipStream_t st
         D.xm.src = x_dev; D.xm.dst = x_dev; D.xm.q = D.q;
         if (h->use_graph) {
             const auto key = std::make_pair(nrhs, (const void *) x_dev);
-            auto it = h->solve_graphs_px.find(key);
-            if (it == h->solve_graphs_px.end()) {
-                if (h->solve_graphs_px.size() >= 8) {           // callers that rotate buffers: bounded cache
+            auto it = graphs_px.find(key);
+            if (it == graphs_px.end()) {
+                if (graphs_px.size() >= 8) {                    // callers that rotate buffers: bounded cache
                     CS3_HIP(hipDeviceSynchronize());            // (graphs launched earlier on OTHER streams may still be running)
-                    for (auto &kv : h->solve_graphs_px) (void) hipGraphExecDestroy(kv.second);
-                    h->solve_graphs_px.clear();
+                    for (auto &kv : graphs_px) (void) hipGraphExecDestroy(kv.second);
+                    graphs_px.clear();
                 }
                 hipGraphExec_t exec = nullptr;
                 rc = capture(h, &exec, [&](hipStream_t cs) {
@@ -379,7 +395,7 @@ int run_solve(cs3_handle h, double *x_dev, long long k, int mode, hipStream_t st
                     return launch_solve_levels(D, sg, D.xp, nrhs, false, cs, h->fj);
                 });
                 if (rc) { D.xm = XMap(); return rc; }
-                it = h->solve_graphs_px.emplace(key, exec).first;
+                it = graphs_px.emplace(key, exec).first;
             }
             CS3_HIP(hipGraphLaunch(it->second, st));
         } else {
@@ -390,8 +406,8 @@ int run_solve(cs3_handle h, double *x_dev, long long k, int mode, hipStream_t st
     } else if (mode == 0) {
         CS3_HIP(launch_permute(D, x_dev, D.xp, nrhs, false, st));
         if (h->use_graph) {
-            auto it = h->solve_graphs.find(nrhs);
-            if (it == h->solve_graphs.end()) {
+            auto it = graphs.find(nrhs);
+            if (it == graphs.end()) {
                 hipGraphExec_t exec = nullptr;
                 rc = capture(h, &exec, [&](hipStream_t cs) {
                     hipError_t e = launch_solve_levels(D, sg, D.xp, nrhs, true, cs, h->fj);
@@ -399,7 +415,7 @@ int run_solve(cs3_handle h, double *x_dev, long long k, int mode, hipStream_t st
                     return launch_solve_levels(D, sg, D.xp, nrhs, false, cs, h->fj);
                 });
                 if (rc) return rc;
-                it = h->solve_graphs.emplace(nrhs, exec).first;
+                it = graphs.emplace(nrhs, exec).first;
             }
             CS3_HIP(hipGraphLaunch(it->second, st));
         } else {
@@ -716,17 +732,44 @@ int cs3_usolve_dev(cs3_handle h, double *X_dev, int64_t k, void *stream)
     return run_solve(h, X_dev, k, 2, (hipStream_t) stream);
 }
 
-static int solve_host(cs3_handle h, double *X, int64_t k, int mode)
+// Transposed solves: mode as in run_solve (1: U' \ x, 2: L' \ x).  A Cholesky handle has no U: utsolve is refused,
+// ltsolve is L' \ x (its usolve), the full solve is the plain one.
+static int run_solve_t(cs3_handle h, double *x_dev, long long k, int mode, hipStream_t st)
+{
+    if (mode == 1 && h->S.kind != CS3_LU) { set_error("utsolve: a Cholesky factorisation has no U"); return CS3_ERR_ARG; }
+    return run_solve(h, x_dev, k, mode, st, true);
+}
+
+int cs3_solve_t_dev(cs3_handle h, double *X_dev, int64_t k, void *stream)
+{
+    int rc = guard(h); if (rc) return rc;
+    return run_solve_t(h, X_dev, k, 0, (hipStream_t) stream);
+}
+
+int cs3_utsolve_dev(cs3_handle h, double *X_dev, int64_t k, void *stream)
+{
+    int rc = guard(h); if (rc) return rc;
+    return run_solve_t(h, X_dev, k, 1, (hipStream_t) stream);
+}
+
+int cs3_ltsolve_dev(cs3_handle h, double *X_dev, int64_t k, void *stream)
+{
+    int rc = guard(h); if (rc) return rc;
+    return run_solve_t(h, X_dev, k, 2, (hipStream_t) stream);
+}
+
+static int solve_host(cs3_handle h, double *X, int64_t k, int mode, bool trans = false)
 {
     int rc = guard(h); if (rc) return rc;
     if (!X) { set_error("solve: null right-hand side"); return CS3_ERR_ARG; }
+    if (trans && mode == 1 && h->S.kind != CS3_LU) { set_error("utsolve: a Cholesky factorisation has no U"); return CS3_ERR_ARG; }
     if (!h->factored) { set_error("solve before a successful factorisation"); return CS3_ERR_STATE; }
     const size_t bytes = (size_t) (h->batch * h->S.n * k) * sizeof(double);
     double *d_x = nullptr;
     CS3_HIP(hipMalloc((void **) &d_x, std::max<size_t>(bytes, 8)));
     hipError_t e = hipMemcpy(d_x, X, bytes, hipMemcpyHostToDevice);
     if (e == hipSuccess) {
-        rc = run_solve(h, d_x, k, mode, nullptr);
+        rc = trans ? run_solve_t(h, d_x, k, mode, nullptr) : run_solve(h, d_x, k, mode, nullptr);
         if (rc == CS3_OK) e = hipMemcpy(X, d_x, bytes, hipMemcpyDeviceToHost);
     }
     (void) hipFree(d_x);
@@ -738,6 +781,9 @@ static int solve_host(cs3_handle h, double *X, int64_t k, int mode)
 int cs3_solve(cs3_handle h, double *X, int64_t k) { return solve_host(h, X, k, 0); }
 int cs3_lsolve(cs3_handle h, double *X, int64_t k) { return solve_host(h, X, k, 1); }
 int cs3_usolve(cs3_handle h, double *X, int64_t k) { return solve_host(h, X, k, 2); }
+int cs3_solve_t(cs3_handle h, double *X, int64_t k) { return solve_host(h, X, k, 0, true); }
+int cs3_utsolve(cs3_handle h, double *X, int64_t k) { return solve_host(h, X, k, 1, true); }
+int cs3_ltsolve(cs3_handle h, double *X, int64_t k) { return solve_host(h, X, k, 2, true); }
 
 int cs3_export_factor_dev(cs3_handle h, double *dst_dev, void *stream)
 {
@@ -862,15 +908,16 @@ int cs3_get_factors(cs3_handle h, int64_t b, int32_t *Lp, int32_t *Li, double *L
     return CS3_OK;
 }
 
+// trans: x = G' \ x on the same arrays
 static int csc_trisolve(int64_t n, const int32_t *Gp, const int32_t *Gi, const double *Gx, double *x,
-                        int64_t k, bool lower)
+                        int64_t k, bool lower, bool trans = false)
 {
     if (n < 0 || k < 1 || k > INT_MAX || !Gp || !x) { set_error("triangular solve: bad argument"); return CS3_ERR_ARG; }
     if (n == 0) return CS3_OK;
     if (int rc = check_pattern("triangular solve", n, Gp, Gi)) return rc;
     if (!Gx) { set_error("triangular solve: null values"); return CS3_ERR_ARG; }
     TriSchedule T;
-    try { tri_schedule(n, Gp, Gi, lower, T); }
+    try { tri_schedule(n, Gp, Gi, lower, T, trans); }
     catch (const std::bad_alloc &) { set_error("triangular solve: out of memory"); return CS3_ERR_ALLOC; }
     catch (const std::exception &e) { set_error(e.what()); return CS3_ERR_ARG; }
     int ndev = 0;
@@ -911,6 +958,16 @@ int cs3_csc_lsolve(int64_t n, const int32_t *Lp, const int32_t *Li, const double
 int cs3_csc_usolve(int64_t n, const int32_t *Up, const int32_t *Ui, const double *Ux, double *x, int64_t k)
 {
     return csc_trisolve(n, Up, Ui, Ux, x, k, false);
+}
+
+int cs3_csc_ltsolve(int64_t n, const int32_t *Lp, const int32_t *Li, const double *Lx, double *x, int64_t k)
+{
+    return csc_trisolve(n, Lp, Li, Lx, x, k, true, true);
+}
+
+int cs3_csc_utsolve(int64_t n, const int32_t *Up, const int32_t *Ui, const double *Ux, double *x, int64_t k)
+{
+    return csc_trisolve(n, Up, Ui, Ux, x, k, false, true);
 }
 
 int cs3_csc_matvec(int64_t m, int64_t n, const int32_t *Ap, const int32_t *Ai, const double *Ax,
@@ -1030,6 +1087,19 @@ static int ensure_row_view(cs3_handle h, long long k)
     return CS3_OK;
 }
 
+// The analysed pattern in column view for the transposed products: row j of A' = column j of A, in storage order
+static int ensure_col_view(cs3_handle h, long long k)
+{
+    int rc = ensure_row_view(h, k);
+    if (rc) return rc;
+    if (!h->d_cp) {
+        std::vector<int> Cmap(h->S.nnzA);
+        for (i64 p = 0; p < h->S.nnzA; ++p) Cmap[p] = (int) p;
+        if ((rc = upload(&h->d_cp, h->Ap_host)) || (rc = upload(&h->d_ci, h->Ai_host)) || (rc = upload(&h->d_cmap, Cmap))) return rc;
+    }
+    return CS3_OK;
+}
+
 int cs3_residual_dev(cs3_handle h, const double *Ax_dev, const double *B_dev, const double *X_dev, double *R_dev, int64_t k, void *stream)
 {
     int rc = guard(h); if (rc) return rc;
@@ -1049,18 +1119,38 @@ int cs3_matvec_dev(cs3_handle h, const double *Ax_dev, const double *X_dev, doub
     return CS3_OK;
 }
 
-int cs3_refine_dev(cs3_handle h, const double *Ax_dev, const double *B_dev, double *X_dev, int64_t k, int64_t steps,
-                   double *last_correction, void *stream)
+int cs3_residual_t_dev(cs3_handle h, const double *Ax_dev, const double *B_dev, const double *X_dev, double *R_dev, int64_t k, void *stream)
 {
     int rc = guard(h); if (rc) return rc;
-    if (!Ax_dev || !B_dev || !X_dev || k < 1 || k > INT_MAX || steps < 0) { set_error("cs3_refine_dev: bad argument"); return CS3_ERR_ARG; }
-    if (!h->factored) { set_error("cs3_refine_dev: refinement needs a factorisation"); return CS3_ERR_STATE; }
-    if ((rc = ensure_row_view(h, k))) return rc;
+    if (!Ax_dev || !B_dev || !X_dev || !R_dev || k < 1 || k > INT_MAX) { set_error("cs3_residual_t_dev: bad argument"); return CS3_ERR_ARG; }
+    if ((rc = ensure_col_view(h, 0))) return rc;
+    CS3_HIP(launch_residual(h->d_cp, h->d_ci, h->d_cmap, Ax_dev, X_dev, B_dev, R_dev, h->S.n, (int) k, h->S.nnzA, h->batch, (hipStream_t) stream));
+    return CS3_OK;
+}
+
+int cs3_matvec_t_dev(cs3_handle h, const double *Ax_dev, const double *X_dev, double *Y_dev, int64_t k, void *stream)
+{
+    int rc = guard(h); if (rc) return rc;
+    if (!Ax_dev || !X_dev || !Y_dev || k < 1 || k > INT_MAX) { set_error("cs3_matvec_t_dev: bad argument"); return CS3_ERR_ARG; }
+    if ((rc = ensure_col_view(h, 0))) return rc;
+    CS3_HIP(launch_residual(h->d_cp, h->d_ci, h->d_cmap, Ax_dev, X_dev, nullptr, Y_dev, h->S.n, (int) k, h->S.nnzA, h->batch, (hipStream_t) stream));
+    return CS3_OK;
+}
+
+static int refine(cs3_handle h, const double *Ax_dev, const double *B_dev, double *X_dev, int64_t k, int64_t steps,
+                  double *last_correction, void *stream, bool trans)
+{
+    const char *who = trans ? "cs3_refine_t_dev" : "cs3_refine_dev";
+    int rc = guard(h); if (rc) return rc;
+    if (!Ax_dev || !B_dev || !X_dev || k < 1 || k > INT_MAX || steps < 0) { set_error(std::string(who) + ": bad argument"); return CS3_ERR_ARG; }
+    if (!h->factored) { set_error(std::string(who) + ": refinement needs a factorisation"); return CS3_ERR_STATE; }
+    if ((rc = trans ? ensure_col_view(h, k) : ensure_row_view(h, k))) return rc;
     hipStream_t st = (hipStream_t) stream;
     const long long total = h->batch * h->S.n * k;
+    const int *vp = trans ? h->d_cp : h->d_rp, *vj = trans ? h->d_ci : h->d_rj, *vmap = trans ? h->d_cmap : h->d_rmap;
     for (int64_t s = 0; s < steps; ++s) {
-        CS3_HIP(launch_residual(h->d_rp, h->d_rj, h->d_rmap, Ax_dev, X_dev, B_dev, h->d_res, h->S.n, (int) k, h->S.nnzA, h->batch, st));
-        if ((rc = run_solve(h, h->d_res, k, 0, st))) return rc;           // d = A \ r with the factors at hand
+        CS3_HIP(launch_residual(vp, vj, vmap, Ax_dev, X_dev, B_dev, h->d_res, h->S.n, (int) k, h->S.nnzA, h->batch, st));
+        if ((rc = run_solve(h, h->d_res, k, 0, st, trans))) return rc;    // d = A \ r (A' \ r) with the factors at hand
         const bool want = last_correction && s + 1 == steps;
         if (want) CS3_HIP(hipMemsetAsync(h->d_maxbits, 0, sizeof(unsigned long long), st));
         CS3_HIP(launch_axpy_max(X_dev, h->d_res, total, want ? h->d_maxbits : nullptr, st));      // x += d
@@ -1073,6 +1163,18 @@ int cs3_refine_dev(cs3_handle h, const double *Ax_dev, const double *B_dev, doub
     }
     if (steps == 0 && last_correction) *last_correction = 0.0;
     return CS3_OK;
+}
+
+int cs3_refine_dev(cs3_handle h, const double *Ax_dev, const double *B_dev, double *X_dev, int64_t k, int64_t steps,
+                   double *last_correction, void *stream)
+{
+    return refine(h, Ax_dev, B_dev, X_dev, k, steps, last_correction, stream, false);
+}
+
+int cs3_refine_t_dev(cs3_handle h, const double *Ax_dev, const double *B_dev, double *X_dev, int64_t k, int64_t steps,
+                     double *last_correction, void *stream)
+{
+    return refine(h, Ax_dev, B_dev, X_dev, k, steps, last_correction, stream, true);
 }
 
 // The same on data that already lives in HBM: nothing crosses PCIe and nothing synchronises.  The caller knows the

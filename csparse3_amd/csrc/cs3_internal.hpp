@@ -208,6 +208,7 @@ struct TriSchedule {
     std::vector<i64> Rmap;                    // CSR entry -> CSC entry
     std::vector<i64> diag;                    // CSC entry of each diagonal
 };
-void tri_schedule(i64 n, const i32 *Gp, const i32 *Gi, bool lower, TriSchedule &T);
+// trans: the schedule of G' (rows of G' = columns of G, nothing transposed; G' is solved in the other direction)
+void tri_schedule(i64 n, const i32 *Gp, const i32 *Gi, bool lower, TriSchedule &T, bool trans = false);
 
 }  // namespace cs3

@@ -1628,6 +1628,24 @@ k_big_step(const FrontDesc *__restrict__ fdesc, int first, int kb, double *__res
 // waits on memory by itself.
 constexpr int SOLVE_PF = 8;
 
+// Transposed LU solves (A' x = b) sweep the same fronts in the same order with the other triangle of each pivot block:
+// forward with U' (lower, WITH its diagonal: the rows are pre-divided as in the Cholesky forward sweep), backward with L'
+// (upper, unit diagonal: the Cholesky backward addressing with nothing divided).  A sweep kind only: the factorisation and
+// cs3_analyze never see it.
+//   forward  entry (i, k), row i > k, pivot k:  L(i, k) (LU, Cholesky);  U(k, i) = L panel (k, i) for i < w, U12 beyond (LU_T)
+//   backward entry (k, j), pivot k, j > k:      U(k, j) (LU);  L(j, k) (Cholesky, LU_T)
+constexpr int CS3_LU_T = 2;
+template <int KIND> constexpr bool FWD_DIAG = KIND != CS3_LU;        // the forward triangle carries a non-unit diagonal
+template <int KIND> constexpr bool BWD_DIAG = KIND != CS3_LU_T;      // the backward triangle carries a non-unit diagonal
+// U(k, i), k < w, i > k, of a front: in the L panel's pivot block for i < w, in the U panel beyond.  A masked entry reads
+// the L panel (a front without ancestors has an empty U panel: its offset may be the end of the pool)
+__device__ __forceinline__ double u_entry(const double *__restrict__ L, const double *__restrict__ U, const SolveDesc &d,
+                                          long long k, long long i, bool ok)
+{
+    const bool pv = i < d.w || !ok;
+    return load_if(pv ? L : U, pv ? k + i * d.r : k * d.u_sk + (i - d.w) * d.u_sj, ok);
+}
+
 
 // One wave per front (r <= 128, w <= 64): lane l owns rows l and l + 64, for KT
 // right-hand sides at once (blockIdx.z = tile of KT columns of X): the panel is
@@ -1662,10 +1680,11 @@ k_fwd_wave(const SolveDesc *__restrict__ sd, int first, int count,
 #pragma unroll
     for (int q = 0; q < KT; ++q) { v0[q] = vs[wv][q][lane]; v1[q] = vs[wv][q][lane + 64]; }
     const double *L = pool + d.lpan;
-    // Cholesky: row i < w of the panel and of the vector is divided by L_ii up front (rdg = 1 on the other rows), so that a
-    // column step is one lane-to-scalar broadcast and the FMAs
-    const double rdg = (KIND == CS3_CHOLESKY) ? recip_diag(L, lane, r, lane < w) : 1.0;
-    if (KIND == CS3_CHOLESKY) {
+    const double *U = pool + d.upan;
+    // Cholesky (LU_T): row i < w of the panel and of the vector is divided by L_ii (U_ii) up front (rdg = 1 on the other
+    // rows), so that a column step is one lane-to-scalar broadcast and the FMAs
+    const double rdg = FWD_DIAG<KIND> ? recip_diag(L, lane, r, lane < w) : 1.0;
+    if (FWD_DIAG<KIND>) {
 #pragma unroll
         for (int q = 0; q < KT; ++q) v0[q] *= rdg;
     }
@@ -1674,10 +1693,15 @@ k_fwd_wave(const SolveDesc *__restrict__ sd, int first, int count,
 #pragma unroll
         for (int j = 0; j < SOLVE_PF; ++j) {
             const int k = k0 + j;
-            l0[j] = load_if(L, lane + (long long) k * r, k < w && lane < r && lane > k);
-            l1[j] = load_if(L, lane + 64 + (long long) k * r, k < w && lane + 64 < r);
+            if constexpr (KIND == CS3_LU_T) {
+                l0[j] = u_entry(L, U, d, k, lane, k < w && lane < r && lane > k);
+                l1[j] = u_entry(L, U, d, k, lane + 64, k < w && lane + 64 < r);
+            } else {
+                l0[j] = load_if(L, lane + (long long) k * r, k < w && lane < r && lane > k);
+                l1[j] = load_if(L, lane + 64 + (long long) k * r, k < w && lane + 64 < r);
+            }
         }
-        if (KIND == CS3_CHOLESKY) {
+        if (FWD_DIAG<KIND>) {
 #pragma unroll
             for (int j = 0; j < SOLVE_PF; ++j) l0[j] *= rdg;
         }
@@ -1731,8 +1755,8 @@ k_bwd_wave(const SolveDesc *__restrict__ sd, int first, int count, const int *__
     }
     const double *L = pool + d.lpan;
     const double *U = pool + d.upan;
-    const double rdg = recip_diag(L, lane, r, lane < w);
-    // pivot row `lane` minus U(lane, k) x_k over the ancestors k = w .. r-1
+    const double rdg = BWD_DIAG<KIND> ? recip_diag(L, lane, r, lane < w) : 1.0;
+    // pivot row `lane` minus U(lane, k) x_k over the ancestors k = w .. r-1 (LU_T, Cholesky: L(k, lane))
     double a0[KT], a1[KT];
 #pragma unroll
     for (int q = 0; q < KT; ++q) a0[q] = a1[q] = 0.0;
@@ -1841,17 +1865,18 @@ k_fwd_rhs(const SolveDesc *__restrict__ sd, int first, const int *__restrict__ s
     int sidx[SR];
 #pragma unroll
     for (int j = 0; j < SR; ++j) sidx[j] = (j < rounds && lane < r) ? sl[j * stride + lane] : -1;
-    PanelRegs<RMAX> P;                                         // P(i, k) = L(i, k), zero outside r x w
+    PanelRegs<RMAX> P;                                         // P(i, k) = L(i, k) (LU_T: U(k, i)), zero outside r x w
     {
         const int i = P.row_of(lane);
 #pragma unroll
         for (int q = 0; q < P.NREG; ++q) {
             const int k = P.col_of(lane, q);
-            P.reg[q] = load_if(L, i + (long long) k * r, i < r && k < w);
+            if constexpr (KIND == CS3_LU_T) P.reg[q] = u_entry(L, pool + d.upan, d, k, i, i < r && k < w);
+            else P.reg[q] = load_if(L, i + (long long) k * r, i < r && k < w);
         }
     }
     double rd = 1.0;
-    if (KIND == CS3_CHOLESKY) rd = L[(lane < w ? lane : 0) * (long long) (r + 1)];
+    if (FWD_DIAG<KIND>) rd = L[(lane < w ? lane : 0) * (long long) (r + 1)];
     // own rows of X, zeros below them
     double v[RMAX + (RMAX == 16 ? 1 : 0)];                     // (17, not 16: hipcc turns a 16-double array into a vector
                                                                //  value and spills 3 k registers around its updates)
@@ -1886,11 +1911,11 @@ k_fwd_rhs(const SolveDesc *__restrict__ sd, int first, const int *__restrict__ s
             }
         }
     }
-    if (KIND == CS3_CHOLESKY) rd = 1.0 / rd;                   // 1 / L(k, k), pivot k in lane k
+    if (FWD_DIAG<KIND>) rd = 1.0 / rd;                         // 1 / L(k, k), pivot k in lane k
 #pragma unroll
     for (int k = 0; k < RMAX; ++k) {
         if (k < w) {
-            if (KIND == CS3_CHOLESKY) v[k] *= bcast_lane(rd, k);
+            if (FWD_DIAG<KIND>) v[k] *= bcast_lane(rd, k);
 #pragma unroll
             for (int i0 = (k + 1) & ~7; i0 < RMAX; i0 += 8) {
                 if (i0 < r) {                                   // the group's panel entries first, then its FMAs (see eliminate_block)
@@ -1916,7 +1941,7 @@ k_fwd_rhs(const SolveDesc *__restrict__ sd, int first, const int *__restrict__ s
 
 // Backward: the whole front vector x[0 .. r) in registers (pivot rows, then the ancestors' rows, which
 // are final), one descending recurrence  x[t] final -> x[i] -= M(i, t) x[t]  for the pivot rows i < t,
-// with M = [U11 U12] (Cholesky: [L11' L21']) and zero rows below w.
+// with M = [U11 U12] (Cholesky, LU_T: [L11' L21']) and zero rows below w.
 template <int KIND, int RMAX>
 __global__ void __launch_bounds__(64, (RMAX <= 16) ? 4 : (RMAX <= 32) ? 2 : 1)
 k_bwd_rhs(const SolveDesc *__restrict__ sd, int first, const int *__restrict__ st_idx,
@@ -1959,7 +1984,7 @@ k_bwd_rhs(const SolveDesc *__restrict__ sd, int first, const int *__restrict__ s
 #pragma unroll
     for (int t = RMAX - 1; t >= 0; --t) {
         if (t < r) {
-            if (t < w) x[t] *= bcast_lane(rd, t);
+            if (BWD_DIAG<KIND> && t < w) x[t] *= bcast_lane(rd, t);
 #pragma unroll
             for (int i0 = 0; i0 < t; i0 += 8) {
                 if (i0 < w) {                                   // the group's panel entries first, then its FMAs
@@ -2002,6 +2027,7 @@ constexpr int SOLVE_BW = 64;
 // are in flight while the first is being solved.
 template <int KIND, bool FORWARD>
 struct BlockTriangle {
+    static constexpr bool DIAG = FORWARD ? FWD_DIAG<KIND> : BWD_DIAG<KIND>;
     // Row `lane` of the 64 x 64 triangle, STRICTLY off the diagonal and already divided by the row's own diagonal entry
     // (backward sweep, Cholesky forward sweep), zero outside bw x bw: a substitution step is then one lane-to-scalar
     // broadcast and one FMA -- no per-step scaling, no predicate, no branch on the block's width (round 2: the chain of
@@ -2012,19 +2038,20 @@ struct BlockTriangle {
     {
         const int lane = threadIdx.x & 63;
         const int i = kb + lane;
-        rdg = (!FORWARD || KIND == CS3_CHOLESKY) ? recip_diag(L, i, r, lane < bw) : 1.0;
+        rdg = DIAG ? recip_diag(L, i, r, lane < bw) : 1.0;
 #pragma unroll
         for (int j = 0; j < SOLVE_BW; ++j) {
             long long off;
             bool need;
-            if (FORWARD) { off = (long long) i + (long long) (kb + j) * r; need = lane > j; }
+            if (FORWARD && KIND == CS3_LU_T) { off = (long long) (kb + j) + (long long) i * r; need = lane > j; }     // U(kb + j, i)
+            else if (FORWARD) { off = (long long) i + (long long) (kb + j) * r; need = lane > j; }
             else {
                 off = (KIND == CS3_LU) ? (long long) i + (long long) (kb + j) * r : (long long) (kb + j) + (long long) i * r;
                 need = lane < j;
             }
             t[j] = load_if(L, off, j < bw && lane < bw && need);
         }
-        if (!FORWARD || KIND == CS3_CHOLESKY) {
+        if (DIAG) {
 #pragma unroll
             for (int j = 0; j < SOLVE_BW; ++j) t[j] *= rdg;
         }
@@ -2034,7 +2061,7 @@ struct BlockTriangle {
     template <int KT>
     __device__ __forceinline__ void solve_multi(double (&vi)[KT], int) const
     {
-        if (!FORWARD || KIND == CS3_CHOLESKY) {
+        if (DIAG) {
 #pragma unroll
             for (int q = 0; q < KT; ++q) vi[q] *= rdg;
         }
@@ -2050,7 +2077,7 @@ struct BlockTriangle {
     }
     __device__ __forceinline__ double solve(double vi, int) const
     {
-        if (!FORWARD || KIND == CS3_CHOLESKY) vi *= rdg;
+        if (DIAG) vi *= rdg;
 #pragma unroll
         for (int jj = 0; jj < SOLVE_BW; ++jj) {
             const int j = FORWARD ? jj : SOLVE_BW - 1 - jj;
@@ -2102,7 +2129,10 @@ k_fwd_blk(const SolveDesc *__restrict__ sd, int first,
             for (int j0 = 0; j0 < bw; j0 += 16) {
                 double lv[16];
 #pragma unroll
-                for (int j = 0; j < 16; ++j) lv[j] = load_if(L, i + (long long) (kb + j0 + j) * r, j0 + j < bw);
+                for (int j = 0; j < 16; ++j) {
+                    if constexpr (KIND == CS3_LU_T) lv[j] = u_entry(L, pool + d.upan, d, kb + j0 + j, i, j0 + j < bw);
+                    else lv[j] = load_if(L, i + (long long) (kb + j0 + j) * r, j0 + j < bw);
+                }
 #pragma unroll
                 for (int j = 0; j < 16; ++j) acc += lv[j] * y[j0 + j];
             }
@@ -2274,7 +2304,8 @@ k_fwd_big_step(const SolveDesc *__restrict__ sd, int first, int kb,
 #pragma unroll
     for (int j = 0; j < SC; ++j) {
         const int jj = wv * SC + j;
-        ls[j] = load_if(L, (long long) row + (long long) (kb + jj) * r, row < r && jj < bw);
+        if constexpr (KIND == CS3_LU_T) ls[j] = u_entry(L, pool_all + (long long) b * pool_stride + d.upan, d, kb + jj, row, row < r && jj < bw);
+        else ls[j] = load_if(L, (long long) row + (long long) (kb + jj) * r, row < r && jj < bw);
     }
     if (wv == 0) {
         BlockTriangle<KIND, true> ta;
@@ -2291,10 +2322,12 @@ k_fwd_big_step(const SolveDesc *__restrict__ sd, int first, int kb,
         const double vi = tb.solve(cpl[lane], bwb);
         if (lane < bwb) y[SOLVE_BW + lane] = vi;
     } else if (wv == 2) {
-        double tm[SOLVE_BW];                        // L(second block row, first block columns)
+        double tm[SOLVE_BW];                        // L(second block row, first block columns) (LU_T: U(first, second))
 #pragma unroll
-        for (int j = 0; j < SOLVE_BW; ++j)
-            tm[j] = load_if(L, (long long) (kb + SOLVE_BW + lane) + (long long) (kb + j) * r, lane < bwb);
+        for (int j = 0; j < SOLVE_BW; ++j) {
+            if constexpr (KIND == CS3_LU_T) tm[j] = load_if(L, (long long) (kb + j) + (long long) (kb + SOLVE_BW + lane) * r, lane < bwb);
+            else tm[j] = load_if(L, (long long) (kb + SOLVE_BW + lane) + (long long) (kb + j) * r, lane < bwb);
+        }
         double vi = load_if(v, kb + SOLVE_BW + lane, lane < bwb);
         __syncthreads();
 #pragma unroll
@@ -2355,7 +2388,8 @@ k_fwd_big_step_multi(const SolveDesc *__restrict__ sd, int first, int kb,
 #pragma unroll
     for (int j = 0; j < 16; ++j) {
         const int jj = wv * 16 + j;
-        ls[j] = load_if(L, (long long) row + (long long) (kb + jj) * r, row < r && jj < bw);
+        if constexpr (KIND == CS3_LU_T) ls[j] = u_entry(L, pool_all + (long long) b * pool_stride + d.upan, d, kb + jj, row, row < r && jj < bw);
+        else ls[j] = load_if(L, (long long) row + (long long) (kb + jj) * r, row < r && jj < bw);
     }
     {                                               // every wave solves the triangle for BIG_KT / 4 of the vectors
         constexpr int QW = BIG_KT / 4;
@@ -2858,13 +2892,15 @@ k_fwd_il(const SolveDesc *__restrict__ sd, int first, const int *__restrict__ rl
         // two register buffers, two columns per trip: while column k updates the vector, column k + 1 is in flight
         double ca[RMAX + 1], cb[RMAX + 1];                         // (+ 1: a power-of-two array becomes a vector value, see k_fwd_rhs)
         auto fetch = [&](int k, double (&c)[RMAX + 1]) {           // rows k .. r - 1 of column k (the diagonal included)
-            const double *Lk = L + (long long) k * r * 64;
+            // (LU_T: row k of U from the diagonal on, at (k + i r) 64)
+            const double *Lk = (KIND == CS3_LU_T) ? L + (long long) k * 64 : L + (long long) k * r * 64;
+            const long long is = (KIND == CS3_LU_T) ? (long long) r * 64 : 64;
 #pragma unroll
-            for (int i = 0; i < RMAX; ++i) { c[i] = 1.0; if (i >= k && i < r && k < w) c[i] = Lk[(long long) i * 64]; }
+            for (int i = 0; i < RMAX; ++i) { c[i] = 1.0; if (i >= k && i < r && k < w) c[i] = Lk[(long long) i * is]; }
         };
         auto apply = [&](int k, const double (&c)[RMAX + 1]) {
             double vk = v[k * 64], dg = 1.0;
-            if (KIND == CS3_CHOLESKY) {
+            if (FWD_DIAG<KIND>) {
 #pragma unroll
                 for (int i = 0; i < RMAX; ++i) if (i == k) dg = c[i];
                 vk *= fast_rcp(dg); v[k * 64] = vk;
@@ -2936,7 +2972,7 @@ k_bwd_il(const SolveDesc *__restrict__ sd, int first, const int *__restrict__ st
             double acc = x[i * 64], dg = 1.0;
 #pragma unroll
             for (int t = 0; t < RMAX; ++t) {
-                if (t == i) dg = rowv[t];
+                if (BWD_DIAG<KIND> && t == i) dg = rowv[t];                 // (LU_T: L' has a unit diagonal)
                 if (t > i && t < r) acc -= rowv[t] * x[t * 64];
             }
             x[i * 64] = acc * fast_rcp(dg);
@@ -3108,7 +3144,8 @@ k_gemm_fwd(const SolveDesc *__restrict__ sd, int first, int c,
     if ((int) blockIdx.x > 0 && (int) blockIdx.x >= nsl) return;
     const int n0 = blockIdx.y * GC, nlive = min(GC, nrhs - n0);
     const double *L = pool_all + (long long) b * pool_stride + d.lpan;
-    const double *Linv = dinv_all + (long long) b * dinv_stride + d.dinv + (long long) c * 2 * GC * GC;
+    // LU_T: (U11')^-1 = (U11^-1)', the second inverse of the chunk, staged transposed
+    const double *Linv = dinv_all + (long long) b * dinv_stride + d.dinv + (long long) c * 2 * GC * GC + ((KIND == CS3_LU_T) ? GC * GC : 0);
     double *V = gv_all + (long long) b * gv_stride + d.gv * (long long) nrhs;                 // V[row * nrhs + rhs]
     const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63, mi = lane & 15, mq = lane >> 4, rbk = wv & 3, ch = wv >> 2;
     // every global load of the workgroup goes out first (one round trip): the inverse, the chunk's rows of V, my
@@ -3121,7 +3158,9 @@ k_gemm_fwd(const SolveDesc *__restrict__ sd, int first, int c,
         const int e = tid + 512 * q, k = e >> 6, i = e & 63;
         ra[q] = Linv[e];
         rb[q] = load_if(V, (long long) (kb + k) * nrhs + n0 + i, k < bw && i < nlive);
-        rl[q] = load_if(L, (long long) (row0 + i) + (long long) (kb + k) * r, has_rows && row0 + i < r && k < bw);
+        if constexpr (KIND == CS3_LU_T)
+            rl[q] = u_entry(L, pool_all + (long long) b * pool_stride + d.upan, d, kb + k, row0 + i, has_rows && row0 + i < r && k < bw);
+        else rl[q] = load_if(L, (long long) (row0 + i) + (long long) (kb + k) * r, has_rows && row0 + i < r && k < bw);
     }
     double4_t acc2[2];
 #pragma unroll
@@ -3135,7 +3174,8 @@ k_gemm_fwd(const SolveDesc *__restrict__ sd, int first, int c,
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
         const int e = tid + 512 * q, k = e >> 6, i = e & 63;
-        As[k * GLD + i] = ra[q];
+        if (KIND == CS3_LU_T) As[i * GLD + k] = ra[q];
+        else As[k * GLD + i] = ra[q];
         Bs[k * GLD + i] = rb[q];
     }
     __syncthreads();
@@ -3270,7 +3310,8 @@ k_gemm_bwd(const SolveDesc *__restrict__ sd, int first, int chunk_from_right,
     if ((int) blockIdx.x > 0 && (int) blockIdx.x >= nsl) return;
     const int n0 = blockIdx.y * GC, nlive = min(GC, nrhs - n0);
     const double *L = pool_all + (long long) b * pool_stride + d.lpan;
-    const double *Uinv = dinv_all + (long long) b * dinv_stride + d.dinv + (long long) c * 2 * GC * GC + GC * GC;
+    // LU_T: (L11')^-1 = (L11^-1)', the first inverse of the chunk, staged transposed
+    const double *Uinv = dinv_all + (long long) b * dinv_stride + d.dinv + (long long) c * 2 * GC * GC + ((KIND == CS3_LU_T) ? 0 : GC * GC);
     double *V = gv_all + (long long) b * gv_stride + d.gv * (long long) nrhs;
     const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63, mi = lane & 15, mq = lane >> 4, rbk = wv & 3, ch = wv >> 2;
     const bool has_rows = nsl > 0;
@@ -3303,7 +3344,8 @@ k_gemm_bwd(const SolveDesc *__restrict__ sd, int first, int chunk_from_right,
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
         const int e = tid + 512 * q, k = e >> 6, i = e & 63;
-        As[k * GLD + i] = ra[q];
+        if (KIND == CS3_LU_T) As[i * GLD + k] = ra[q];
+        else As[k * GLD + i] = ra[q];
         Bs[k * GLD + i] = rb[q];
     }
     __syncthreads();
@@ -3958,7 +4000,7 @@ static hipError_t launch_gemm_group(const DeviceFactor &D, const LaunchGroup &g,
         while (t1 < nt && T[2 * t1] < g.first + g.count) ++t1;
     }
     if (with_inverse) {
-        hipError_t ie = launch_inv_tasks<KIND>(D, t0, t1, st);
+        hipError_t ie = launch_inv_tasks<(KIND == CS3_LU_T) ? CS3_LU : KIND>(D, t0, t1, st);
         if (ie != hipSuccess) return ie;
     }
     const int nchunk = (g.max_w + GC - 1) / GC;
@@ -4005,7 +4047,8 @@ static hipError_t launch_solve_group(const DeviceFactor &D, const LaunchGroup &g
 {
     const long long xs = D.n * (long long) nrhs;
     const long long cvs = D.cv_size * (long long) nrhs;
-    if (g.cls == SK_SUB) return (nrhs == 1) ? launch_sub_sweep(D, g.first, X, forward, st) : hipErrorInvalidValue;
+    // (the bottom forest's sweeps have no transposed form: transposed solves take the level schedule)
+    if (g.cls == SK_SUB) return (nrhs == 1 && KIND != CS3_LU_T) ? launch_sub_sweep(D, g.first, X, forward, st) : hipErrorInvalidValue;
     static const bool use_gemm = !(getenv("CS3_NO_GEMM_SWEEPS") && getenv("CS3_NO_GEMM_SWEEPS")[0] == '1');
     if (use_gemm && nrhs >= RHS_LANES_MIN && (g.cls == SK_WAVE || g.cls == SK_BLOCK || g.cls == SK_BIG))
         return launch_gemm_group<KIND>(D, g, X, nrhs, forward, forward && D.inverses_in_sweep, st);
@@ -4141,6 +4184,7 @@ hipError_t launch_solve_levels(const DeviceFactor &D, const std::vector<LaunchGr
     //  -- 128: 0.82 ms forked, 0.77 in line; 256: equal; 1024: equal to 0.5 %)
     const bool solve_parallel = nrhs >= 512;
     auto launch = [&](const LaunchGroup &g, hipStream_t s) {
+        if (D.kind == CS3_LU && D.trans) return launch_solve_group<CS3_LU_T>(D, g, X, nrhs, forward, s);
         return (D.kind == CS3_LU) ? launch_solve_group<CS3_LU>(D, g, X, nrhs, forward, s)
                                   : launch_solve_group<CS3_CHOLESKY>(D, g, X, nrhs, forward, s);
     };

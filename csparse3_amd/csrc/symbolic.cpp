@@ -1163,7 +1163,7 @@ void build_csc_factors(Symbolic &S)
 // ----------------------------------------------- general triangular CSC --
 // Row-oriented level schedule: row i can be solved once every row j with
 // G(i,j) != 0 (j != i) is done; level = longest such chain.
-void tri_schedule(i64 n, const i32 *Gp, const i32 *Gi, bool lower, TriSchedule &T)
+void tri_schedule(i64 n, const i32 *Gp, const i32 *Gi, bool lower, TriSchedule &T, bool trans)
 {
     T = TriSchedule();
     T.n = n;
@@ -1179,12 +1179,21 @@ void tri_schedule(i64 n, const i32 *Gp, const i32 *Gi, bool lower, TriSchedule &
             i32 i = Gi[p];
             if (i < 0 || i >= n || (lower ? i <= j : i >= j))
                 throw std::runtime_error("triangular solve: entry on the wrong side of the diagonal");
-            ++T.Rp[i + 1];
+            ++T.Rp[(trans ? j : i) + 1];
         }
     }
     for (i64 i = 0; i < n; ++i) T.Rp[i + 1] += T.Rp[i];
     T.Rj.resize(T.Rp[n]); T.Rmap.resize(T.Rp[n]);
-    {
+    if (trans) {                                 // row j of G' = column j of G without its diagonal, in storage order
+        i64 q = 0;
+        for (i64 j = 0; j < n; ++j)
+            for (i64 p = Gp[j]; p < Gp[j + 1]; ++p) {
+                if (p == T.diag[j]) continue;
+                T.Rj[q] = Gi[p];
+                T.Rmap[q++] = p;
+            }
+        lower = !lower;                          // G' is triangular the other way round
+    } else {
         std::vector<i32> fill(T.Rp.begin(), T.Rp.end() - 1);
         for (i64 j = 0; j < n; ++j)
             for (i64 p = Gp[j]; p < Gp[j + 1]; ++p) {

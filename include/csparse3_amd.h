@@ -129,6 +129,17 @@ int cs3_usolve(cs3_handle h, double *X, int64_t k);
 int cs3_solve_dev(cs3_handle h, double *X_dev, int64_t k, void *stream);
 int cs3_lsolve_dev(cs3_handle h, double *X_dev, int64_t k, void *stream);
 int cs3_usolve_dev(cs3_handle h, double *X_dev, int64_t k, void *stream);
+/* Transposed solves on the same factors (cs_ltsolve / cs_utsolve lineage), same layouts and error codes:
+ * cs3_solve_t:  full solve A' x = b, both permutations included (x = P' (L' \ (U' \ (Q' b))))
+ * cs3_utsolve:  x = U' \ x   in pivot order (Cholesky handles: CS3_ERR_ARG, there is no U)
+ * cs3_ltsolve:  x = L' \ x   in pivot order, unit diagonal for LU (Cholesky: what cs3_usolve does)
+ * On a Cholesky handle A' = A: cs3_solve_t is cs3_solve, bit for bit. */
+int cs3_solve_t(cs3_handle h, double *X, int64_t k);
+int cs3_utsolve(cs3_handle h, double *X, int64_t k);
+int cs3_ltsolve(cs3_handle h, double *X, int64_t k);
+int cs3_solve_t_dev(cs3_handle h, double *X_dev, int64_t k, void *stream);
+int cs3_utsolve_dev(cs3_handle h, double *X_dev, int64_t k, void *stream);
+int cs3_ltsolve_dev(cs3_handle h, double *X_dev, int64_t k, void *stream);
 
 /* ---- residual and iterative refinement on resident data ----
  * R = B - A X with the handle's analysed pattern and the values Ax_dev [batch][nnz]; X, B, R [batch][n, k] row-major.
@@ -143,6 +154,14 @@ int cs3_matvec_dev(cs3_handle h, const double *Ax_dev, const double *X_dev, doub
  * (reading it synchronises the stream). */
 int cs3_refine_dev(cs3_handle h, const double *Ax_dev, const double *B_dev, double *X_dev, int64_t k, int64_t steps,
                    double *last_correction, void *stream);
+/* The transposed counterparts: R = B - A' X, Y = A' X, and x += A^-T (b - A' x).  Row j of A' X sums column j of A in
+ * storage order with the same rounding discipline (bit-exact with csc_mat_vec_ff applied to A' when the columns of A are
+ * sorted). */
+int cs3_residual_t_dev(cs3_handle h, const double *Ax_dev, const double *B_dev, const double *X_dev, double *R_dev,
+                       int64_t k, void *stream);
+int cs3_matvec_t_dev(cs3_handle h, const double *Ax_dev, const double *X_dev, double *Y_dev, int64_t k, void *stream);
+int cs3_refine_t_dev(cs3_handle h, const double *Ax_dev, const double *B_dev, double *X_dev, int64_t k, int64_t steps,
+                     double *last_correction, void *stream);
 
 /* ---- factors back to the host in CSparse's CSC form ---------------------
  * L: diagonal FIRST in each column (unit for LU); U: diagonal LAST; row
@@ -189,6 +208,12 @@ int cs3_csc_lsolve(int64_t n, const int32_t *Lp, const int32_t *Li, const double
                    double *x, int64_t k);
 int cs3_csc_usolve(int64_t n, const int32_t *Up, const int32_t *Ui, const double *Ux,
                    double *x, int64_t k);
+/* x = L' \ x and x = U' \ x on the same arrays (cs_ltsolve / cs_utsolve): the columns of L and U are the rows of
+ * their transposes, so nothing is transposed; level-scheduled on the device. */
+int cs3_csc_ltsolve(int64_t n, const int32_t *Lp, const int32_t *Li, const double *Lx,
+                    double *x, int64_t k);
+int cs3_csc_utsolve(int64_t n, const int32_t *Up, const int32_t *Ui, const double *Ux,
+                    double *x, int64_t k);
 
 /* ---- neighbours of the path -----------------------
  * y = A x on the device, csc_mat_vec_ff (csc_numba.py:309-328) semantics;
