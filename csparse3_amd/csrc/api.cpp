@@ -186,10 +186,10 @@ int ensure_device_impl(cs3_handle h)
     for (i32 t = 0; t < S.nsuper; ++t) sdesc[t] = solve_desc_of(S, S.ssched[t]);
     int rc;
     // the bottom forest and the sweep schedule of one right-hand side that goes with it
-    D.sub_tiers = S.sub_tiers;
+    D.sub_forest = S.sub_forest;
     D.n_sub_a = (long long) S.sub_a_tgt.size();
     D.sd_active = nullptr; D.fwd_in_factor = false;
-    if (!S.sub_tiers.empty()) {
+    if (!S.sub_forest.empty()) {
         std::vector<SolveDesc> sdesc1(S.nsuper);
         for (i32 t = 0; t < S.nsuper; ++t) sdesc1[t] = solve_desc_of(S, S.ssched1[t]);
         if ((rc = upload(&D.sdesc1, sdesc1))) return rc;
@@ -285,12 +285,12 @@ int capture(cs3_handle h, hipGraphExec_t *exec, Body body)
     return CS3_OK;
 }
 
-// One right-hand side on a handle with a bottom forest: the sweeps follow the factor schedule (tiers, then the levels
-// above them) with their own descriptor array.  Sets what the launchers read; returns the launch groups to pass.
+// One right-hand side on a handle with a bottom forest: the sweeps follow the factor schedule (the forest, then the
+// levels above it) with their own descriptor array.  Sets what the launchers read; returns the launch groups to pass.
 // (The forest's sweeps have no transposed form: a transposed solve takes the level schedule whatever nrhs is.)
 const std::vector<LaunchGroup> &select_sweep_schedule(cs3_handle h, int nrhs, bool trans = false)
 {
-    const bool forest = nrhs == 1 && !trans && !h->S.sub_tiers.empty();
+    const bool forest = nrhs == 1 && !trans && !h->S.sub_forest.empty();
     h->D.sd_active = forest ? h->D.sdesc1 : nullptr;
     return forest ? h->S.sgroups1 : h->S.sgroups;
 }
@@ -330,8 +330,8 @@ int read_status(cs3_handle h, hipStream_t st)
     CS3_HIP(hipStreamSynchronize(st));
     if (word[3] != 0) {
         // a wait inside the step was given up: a wave of a shared elimination never saw the multipliers of its partner
-        // (eliminate_pair / eliminate_parts / the shared fronts of the forest).  Whatever was computed behind that point
-        // is not to be used.
+        // (eliminate_pair in k_big_step / the shared fronts of the forest).  Whatever was computed behind that point is
+        // not to be used.
         CS3_HIP(hipMemsetAsync(h->D.status + 3, 0, sizeof(int), st));
         h->factored = false;
         set_error("a hand-over between the waves of a shared elimination timed out: the factors and solutions of this step are not valid");
@@ -440,7 +440,7 @@ int run_factor_solve(cs3_handle h, const double *ax_dev, const double *b_dev, do
     const double inv_tol = (tol > 0.0) ? 1.0 / tol : HUGE_VAL;
     D.xm = XMap();                                              // (never a caller's pointer left over from a failed solve)
     const std::vector<LaunchGroup> &sg = select_sweep_schedule(h, nrhs);
-    D.fwd_in_factor = nrhs == 1 && !h->S.sub_tiers.empty();   // the tiers' factor launches carry their forward sweep
+    D.fwd_in_factor = nrhs == 1 && !h->S.sub_forest.empty();  // the forest's factor launch carries its forward sweep
     D.inverses_in_sweep = true;                                // captured with the graph: the forward sweep inverts group by group
     CS3_HIP(launch_prologue(D, ax_dev, b_dev, nrhs, st));      // right-hand sides are read from b_dev, the solution goes to x_dev
     if (h->use_graph) {
@@ -839,18 +839,15 @@ int64_t cs3_debug_forest(cs3_handle h, int32_t *supernode, int32_t *task, int32_
 {
     if (guard(h)) return -1;
     const Symbolic &S = h->S;
-    for (size_t ti = 0; ti < S.sub_tiers.size(); ++ti) {
-        const SubTier &T = S.sub_tiers[ti];
-        for (i32 k = T.task0; k < T.task0 + T.ntasks; ++k) {
-            const SubTask &K = S.sub_tasks[k];
-            for (i32 l = 0; l < K.nlevels; ++l)
-                for (i32 f = K.front0 + S.sub_lvl[K.lvl0 + 2 * l]; f < K.front0 + S.sub_lvl[K.lvl0 + 2 * l + 2]; ++f) {
-                    if (supernode) supernode[f] = S.sub_sn[f];
-                    if (task) task[f] = k;
-                    if (level) level[f] = l;
-                    if (tier) tier[f] = (i32) ti;
-                }
-        }
+    for (i32 k = 0; k < (i32) S.sub_tasks.size(); ++k) {
+        const SubTask &K = S.sub_tasks[k];
+        for (i32 l = 0; l < K.nlevels; ++l)
+            for (i32 f = K.front0 + S.sub_lvl[K.lvl0 + 2 * l]; f < K.front0 + S.sub_lvl[K.lvl0 + 2 * l + 2]; ++f) {
+                if (supernode) supernode[f] = S.sub_sn[f];
+                if (task) task[f] = k;
+                if (level) level[f] = l;
+                if (tier) tier[f] = 0;
+            }
     }
     return (int64_t) S.sub_sn.size();
 }

@@ -71,7 +71,7 @@ __device__ __forceinline__ void flag_column(int *status, int col)
     atomicMin(status, col);
 }
 
-// ---- multipliers handed from wave to wave through LDS (eliminate_pair / eliminate_parts, the shared fronts of forest.hip) --
+// ---- multipliers handed from wave to wave through LDS (eliminate_pair in k_big_step, the shared fronts of forest.hip) ----
 // The producer stores a vector of multipliers, then the number of pivots handed over so far; the consumer polls that number.
 // LDS operations of one wave complete in order, so no fence sits on the producer's pivot chain (a release fence per pivot
 // measured 350 instead of 275 cycles per pivot); the counter is accessed with relaxed workgroup-scope atomics so that the

@@ -43,7 +43,7 @@ enum SolveKind : int {
     SK_BLOCK = 2,      // one workgroup per front
     SK_BIG = 3,        // w > 64, r > 136: one launch per 64-column chunk, many workgroups
     SK_IL = 4,         // matrix-interleaved small fronts of a large batch: lane = matrix (k_fwd_il / k_bwd_il)
-    SK_SUB = 5         // a tier of the bottom forest: one workgroup per task (k_sub_fwd / k_sub_bwd), one right-hand side
+    SK_SUB = 5         // the bottom forest: one workgroup per task (k_sub_fwd / k_sub_bwd), one right-hand side
 };
 
 struct LaunchGroup {          // fronts of one level that share a kernel configuration
@@ -60,20 +60,20 @@ struct LaunchGroup {          // fronts of one level that share a kernel configu
 // dozen levels.  Subtrees whose fronts all have order <= SUB_RMAX are cut out of the level schedule and handed to ONE
 // workgroup each (a TASK; small subtrees are packed together): the workgroup walks its fronts level by level with
 // block barriers in between, one wave per front, and the contribution blocks (and vectors) of its fronts stay in
-// its LDS.  What is left above a tier of tasks is searched again (tier 1, 2, ...: their tasks read the blocks of
-// the tier below from the pool), and what is left above the last tier runs level by level as before.
+// its LDS.  All tasks go out in ONE launch; a task holds whole subtrees, so every child of a forest front sits in its
+// parent's task.  What is left above the forest runs level by level as before.
 constexpr i32 SUB_RMAX = 32;                  // one wave holds a front of this order in registers (lane = row)
 
 // One front of a task as the k_sub_* kernels read it (staged in LDS for the whole task).  16 ints.
 struct SubFront {
     i32 lpan, upan;               // pool offsets of the panels
-    i32 cb;                       // contribution block: >= 0 pool offset (compact nb x nb; the parent is outside the task),
+    i32 cb;                       // contribution block: >= 0 pool offset (compact nb x nb; the parent is outside the forest),
                                   //   < 0: ~offset (doubles) in the task's LDS arena, nb x (nb + 1): the last column is the
                                   //   contribution vector of the fused forward sweep
-    i32 cv;                       // contribution vector in the global pool (parent outside the task, and every stand-alone sweep)
+    i32 cv;                       // contribution vector in the global pool (the parent is outside the forest)
     i32 c0, r, w;
     i32 a_begin, a_count;         // entries of A: sub_a_tgt / the forest-ordered copy of the values
-    i32 child_begin, child_count; // sub_child (4 ints per child): update rows nbc | own task << 16, row map, block, vector
+    i32 child_begin, child_count; // sub_child (4 ints per child, all in the task's LDS): update rows nbc, row map, block, vector
     i32 rel;                      // sub_rel + rel: where my update rows sit in the parent's structure (nb entries)
     i32 st;                       // st_idx + st: my row structure (backward sweep: the ancestors' rows)
     i32 u_sj;                     // U(k, j) = pool[upan + k + (j - w) u_sj]
@@ -89,12 +89,13 @@ struct SubTask {                  // one workgroup
     i32 child0, nchild;           // its slice of sub_child, in children (4 ints each)
 };
 
-struct SubTier {                  // one launch
-    i32 task0 = 0, ntasks = 0;
+struct SubForest {                // the forest's launch: one workgroup per task
+    i32 ntasks = 0;
     i32 max_fronts = 0, max_levels = 0, max_rel = 0, max_child = 0;   // LDS staging sizes
     i32 max_arena = 0;            // doubles: contribution blocks of a task that stay in LDS
     i32 max_varena = 0;           // doubles: contribution vectors (stand-alone sweeps)
     i32 max_r = 0;
+    bool empty() const { return ntasks == 0; }
 };
 
 struct Symbolic {
@@ -158,16 +159,17 @@ struct Symbolic {
     i64 gv_size = 0, dinv_size = 0;
     std::vector<i32> inv_tasks;
     std::vector<LaunchGroup> sgroups;
-    // bottom forest (empty when off): sn_tier[s] = tier of supernode s, -1 above the forest
-    std::vector<i32> sn_tier, sn_tlevel;      // sn_tlevel: tier for forest fronts, ntiers + height above the forest otherwise
-    std::vector<SubTier> sub_tiers;
+    // bottom forest (empty when off): sn_in_forest[s] = supernode s is a front of the forest
+    std::vector<char> sn_in_forest;
+    std::vector<i32> sn_tlevel;               // schedule level: 0 for forest fronts, else height above the forest (+ 1 with one)
+    SubForest sub_forest;
     std::vector<SubTask> sub_tasks;
     std::vector<SubFront> sub_fronts;
     std::vector<i32> sub_sn;                  // supernode of each SubFront
     std::vector<i32> sub_lvl, sub_rel, sub_child;
     std::vector<i32> sub_st;                  // parallel to sub_rel: the global row behind each update row (backward sweep)
     std::vector<i32> sub_a_tgt, sub_a_src;    // A entries of the forest fronts: target in the LDS image, entry of Ax
-    // one right-hand side with a forest: the sweeps follow the factor schedule (tiers, then the levels above them)
+    // one right-hand side with a forest: the sweeps follow the factor schedule (the forest, then the levels above it)
     std::vector<i32> ssched1;
     std::vector<LaunchGroup> sgroups1;
     // schedule

@@ -10,8 +10,8 @@
 //   * a front is assembled by scatter (entries of A, from a copy of the values in forest order: no index
 //     indirection) and EXTEND-ADD of its children's contribution blocks through their row maps: index lists of
 //     O(r) per child instead of the O(r^2) sorted gather lists of the level kernels;
-//   * the contribution blocks of its fronts never leave the LDS; only a front whose parent lies outside the task
-//     writes its block to the pool (for a later tier or for the level schedule above the forest);
+//   * the contribution blocks of its fronts never leave the LDS (a task holds whole subtrees); only a front whose parent
+//     lies outside the forest writes its block to the pool, for the level schedule above the forest;
 //   * with one right-hand side in a fused factor + solve step the forward sweep rides along as ONE MORE COLUMN of
 //     every front (eliminating [F | b] is the forward substitution): no panel is read back for it.
 // The sweeps (k_sub_fwd / k_sub_bwd, one right-hand side) walk the same tasks with the contribution vectors in LDS.
@@ -46,7 +46,7 @@ constexpr int COOP_NC = 8;
 constexpr int COOP_SLICE = 9 * 33 + 7;          // 304 doubles (ld <= 33; one dummy slot behind the slice)
 constexpr int COOP_IMG = COOP_SLICE + COOP_NC * 64;
 
-static SubLds sub_lds_layout(const SubTier &T, int arena_doubles, int img_doubles, size_t *bytes)
+static SubLds sub_lds_layout(const SubForest &T, int arena_doubles, int img_doubles, size_t *bytes)
 {
     SubLds L;
     L.child = 16 * T.max_fronts;                // (a multiple of 4 ints: the child table is read as int4)
@@ -101,9 +101,9 @@ __device__ __forceinline__ void sub_stage(const SubTask &t, const SubFront *__re
 // eight columns each per pass (one pass for nbc <= 15): the sixteen targets of a pass are distinct, so their loads go
 // out together, before the stores.  The target column of a source column is the row map entry of the lane of that
 // number: read lane-to-scalar, no second trip to the map.  Lanes without work add to the dummy slot.
-// relp / cbp / cvp may live in LDS or in global memory (the caller instantiates both).
-template <int KIND, bool RHS, class RelPtr, class BlkPtr, class VecPtr>
-__device__ __forceinline__ void sub_extend_add(double *F, int ld, int r, int dummy, RelPtr relp, BlkPtr cbp, VecPtr cvp, int nbc)
+template <int KIND, bool RHS>
+__device__ __forceinline__ void sub_extend_add(double *F, int ld, int r, int dummy, const int *relp, const double *cbp,
+                                               const double *cvp, int nbc)
 {
     constexpr int EU = 8;
     const int lane = threadIdx.x & 63, ii = lane & 31, half = lane >> 5;
@@ -148,9 +148,9 @@ __device__ __forceinline__ void sub_extend_add(double *F, int ld, int r, int dum
 // The vector column of the fused forward sweep rides in the last part.  The counter only grows (gbase: 64 per
 // shared front of the group), so no reset can race with a reader.  A wave never waits for a wave to its right: no cycle;
 // the wait is bounded anyway and a wave that gives up raises status[3] (the step is reported as failed).
-template <int KIND, bool RHS, class BlkPtr, class VecPtr>
-__device__ __forceinline__ void coop_extend_add(double *S, int ld, int sdummy, int part, bool last, int myrel, BlkPtr cbp,
-                                                VecPtr cvp, int nbc)
+template <int KIND, bool RHS>
+__device__ __forceinline__ void coop_extend_add(double *S, int ld, int sdummy, int part, bool last, int myrel, const double *cbp,
+                                                const double *cvp, int nbc)
 {
     // myrel: the child's row map, lane ii = lane & 31 holds entry ii (read by the caller one child ahead)
     const int lane = threadIdx.x & 63, ii = lane & 31, half = lane >> 5;
@@ -219,7 +219,7 @@ __device__ __forceinline__ void coop_own_pivots_lu(double (&d)[COOP_NC], double 
 template <int KIND, bool RHS>
 __device__ __forceinline__ void
 sub_coop_front(const SubScalars &ds, int part, double *gimg, int img_stride, int *ready_generic, int gbase, const SubTask &t,
-               const int4 *childs, const int *rels, double *arena, const int *__restrict__ rel_g, const int *__restrict__ a_tgt,
+               const int4 *childs, const int *rels, double *arena, const int *__restrict__ a_tgt,
                const double *__restrict__ axf, double *__restrict__ pool, double *__restrict__ xp, double *__restrict__ cvg,
                double inv_tol, int *status, long long *stamps, long long t_start)
 {
@@ -272,8 +272,8 @@ sub_coop_front(const SubScalars &ds, int part, double *gimg, int img_stride, int
         const int child_begin = ds.child_begin - t.child0, child_count = ds.child_count;
         auto entry = [&](int ci) { return childs[child_begin + (ci < child_count ? ci : (child_count > 0 ? child_count - 1 : -child_begin))]; };
         auto rowmap = [&](const int4 &e) {
-            const int n = uni(e.x) & 0xffff, o = uni(e.y), i = (lane & 31) < n ? (lane & 31) : 0;
-            return (uni(e.x) >> 16) ? rels[o + i] : rel_g[o + i];
+            const int n = uni(e.x), i = (lane & 31) < n ? (lane & 31) : 0;
+            return rels[uni(e.y) + i];
         };
         int4 e1 = entry(0), e2 = entry(1);
         int rel1 = child_count > 0 ? rowmap(e1) : 0;
@@ -283,13 +283,9 @@ sub_coop_front(const SubScalars &ds, int part, double *gimg, int img_stride, int
             e1 = e2;
             e2 = entry(ci + 2);
             if (ci + 1 < child_count) rel1 = rowmap(e1);
-            const int nbc = uni(cur.x) & 0xffff, cblk = uni(cur.z);
-            if (uni(cur.x) >> 16) {
-                const double *cb = arena + cblk;
-                coop_extend_add<KIND, RHS>(S, ld, sdummy, part, last, myrel, cb, cb + nbc * nbc, nbc);
-            } else {
-                coop_extend_add<KIND, RHS>(S, ld, sdummy, part, last, myrel, pool + cblk, cvg + uni(cur.w), nbc);
-            }
+            const int nbc = uni(cur.x);
+            const double *cb = arena + uni(cur.z);
+            coop_extend_add<KIND, RHS>(S, ld, sdummy, part, last, myrel, cb, cb + nbc * nbc, nbc);
             __builtin_amdgcn_wave_barrier();
         }
     }
@@ -492,7 +488,7 @@ sub_coop_front(const SubScalars &ds, int part, double *gimg, int img_stride, int
 
 template <int KIND, bool RHS>
 __global__ void __launch_bounds__(SUB_NT)
-k_sub_factor(const SubTask *__restrict__ tasks, int task0, const SubFront *__restrict__ fronts, const int *__restrict__ lvl_g,
+k_sub_factor(const SubTask *__restrict__ tasks, const SubFront *__restrict__ fronts, const int *__restrict__ lvl_g,
              const int *__restrict__ rel_g, const int *__restrict__ child_g, const int *__restrict__ a_tgt,
              const double *__restrict__ axf_all, long long na, double *__restrict__ pool_all, long long pool_stride,
              double *__restrict__ xp_all, double *__restrict__ cv_all, long long n, long long cv_stride,
@@ -504,7 +500,7 @@ k_sub_factor(const SubTask *__restrict__ tasks, int task0, const SubFront *__res
     // the image, 2 children added, 3 row in registers, 4 eliminated, 5 stored, 6 the level's barrier passed (first front of a wave)
     const long long t_start = tbuf ? (long long) __builtin_amdgcn_s_memtime() : 0;
 #define CS3_SSTAMP(f, p) do { if (tbuf && blockIdx.y == 0 && (threadIdx.x & 63) == 0) tbuf[(long long) (t.front0 + (f)) * 8 + (p)] = (long long) __builtin_amdgcn_s_memtime() - t_start; } while (0)
-    const SubTask t = tasks[task0 + blockIdx.x];
+    const SubTask t = tasks[blockIdx.x];
     sub_stage(t, fronts, lvl_g, rel_g, child_g, smi, lay);
     const SubFront *fd = (const SubFront *) smi;
     const int4 *childs = (const int4 *) (smi + lay.child);
@@ -548,19 +544,15 @@ k_sub_factor(const SubTask *__restrict__ tasks, int task0, const SubFront *__res
         if (RHS && lane < w) F[lane + r * ld] = xv;
         __builtin_amdgcn_wave_barrier();
         CS3_SSTAMP(f, 1);
-        // ---- children, in order (the table entry of the next child is requested before the current one is added)
+        // ---- children, in order, from the arena (the table entry of the next child is requested before the current one is added)
         const int child_begin = ds.child_begin - t.child0, child_count = ds.child_count;
         int4 ce = childs[child_count > 0 ? child_begin : 0];
         for (int ci = 0; ci < child_count; ++ci) {
             const int4 cur = ce;
             ce = childs[child_begin + (ci + 1 < child_count ? ci + 1 : ci)];
-            const int nbc = uni(cur.x) & 0xffff, crel = uni(cur.y), cblk = uni(cur.z);
-            if (uni(cur.x) >> 16) {                         // my own task: block and vector in the arena
-                const double *cb = arena + cblk;
-                sub_extend_add<KIND, RHS>(F, ld, r, dummy, rels + crel, cb, cb + nbc * nbc, nbc);
-            } else {                                        // a tier below: block and vector in the pools
-                sub_extend_add<KIND, RHS>(F, ld, r, dummy, rel_g + crel, pool + cblk, cvg + uni(cur.w), nbc);
-            }
+            const int nbc = uni(cur.x);
+            const double *cb = arena + uni(cur.z);
+            sub_extend_add<KIND, RHS>(F, ld, r, dummy, rels + uni(cur.y), cb, cb + nbc * nbc, nbc);
             __builtin_amdgcn_wave_barrier();
         }
         CS3_SSTAMP(f, 2);
@@ -694,7 +686,7 @@ k_sub_factor(const SubTask *__restrict__ tasks, int task0, const SubFront *__res
             if (f < f0 + nco) {
                 const SubScalars ds = sub_load_desc(fd, f);
                 sub_coop_front<KIND, RHS>(ds, part, sm + lay.img + 4 * grp * lay.img_stride, lay.img_stride, smi + lay.ready + grp, gbase,
-                                          t, childs, rels, arena, rel_g, a_tgt, axf, pool, xp, cvg, inv_tol, status,
+                                          t, childs, rels, arena, a_tgt, axf, pool, xp, cvg, inv_tol, status,
                                           tbuf ? tbuf + (long long) (t.front0 + f) * 8 : nullptr, t_start);
             } else {
                 if (fs + part < f1) single_front(fs + part);
@@ -716,13 +708,13 @@ k_sub_factor(const SubTask *__restrict__ tasks, int task0, const SubFront *__res
 // vector column of k_sub_factor), then column by column  y_k = v_k (Cholesky: times 1 / L_kk),  v_i -= L_ik y_k.
 template <int KIND>
 __global__ void __launch_bounds__(SUB_NT)
-k_sub_fwd(const SubTask *__restrict__ tasks, int task0, const SubFront *__restrict__ fronts, const int *__restrict__ lvl_g,
+k_sub_fwd(const SubTask *__restrict__ tasks, const SubFront *__restrict__ fronts, const int *__restrict__ lvl_g,
           const int *__restrict__ rel_g, const int *__restrict__ child_g, const double *__restrict__ pool_all, long long pool_stride,
           double *__restrict__ X_all, double *__restrict__ cv_all, long long n, long long cv_stride, SubLds lay)
 {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     int *smi = (int *) sm;
-    const SubTask t = tasks[task0 + blockIdx.x];
+    const SubTask t = tasks[blockIdx.x];
     sub_stage(t, fronts, lvl_g, rel_g, child_g, smi, lay);
     const SubFront *fd = (const SubFront *) smi;
     const int4 *childs = (const int4 *) (smi + lay.child);
@@ -761,16 +753,10 @@ k_sub_fwd(const SubTask *__restrict__ tasks, int task0, const SubFront *__restri
             for (int ci = 0; ci < child_count; ++ci) {
                 const int4 cur = ce;
                 ce = childs[child_begin + (ci + 1 < child_count ? ci + 1 : ci)];
-                const int nbc = uni(cur.x) & 0xffff, crel = uni(cur.y), cvec = uni(cur.w);
-                if (uni(cur.x) >> 16) {
-                    const int tg = rels[crel + (lane < nbc ? lane : 0)];
-                    const double a = arena[cvec + (lane < nbc ? lane : 0)], b = vs[lane < nbc ? tg : r];
-                    vs[lane < nbc ? tg : r] = a + b;
-                } else {
-                    const int tg = rel_g[crel + (lane < nbc ? lane : 0)];
-                    const double a = cvg[cvec + (lane < nbc ? lane : 0)], b = vs[lane < nbc ? tg : r];
-                    vs[lane < nbc ? tg : r] = b + a;
-                }
+                const int nbc = uni(cur.x), crel = uni(cur.y), cvec = uni(cur.w);
+                const int tg = rels[crel + (lane < nbc ? lane : 0)];
+                const double a = arena[cvec + (lane < nbc ? lane : 0)], b = vs[lane < nbc ? tg : r];
+                vs[lane < nbc ? tg : r] = a + b;
                 __builtin_amdgcn_wave_barrier();
             }
             double v = vs[lane < r ? lane : r];
@@ -805,13 +791,13 @@ k_sub_fwd(const SubTask *__restrict__ tasks, int task0, const SubFront *__restri
 // lane-to-scalar broadcast and one FMA.
 template <int KIND>
 __global__ void __launch_bounds__(SUB_NT)
-k_sub_bwd(const SubTask *__restrict__ tasks, int task0, const SubFront *__restrict__ fronts, const int *__restrict__ lvl_g,
+k_sub_bwd(const SubTask *__restrict__ tasks, const SubFront *__restrict__ fronts, const int *__restrict__ lvl_g,
           const int *__restrict__ st_g, const int *__restrict__ child_g, const double *__restrict__ pool_all, long long pool_stride,
           double *__restrict__ X_all, long long n, SubLds lay)
 {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     int *smi = (int *) sm;
-    const SubTask t = tasks[task0 + blockIdx.x];
+    const SubTask t = tasks[blockIdx.x];
     sub_stage(t, fronts, lvl_g, st_g, child_g, smi, lay);          // (the row maps staged here are the GLOBAL rows, sub_st)
     const SubFront *fd = (const SubFront *) smi;
     const int *rows = smi + lay.rel, *lvls = smi + lay.lvl;
@@ -891,14 +877,14 @@ hipError_t prepare_forest_kernels()
     return hipSuccess;
 }
 
-hipError_t launch_sub_factor(const DeviceFactor &D, int tier, bool with_forward, double inv_tol, hipStream_t st)
+hipError_t launch_sub_factor(const DeviceFactor &D, bool with_forward, double inv_tol, hipStream_t st)
 {
-    const SubTier &T = D.sub_tiers[(size_t) tier];
+    const SubForest &T = D.sub_forest;
     size_t bytes = 0;
     const SubLds lay = sub_lds_layout(T, T.max_arena, std::max((T.max_r + 1) * (T.max_r | 1) + 1, COOP_IMG), &bytes);
     if (bytes > 160 * 1024) return hipErrorInvalidValue;           // (the analysis caps keep a task far below this)
     const dim3 grid((unsigned) T.ntasks, (unsigned) D.batch), block(SUB_NT);
-#define CS3_SUB_ARGS D.sub_tasks, T.task0, D.sub_fronts, D.sub_lvl, D.sub_rel, D.sub_child, D.sub_a_tgt, D.axf, D.n_sub_a, D.pool_pm, \
+#define CS3_SUB_ARGS D.sub_tasks, D.sub_fronts, D.sub_lvl, D.sub_rel, D.sub_child, D.sub_a_tgt, D.axf, D.n_sub_a, D.pool_pm, \
                      D.pm_stride, D.xp, D.cv, D.n, D.cv_size, inv_tol, D.status, lay, D.tbuf
     if (D.kind == CS3_LU) {
         if (with_forward) hipLaunchKernelGGL((k_sub_factor<CS3_LU, true>), grid, block, bytes, st, CS3_SUB_ARGS);
@@ -912,26 +898,26 @@ hipError_t launch_sub_factor(const DeviceFactor &D, int tier, bool with_forward,
     return hipSuccess;
 }
 
-hipError_t launch_sub_sweep(const DeviceFactor &D, int tier, double *X, bool forward, hipStream_t st)
+hipError_t launch_sub_sweep(const DeviceFactor &D, double *X, bool forward, hipStream_t st)
 {
-    const SubTier &T = D.sub_tiers[(size_t) tier];
+    const SubForest &T = D.sub_forest;
     size_t bytes = 0;
     const SubLds lay = sub_lds_layout(T, forward ? T.max_varena : 0, forward ? T.max_r + 2 : 0, &bytes);
     if (bytes > 160 * 1024) return hipErrorInvalidValue;
     const dim3 grid((unsigned) T.ntasks, (unsigned) D.batch), block(SUB_NT);
     if (forward) {
         if (D.kind == CS3_LU)
-            hipLaunchKernelGGL((k_sub_fwd<CS3_LU>), grid, block, bytes, st, D.sub_tasks, T.task0, D.sub_fronts, D.sub_lvl, D.sub_rel,
+            hipLaunchKernelGGL((k_sub_fwd<CS3_LU>), grid, block, bytes, st, D.sub_tasks, D.sub_fronts, D.sub_lvl, D.sub_rel,
                                D.sub_child, D.pool_pm, D.pm_stride, X, D.cv, D.n, D.cv_size, lay);
         else
-            hipLaunchKernelGGL((k_sub_fwd<CS3_CHOLESKY>), grid, block, bytes, st, D.sub_tasks, T.task0, D.sub_fronts, D.sub_lvl, D.sub_rel,
+            hipLaunchKernelGGL((k_sub_fwd<CS3_CHOLESKY>), grid, block, bytes, st, D.sub_tasks, D.sub_fronts, D.sub_lvl, D.sub_rel,
                                D.sub_child, D.pool_pm, D.pm_stride, X, D.cv, D.n, D.cv_size, lay);
     } else {
         if (D.kind == CS3_LU)
-            hipLaunchKernelGGL((k_sub_bwd<CS3_LU>), grid, block, bytes, st, D.sub_tasks, T.task0, D.sub_fronts, D.sub_lvl, D.sub_st,
+            hipLaunchKernelGGL((k_sub_bwd<CS3_LU>), grid, block, bytes, st, D.sub_tasks, D.sub_fronts, D.sub_lvl, D.sub_st,
                                D.sub_child, D.pool_pm, D.pm_stride, X, D.n, lay);
         else
-            hipLaunchKernelGGL((k_sub_bwd<CS3_CHOLESKY>), grid, block, bytes, st, D.sub_tasks, T.task0, D.sub_fronts, D.sub_lvl, D.sub_st,
+            hipLaunchKernelGGL((k_sub_bwd<CS3_CHOLESKY>), grid, block, bytes, st, D.sub_tasks, D.sub_fronts, D.sub_lvl, D.sub_st,
                                D.sub_child, D.pool_pm, D.pm_stride, X, D.n, lay);
     }
     CS3_LAUNCH_CHECK();

@@ -3686,7 +3686,7 @@ template <int KIND>
 static hipError_t launch_front_group(const DeviceFactor &D, const LaunchGroup &g, double inv_tol, hipStream_t st)
 {
     const unsigned batch = (unsigned) D.batch;
-    if (g.cls == FC_SUB) return launch_sub_factor(D, g.first, D.fwd_in_factor, inv_tol, st);     // a tier of the bottom forest
+    if (g.cls == FC_SUB) return launch_sub_factor(D, D.fwd_in_factor, inv_tol, st);     // the bottom forest
     if (big_group_in_one_workgroup(KIND, D.batch, g)) {
         hipLaunchKernelGGL((k_front_wg<KIND, WG_NB>), dim3((unsigned) g.count, batch), dim3(512), wg_lds_bytes(KIND, g), st, D.fdesc,
                            g.first, AsmLists{D.fa_tgt, D.fa_src, D.ch_tab, D.rel_idx}, D.ax, D.pool_pm, D.nnz_a, D.pm_stride,
@@ -4048,7 +4048,7 @@ static hipError_t launch_solve_group(const DeviceFactor &D, const LaunchGroup &g
     const long long xs = D.n * (long long) nrhs;
     const long long cvs = D.cv_size * (long long) nrhs;
     // (the bottom forest's sweeps have no transposed form: transposed solves take the level schedule)
-    if (g.cls == SK_SUB) return (nrhs == 1 && KIND != CS3_LU_T) ? launch_sub_sweep(D, g.first, X, forward, st) : hipErrorInvalidValue;
+    if (g.cls == SK_SUB) return (nrhs == 1 && KIND != CS3_LU_T) ? launch_sub_sweep(D, X, forward, st) : hipErrorInvalidValue;
     static const bool use_gemm = !(getenv("CS3_NO_GEMM_SWEEPS") && getenv("CS3_NO_GEMM_SWEEPS")[0] == '1');
     if (use_gemm && nrhs >= RHS_LANES_MIN && (g.cls == SK_WAVE || g.cls == SK_BLOCK || g.cls == SK_BIG))
         return launch_gemm_group<KIND>(D, g, X, nrhs, forward, forward && D.inverses_in_sweep, st);
@@ -4228,7 +4228,7 @@ hipError_t launch_factor_with_forward(const DeviceFactor &D, const std::vector<L
                                       hipStream_t st, ForkJoin &fj)
 {
     hipError_t e;
-    if (!D.sub_tiers.empty() && !D.sd_active) {
+    if (!D.sub_forest.empty() && !D.sd_active) {
         // a bottom forest under the factorisation, but sweeps on the level schedule of the whole tree (several right-hand
         // sides): the two number their levels differently, so nothing is overlapped
         if ((e = launch_factor_levels(D, all_fgroups, inv_tol, st, fj)) != hipSuccess) return e;
@@ -4241,7 +4241,7 @@ hipError_t launch_factor_with_forward(const DeviceFactor &D, const std::vector<L
     std::vector<long long> tail(nlevels + 1, 0), head(nlevels + 1, 0);   // factor cost of levels >= l; sweep cost of levels < l
     for (const LaunchGroup &g : fgroups) tail[g.level] += factor_group_cost(g);
     for (int l = nlevels - 1; l >= 0; --l) tail[l] += tail[l + 1];
-    // (a tier of the bottom forest whose factor launch carries the forward sweep has nothing left to sweep)
+    // (the bottom forest, when its factor launch carries the forward sweep, has nothing left to sweep)
     for (const LaunchGroup &g : sgroups) head[g.level + 1] += (g.cls == SK_SUB && D.fwd_in_factor) ? 0 : sweep_group_cost(g);
     for (int l = 0; l < nlevels; ++l) head[l + 1] += head[l];
     int fork_level = -1;

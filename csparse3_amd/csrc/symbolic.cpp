@@ -126,17 +126,16 @@ int front_class(i64 r, i64 w, bool split_small, bool interleave)
 }
 
 // ---------------------------------------------------------- bottom forest --
-// Step 6b of the analysis (see cs3_internal.hpp): tiers of tasks.  Everything here works on supernode orders and the
-// supernodal tree only; pool offsets and the entries of A are filled in later (fill_forest, after step 9).
+// Step 6b of the analysis (see cs3_internal.hpp): the tasks of the forest.  Everything here works on supernode orders
+// and the supernodal tree only; pool offsets and the entries of A are filled in later (fill_forest, after step 9).
 struct ForestLimits {
     i64 fronts = 64;            // fronts per task (their descriptors, child and row lists are staged in LDS)
     i64 arena = 5000;           // doubles: contribution blocks nb x (nb + 1) of a task that stay in its LDS (40 KB)
     i64 bins = 256;             // tasks per launch to aim for: one workgroup per CU
-    // One tier of SHALLOW subtrees: a task that holds a tall chain runs as long as the chain, and everything above the
-    // tier waits for it, while in the level schedule the upper fronts of a chain share their launches with the rest of
-    // their level (measured on config 3: unlimited height and 2 tiers 0.663 ms per step, height 4 and 1 tier 0.608,
-    // no forest 0.641).
-    i64 max_tiers = 1;
+    // SHALLOW subtrees: a task that holds a tall chain runs as long as the chain, and everything above the forest waits
+    // for it, while in the level schedule the upper fronts of a chain share their launches with the rest of their level
+    // (measured on config 3: unlimited height and 2 tiers -- launches of the forest one above the other -- 0.663 ms per
+    // step, height 4 and 1 tier 0.608, no forest 0.641).
     i64 max_height = 4;         // tallest subtree (local levels - 1) a task may hold
     i64 coop_w = 6;             // fronts with this many pivots or more are shared by four waves (forest.hip) ...
     i64 coop_level = 2;         // ... on local levels of at most this many fronts (one round of two groups): a fuller level keeps every wave busy with a
@@ -154,103 +153,96 @@ static ForestLimits forest_limits()
     return L;
 }
 
-// Chooses the forest: S.sn_tier, S.sub_tiers, S.sub_tasks, S.sub_sn (fronts in task order, by local level), S.sub_lvl.
+// Chooses the forest: S.sn_in_forest, S.sub_forest, S.sub_tasks, S.sub_sn (fronts in task order, by local level), S.sub_lvl.
 static void build_forest(Symbolic &S, const ForestLimits &lim)
 {
     const i32 ns = S.nsuper;
-    S.sn_tier.assign(ns, -1);
-    S.sub_tiers.clear(); S.sub_tasks.clear(); S.sub_sn.clear(); S.sub_lvl.clear();
+    S.sn_in_forest.assign(ns, 0);
+    S.sub_forest = SubForest{}; S.sub_tasks.clear(); S.sub_sn.clear(); S.sub_lvl.clear();
     auto width = [&](i32 s) -> i64 { return S.sn_ptr[s + 1] - S.sn_ptr[s]; };
     auto order_r = [&](i32 s) -> i64 { return S.st_ptr[s + 1] - S.st_ptr[s]; };
     std::vector<char> ok(ns);
     std::vector<i64> nf(ns), ar(ns);
     std::vector<i32> hgt(ns), root_of(ns), task_of(ns, -1);
     struct Bin { i64 nf = 0, ar = 0; std::vector<i32> roots; };
-    for (i64 tier = 0; tier < lim.max_tiers; ++tier) {
-        // a front qualifies when its order fits one wave and everything below it that is still unassigned qualifies
-        // and fits one task together with it (children precede parents: one pass)
-        i32 tallest = 0;
-        for (i32 s = 0; s < ns; ++s) {
-            if (S.sn_tier[s] >= 0) continue;
-            const i64 r = order_r(s), nb = r - width(s);
-            ok[s] = r <= SUB_RMAX; nf[s] = 1; ar[s] = nb * (nb + 1); hgt[s] = 0;
-            for (i32 cp = S.child_ptr[s]; cp < S.child_ptr[s + 1]; ++cp) {
-                const i32 c = S.child_idx[cp];
-                if (S.sn_tier[c] >= 0) continue;                // done in a tier below: its block comes from the pool
-                ok[s] = ok[s] && ok[c];
-                nf[s] += nf[c]; ar[s] += ar[c]; hgt[s] = std::max(hgt[s], hgt[c] + 1);
-            }
-            if (nf[s] > lim.fronts || ar[s] > lim.arena || hgt[s] > lim.max_height) ok[s] = 0;
-            if (ok[s]) tallest = std::max(tallest, hgt[s]);
+    // a front qualifies when its order fits one wave and everything below it qualifies and fits one task together with
+    // it (children precede parents: one pass)
+    i32 tallest = 0;
+    for (i32 s = 0; s < ns; ++s) {
+        const i64 r = order_r(s), nb = r - width(s);
+        ok[s] = r <= SUB_RMAX; nf[s] = 1; ar[s] = nb * (nb + 1); hgt[s] = 0;
+        for (i32 cp = S.child_ptr[s]; cp < S.child_ptr[s + 1]; ++cp) {
+            const i32 c = S.child_idx[cp];
+            ok[s] = ok[s] && ok[c];
+            nf[s] += nf[c]; ar[s] += ar[c]; hgt[s] = std::max(hgt[s], hgt[c] + 1);
         }
-        // a tier of single fronts is a level launch with a slower kernel: leave those to the level schedule
-        if (tallest < 1) break;
-        std::vector<i32> roots;
-        for (i32 s = 0; s < ns; ++s)
-            if (S.sn_tier[s] < 0 && ok[s] && (S.sn_parent[s] < 0 || !ok[S.sn_parent[s]])) roots.push_back(s);
-        if (roots.empty()) break;
-        // parents before children is what marks the members: walk down from the roots (ids descend along a subtree)
-        for (i32 s = ns - 1; s >= 0; --s) {
-            if (S.sn_tier[s] >= 0 || !ok[s]) continue;
-            const i32 p = S.sn_parent[s];
-            root_of[s] = (p >= 0 && S.sn_tier[p] == tier && ok[p]) ? root_of[p] : s;
-            S.sn_tier[s] = (i32) tier;
+        if (nf[s] > lim.fronts || ar[s] > lim.arena || hgt[s] > lim.max_height) ok[s] = 0;
+        if (ok[s]) tallest = std::max(tallest, hgt[s]);
+    }
+    // a forest of single fronts is a level launch with a slower kernel: leave those to the level schedule
+    if (tallest < 1) return;
+    std::vector<i32> roots;
+    for (i32 s = 0; s < ns; ++s)
+        if (ok[s] && (S.sn_parent[s] < 0 || !ok[S.sn_parent[s]])) roots.push_back(s);
+    // parents before children is what marks the members: walk down from the roots (ids descend along a subtree)
+    for (i32 s = ns - 1; s >= 0; --s) {
+        if (!ok[s]) continue;
+        const i32 p = S.sn_parent[s];
+        root_of[s] = (p >= 0 && ok[p]) ? root_of[p] : s;
+        S.sn_in_forest[s] = 1;
+    }
+    // tasks: the largest subtrees get a workgroup each; once there are `bins` of them the rest joins the least
+    // loaded task that still has room
+    std::stable_sort(roots.begin(), roots.end(), [&](i32 a, i32 b) { return nf[a] > nf[b]; });
+    std::vector<Bin> bins;
+    for (i32 rt : roots) {
+        i64 best = -1;
+        if ((i64) bins.size() >= lim.bins)
+            for (size_t b = 0; b < bins.size(); ++b)
+                if (bins[b].nf + nf[rt] <= lim.fronts && bins[b].ar + ar[rt] <= lim.arena &&
+                    (best < 0 || bins[b].nf < bins[(size_t) best].nf)) best = (i64) b;
+        if (best < 0) { bins.emplace_back(); best = (i64) bins.size() - 1; }
+        Bin &B = bins[(size_t) best];
+        B.nf += nf[rt]; B.ar += ar[rt]; B.roots.push_back(rt);
+    }
+    SubForest &T = S.sub_forest;
+    T.ntasks = (i32) bins.size();
+    for (size_t b = 0; b < bins.size(); ++b)
+        for (i32 rt : bins[b].roots) task_of[rt] = (i32) b;
+    // members by task: (task, local level, id)
+    std::vector<i32> members;
+    for (i32 s = 0; s < ns; ++s) if (S.sn_in_forest[s]) members.push_back(s);
+    std::stable_sort(members.begin(), members.end(), [&](i32 a, i32 b) {
+        const i32 ta = task_of[root_of[a]], tb = task_of[root_of[b]];
+        if (ta != tb) return ta < tb;
+        if (hgt[a] != hgt[b]) return hgt[a] < hgt[b];
+        // the shared (wide) fronts of a local level first, then the others, largest first: they start at once and the
+        // small ones fill the other waves
+        const bool ca = width(a) >= lim.coop_w, cb = width(b) >= lim.coop_w;
+        if (ca != cb) return ca;
+        return width(a) * order_r(a) > width(b) * order_r(b);
+    });
+    size_t m = 0;
+    for (size_t b = 0; b < bins.size(); ++b) {
+        SubTask K{};
+        K.front0 = (i32) S.sub_sn.size(); K.lvl0 = (i32) S.sub_lvl.size();
+        // per local level two entries: its first front (relative to front0) and how many of its leading fronts are shared
+        i32 cur = -1;
+        while (m < members.size() && task_of[root_of[members[m]]] == (i32) b) {
+            const i32 s = members[m++];
+            while (cur < hgt[s]) { S.sub_lvl.push_back((i32) S.sub_sn.size() - K.front0); S.sub_lvl.push_back(0); ++cur; }
+            S.sub_sn.push_back(s);
+            if (width(s) >= lim.coop_w) ++S.sub_lvl.back();
+            T.max_r = std::max<i32>(T.max_r, (i32) order_r(s));
         }
-        // tasks: the largest subtrees get a workgroup each; once there are `bins` of them the rest joins the least
-        // loaded task that still has room
-        std::stable_sort(roots.begin(), roots.end(), [&](i32 a, i32 b) { return nf[a] > nf[b]; });
-        std::vector<Bin> bins;
-        for (i32 rt : roots) {
-            i64 best = -1;
-            if ((i64) bins.size() >= lim.bins)
-                for (size_t b = 0; b < bins.size(); ++b)
-                    if (bins[b].nf + nf[rt] <= lim.fronts && bins[b].ar + ar[rt] <= lim.arena &&
-                        (best < 0 || bins[b].nf < bins[(size_t) best].nf)) best = (i64) b;
-            if (best < 0) { bins.emplace_back(); best = (i64) bins.size() - 1; }
-            Bin &B = bins[(size_t) best];
-            B.nf += nf[rt]; B.ar += ar[rt]; B.roots.push_back(rt);
-        }
-        SubTier T;
-        T.task0 = (i32) S.sub_tasks.size(); T.ntasks = (i32) bins.size();
-        const i32 base_task = T.task0;
-        for (size_t b = 0; b < bins.size(); ++b)
-            for (i32 rt : bins[b].roots) task_of[rt] = base_task + (i32) b;
-        // members by task: (task, local level, id)
-        std::vector<i32> members;
-        for (i32 s = 0; s < ns; ++s) if (S.sn_tier[s] == tier) members.push_back(s);
-        std::stable_sort(members.begin(), members.end(), [&](i32 a, i32 b) {
-            const i32 ta = task_of[root_of[a]], tb = task_of[root_of[b]];
-            if (ta != tb) return ta < tb;
-            if (hgt[a] != hgt[b]) return hgt[a] < hgt[b];
-            // the shared (wide) fronts of a local level first, then the others, largest first: they start at once and the
-            // small ones fill the other waves
-            const bool ca = width(a) >= lim.coop_w, cb = width(b) >= lim.coop_w;
-            if (ca != cb) return ca;
-            return width(a) * order_r(a) > width(b) * order_r(b);
-        });
-        size_t m = 0;
-        for (size_t b = 0; b < bins.size(); ++b) {
-            SubTask K{};
-            K.front0 = (i32) S.sub_sn.size(); K.lvl0 = (i32) S.sub_lvl.size();
-            // per local level two entries: its first front (relative to front0) and how many of its leading fronts are shared
-            i32 cur = -1;
-            while (m < members.size() && task_of[root_of[members[m]]] == base_task + (i32) b) {
-                const i32 s = members[m++];
-                while (cur < hgt[s]) { S.sub_lvl.push_back((i32) S.sub_sn.size() - K.front0); S.sub_lvl.push_back(0); ++cur; }
-                S.sub_sn.push_back(s);
-                if (width(s) >= lim.coop_w) ++S.sub_lvl.back();
-                T.max_r = std::max<i32>(T.max_r, (i32) order_r(s));
-            }
-            K.nfronts = (i32) S.sub_sn.size() - K.front0;
-            K.nlevels = cur + 1;
-            S.sub_lvl.push_back(K.nfronts);
-            for (i32 l = 0; l < K.nlevels; ++l)                 // full levels: nobody shares
-                if (S.sub_lvl[K.lvl0 + 2 * l + 2] - S.sub_lvl[K.lvl0 + 2 * l] > lim.coop_level) S.sub_lvl[K.lvl0 + 2 * l + 1] = 0;
-            S.sub_tasks.push_back(K);
-            T.max_fronts = std::max(T.max_fronts, K.nfronts);
-            T.max_levels = std::max(T.max_levels, K.nlevels);
-        }
-        S.sub_tiers.push_back(T);
+        K.nfronts = (i32) S.sub_sn.size() - K.front0;
+        K.nlevels = cur + 1;
+        S.sub_lvl.push_back(K.nfronts);
+        for (i32 l = 0; l < K.nlevels; ++l)                 // full levels: nobody shares
+            if (S.sub_lvl[K.lvl0 + 2 * l + 2] - S.sub_lvl[K.lvl0 + 2 * l] > lim.coop_level) S.sub_lvl[K.lvl0 + 2 * l + 1] = 0;
+        S.sub_tasks.push_back(K);
+        T.max_fronts = std::max(T.max_fronts, K.nfronts);
+        T.max_levels = std::max(T.max_levels, K.nlevels);
     }
 }
 
@@ -264,61 +256,58 @@ static void fill_forest(Symbolic &S, const std::vector<i64> &fa_ptr, const std::
     S.sub_rel.clear(); S.sub_st.clear(); S.sub_child.clear(); S.sub_a_tgt.clear(); S.sub_a_src.clear();
     std::vector<i32> pos(S.nsuper, -1);
     for (size_t f = 0; f < nfr; ++f) pos[S.sub_sn[f]] = (i32) f;
-    for (SubTier &T : S.sub_tiers) {
-        for (i32 k = T.task0; k < T.task0 + T.ntasks; ++k) {
-            SubTask &K = S.sub_tasks[k];
-            K.rel0 = (i32) S.sub_rel.size(); K.child0 = (i32) S.sub_child.size() / 4;
-            i64 arena = 0, varena = 0;
-            for (i32 f = K.front0; f < K.front0 + K.nfronts; ++f) {
-                const i32 s = S.sub_sn[f];
-                SubFront &d = S.sub_fronts[f];
-                const i64 r = S.st_ptr[s + 1] - S.st_ptr[s], w = S.sn_ptr[s + 1] - S.sn_ptr[s], nb = r - w;
-                d.lpan = (i32) S.lpan_off[s]; d.upan = (i32) S.upan_off[s];
-                d.c0 = S.sn_ptr[s]; d.r = (i32) r; d.w = (i32) w;
-                d.cv = (i32) S.cv_off[s];
-                d.st = (i32) S.st_ptr[s];
-                d.u_sj = S.u_sj[s];
-                const i32 p = S.sn_parent[s];
-                const bool inside = p >= 0 && pos[p] >= K.front0 && pos[p] < K.front0 + K.nfronts;
-                d.parent = inside ? pos[p] : -1;
-                if (inside) { d.cb = (i32) ~arena; arena += nb * (nb + 1); }
-                else d.cb = (p >= 0) ? (i32) S.cb_off[s] : INT32_MIN;
-                d.arena = (i32) varena; varena += nb;
-                d.rel = (i32) S.sub_rel.size();
-                if (p >= 0)
-                    for (i64 i = 0; i < nb; ++i) {
-                        S.sub_rel.push_back(S.rel_idx[S.rel_ptr[s] + i]);
-                        S.sub_st.push_back(S.st_idx[S.st_ptr[s] + w + i]);
-                    }
-                // children: 4 ints each, filled in below (a child sits in front of its parent in the array, so its own
-                // descriptor is complete by now)
-                d.child_begin = (i32) S.sub_child.size() / 4;
-                for (i32 cp = S.child_ptr[s]; cp < S.child_ptr[s + 1]; ++cp) {
-                    const i32 c = S.child_idx[cp];
-                    if (pos[c] < 0 || pos[c] >= f) throw std::runtime_error("analyze: a forest front has a child outside the forest");
-                    const SubFront &cd = S.sub_fronts[pos[c]];
-                    const bool mine = pos[c] >= K.front0;
-                    const i32 nbc = cd.r - cd.w;
-                    S.sub_child.push_back(nbc | (mine ? 1 << 16 : 0));
-                    S.sub_child.push_back(mine ? cd.rel - K.rel0 : cd.rel);      // row map: in the task's staged slice / in sub_rel
-                    S.sub_child.push_back(mine ? ~cd.cb : cd.cb);                // block: arena offset / pool offset
-                    S.sub_child.push_back(mine ? cd.arena : cd.cv);              // vector: arena of the stand-alone sweep / cv pool
+    SubForest &T = S.sub_forest;
+    for (SubTask &K : S.sub_tasks) {
+        K.rel0 = (i32) S.sub_rel.size(); K.child0 = (i32) S.sub_child.size() / 4;
+        i64 arena = 0, varena = 0;
+        for (i32 f = K.front0; f < K.front0 + K.nfronts; ++f) {
+            const i32 s = S.sub_sn[f];
+            SubFront &d = S.sub_fronts[f];
+            const i64 r = S.st_ptr[s + 1] - S.st_ptr[s], w = S.sn_ptr[s + 1] - S.sn_ptr[s], nb = r - w;
+            d.lpan = (i32) S.lpan_off[s]; d.upan = (i32) S.upan_off[s];
+            d.c0 = S.sn_ptr[s]; d.r = (i32) r; d.w = (i32) w;
+            d.cv = (i32) S.cv_off[s];
+            d.st = (i32) S.st_ptr[s];
+            d.u_sj = S.u_sj[s];
+            // (a parent in the forest is in this task: the check of its children below makes sure)
+            const i32 p = S.sn_parent[s];
+            const bool inside = p >= 0 && pos[p] >= 0;
+            d.parent = inside ? pos[p] : -1;
+            if (inside) { d.cb = (i32) ~arena; arena += nb * (nb + 1); }
+            else d.cb = (p >= 0) ? (i32) S.cb_off[s] : INT32_MIN;
+            d.arena = (i32) varena; varena += nb;
+            d.rel = (i32) S.sub_rel.size();
+            if (p >= 0)
+                for (i64 i = 0; i < nb; ++i) {
+                    S.sub_rel.push_back(S.rel_idx[S.rel_ptr[s] + i]);
+                    S.sub_st.push_back(S.st_idx[S.st_ptr[s] + w + i]);
                 }
-                d.child_count = (i32) S.sub_child.size() / 4 - d.child_begin;
-                d.a_begin = (i32) S.sub_a_tgt.size();
-                // (target: row | column << 8 of the front; from_a holds row + column (r | 1))
-                for (i64 e = fa_ptr[s]; e < fa_ptr[s + 1]; ++e) {
-                    const Item &it = fa_item[e];
-                    const i32 ld = (i32) (r | 1);
-                    S.sub_a_tgt.push_back((it.tgt % ld) | ((it.tgt / ld) << 8));
-                    S.sub_a_src.push_back(~it.src);
-                }
-                d.a_count = (i32) S.sub_a_tgt.size() - d.a_begin;
+            // children: 4 ints each, all of it in the task's LDS (a child sits in front of its parent in the array, so its
+            // own descriptor is complete by now)
+            d.child_begin = (i32) S.sub_child.size() / 4;
+            for (i32 cp = S.child_ptr[s]; cp < S.child_ptr[s + 1]; ++cp) {
+                const i32 c = S.child_idx[cp];
+                if (pos[c] < K.front0 || pos[c] >= f) throw std::runtime_error("analyze: a forest front has a child outside its task");
+                const SubFront &cd = S.sub_fronts[pos[c]];
+                S.sub_child.push_back(cd.r - cd.w);
+                S.sub_child.push_back(cd.rel - K.rel0);
+                S.sub_child.push_back(~cd.cb);
+                S.sub_child.push_back(cd.arena);
             }
-            K.nrel = (i32) S.sub_rel.size() - K.rel0; K.nchild = (i32) S.sub_child.size() / 4 - K.child0;
-            T.max_rel = std::max(T.max_rel, K.nrel); T.max_child = std::max(T.max_child, K.nchild);
-            T.max_arena = std::max<i32>(T.max_arena, (i32) arena); T.max_varena = std::max<i32>(T.max_varena, (i32) varena);
+            d.child_count = (i32) S.sub_child.size() / 4 - d.child_begin;
+            d.a_begin = (i32) S.sub_a_tgt.size();
+            // (target: row | column << 8 of the front; from_a holds row + column (r | 1))
+            for (i64 e = fa_ptr[s]; e < fa_ptr[s + 1]; ++e) {
+                const Item &it = fa_item[e];
+                const i32 ld = (i32) (r | 1);
+                S.sub_a_tgt.push_back((it.tgt % ld) | ((it.tgt / ld) << 8));
+                S.sub_a_src.push_back(~it.src);
+            }
+            d.a_count = (i32) S.sub_a_tgt.size() - d.a_begin;
         }
+        K.nrel = (i32) S.sub_rel.size() - K.rel0; K.nchild = (i32) S.sub_child.size() / 4 - K.child0;
+        T.max_rel = std::max(T.max_rel, K.nrel); T.max_child = std::max(T.max_child, K.nchild);
+        T.max_arena = std::max<i32>(T.max_arena, (i32) arena); T.max_varena = std::max<i32>(T.max_varena, (i32) varena);
     }
 }
 
@@ -618,13 +607,13 @@ void analyze(int kind, int order, i64 n, const i32 *Ap, const i32 *Ai,
         static const bool sub_on = !(std::getenv("CS3_SUBTREE") && std::getenv("CS3_SUBTREE")[0] == '0');
         // (single matrices: batches of 16 .. 64 Cholesky matrices of 5000 columns measured 1.02 .. 2.1 ms through the forest
         //  against 0.77 .. 1.12 level by level)
-        S.sn_tier.assign(ns, -1);
+        S.sn_in_forest.assign(ns, 0);
         if (sub_on && S.batch == 1) build_forest(S, forest_limits());
     }
-    const i32 ntiers = (i32) S.sub_tiers.size();
-    auto in_forest = [&](i32 s) { return S.sn_tier[s] >= 0; };
-    // (a forest front whose parent sits in the same tier sits in the same task: its contribution block never leaves the LDS)
-    auto block_stays_in_lds = [&](i32 s) { const i32 p = S.sn_parent[s]; return in_forest(s) && p >= 0 && S.sn_tier[p] == S.sn_tier[s]; };
+    const bool has_forest = !S.sub_forest.empty();
+    auto in_forest = [&](i32 s) { return S.sn_in_forest[s] != 0; };
+    // (a forest front whose parent is in the forest sits in its parent's task: its contribution block never leaves the LDS)
+    auto block_stays_in_lds = [&](i32 s) { const i32 p = S.sn_parent[s]; return in_forest(s) && p >= 0 && in_forest(p); };
 
     tick("6b. forest");
     // ---- 7. size classes, pool layout, child -> parent relative indices
@@ -745,9 +734,9 @@ void analyze(int kind, int order, i64 n, const i32 *Ap, const i32 *Ai,
     }
     S.nlevels = 0;
     for (i32 s = 0; s < ns; ++s) S.nlevels = std::max(S.nlevels, S.sn_level[s] + 1);
-    // the factor schedule (and the sweeps of one right-hand side): tiers of the forest, then the levels above it
+    // the factor schedule (and the sweeps of one right-hand side): the forest, then the levels above it
     S.sn_tlevel.assign(ns, 0);
-    for (i32 s = 0; s < ns; ++s) S.sn_tlevel[s] = in_forest(s) ? S.sn_tier[s] : ntiers + lvl[s];
+    for (i32 s = 0; s < ns; ++s) S.sn_tlevel[s] = in_forest(s) ? 0 : (has_forest ? 1 : 0) + lvl[s];
 
     tick("8. levels");
     // ---- 9. assembly lists: every entry of a front is the sum of its sources
@@ -900,7 +889,7 @@ void analyze(int kind, int order, i64 n, const i32 *Ap, const i32 *Ai,
             S.ila_ptr[s + 1] = (i64) (S.ila_pairs.size() / 2);
         }
     }
-    if (ntiers > 0) fill_forest(S, fa_ptr, fa_item);
+    if (has_forest) fill_forest(S, fa_ptr, fa_item);
 
     tick("9. assembly lists");
     // ---- 10. launch groups by (level, size class)
@@ -921,7 +910,6 @@ void analyze(int kind, int order, i64 n, const i32 *Ap, const i32 *Ai,
             ++t;
         }
         g.count = t - g.first;
-        if (g.cls == FC_SUB) { g.first = g.level; g.count = S.sub_tiers[g.level].ntasks; }   // a tier: `first` names it, one workgroup per task
         S.groups.push_back(g);
     }
     tick("10. launch groups");
@@ -1048,10 +1036,10 @@ void analyze(int kind, int order, i64 n, const i32 *Ap, const i32 *Ai,
         S.sgroups.push_back(g);
     }
 
-    // one right-hand side with a forest: the sweeps follow the factor schedule -- one launch per tier (SK_SUB: `first`
-    // names the tier), then the levels above the forest
+    // one right-hand side with a forest: the sweeps follow the factor schedule -- one launch for the forest (SK_SUB),
+    // then the levels above it
     S.ssched1.clear(); S.sgroups1.clear();
-    if (ntiers > 0) {
+    if (has_forest) {
         auto kind1 = [&](i32 s) { return in_forest(s) ? (int) SK_SUB : solve_kind(s); };
         S.ssched1.resize(ns);
         std::iota(S.ssched1.begin(), S.ssched1.end(), 0);
@@ -1069,7 +1057,6 @@ void analyze(int kind, int order, i64 n, const i32 *Ap, const i32 *Ai,
                 ++t;
             }
             g.count = t - g.first;
-            if (g.cls == SK_SUB) { g.first = g.level; g.count = S.sub_tiers[g.level].ntasks; }
             S.sgroups1.push_back(g);
         }
     }
@@ -1081,8 +1068,9 @@ void analyze(int kind, int order, i64 n, const i32 *Ap, const i32 *Ai,
             fprintf(stderr, "solve  level %2d kind %d count %6d max_r %4d max_w %4d\n", g.level, g.cls, g.count, g.max_r, g.max_w);
         for (const LaunchGroup &g : S.sgroups1)
             fprintf(stderr, "solve1 level %2d kind %d count %6d max_r %4d max_w %4d\n", g.level, g.cls, g.count, g.max_r, g.max_w);
-        for (const SubTier &T : S.sub_tiers)
-            fprintf(stderr, "tier: %d tasks, max fronts %d levels %d rel %d child %d arena %d max_r %d\n", T.ntasks, T.max_fronts,
+        const SubForest &T = S.sub_forest;
+        if (!T.empty())
+            fprintf(stderr, "forest: %d tasks, max fronts %d levels %d rel %d child %d arena %d max_r %d\n", T.ntasks, T.max_fronts,
                     T.max_levels, T.max_rel, T.max_child, T.max_arena, T.max_r);
     }
 

@@ -1,6 +1,6 @@
 """The hand-overs between waves inside a kernel must fail loudly (ADVICE: kernels.hip:411).
 
-Waves that share an elimination (eliminate_pair / eliminate_parts in kernels.hip, the shared fronts of forest.hip) pass
+Waves that share an elimination (eliminate_pair in k_big_step of kernels.hip, the shared fronts of forest.hip) pass
 multipliers through LDS and poll a counter.  The poll is bounded; a wave that gives up used to carry on with whatever the
 buffer held and the step passed as a success.  Now it raises a status word and cs3_factor_status reports CS3_ERR_STATE.
 cs3_debug_withhold_handover(1) makes every producer keep its counter back, so every consumer gives up: the test of that
@@ -24,7 +24,7 @@ def _withhold(hip, on):
 @pytest.mark.parametrize("case", ["grid_lu", "grid_cholesky", "dense_root"])
 def test_a_withheld_hand_over_is_reported_not_swallowed(gpu, case):
     hip = gpu
-    if case == "grid_lu":                       # shared fronts of the forest + the two-wave eliminations of k_front_mix
+    if case == "grid_lu":                       # the shared fronts of the forest
         m, n, Ap, Ai, Ax = synth.grid_jacobian(4000, seed=7)
         kind = hip.CS3_LU
     elif case == "grid_cholesky":

@@ -117,6 +117,33 @@ def test_supernode_partition_is_consistent(hip):
         assert p == -1 or (p > s and sn_level[p] > sn_level[s])
 
 
+@pytest.mark.parametrize("name", ["grid50k", "config2", "denseblock"])
+def test_forest_tasks_hold_whole_subtrees(hip, name):
+    """The bottom forest is one launch: a task holds whole subtrees, so the parent of a forest front is either above the
+    forest or a front of the same task on a higher local level (its child's block never leaves the task's LDS)."""
+    m, n, Ap, Ai, Ax = CASES[name]
+    lib = hip.lib()
+    lib.cs3_debug_forest.argtypes = [C.c_void_p] + [C.POINTER(C.c_int32)] * 4
+    lib.cs3_debug_forest.restype = C.c_int64
+    with hip.Factorization(m, n, Ap, Ai) as F:
+        ns = int(F.info.nsuper)
+        sn, task, level, tier = (np.full(ns, -1, dtype=np.int32) for _ in range(4))
+        p = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+        nf = int(lib.cs3_debug_forest(F._h, p(sn), p(task), p(level), p(tier)))
+        parent = F.supernodes()[1]
+    assert 0 <= nf <= ns
+    if name == "grid50k":                       # config 3: the forest is what its step time rests on
+        assert nf > 0
+    sn, task, level, tier = sn[:nf], task[:nf], level[:nf], tier[:nf]
+    assert len(np.unique(sn)) == nf and np.all(tier == 0)
+    at = np.full(ns, -1)
+    at[sn] = np.arange(nf)
+    for f in range(nf):
+        q = parent[sn[f]]
+        if q >= 0 and at[q] >= 0:
+            assert task[at[q]] == task[f] and level[at[q]] > level[f], (f, sn[f], q)
+
+
 def test_given_order_and_natural_order(hip, orc):
     m, n, Ap, Ai, Ax = CASES["jacobian118"]
     q = np.random.default_rng(1).permutation(n).astype(np.int32)
