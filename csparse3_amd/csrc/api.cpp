@@ -2,13 +2,14 @@
 // residency, hipGraph capture of the level schedules, host <-> device copies.
 #include <hip/hip_runtime_api.h>
 
+#include <algorithm>
 #include <climits>
 #include <cstdlib>
 #include <cstring>
 #include <map>
-#include <utility>
 #include <stdexcept>
 #include <string>
+#include <tuple>
 
 #include "cs3_device.hpp"
 
@@ -31,6 +32,19 @@ void set_error(const std::string &msg) { g_error = msg; }
         }                                                                               \
     } while (0)
 
+// Captured graphs, one cache per handle, keyed by what a capture bakes in: (operation, trans, nrhs, the caller's X when
+// its address is inside the graph, else null).
+//   - GRAPH_FACTOR: one graph (trans false, nrhs 0), dropped when inv_tol changes.
+//   - GRAPH_SOLVE per (trans, nrhs): unbounded.  With fused permutations (X baked in) per (trans, nrhs, X): at most 8 per
+//     trans -- the 9th clears that class (callers that rotate buffers).
+//   - GRAPH_FUSED (factor + overlapped forward + backward) per nrhs: unbounded.  The same with the closing permutation
+//     inside the graph (no eager launch behind it: 5 us) per (nrhs, X): at most 4, and only from the third call in a row
+//     with the same X (fused_last_x / fused_same_x).  A change of inv_tol drops every fused-step graph.
+//   - ensure_rhs_capacity drops every solve and fused-step graph (the buffers they read move).
+// A graph that may still be running on another stream is destroyed only after a hipDeviceSynchronize.
+enum GraphOp { GRAPH_FACTOR, GRAPH_SOLVE, GRAPH_FUSED };
+using GraphKey = std::tuple<int, bool, int, const void *>;     // (GraphOp, trans, nrhs, X)
+
 struct cs3_handle_s {
     Symbolic S;
     DeviceFactor D;
@@ -39,20 +53,10 @@ struct cs3_handle_s {
     bool use_graph = true;
     hipStream_t cap_stream = nullptr;
     ForkJoin fj;
-    hipGraphExec_t factor_graph = nullptr;
-    double factor_graph_inv_tol = 0.0;
-    std::map<int, hipGraphExec_t> solve_graphs;   // keyed by nrhs
-    std::map<std::pair<int, const void *>, hipGraphExec_t> solve_graphs_px;   // fused permutations: keyed by (nrhs, caller's X)
-    // transposed solves (LU: A' X = B) keep graphs of their own, with the same keys and bounds
-    std::map<int, hipGraphExec_t> solve_graphs_t;
-    std::map<std::pair<int, const void *>, hipGraphExec_t> solve_graphs_px_t;
-    std::map<int, hipGraphExec_t> fused_graphs;   // factor + overlapped forward + backward, keyed by nrhs
-    // the same with the closing permutation inside the graph (no eager launch behind it: 5 us): X's address is baked in, so
-    // these are kept per (nrhs, X) and only for a caller that keeps handing in the same X
-    std::map<std::pair<int, const void *>, hipGraphExec_t> fused_graphs_px;
+    std::map<GraphKey, hipGraphExec_t> graphs;
+    double factor_inv_tol = 0.0, fused_inv_tol = 0.0;     // what the factor / fused-step graphs were captured with
     const void *fused_last_x = nullptr;
     int fused_same_x = 0;
-    double fused_inv_tol = 0.0;
     i64 *d_lmap = nullptr, *d_umap = nullptr;
     double *d_lx = nullptr, *d_ux = nullptr;
     long long fail_col = -1;
@@ -77,28 +81,29 @@ int upload(T **dst, const std::vector<T> &src)
     return CS3_OK;
 }
 
-void drop_solve_graphs(cs3_handle h)
+// Destroys the cached graphs whose key satisfies `drop`, after a device synchronisation when there are any (unless the
+// caller has just synchronised).
+template <class Pred>
+int drop_graphs(cs3_handle h, Pred drop, bool synced = false)
 {
-    for (auto &kv : h->solve_graphs) (void) hipGraphExecDestroy(kv.second);
-    h->solve_graphs.clear();
-    for (auto &kv : h->solve_graphs_px) (void) hipGraphExecDestroy(kv.second);
-    h->solve_graphs_px.clear();
-    for (auto &kv : h->solve_graphs_t) (void) hipGraphExecDestroy(kv.second);
-    h->solve_graphs_t.clear();
-    for (auto &kv : h->solve_graphs_px_t) (void) hipGraphExecDestroy(kv.second);
-    h->solve_graphs_px_t.clear();
-    for (auto &kv : h->fused_graphs) (void) hipGraphExecDestroy(kv.second);
-    h->fused_graphs.clear();
-    for (auto &kv : h->fused_graphs_px) (void) hipGraphExecDestroy(kv.second);
-    h->fused_graphs_px.clear();
+    bool any = false;
+    for (const auto &kv : h->graphs) any = any || drop(kv.first);
+    if (!any) return CS3_OK;
+    if (!synced) CS3_HIP(hipDeviceSynchronize());
+    for (auto it = h->graphs.begin(); it != h->graphs.end(); ) {
+        if (drop(it->first)) { (void) hipGraphExecDestroy(it->second); it = h->graphs.erase(it); }
+        else ++it;
+    }
+    return CS3_OK;
 }
+
+bool graph_op_is(const GraphKey &k, int op) { return std::get<0>(k) == op; }
 
 // Frees every HBM allocation of the handle (ensure_device's error path and cs3_free).
 void release_device(cs3_handle h)
 {
     DeviceFactor &D = h->D;
-    if (h->factor_graph) { (void) hipGraphExecDestroy(h->factor_graph); h->factor_graph = nullptr; }
-    drop_solve_graphs(h);
+    (void) drop_graphs(h, [](const GraphKey &) { return true; }, true);     // (cs3_free has synchronised)
     if (h->cap_stream) { (void) hipStreamDestroy(h->cap_stream); h->cap_stream = nullptr; }
     h->fj.destroy();
     void **ptrs[] = {(void **) &D.fdesc, (void **) &D.st_idx, (void **) &D.fa_tgt, (void **) &D.fa_src, (void **) &D.ch_tab, (void **) &D.rel_idx,
@@ -188,7 +193,6 @@ int ensure_device_impl(cs3_handle h)
     // the bottom forest and the sweep schedule of one right-hand side that goes with it
     D.sub_forest = S.sub_forest;
     D.n_sub_a = (long long) S.sub_a_tgt.size();
-    D.sd_active = nullptr; D.fwd_in_factor = false;
     if (!S.sub_forest.empty()) {
         std::vector<SolveDesc> sdesc1(S.nsuper);
         for (i32 t = 0; t < S.nsuper; ++t) sdesc1[t] = solve_desc_of(S, S.ssched1[t]);
@@ -254,7 +258,7 @@ int ensure_rhs_capacity(cs3_handle h, long long nrhs)
     DeviceFactor &D = h->D;
     if (nrhs <= D.nrhs_cap) return CS3_OK;
     CS3_HIP(hipDeviceSynchronize());
-    drop_solve_graphs(h);
+    if (int rc = drop_graphs(h, [](const GraphKey &k) { return !graph_op_is(k, GRAPH_FACTOR); }, true)) return rc;
     if (D.cv) (void) hipFree(D.cv);
     if (D.xp) (void) hipFree(D.xp);
     if (D.bigv) (void) hipFree(D.bigv);
@@ -285,39 +289,57 @@ int capture(cs3_handle h, hipGraphExec_t *exec, Body body)
     return CS3_OK;
 }
 
-// One right-hand side on a handle with a bottom forest: the sweeps follow the factor schedule (the forest, then the
-// levels above it) with their own descriptor array.  Sets what the launchers read; returns the launch groups to pass.
-// (The forest's sweeps have no transposed form: a transposed solve takes the level schedule whatever nrhs is.)
-const std::vector<LaunchGroup> &select_sweep_schedule(cs3_handle h, int nrhs, bool trans = false)
+// Replays the cached graph of `key` on st, capturing `body` (launches on the stream it is given) on cap_stream first when
+// the graph is missing; a bounded class that is full is cleared first.  CS3_NO_GRAPH=1: runs `body` on st.
+template <class Body>
+int replay_or_run(cs3_handle h, const GraphKey &key, hipStream_t st, Body body)
+{
+    if (!h->use_graph) { CS3_HIP(body(st)); return CS3_OK; }
+    auto it = h->graphs.find(key);
+    if (it == h->graphs.end()) {
+        // bounded classes (the cache's policy above): graphs with the caller's X, per operation and trans
+        const long bound = !std::get<3>(key) ? 0 : graph_op_is(key, GRAPH_SOLVE) ? 8 : 4;
+        auto same_class = [&](const GraphKey &k) {
+            return std::get<0>(k) == std::get<0>(key) && std::get<1>(k) == std::get<1>(key) && std::get<3>(k) != nullptr;
+        };
+        const long count = std::count_if(h->graphs.begin(), h->graphs.end(), [&](const auto &kv) { return same_class(kv.first); });
+        if (bound && count >= bound)
+            if (int rc = drop_graphs(h, same_class)) return rc;
+        hipGraphExec_t exec = nullptr;
+        if (int rc = capture(h, &exec, body)) return rc;
+        it = h->graphs.emplace(key, exec).first;
+    }
+    CS3_HIP(hipGraphLaunch(it->second, st));
+    return CS3_OK;
+}
+
+// The sweeps of one call: launch groups and their descriptors.  One right-hand side on a handle with a bottom forest
+// follows the factor schedule (the forest, then the levels above it) with descriptors of its own.  (The forest's sweeps
+// have no transposed form: a transposed solve takes the level schedule whatever nrhs is.)
+SweepCall select_sweep_schedule(cs3_handle h, int nrhs, bool trans = false)
 {
     const bool forest = nrhs == 1 && !trans && !h->S.sub_forest.empty();
-    h->D.sd_active = forest ? h->D.sdesc1 : nullptr;
-    return forest ? h->S.sgroups1 : h->S.sgroups;
+    SweepCall c;
+    c.groups = forest ? &h->S.sgroups1 : &h->S.sgroups;
+    c.sd = forest ? h->D.sdesc1 : h->D.sdesc;
+    c.trans = trans;
+    return c;
 }
 
 int run_factor(cs3_handle h, const double *ax_dev, double tol, hipStream_t st)
 {
-    DeviceFactor &D = h->D;
-    D.fwd_in_factor = false;
+    const DeviceFactor &D = h->D;
     const double inv_tol = (tol > 0.0) ? 1.0 / tol : HUGE_VAL;
     CS3_HIP(launch_prologue(D, ax_dev, nullptr, 0, st));        // status 0x7f7f7f7f = clean, zeros, values
-    if (h->use_graph) {
-        if (h->factor_graph && h->factor_graph_inv_tol != inv_tol) {
-            CS3_HIP(hipDeviceSynchronize());                    // (a launch of it on another stream may still be running)
-            (void) hipGraphExecDestroy(h->factor_graph);
-            h->factor_graph = nullptr;
-        }
-        if (!h->factor_graph) {
-            int rc = capture(h, &h->factor_graph, [&](hipStream_t cs) {
-                return launch_factor_levels(D, h->S.groups, inv_tol, cs, h->fj);
-            });
-            if (rc) return rc;
-            h->factor_graph_inv_tol = inv_tol;
-        }
-        CS3_HIP(hipGraphLaunch(h->factor_graph, st));
-    } else {
-        CS3_HIP(launch_factor_levels(D, h->S.groups, inv_tol, st, h->fj));
+    if (h->factor_inv_tol != inv_tol) {
+        if (int rc = drop_graphs(h, [](const GraphKey &k) { return graph_op_is(k, GRAPH_FACTOR); })) return rc;
+        h->factor_inv_tol = inv_tol;
     }
+    const SweepCall call;
+    int rc = replay_or_run(h, GraphKey(GRAPH_FACTOR, false, 0, nullptr), st, [&](hipStream_t s) {
+        return launch_factor_levels(D, call, h->S.groups, inv_tol, s, h->fj);
+    });
+    if (rc) return rc;
     h->factored = true;
     h->inverses_valid = false;
     return CS3_OK;
@@ -359,73 +381,29 @@ int run_solve(cs3_handle h, double *x_dev, long long k, int mode, hipStream_t st
     if (k < 1 || k > INT_MAX) { set_error("solve: bad number of right-hand sides"); return CS3_ERR_ARG; }
     int rc = ensure_rhs_capacity(h, k);
     if (rc) return rc;
-    DeviceFactor &D = h->D;
+    const DeviceFactor &D = h->D;
     const int nrhs = (int) k;
-    D.inverses_in_sweep = false;
-    D.fwd_in_factor = false;
     trans = trans && D.kind == CS3_LU;
-    const std::vector<LaunchGroup> &sg = select_sweep_schedule(h, nrhs, trans);
-    std::map<int, hipGraphExec_t> &graphs = trans ? h->solve_graphs_t : h->solve_graphs;
-    std::map<std::pair<int, const void *>, hipGraphExec_t> &graphs_px = trans ? h->solve_graphs_px_t : h->solve_graphs_px;
-    D.trans = trans;
-    struct TransReset { DeviceFactor &D; ~TransReset() { D.trans = false; } } trans_reset{D};
+    SweepCall call = select_sweep_schedule(h, nrhs, trans);
     if (nrhs >= 16 && D.n_inv_tasks > 0 && !h->inverses_valid) {      // many right-hand sides: GEMM sweeps need the inverted blocks
         CS3_HIP(launch_diag_inverses(D, st));
         h->inverses_valid = true;
     }
-    D.xm = XMap();
-    struct XmReset { DeviceFactor &D; ~XmReset() { D.xm = XMap(); } } xm_reset{D};    // (also on every error return below)
-    if (mode == 0 && permutation_can_fuse(D, nrhs)) {
-        // the permutations ride on the sweeps: the forward sweep reads row q[k] of the caller's X, the backward sweep
-        // writes the solution rows back there; X's address is baked into the graph, so graphs are kept per (nrhs, X)
-        D.xm.src = x_dev; D.xm.dst = x_dev; D.xm.q = D.q;
-        if (h->use_graph) {
-            const auto key = std::make_pair(nrhs, (const void *) x_dev);
-            auto it = graphs_px.find(key);
-            if (it == graphs_px.end()) {
-                if (graphs_px.size() >= 8) {                    // callers that rotate buffers: bounded cache
-                    CS3_HIP(hipDeviceSynchronize());            // (graphs launched earlier on OTHER streams may still be running)
-                    for (auto &kv : graphs_px) (void) hipGraphExecDestroy(kv.second);
-                    graphs_px.clear();
-                }
-                hipGraphExec_t exec = nullptr;
-                rc = capture(h, &exec, [&](hipStream_t cs) {
-                    hipError_t e = launch_solve_levels(D, sg, D.xp, nrhs, true, cs, h->fj);
-                    if (e != hipSuccess) return e;
-                    return launch_solve_levels(D, sg, D.xp, nrhs, false, cs, h->fj);
-                });
-                if (rc) { D.xm = XMap(); return rc; }
-                it = graphs_px.emplace(key, exec).first;
-            }
-            CS3_HIP(hipGraphLaunch(it->second, st));
-        } else {
-            CS3_HIP(launch_solve_levels(D, sg, D.xp, nrhs, true, st, h->fj));
-            CS3_HIP(launch_solve_levels(D, sg, D.xp, nrhs, false, st, h->fj));
-        }
-        D.xm = XMap();
-    } else if (mode == 0) {
-        CS3_HIP(launch_permute(D, x_dev, D.xp, nrhs, false, st));
-        if (h->use_graph) {
-            auto it = graphs.find(nrhs);
-            if (it == graphs.end()) {
-                hipGraphExec_t exec = nullptr;
-                rc = capture(h, &exec, [&](hipStream_t cs) {
-                    hipError_t e = launch_solve_levels(D, sg, D.xp, nrhs, true, cs, h->fj);
-                    if (e != hipSuccess) return e;
-                    return launch_solve_levels(D, sg, D.xp, nrhs, false, cs, h->fj);
-                });
-                if (rc) return rc;
-                it = graphs.emplace(nrhs, exec).first;
-            }
-            CS3_HIP(hipGraphLaunch(it->second, st));
-        } else {
-            CS3_HIP(launch_solve_levels(D, sg, D.xp, nrhs, true, st, h->fj));
-            CS3_HIP(launch_solve_levels(D, sg, D.xp, nrhs, false, st, h->fj));
-        }
-        CS3_HIP(launch_permute(D, D.xp, x_dev, nrhs, true, st));
-    } else {
-        CS3_HIP(launch_solve_levels(D, sg, x_dev, nrhs, mode == 1, st, h->fj));
+    if (mode != 0) {
+        CS3_HIP(launch_solve_levels(D, call, x_dev, nrhs, mode == 1, st, h->fj));
+        return CS3_OK;
     }
+    // fused permutations: the forward sweep reads row q[k] of the caller's X, the backward sweep writes the solution rows
+    // back there; X's address is baked into the graph
+    const bool fused = permutation_can_fuse(D, nrhs);
+    if (fused) call.xm = XMap{x_dev, x_dev, D.q};
+    else CS3_HIP(launch_permute(D, x_dev, D.xp, nrhs, false, st));
+    rc = replay_or_run(h, GraphKey(GRAPH_SOLVE, trans, nrhs, fused ? x_dev : nullptr), st, [&](hipStream_t s) {
+        hipError_t e = launch_solve_levels(D, call, D.xp, nrhs, true, s, h->fj);
+        return (e != hipSuccess) ? e : launch_solve_levels(D, call, D.xp, nrhs, false, s, h->fj);
+    });
+    if (rc) return rc;
+    if (!fused) CS3_HIP(launch_permute(D, D.xp, x_dev, nrhs, true, st));
     return CS3_OK;
 }
 
@@ -435,72 +413,30 @@ int run_factor_solve(cs3_handle h, const double *ax_dev, const double *b_dev, do
     if (k < 1 || k > INT_MAX) { set_error("factor_solve: bad number of right-hand sides"); return CS3_ERR_ARG; }
     int rc = ensure_rhs_capacity(h, k);
     if (rc) return rc;
-    DeviceFactor &D = h->D;
+    const DeviceFactor &D = h->D;
     const int nrhs = (int) k;
     const double inv_tol = (tol > 0.0) ? 1.0 / tol : HUGE_VAL;
-    D.xm = XMap();                                              // (never a caller's pointer left over from a failed solve)
-    const std::vector<LaunchGroup> &sg = select_sweep_schedule(h, nrhs);
-    D.fwd_in_factor = nrhs == 1 && !h->S.sub_forest.empty();  // the forest's factor launch carries its forward sweep
-    D.inverses_in_sweep = true;                                // captured with the graph: the forward sweep inverts group by group
-    CS3_HIP(launch_prologue(D, ax_dev, b_dev, nrhs, st));      // right-hand sides are read from b_dev, the solution goes to x_dev
-    if (h->use_graph) {
-        if (h->fused_inv_tol != inv_tol) {
-            if (!h->fused_graphs.empty() || !h->fused_graphs_px.empty()) CS3_HIP(hipDeviceSynchronize());   // they may still be running
-            for (auto &kv : h->fused_graphs) (void) hipGraphExecDestroy(kv.second);
-            h->fused_graphs.clear();
-            for (auto &kv : h->fused_graphs_px) (void) hipGraphExecDestroy(kv.second);
-            h->fused_graphs_px.clear();
-            h->fused_inv_tol = inv_tol;
-        }
-        h->fused_same_x = (x_dev == h->fused_last_x) ? h->fused_same_x + 1 : 0;
-        h->fused_last_x = x_dev;
-        if (h->fused_same_x >= 2) {                            // third call in a row with this X: its own graph, permutation included
-            const auto key = std::make_pair(nrhs, (const void *) x_dev);
-            auto px = h->fused_graphs_px.find(key);
-            if (px == h->fused_graphs_px.end()) {
-                if (h->fused_graphs_px.size() >= 4) {
-                    CS3_HIP(hipDeviceSynchronize());            // (see solve_graphs_px)
-                    for (auto &kv : h->fused_graphs_px) (void) hipGraphExecDestroy(kv.second);
-                    h->fused_graphs_px.clear();
-                }
-                hipGraphExec_t exec = nullptr;
-                rc = capture(h, &exec, [&](hipStream_t cs) {
-                    hipError_t e = launch_factor_with_forward(D, h->S.groups, sg, inv_tol, D.xp, nrhs, cs, h->fj);
-                    if (e != hipSuccess) return e;
-                    if ((e = launch_solve_levels(D, sg, D.xp, nrhs, false, cs, h->fj)) != hipSuccess) return e;
-                    return launch_permute(D, D.xp, x_dev, nrhs, true, cs);
-                });
-                if (rc) return rc;
-                px = h->fused_graphs_px.emplace(key, exec).first;
-            }
-            CS3_HIP(hipGraphLaunch(px->second, st));
-            D.inverses_in_sweep = false;
-    D.fwd_in_factor = false;
-            h->factored = true;
-            h->inverses_valid = nrhs >= 16;
-            return CS3_OK;
-        }
-        auto it = h->fused_graphs.find(nrhs);
-        if (it == h->fused_graphs.end()) {
-            hipGraphExec_t exec = nullptr;
-            rc = capture(h, &exec, [&](hipStream_t cs) {
-                hipError_t e = launch_factor_with_forward(D, h->S.groups, sg, inv_tol, D.xp, nrhs, cs, h->fj);
-                if (e != hipSuccess) return e;
-                return launch_solve_levels(D, sg, D.xp, nrhs, false, cs, h->fj);
-            });
-            if (rc) return rc;
-            it = h->fused_graphs.emplace(nrhs, exec).first;
-        }
-        CS3_HIP(hipGraphLaunch(it->second, st));
-    } else {
-        CS3_HIP(launch_factor_with_forward(D, h->S.groups, sg, inv_tol, D.xp, nrhs, st, h->fj));
-        CS3_HIP(launch_solve_levels(D, sg, D.xp, nrhs, false, st, h->fj));
+    SweepCall call = select_sweep_schedule(h, nrhs);
+    call.fwd_in_factor = nrhs == 1 && !h->S.sub_forest.empty();   // the forest's factor launch carries its forward sweep
+    call.inverses_in_sweep = true;                                 // the forward sweep inverts group by group
+    CS3_HIP(launch_prologue(D, ax_dev, b_dev, nrhs, st));          // right-hand sides are read from b_dev, the solution goes to x_dev
+    if (h->fused_inv_tol != inv_tol) {
+        if ((rc = drop_graphs(h, [](const GraphKey &g) { return graph_op_is(g, GRAPH_FUSED); }))) return rc;
+        h->fused_inv_tol = inv_tol;
     }
-    CS3_HIP(launch_permute(D, D.xp, x_dev, nrhs, true, st));
-    D.inverses_in_sweep = false;
-    D.fwd_in_factor = false;
+    h->fused_same_x = (x_dev == h->fused_last_x) ? h->fused_same_x + 1 : 0;
+    h->fused_last_x = x_dev;
+    const bool per_x = h->fused_same_x >= 2;                       // third call in a row with this X: its own graph, permutation included
+    rc = replay_or_run(h, GraphKey(GRAPH_FUSED, false, nrhs, per_x ? x_dev : nullptr), st, [&](hipStream_t s) {
+        hipError_t e = launch_factor_with_forward(D, call, h->S.groups, inv_tol, D.xp, nrhs, s, h->fj);
+        if (e == hipSuccess) e = launch_solve_levels(D, call, D.xp, nrhs, false, s, h->fj);
+        if (e == hipSuccess && per_x) e = launch_permute(D, D.xp, x_dev, nrhs, true, s);
+        return e;
+    });
+    if (rc) return rc;
+    if (!per_x) CS3_HIP(launch_permute(D, D.xp, x_dev, nrhs, true, st));
     h->factored = true;
-    h->inverses_valid = nrhs >= 16;                            // a many-RHS fused call leaves them current
+    h->inverses_valid = nrhs >= 16;                                // a many-RHS fused call leaves them current
     return CS3_OK;
 }
 
@@ -1097,41 +1033,37 @@ static int ensure_col_view(cs3_handle h, long long k)
     return CS3_OK;
 }
 
-int cs3_residual_dev(cs3_handle h, const double *Ax_dev, const double *B_dev, const double *X_dev, double *R_dev, int64_t k, void *stream)
+// R = B - A X (B null: Y = A X) on resident data; trans: with A', through the column view.  The products of a row are
+// summed in csc_mat_vec_ff's order (bit-exact with cs3_csc_matvec).
+static int product(const char *who, cs3_handle h, const double *Ax_dev, const double *B_dev, bool with_b, const double *X_dev,
+                   double *R_dev, int64_t k, void *stream, bool trans)
 {
     int rc = guard(h); if (rc) return rc;
-    if (!Ax_dev || !B_dev || !X_dev || !R_dev || k < 1 || k > INT_MAX) { set_error("cs3_residual_dev: bad argument"); return CS3_ERR_ARG; }
-    if ((rc = ensure_row_view(h, 0))) return rc;
-    CS3_HIP(launch_residual(h->d_rp, h->d_rj, h->d_rmap, Ax_dev, X_dev, B_dev, R_dev, h->S.n, (int) k, h->S.nnzA, h->batch, (hipStream_t) stream));
+    if (!Ax_dev || (with_b && !B_dev) || !X_dev || !R_dev || k < 1 || k > INT_MAX) { set_error(std::string(who) + ": bad argument"); return CS3_ERR_ARG; }
+    if ((rc = trans ? ensure_col_view(h, 0) : ensure_row_view(h, 0))) return rc;
+    const int *vp = trans ? h->d_cp : h->d_rp, *vj = trans ? h->d_ci : h->d_rj, *vmap = trans ? h->d_cmap : h->d_rmap;
+    CS3_HIP(launch_residual(vp, vj, vmap, Ax_dev, X_dev, B_dev, R_dev, h->S.n, (int) k, h->S.nnzA, h->batch, (hipStream_t) stream));
     return CS3_OK;
 }
 
-// Y = A X on resident data, the products of a row summed in csc_mat_vec_ff's order (bit-exact with cs3_csc_matvec)
+int cs3_residual_dev(cs3_handle h, const double *Ax_dev, const double *B_dev, const double *X_dev, double *R_dev, int64_t k, void *stream)
+{
+    return product("cs3_residual_dev", h, Ax_dev, B_dev, true, X_dev, R_dev, k, stream, false);
+}
+
 int cs3_matvec_dev(cs3_handle h, const double *Ax_dev, const double *X_dev, double *Y_dev, int64_t k, void *stream)
 {
-    int rc = guard(h); if (rc) return rc;
-    if (!Ax_dev || !X_dev || !Y_dev || k < 1 || k > INT_MAX) { set_error("cs3_matvec_dev: bad argument"); return CS3_ERR_ARG; }
-    if ((rc = ensure_row_view(h, 0))) return rc;
-    CS3_HIP(launch_residual(h->d_rp, h->d_rj, h->d_rmap, Ax_dev, X_dev, nullptr, Y_dev, h->S.n, (int) k, h->S.nnzA, h->batch, (hipStream_t) stream));
-    return CS3_OK;
+    return product("cs3_matvec_dev", h, Ax_dev, nullptr, false, X_dev, Y_dev, k, stream, false);
 }
 
 int cs3_residual_t_dev(cs3_handle h, const double *Ax_dev, const double *B_dev, const double *X_dev, double *R_dev, int64_t k, void *stream)
 {
-    int rc = guard(h); if (rc) return rc;
-    if (!Ax_dev || !B_dev || !X_dev || !R_dev || k < 1 || k > INT_MAX) { set_error("cs3_residual_t_dev: bad argument"); return CS3_ERR_ARG; }
-    if ((rc = ensure_col_view(h, 0))) return rc;
-    CS3_HIP(launch_residual(h->d_cp, h->d_ci, h->d_cmap, Ax_dev, X_dev, B_dev, R_dev, h->S.n, (int) k, h->S.nnzA, h->batch, (hipStream_t) stream));
-    return CS3_OK;
+    return product("cs3_residual_t_dev", h, Ax_dev, B_dev, true, X_dev, R_dev, k, stream, true);
 }
 
 int cs3_matvec_t_dev(cs3_handle h, const double *Ax_dev, const double *X_dev, double *Y_dev, int64_t k, void *stream)
 {
-    int rc = guard(h); if (rc) return rc;
-    if (!Ax_dev || !X_dev || !Y_dev || k < 1 || k > INT_MAX) { set_error("cs3_matvec_t_dev: bad argument"); return CS3_ERR_ARG; }
-    if ((rc = ensure_col_view(h, 0))) return rc;
-    CS3_HIP(launch_residual(h->d_cp, h->d_ci, h->d_cmap, Ax_dev, X_dev, nullptr, Y_dev, h->S.n, (int) k, h->S.nnzA, h->batch, (hipStream_t) stream));
-    return CS3_OK;
+    return product("cs3_matvec_t_dev", h, Ax_dev, nullptr, false, X_dev, Y_dev, k, stream, true);
 }
 
 static int refine(cs3_handle h, const double *Ax_dev, const double *B_dev, double *X_dev, int64_t k, int64_t steps,

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime_api.h>
 
+#include <type_traits>
 #include <vector>
 
 #include "cs3_internal.hpp"
@@ -60,11 +61,7 @@ struct DeviceFactor {
     int *st_idx = nullptr;        // row structures (backward sweep: rows of the ancestors)
     int *fa_tgt = nullptr, *fa_src = nullptr, *ch_tab = nullptr, *rel_idx = nullptr;   // assembly: entries of A, children tables, row maps
     SolveDesc *sdesc = nullptr;
-    // one right-hand side with a bottom forest: descriptors in the order of Symbolic::ssched1; sd_active is what the sweep
-    // launchers hand to the kernels (set by the caller together with the launch groups it passes: sdesc or sdesc1)
-    SolveDesc *sdesc1 = nullptr;
-    const SolveDesc *sd_active = nullptr;
-    const SolveDesc *sd() const { return sd_active ? sd_active : sdesc; }
+    SolveDesc *sdesc1 = nullptr;  // one right-hand side with a bottom forest: descriptors in the order of Symbolic::ssched1
     // bottom forest (cs3_internal.hpp): tasks, their fronts and lists; axf = the values of A in the order of sub_a_tgt
     SubForest sub_forest;
     SubTask *sub_tasks = nullptr;
@@ -72,7 +69,6 @@ struct DeviceFactor {
     int *sub_lvl = nullptr, *sub_rel = nullptr, *sub_st = nullptr, *sub_child = nullptr, *sub_a_tgt = nullptr, *sub_a_src = nullptr;
     double *axf = nullptr;        // [batch][n_sub_a]
     long long n_sub_a = 0;
-    bool fwd_in_factor = false;   // the forest's factor launch carries the forward sweep of its fronts (fused factor + solve, one right-hand side)
     int *fasm_src = nullptr, *fasm_tgt = nullptr, *flong_src = nullptr;
     int *rl_pairs = nullptr, *sl_src = nullptr;
     int *q = nullptr;             // [n] pivot order
@@ -96,13 +92,28 @@ struct DeviceFactor {
     int *inv_tasks = nullptr;     // (position in the solve schedule, chunk) pairs
     int n_inv_tasks = 0;
     std::vector<int> inv_tasks_host;
-    bool inverses_in_sweep = false;   // the forward sweep computes them group by group (fused factor + solve graph)
-    XMap xm;                          // what the sweeps captured / launched next should use (set by the caller)
-    bool trans = false;               // LU: the sweeps launched next solve with U' (forward) and L' (backward) (set by the caller)
     long long nrhs_cap = 0;
     int *status = nullptr;        // [0] first failing pivot column, 0x7f7f7f7f when clean; [3]: a hand-over between waves timed out
     long long *tbuf = nullptr;    // diagnostics (CS3_PROFILE=1): 8 shader-clock stamps per front, schedule order
 };
+
+// What one solve, factorisation or fused step needs beyond the handle's resident state: built per call by api.cpp and
+// passed down to every launcher (nothing of it is left on the DeviceFactor).
+struct SweepCall {
+    const std::vector<LaunchGroup> *groups = nullptr;   // the sweeps' launch groups (Symbolic::sgroups, or sgroups1 for one
+    const SolveDesc *sd = nullptr;                      //   right-hand side on a forest handle) and their descriptors (sdesc / sdesc1)
+    XMap xm;                      // fused permutations: the sweeps read and write the caller's X through q
+    bool trans = false;           // LU: the forward sweep solves with U', the backward sweep with L'
+    bool inverses_in_sweep = false;   // the forward sweep inverts the diagonal blocks group by group (fused factor + solve)
+    bool fwd_in_factor = false;   // the forest's factor launch carries the forward sweep of its fronts (fused, one right-hand side)
+};
+
+// f(std::integral_constant<int, KIND>{}) for the handle's kind: the factorisation instances (never CS3_LU_T).
+template <class F>
+auto with_kind(int kind, F &&f)
+{
+    return (kind == CS3_LU) ? f(std::integral_constant<int, CS3_LU>{}) : f(std::integral_constant<int, CS3_CHOLESKY>{});
+}
 
 // What the assembly of a front reads, as a kernel argument (by value).
 struct AsmLists {
@@ -136,22 +147,22 @@ hipError_t launch_poison_lds(hipStream_t st);     // diagnostics: NaN patterns i
 hipError_t launch_diag_inverses(const DeviceFactor &D, hipStream_t st);
 bool permutation_can_fuse(const DeviceFactor &D, int nrhs);   // once after a factorisation, before a many-RHS sweep
 bool big_group_in_one_workgroup(int kind, long long batch, const LaunchGroup &g);
-hipError_t launch_factor_levels(const DeviceFactor &D, const std::vector<LaunchGroup> &groups,
+hipError_t launch_factor_levels(const DeviceFactor &D, const SweepCall &call, const std::vector<LaunchGroup> &groups,
                                 double inv_tol, hipStream_t st, ForkJoin &fj);
-hipError_t launch_solve_levels(const DeviceFactor &D, const std::vector<LaunchGroup> &groups,
-                               double *X, int nrhs, bool forward, hipStream_t st, ForkJoin &fj);
+// sweeps over call.groups
+hipError_t launch_solve_levels(const DeviceFactor &D, const SweepCall &call, double *X, int nrhs, bool forward, hipStream_t st,
+                               ForkJoin &fj);
 // Factorisation with the forward sweep partly hidden behind it: the sweep of the finished levels
 // runs on fj.aux beside the factorisation of the tail of the tree (one fork, one join).
-hipError_t launch_factor_with_forward(const DeviceFactor &D, const std::vector<LaunchGroup> &fgroups,
-                                      const std::vector<LaunchGroup> &sgroups, double inv_tol, double *X, int nrhs,
-                                      hipStream_t st, ForkJoin &fj);
+hipError_t launch_factor_with_forward(const DeviceFactor &D, const SweepCall &call, const std::vector<LaunchGroup> &fgroups,
+                                      double inv_tol, double *X, int nrhs, hipStream_t st, ForkJoin &fj);
 // status word, big-front zeros, copy of the caller's values and (x_src != null) the permuted right-hand sides, one launch
 hipError_t launch_prologue(const DeviceFactor &D, const double *ax_src, const double *x_src, int nrhs, hipStream_t st);
 // forest.hip: the bottom forest = one launch, one workgroup per task
 hipError_t prepare_forest_kernels();
 hipError_t set_withhold_handover(int on);          // diagnostics: producers of the LDS hand-overs keep their counters back
 hipError_t set_withhold_handover_forest(int on);   //   (the copy of the flag in forest.hip)
-hipError_t launch_sub_factor(const DeviceFactor &D, bool with_forward, double inv_tol, hipStream_t st);
+hipError_t launch_sub_factor(const DeviceFactor &D, const SweepCall &call, double inv_tol, hipStream_t st);
 hipError_t launch_sub_sweep(const DeviceFactor &D, double *X, bool forward, hipStream_t st);
 hipError_t launch_permute(const DeviceFactor &D, const double *src, double *dst, int nrhs, bool scatter,
                           hipStream_t st);

@@ -877,23 +877,20 @@ hipError_t prepare_forest_kernels()
     return hipSuccess;
 }
 
-hipError_t launch_sub_factor(const DeviceFactor &D, bool with_forward, double inv_tol, hipStream_t st)
+hipError_t launch_sub_factor(const DeviceFactor &D, const SweepCall &call, double inv_tol, hipStream_t st)
 {
     const SubForest &T = D.sub_forest;
     size_t bytes = 0;
     const SubLds lay = sub_lds_layout(T, T.max_arena, std::max((T.max_r + 1) * (T.max_r | 1) + 1, COOP_IMG), &bytes);
     if (bytes > 160 * 1024) return hipErrorInvalidValue;           // (the analysis caps keep a task far below this)
     const dim3 grid((unsigned) T.ntasks, (unsigned) D.batch), block(SUB_NT);
+    with_kind(D.kind, [&](auto K) {
 #define CS3_SUB_ARGS D.sub_tasks, D.sub_fronts, D.sub_lvl, D.sub_rel, D.sub_child, D.sub_a_tgt, D.axf, D.n_sub_a, D.pool_pm, \
                      D.pm_stride, D.xp, D.cv, D.n, D.cv_size, inv_tol, D.status, lay, D.tbuf
-    if (D.kind == CS3_LU) {
-        if (with_forward) hipLaunchKernelGGL((k_sub_factor<CS3_LU, true>), grid, block, bytes, st, CS3_SUB_ARGS);
-        else hipLaunchKernelGGL((k_sub_factor<CS3_LU, false>), grid, block, bytes, st, CS3_SUB_ARGS);
-    } else {
-        if (with_forward) hipLaunchKernelGGL((k_sub_factor<CS3_CHOLESKY, true>), grid, block, bytes, st, CS3_SUB_ARGS);
-        else hipLaunchKernelGGL((k_sub_factor<CS3_CHOLESKY, false>), grid, block, bytes, st, CS3_SUB_ARGS);
-    }
+        if (call.fwd_in_factor) hipLaunchKernelGGL((k_sub_factor<K, true>), grid, block, bytes, st, CS3_SUB_ARGS);
+        else hipLaunchKernelGGL((k_sub_factor<K, false>), grid, block, bytes, st, CS3_SUB_ARGS);
 #undef CS3_SUB_ARGS
+    });
     CS3_LAUNCH_CHECK();
     return hipSuccess;
 }
@@ -905,21 +902,14 @@ hipError_t launch_sub_sweep(const DeviceFactor &D, double *X, bool forward, hipS
     const SubLds lay = sub_lds_layout(T, forward ? T.max_varena : 0, forward ? T.max_r + 2 : 0, &bytes);
     if (bytes > 160 * 1024) return hipErrorInvalidValue;
     const dim3 grid((unsigned) T.ntasks, (unsigned) D.batch), block(SUB_NT);
-    if (forward) {
-        if (D.kind == CS3_LU)
-            hipLaunchKernelGGL((k_sub_fwd<CS3_LU>), grid, block, bytes, st, D.sub_tasks, D.sub_fronts, D.sub_lvl, D.sub_rel,
+    with_kind(D.kind, [&](auto K) {
+        if (forward)
+            hipLaunchKernelGGL((k_sub_fwd<K>), grid, block, bytes, st, D.sub_tasks, D.sub_fronts, D.sub_lvl, D.sub_rel,
                                D.sub_child, D.pool_pm, D.pm_stride, X, D.cv, D.n, D.cv_size, lay);
         else
-            hipLaunchKernelGGL((k_sub_fwd<CS3_CHOLESKY>), grid, block, bytes, st, D.sub_tasks, D.sub_fronts, D.sub_lvl, D.sub_rel,
-                               D.sub_child, D.pool_pm, D.pm_stride, X, D.cv, D.n, D.cv_size, lay);
-    } else {
-        if (D.kind == CS3_LU)
-            hipLaunchKernelGGL((k_sub_bwd<CS3_LU>), grid, block, bytes, st, D.sub_tasks, D.sub_fronts, D.sub_lvl, D.sub_st,
+            hipLaunchKernelGGL((k_sub_bwd<K>), grid, block, bytes, st, D.sub_tasks, D.sub_fronts, D.sub_lvl, D.sub_st,
                                D.sub_child, D.pool_pm, D.pm_stride, X, D.n, lay);
-        else
-            hipLaunchKernelGGL((k_sub_bwd<CS3_CHOLESKY>), grid, block, bytes, st, D.sub_tasks, D.sub_fronts, D.sub_lvl, D.sub_st,
-                               D.sub_child, D.pool_pm, D.pm_stride, X, D.n, lay);
-    }
+    });
     CS3_LAUNCH_CHECK();
     return hipSuccess;
 }

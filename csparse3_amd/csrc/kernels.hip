@@ -3683,10 +3683,10 @@ bool big_group_in_one_workgroup(int kind, long long batch, const LaunchGroup &g)
 }
 
 template <int KIND>
-static hipError_t launch_front_group(const DeviceFactor &D, const LaunchGroup &g, double inv_tol, hipStream_t st)
+static hipError_t launch_front_group(const DeviceFactor &D, const SweepCall &call, const LaunchGroup &g, double inv_tol, hipStream_t st)
 {
     const unsigned batch = (unsigned) D.batch;
-    if (g.cls == FC_SUB) return launch_sub_factor(D, D.fwd_in_factor, inv_tol, st);     // the bottom forest
+    if (g.cls == FC_SUB) return launch_sub_factor(D, call, inv_tol, st);     // the bottom forest
     if (big_group_in_one_workgroup(KIND, D.batch, g)) {
         hipLaunchKernelGGL((k_front_wg<KIND, WG_NB>), dim3((unsigned) g.count, batch), dim3(512), wg_lds_bytes(KIND, g), st, D.fdesc,
                            g.first, AsmLists{D.fa_tgt, D.fa_src, D.ch_tab, D.rel_idx}, D.ax, D.pool_pm, D.nnz_a, D.pm_stride,
@@ -3823,6 +3823,23 @@ hipError_t ForkJoin::event(hipEvent_t *out)
     return hipSuccess;
 }
 
+// The groups of one level: forward, the end of the run that starts at g; backward, the start of the run that ends at g.
+static size_t level_edge(const std::vector<LaunchGroup> &groups, size_t g, bool forward)
+{
+    const int level = groups[forward ? g : g - 1].level;
+    if (forward) while (g < groups.size() && groups[g].level == level) ++g;
+    else while (g > 0 && groups[g - 1].level == level) --g;
+    return g;
+}
+
+// with_kind for the sweeps: a transposed solve on an LU handle takes the CS3_LU_T instances.
+template <class F>
+static auto with_sweep_kind(int kind, bool trans, F &&f)
+{
+    if (kind == CS3_LU && trans) return f(std::integral_constant<int, CS3_LU_T>{});
+    return with_kind(kind, f);
+}
+
 // Run the launch groups of one tree level concurrently: the first on `st`, the others on side
 // streams that fork from `st` and join it again.  `launch(group, stream)` enqueues one group.
 template <class Launch>
@@ -3858,17 +3875,15 @@ static hipError_t run_level(const std::vector<LaunchGroup> &groups, size_t g0, s
 
 static std::vector<LaunchGroup> factor_groups(const DeviceFactor &D, const std::vector<LaunchGroup> &groups);
 
-hipError_t launch_factor_levels(const DeviceFactor &D, const std::vector<LaunchGroup> &all_groups,
+hipError_t launch_factor_levels(const DeviceFactor &D, const SweepCall &call, const std::vector<LaunchGroup> &all_groups,
                                 double inv_tol, hipStream_t st, ForkJoin &fj)
 {
     const std::vector<LaunchGroup> groups = factor_groups(D, all_groups);
     fj.rewind();                         // (the big-front buffers were zeroed by launch_prologue)
     for (size_t g0 = 0; g0 < groups.size(); ) {
-        size_t g1 = g0;
-        while (g1 < groups.size() && groups[g1].level == groups[g0].level) ++g1;
+        const size_t g1 = level_edge(groups, g0, true);
         hipError_t e = run_level(groups, g0, g1, st, fj, true, [&](const LaunchGroup &g, hipStream_t s) {
-            return (D.kind == CS3_LU) ? launch_front_group<CS3_LU>(D, g, inv_tol, s)
-                                      : launch_front_group<CS3_CHOLESKY>(D, g, inv_tol, s);
+            return with_kind(D.kind, [&](auto K) { return launch_front_group<K>(D, call, g, inv_tol, s); });
         });
         if (e != hipSuccess) return e;
         g0 = g1;
@@ -3896,57 +3911,59 @@ static BigSweepPlan big_sweep_plan(const DeviceFactor &D, const LaunchGroup &g, 
     return pl;
 }
 
-static hipError_t launch_fwd_big_pre(const DeviceFactor &D, const LaunchGroup &g, double *X, int nrhs, hipStream_t st)
+static hipError_t launch_fwd_big_pre(const DeviceFactor &D, const SweepCall &call, const LaunchGroup &g, double *X, int nrhs, hipStream_t st)
 {
     const BigSweepPlan pl = big_sweep_plan(D, g, nrhs);
-    hipLaunchKernelGGL(k_fwd_big_gather, dim3(1, pl.by, g.count), dim3(256), 0, st, D.sd(), g.first, D.fasm_src,
+    hipLaunchKernelGGL(k_fwd_big_gather, dim3(1, pl.by, g.count), dim3(256), 0, st, call.sd, g.first, D.fasm_src,
                        D.fasm_tgt, D.flong_src, D.cv, X, D.bigv, nrhs, D.cv_size * (long long) nrhs, D.n * (long long) nrhs, D.bv_size);
     CS3_LAUNCH_CHECK();
     return hipSuccess;
 }
 
 template <int KIND>
-static hipError_t launch_fwd_big_chunk(const DeviceFactor &D, const LaunchGroup &g, double *X, int nrhs, int c, hipStream_t st)
+static hipError_t launch_fwd_big_chunk(const DeviceFactor &D, const SweepCall &call, const LaunchGroup &g, double *X, int nrhs, int c,
+                                       hipStream_t st)
 {
     const BigSweepPlan pl = big_sweep_plan(D, g, nrhs);
     const long long xs = D.n * (long long) nrhs, cvs = D.cv_size * (long long) nrhs;
     if (pl.wide)
-        hipLaunchKernelGGL((k_fwd_big_step<KIND, BIG_CW>), dim3(pl.slices, pl.by, g.count), dim3(256), 0, st, D.sd(),
+        hipLaunchKernelGGL((k_fwd_big_step<KIND, BIG_CW>), dim3(pl.slices, pl.by, g.count), dim3(256), 0, st, call.sd,
                            g.first, c * pl.cw, D.pool_pm, D.cv, X, D.bigv, nrhs, D.pm_stride, cvs, xs, D.bv_size);
     else if (pl.multi)
-        hipLaunchKernelGGL((k_fwd_big_step_multi<KIND>), dim3(pl.slices, pl.by_multi, g.count), dim3(256), 0, st, D.sd(),
+        hipLaunchKernelGGL((k_fwd_big_step_multi<KIND>), dim3(pl.slices, pl.by_multi, g.count), dim3(256), 0, st, call.sd,
                            g.first, c * pl.cw, D.pool_pm, D.cv, X, D.bigv, nrhs, D.pm_stride, cvs, xs, D.bv_size);
     else
-        hipLaunchKernelGGL((k_fwd_big_step<KIND, SOLVE_BW>), dim3(pl.slices, pl.by, g.count), dim3(256), 0, st, D.sd(),
+        hipLaunchKernelGGL((k_fwd_big_step<KIND, SOLVE_BW>), dim3(pl.slices, pl.by, g.count), dim3(256), 0, st, call.sd,
                            g.first, c * pl.cw, D.pool_pm, D.cv, X, D.bigv, nrhs, D.pm_stride, cvs, xs, D.bv_size);
     CS3_LAUNCH_CHECK();
     return hipSuccess;
 }
 
 template <int KIND>
-static hipError_t launch_bwd_big_pre(const DeviceFactor &D, const LaunchGroup &g, double *X, int nrhs, hipStream_t st)
+static hipError_t launch_bwd_big_pre(const DeviceFactor &D, const SweepCall &call, const LaunchGroup &g, double *X, int nrhs, hipStream_t st)
 {
     const BigSweepPlan pl = big_sweep_plan(D, g, nrhs);
     const size_t lds = (size_t) std::max(1, g.max_r) * sizeof(double);
-    hipLaunchKernelGGL((k_bwd_big_init<KIND>), dim3(2, pl.by, g.count), dim3(256), lds, st, D.sd(), g.first,
+    hipLaunchKernelGGL((k_bwd_big_init<KIND>), dim3(2, pl.by, g.count), dim3(256), lds, st, call.sd, g.first,
                        D.st_idx, D.pool_pm, X, D.bigv, nrhs, D.pm_stride, D.n * (long long) nrhs, D.bv_size);
     CS3_LAUNCH_CHECK();
     return hipSuccess;
 }
 
 template <int KIND>
-static hipError_t launch_bwd_big_chunk(const DeviceFactor &D, const LaunchGroup &g, double *X, int nrhs, int c, hipStream_t st)
+static hipError_t launch_bwd_big_chunk(const DeviceFactor &D, const SweepCall &call, const LaunchGroup &g, double *X, int nrhs, int c,
+                                       hipStream_t st)
 {
     const BigSweepPlan pl = big_sweep_plan(D, g, nrhs);
     const long long xs = D.n * (long long) nrhs;
     if (pl.wide)
-        hipLaunchKernelGGL((k_bwd_big_step<KIND, BIG_CW>), dim3(pl.slices, pl.by, g.count), dim3(256), 0, st, D.sd(),
+        hipLaunchKernelGGL((k_bwd_big_step<KIND, BIG_CW>), dim3(pl.slices, pl.by, g.count), dim3(256), 0, st, call.sd,
                            g.first, c, D.pool_pm, X, D.bigv, nrhs, D.pm_stride, xs, D.bv_size);
     else if (pl.multi)
-        hipLaunchKernelGGL((k_bwd_big_step_multi<KIND>), dim3(pl.slices, pl.by_multi, g.count), dim3(256), 0, st, D.sd(),
+        hipLaunchKernelGGL((k_bwd_big_step_multi<KIND>), dim3(pl.slices, pl.by_multi, g.count), dim3(256), 0, st, call.sd,
                            g.first, c, D.pool_pm, X, D.bigv, nrhs, D.pm_stride, xs, D.bv_size);
     else
-        hipLaunchKernelGGL((k_bwd_big_step<KIND, SOLVE_BW>), dim3(pl.slices, pl.by, g.count), dim3(256), 0, st, D.sd(),
+        hipLaunchKernelGGL((k_bwd_big_step<KIND, SOLVE_BW>), dim3(pl.slices, pl.by, g.count), dim3(256), 0, st, call.sd,
                            g.first, c, D.pool_pm, X, D.bigv, nrhs, D.pm_stride, xs, D.bv_size);
     CS3_LAUNCH_CHECK();
     return hipSuccess;
@@ -3965,28 +3982,35 @@ static hipError_t launch_inv_tasks(const DeviceFactor &D, int t0, int t1, hipStr
     return hipSuccess;
 }
 
+// CS3_NO_GEMM_SWEEPS=1: many right-hand sides sweep the fronts of order > 64 with the substitution kernels
+static bool gemm_sweeps_on()
+{
+    static const bool on = !(getenv("CS3_NO_GEMM_SWEEPS") && getenv("CS3_NO_GEMM_SWEEPS")[0] == '1');
+    return on;
+}
+
 // The permutations can ride on the sweeps when every pivot row of X is read (forward) and written (backward) by a kernel
 // that knows the row map: the lane = right-hand-side kernels and the GEMM sweeps, i.e. 16 or more right-hand sides, no
 // interleaved batch, GEMM sweeps on.
 bool permutation_can_fuse(const DeviceFactor &D, int nrhs)
 {
-    static const bool on = !(getenv("CS3_NO_GEMM_SWEEPS") && getenv("CS3_NO_GEMM_SWEEPS")[0] == '1');
     // (measured on config 4: the extra row-map round trip per front costs more than the two permutation kernels below a
     // few hundred right-hand sides; at 1024 the fused form saves 0.14 ms of 2.3)
     constexpr int min_rhs = 256;
-    return on && nrhs >= std::max(min_rhs, RHS_LANES_MIN) && D.il_len == 0;
+    return gemm_sweeps_on() && nrhs >= std::max(min_rhs, RHS_LANES_MIN) && D.il_len == 0;
 }
 
 hipError_t launch_diag_inverses(const DeviceFactor &D, hipStream_t st)
 {
-    return (D.kind == CS3_LU) ? launch_inv_tasks<CS3_LU>(D, 0, D.n_inv_tasks, st) : launch_inv_tasks<CS3_CHOLESKY>(D, 0, D.n_inv_tasks, st);
+    return with_kind(D.kind, [&](auto K) { return launch_inv_tasks<K>(D, 0, D.n_inv_tasks, st); });
 }
 
-// with_inverse: compute this group's inverted diagonal blocks first (the fused factor + solve graph, where they cannot
-// be prepared ahead of the factorisation); otherwise the caller has run launch_diag_inverses since the last factorisation.
+// call.inverses_in_sweep: the forward sweep computes this group's inverted diagonal blocks first (the fused factor + solve
+// graph, where they cannot be prepared ahead of the factorisation); otherwise the caller has run launch_diag_inverses
+// since the last factorisation.
 template <int KIND>
-static hipError_t launch_gemm_group(const DeviceFactor &D, const LaunchGroup &g, double *X, int nrhs, bool forward, bool with_inverse,
-                                    hipStream_t st)
+static hipError_t launch_gemm_group(const DeviceFactor &D, const SweepCall &call, const LaunchGroup &g, double *X, int nrhs,
+                                    bool forward, hipStream_t st)
 {
     const long long xs = D.n * (long long) nrhs, cvs = D.cv_size * (long long) nrhs, gvs = D.gv_size * (long long) nrhs;
     const unsigned batch = (unsigned) D.batch, tiles = (unsigned) ((nrhs + GC - 1) / GC);
@@ -3999,28 +4023,28 @@ static hipError_t launch_gemm_group(const DeviceFactor &D, const LaunchGroup &g,
         t1 = t0;
         while (t1 < nt && T[2 * t1] < g.first + g.count) ++t1;
     }
-    if (with_inverse) {
+    if (forward && call.inverses_in_sweep) {
         hipError_t ie = launch_inv_tasks<(KIND == CS3_LU_T) ? CS3_LU : KIND>(D, t0, t1, st);
         if (ie != hipSuccess) return ie;
     }
     const int nchunk = (g.max_w + GC - 1) / GC;
     const unsigned slices = (unsigned) std::max(1, (g.max_r + GC - 1) / GC);
     if (forward) {
-        hipLaunchKernelGGL(k_gemm_gather, dim3((unsigned) ((g.max_r + 15) / 16), tiles, g.count * batch), dim3(256), 0, st, D.sd(),
-                           g.first, D.sl_src, D.cv, X, D.gv, nrhs, cvs, xs, gvs, D.xm, (int) batch);
+        hipLaunchKernelGGL(k_gemm_gather, dim3((unsigned) ((g.max_r + 15) / 16), tiles, g.count * batch), dim3(256), 0, st, call.sd,
+                           g.first, D.sl_src, D.cv, X, D.gv, nrhs, cvs, xs, gvs, call.xm, (int) batch);
         CS3_LAUNCH_CHECK();
         for (int c = 0; c < nchunk; ++c) {
-            hipLaunchKernelGGL((k_gemm_fwd<KIND>), dim3(slices, tiles, g.count * batch), dim3(512), GEMM_LDS, st, D.sd(), g.first, c,
+            hipLaunchKernelGGL((k_gemm_fwd<KIND>), dim3(slices, tiles, g.count * batch), dim3(512), GEMM_LDS, st, call.sd, g.first, c,
                                D.pool_pm, D.dinv, D.cv, X, D.gv, nrhs, D.pm_stride, D.dinv_size, cvs, xs, gvs, (int) batch);
             CS3_LAUNCH_CHECK();
         }
     } else {
-        hipLaunchKernelGGL((k_gemm_bwd_init<KIND>), dim3((unsigned) nchunk, tiles, g.count * batch), dim3(512), GEMM_LDS, st, D.sd(),
+        hipLaunchKernelGGL((k_gemm_bwd_init<KIND>), dim3((unsigned) nchunk, tiles, g.count * batch), dim3(512), GEMM_LDS, st, call.sd,
                            g.first, D.st_idx, D.pool_pm, X, D.gv, nrhs, D.pm_stride, xs, gvs, (int) batch);
         CS3_LAUNCH_CHECK();
         for (int c = 0; c < nchunk; ++c) {
             hipLaunchKernelGGL((k_gemm_bwd<KIND>), dim3((unsigned) std::max(1, nchunk), tiles, g.count * batch), dim3(512), GEMM_LDS, st,
-                               D.sd(), g.first, c, D.pool_pm, D.dinv, X, D.gv, nrhs, D.pm_stride, D.dinv_size, xs, gvs, (int) batch, D.xm);
+                               call.sd, g.first, c, D.pool_pm, D.dinv, X, D.gv, nrhs, D.pm_stride, D.dinv_size, xs, gvs, (int) batch, call.xm);
             CS3_LAUNCH_CHECK();
         }
     }
@@ -4028,30 +4052,29 @@ static hipError_t launch_gemm_group(const DeviceFactor &D, const LaunchGroup &g,
 }
 
 template <int KIND, int RMAX>
-static void launch_rhs_sweep(const DeviceFactor &D, int first, int count, double *X, int nrhs, bool forward, hipStream_t st)
+static void launch_rhs_sweep(const DeviceFactor &D, const SweepCall &call, int first, int count, double *X, int nrhs, bool forward, hipStream_t st)
 {
     if (count <= 0) return;
     const long long xs = D.n * (long long) nrhs, cvs = D.cv_size * (long long) nrhs;
     dim3 grid((unsigned) count, (unsigned) D.batch, (unsigned) ((nrhs + 63) / 64));
     if (forward)
-        hipLaunchKernelGGL((k_fwd_rhs<KIND, RMAX>), grid, dim3(64), 0, st, D.sd(), first, D.sl_src, D.pool_pm, D.cv, X,
-                           nrhs, D.pm_stride, cvs, xs, D.xm);
+        hipLaunchKernelGGL((k_fwd_rhs<KIND, RMAX>), grid, dim3(64), 0, st, call.sd, first, D.sl_src, D.pool_pm, D.cv, X,
+                           nrhs, D.pm_stride, cvs, xs, call.xm);
     else
-        hipLaunchKernelGGL((k_bwd_rhs<KIND, RMAX>), grid, dim3(64), 0, st, D.sd(), first, D.st_idx, D.pool_pm, X,
-                           nrhs, D.pm_stride, xs, D.xm);
+        hipLaunchKernelGGL((k_bwd_rhs<KIND, RMAX>), grid, dim3(64), 0, st, call.sd, first, D.st_idx, D.pool_pm, X,
+                           nrhs, D.pm_stride, xs, call.xm);
 }
 
 template <int KIND>
-static hipError_t launch_solve_group(const DeviceFactor &D, const LaunchGroup &g, double *X, int nrhs,
+static hipError_t launch_solve_group(const DeviceFactor &D, const SweepCall &call, const LaunchGroup &g, double *X, int nrhs,
                                      bool forward, hipStream_t st)
 {
     const long long xs = D.n * (long long) nrhs;
     const long long cvs = D.cv_size * (long long) nrhs;
     // (the bottom forest's sweeps have no transposed form: transposed solves take the level schedule)
     if (g.cls == SK_SUB) return (nrhs == 1 && KIND != CS3_LU_T) ? launch_sub_sweep(D, X, forward, st) : hipErrorInvalidValue;
-    static const bool use_gemm = !(getenv("CS3_NO_GEMM_SWEEPS") && getenv("CS3_NO_GEMM_SWEEPS")[0] == '1');
-    if (use_gemm && nrhs >= RHS_LANES_MIN && (g.cls == SK_WAVE || g.cls == SK_BLOCK || g.cls == SK_BIG))
-        return launch_gemm_group<KIND>(D, g, X, nrhs, forward, forward && D.inverses_in_sweep, st);
+    if (gemm_sweeps_on() && nrhs >= RHS_LANES_MIN && (g.cls == SK_WAVE || g.cls == SK_BLOCK || g.cls == SK_BIG))
+        return launch_gemm_group<KIND>(D, call, g, X, nrhs, forward, st);
     if (g.cls == SK_IL) {
         // the fronts of order <= 16 come first in the group: half the LDS per wave (the front vector of 64 matrices),
         // twice the waves per CU -- these sweeps wait on one round trip per pivot
@@ -4059,62 +4082,62 @@ static hipError_t launch_solve_group(const DeviceFactor &D, const LaunchGroup &g
         if (n16 > 0) {
             dim3 grid((unsigned) n16, (unsigned) D.ngroups);
             if (forward)
-                hipLaunchKernelGGL((k_fwd_il<KIND, 16>), grid, dim3(64), 0, st, D.sd(), g.first, D.rl_pairs,
+                hipLaunchKernelGGL((k_fwd_il<KIND, 16>), grid, dim3(64), 0, st, call.sd, g.first, D.rl_pairs,
                                    IlView{D.pool_il, D.il_len}, D.cv, X, nrhs, cvs, xs, (int) D.batch);
             else
-                hipLaunchKernelGGL((k_bwd_il<KIND, 16>), grid, dim3(64), 0, st, D.sd(), g.first, D.st_idx,
+                hipLaunchKernelGGL((k_bwd_il<KIND, 16>), grid, dim3(64), 0, st, call.sd, g.first, D.st_idx,
                                    IlView{D.pool_il, D.il_len}, X, nrhs, xs, (int) D.batch);
         }
         if (g.count > n16) {
             dim3 grid((unsigned) (g.count - n16), (unsigned) D.ngroups);
             if (forward)
-                hipLaunchKernelGGL((k_fwd_il<KIND, IL_RMAX>), grid, dim3(64), 0, st, D.sd(), g.first + n16, D.rl_pairs,
+                hipLaunchKernelGGL((k_fwd_il<KIND, IL_RMAX>), grid, dim3(64), 0, st, call.sd, g.first + n16, D.rl_pairs,
                                    IlView{D.pool_il, D.il_len}, D.cv, X, nrhs, cvs, xs, (int) D.batch);
             else
-                hipLaunchKernelGGL((k_bwd_il<KIND, IL_RMAX>), grid, dim3(64), 0, st, D.sd(), g.first + n16, D.st_idx,
+                hipLaunchKernelGGL((k_bwd_il<KIND, IL_RMAX>), grid, dim3(64), 0, st, call.sd, g.first + n16, D.st_idx,
                                    IlView{D.pool_il, D.il_len}, X, nrhs, xs, (int) D.batch);
         }
     } else if (g.cls == SK_SMALL && nrhs >= RHS_LANES_MIN) {
         // one instance by the group's largest order (fronts of order <= 32 only: the analysis sends the others to the GEMM
         // sweeps; a separate launch for the fronts of order <= 16 of a group paid while the assembly went through LDS and
         // stopped paying with the slot rounds: 256 right-hand sides 1.01 ms split, 0.945 not)
-        if (g.max_r <= 16) launch_rhs_sweep<KIND, 16>(D, g.first, g.count, X, nrhs, forward, st);
-        else if (g.max_r <= 24) launch_rhs_sweep<KIND, 24>(D, g.first, g.count, X, nrhs, forward, st);
-        else if (g.max_r <= 32) launch_rhs_sweep<KIND, 32>(D, g.first, g.count, X, nrhs, forward, st);
+        if (g.max_r <= 16) launch_rhs_sweep<KIND, 16>(D, call, g.first, g.count, X, nrhs, forward, st);
+        else if (g.max_r <= 24) launch_rhs_sweep<KIND, 24>(D, call, g.first, g.count, X, nrhs, forward, st);
+        else if (g.max_r <= 32) launch_rhs_sweep<KIND, 32>(D, call, g.first, g.count, X, nrhs, forward, st);
         else return hipErrorInvalidValue;
     } else if (g.cls == SK_SMALL || g.cls == SK_WAVE) {
         if (nrhs == 1) {
             dim3 grid((unsigned) ((g.count + 3) / 4), (unsigned) D.batch, 1);
             if (forward)
-                hipLaunchKernelGGL((k_fwd_wave<KIND, 1>), grid, dim3(256), 0, st, D.sd(), g.first, g.count, D.fasm_src,
+                hipLaunchKernelGGL((k_fwd_wave<KIND, 1>), grid, dim3(256), 0, st, call.sd, g.first, g.count, D.fasm_src,
                                    D.fasm_tgt, D.flong_src, D.pool_pm, D.cv, X, nrhs, D.pm_stride, cvs, xs);
             else
-                hipLaunchKernelGGL((k_bwd_wave<KIND, 1>), grid, dim3(256), 0, st, D.sd(), g.first, g.count, D.st_idx,
+                hipLaunchKernelGGL((k_bwd_wave<KIND, 1>), grid, dim3(256), 0, st, call.sd, g.first, g.count, D.st_idx,
                                    D.pool_pm, X, nrhs, D.pm_stride, xs);
         } else {
             constexpr int KT = 8;                   // right-hand sides per wave: the panel is read once per tile
             dim3 grid((unsigned) ((g.count + 3) / 4), (unsigned) D.batch, (unsigned) ((nrhs + KT - 1) / KT));
             if (forward)
-                hipLaunchKernelGGL((k_fwd_wave<KIND, KT>), grid, dim3(256), 0, st, D.sd(), g.first, g.count, D.fasm_src,
+                hipLaunchKernelGGL((k_fwd_wave<KIND, KT>), grid, dim3(256), 0, st, call.sd, g.first, g.count, D.fasm_src,
                                    D.fasm_tgt, D.flong_src, D.pool_pm, D.cv, X, nrhs, D.pm_stride, cvs, xs);
             else
-                hipLaunchKernelGGL((k_bwd_wave<KIND, KT>), grid, dim3(256), 0, st, D.sd(), g.first, g.count, D.st_idx,
+                hipLaunchKernelGGL((k_bwd_wave<KIND, KT>), grid, dim3(256), 0, st, call.sd, g.first, g.count, D.st_idx,
                                    D.pool_pm, X, nrhs, D.pm_stride, xs);
         }
     } else if (g.cls == SK_BIG) {
         const BigSweepPlan pl = big_sweep_plan(D, g, nrhs);
-        hipError_t e = forward ? launch_fwd_big_pre(D, g, X, nrhs, st) : launch_bwd_big_pre<KIND>(D, g, X, nrhs, st);
+        hipError_t e = forward ? launch_fwd_big_pre(D, call, g, X, nrhs, st) : launch_bwd_big_pre<KIND>(D, call, g, X, nrhs, st);
         for (int c = 0; e == hipSuccess && c < pl.nchunk; ++c)
-            e = forward ? launch_fwd_big_chunk<KIND>(D, g, X, nrhs, c, st) : launch_bwd_big_chunk<KIND>(D, g, X, nrhs, c, st);
+            e = forward ? launch_fwd_big_chunk<KIND>(D, call, g, X, nrhs, c, st) : launch_bwd_big_chunk<KIND>(D, call, g, X, nrhs, c, st);
         return e;
     } else {
         dim3 grid((unsigned) g.count, (unsigned) D.batch, (unsigned) nrhs);
         const size_t lds = (size_t) (g.max_r + 1 + SOLVE_BW) * sizeof(double);
         if (forward)
-            hipLaunchKernelGGL((k_fwd_blk<KIND>), grid, dim3(256), lds, st, D.sd(), g.first, D.fasm_src,
+            hipLaunchKernelGGL((k_fwd_blk<KIND>), grid, dim3(256), lds, st, call.sd, g.first, D.fasm_src,
                                D.fasm_tgt, D.flong_src, D.pool_pm, D.cv, X, nrhs, D.pm_stride, cvs, xs);
         else
-            hipLaunchKernelGGL((k_bwd_blk<KIND>), grid, dim3(256), lds, st, D.sd(), g.first, D.st_idx,
+            hipLaunchKernelGGL((k_bwd_blk<KIND>), grid, dim3(256), lds, st, call.sd, g.first, D.st_idx,
                                D.pool_pm, X, nrhs, D.pm_stride, xs);
     }
     CS3_LAUNCH_CHECK();
@@ -4172,10 +4195,9 @@ static std::vector<LaunchGroup> factor_groups(const DeviceFactor &D, const std::
     return out;
 }
 
-hipError_t launch_solve_levels(const DeviceFactor &D, const std::vector<LaunchGroup> &all_groups,
-                               double *X, int nrhs, bool forward, hipStream_t st, ForkJoin &fj)
+hipError_t launch_solve_levels(const DeviceFactor &D, const SweepCall &call, double *X, int nrhs, bool forward, hipStream_t st, ForkJoin &fj)
 {
-    const std::vector<LaunchGroup> groups = sweep_groups(all_groups, nrhs, D.batch);
+    const std::vector<LaunchGroup> groups = sweep_groups(*call.groups, nrhs, D.batch);
     fj.rewind();
     // one right-hand side: the per-level launches are short, fork/join costs more than it hides (measured), so they stay
     // in line.  Many right-hand sides: the lane = right-hand-side group and the GEMM group of a level take 10-40 us each
@@ -4184,22 +4206,18 @@ hipError_t launch_solve_levels(const DeviceFactor &D, const std::vector<LaunchGr
     //  -- 128: 0.82 ms forked, 0.77 in line; 256: equal; 1024: equal to 0.5 %)
     const bool solve_parallel = nrhs >= 512;
     auto launch = [&](const LaunchGroup &g, hipStream_t s) {
-        if (D.kind == CS3_LU && D.trans) return launch_solve_group<CS3_LU_T>(D, g, X, nrhs, forward, s);
-        return (D.kind == CS3_LU) ? launch_solve_group<CS3_LU>(D, g, X, nrhs, forward, s)
-                                  : launch_solve_group<CS3_CHOLESKY>(D, g, X, nrhs, forward, s);
+        return with_sweep_kind(D.kind, call.trans, [&](auto K) { return launch_solve_group<K>(D, call, g, X, nrhs, forward, s); });
     };
     if (forward) {
         for (size_t g0 = 0; g0 < groups.size(); ) {
-            size_t g1 = g0;
-            while (g1 < groups.size() && groups[g1].level == groups[g0].level) ++g1;
+            const size_t g1 = level_edge(groups, g0, true);
             hipError_t e = run_level(groups, g0, g1, st, fj, solve_parallel, launch);
             if (e != hipSuccess) return e;
             g0 = g1;
         }
     } else {
         for (size_t g1 = groups.size(); g1 > 0; ) {
-            size_t g0 = g1;
-            while (g0 > 0 && groups[g0 - 1].level == groups[g1 - 1].level) --g0;
+            const size_t g0 = level_edge(groups, g1, false);
             hipError_t e = run_level(groups, g0, g1, st, fj, solve_parallel, launch);
             if (e != hipSuccess) return e;
             g1 = g0;
@@ -4223,26 +4241,25 @@ static int sweep_group_cost(const LaunchGroup &g)
 // factorisation of levels K+1.. (the tail of the tree: few, large fronts, many dependent launches).
 // K is the last level whose tail is still long enough to cover the sweep; one fork, one join -- a
 // fork per level costs more than it hides (measured).  Same kernels, same operands: same bits.
-hipError_t launch_factor_with_forward(const DeviceFactor &D, const std::vector<LaunchGroup> &all_fgroups,
-                                      const std::vector<LaunchGroup> &all_sgroups, double inv_tol, double *X, int nrhs,
-                                      hipStream_t st, ForkJoin &fj)
+hipError_t launch_factor_with_forward(const DeviceFactor &D, const SweepCall &call, const std::vector<LaunchGroup> &all_fgroups,
+                                      double inv_tol, double *X, int nrhs, hipStream_t st, ForkJoin &fj)
 {
     hipError_t e;
-    if (!D.sub_forest.empty() && !D.sd_active) {
+    if (!D.sub_forest.empty() && call.sd != D.sdesc1) {
         // a bottom forest under the factorisation, but sweeps on the level schedule of the whole tree (several right-hand
         // sides): the two number their levels differently, so nothing is overlapped
-        if ((e = launch_factor_levels(D, all_fgroups, inv_tol, st, fj)) != hipSuccess) return e;
-        return launch_solve_levels(D, all_sgroups, X, nrhs, true, st, fj);
+        if ((e = launch_factor_levels(D, call, all_fgroups, inv_tol, st, fj)) != hipSuccess) return e;
+        return launch_solve_levels(D, call, X, nrhs, true, st, fj);
     }
     const std::vector<LaunchGroup> fgroups = factor_groups(D, all_fgroups);
-    const std::vector<LaunchGroup> sgroups = sweep_groups(all_sgroups, nrhs, D.batch);
+    const std::vector<LaunchGroup> sgroups = sweep_groups(*call.groups, nrhs, D.batch);
     fj.rewind();
     const int nlevels = fgroups.empty() ? 0 : fgroups.back().level + 1;
     std::vector<long long> tail(nlevels + 1, 0), head(nlevels + 1, 0);   // factor cost of levels >= l; sweep cost of levels < l
     for (const LaunchGroup &g : fgroups) tail[g.level] += factor_group_cost(g);
     for (int l = nlevels - 1; l >= 0; --l) tail[l] += tail[l + 1];
     // (the bottom forest, when its factor launch carries the forward sweep, has nothing left to sweep)
-    for (const LaunchGroup &g : sgroups) head[g.level + 1] += (g.cls == SK_SUB && D.fwd_in_factor) ? 0 : sweep_group_cost(g);
+    for (const LaunchGroup &g : sgroups) head[g.level + 1] += (g.cls == SK_SUB && call.fwd_in_factor) ? 0 : sweep_group_cost(g);
     for (int l = 0; l < nlevels; ++l) head[l + 1] += head[l];
     int fork_level = -1;
     static const bool overlap = !(getenv("CS3_NO_OVERLAP") && getenv("CS3_NO_OVERLAP")[0] == '1');
@@ -4252,9 +4269,9 @@ hipError_t launch_factor_with_forward(const DeviceFactor &D, const std::vector<L
     auto sweep = [&](int lo, int hi, hipStream_t s) -> hipError_t {      // forward sweep of levels lo..hi
         for (const LaunchGroup &g : sgroups) {
             if (g.level < lo || g.level > hi) continue;
-            if (g.cls == SK_SUB && D.fwd_in_factor) continue;
-            hipError_t se = (D.kind == CS3_LU) ? launch_solve_group<CS3_LU>(D, g, X, nrhs, true, s)
-                                               : launch_solve_group<CS3_CHOLESKY>(D, g, X, nrhs, true, s);
+            if (g.cls == SK_SUB && call.fwd_in_factor) continue;
+            hipError_t se = with_sweep_kind(D.kind, call.trans,
+                                            [&](auto K) { return launch_solve_group<K>(D, call, g, X, nrhs, true, s); });
             if (se != hipSuccess) return se;
         }
         return hipSuccess;
@@ -4277,11 +4294,9 @@ hipError_t launch_factor_with_forward(const DeviceFactor &D, const std::vector<L
         };
         for (size_t f0 = 0; f0 < fgroups.size(); ) {
             const int level = fgroups[f0].level;
-            size_t f1 = f0;
-            while (f1 < fgroups.size() && fgroups[f1].level == level) ++f1;
+            const size_t f1 = level_edge(fgroups, f0, true);
             e = run_level(fgroups, f0, f1, st, fj, true, [&](const LaunchGroup &g, hipStream_t s2) {
-                return (D.kind == CS3_LU) ? launch_front_group<CS3_LU>(D, g, inv_tol, s2)
-                                          : launch_front_group<CS3_CHOLESKY>(D, g, inv_tol, s2);
+                return with_kind(D.kind, [&](auto K) { return launch_front_group<K>(D, call, g, inv_tol, s2); });
             });
             if (e != hipSuccess) return e;
             if ((e = flush()) != hipSuccess) return e;
@@ -4318,8 +4333,7 @@ hipError_t launch_factor_with_forward(const DeviceFactor &D, const std::vector<L
     int root_rest = 0;                             // first chunk of the root's sweep that is still to do after the join
     for (size_t f0 = 0; f0 < fgroups.size(); ) {
         const int level = fgroups[f0].level;
-        size_t f1 = f0;
-        while (f1 < fgroups.size() && fgroups[f1].level == level) ++f1;
+        const size_t f1 = level_edge(fgroups, f0, true);
         if (rootf && level == nlevels - 1) {
             const BigSweepPlan pl = big_sweep_plan(D, *roots, nrhs);
             const int nblk = big_group_blocks(*rootf), cwb = pl.cw / BIG_NB;
@@ -4339,22 +4353,21 @@ hipError_t launch_factor_with_forward(const DeviceFactor &D, const std::vector<L
                     if ((se = hipStreamWaitEvent(fj.aux, ready_deferred, 0)) != hipSuccess) return se;
                     if ((se = sweep(0, fork_level, fj.aux)) != hipSuccess) return se;
                 }
-                return launch_fwd_big_pre(D, *roots, X, nrhs, fj.aux);
+                return launch_fwd_big_pre(D, call, *roots, X, nrhs, fj.aux);
             };
             auto release = [&]() -> hipError_t {                           // chunks 0 .. k - 1 hang off block launch k * cwb
                 hipError_t se;
                 if ((se = hipStreamWaitEvent(fj.aux, home, 0)) != hipSuccess) return se;
                 for (int c = 0; c < k; ++c) {
-                    se = (D.kind == CS3_LU) ? launch_fwd_big_chunk<CS3_LU>(D, *roots, X, nrhs, c, fj.aux)
-                                            : launch_fwd_big_chunk<CS3_CHOLESKY>(D, *roots, X, nrhs, c, fj.aux);
+                    se = with_sweep_kind(D.kind, call.trans,
+                                         [&](auto K) { return launch_fwd_big_chunk<K>(D, call, *roots, X, nrhs, c, fj.aux); });
                     if (se != hipSuccess) return se;
                 }
                 home = nullptr;
                 return hipSuccess;
             };
             for (int blk = 0; blk <= nblk; ++blk) {
-                e = (D.kind == CS3_LU) ? launch_big_block<CS3_LU>(D, *rootf, blk, inv_tol, st)
-                                       : launch_big_block<CS3_CHOLESKY>(D, *rootf, blk, inv_tol, st);
+                e = with_kind(D.kind, [&](auto K) { return launch_big_block<K>(D, *rootf, blk, inv_tol, st); });
                 if (e != hipSuccess) return e;
                 if (!side_started && (e = start_side()) != hipSuccess) return e;      // after the chain's first block is captured
                 if (home && (e = release()) != hipSuccess) return e;                  // after the block that follows the release point
@@ -4371,8 +4384,7 @@ hipError_t launch_factor_with_forward(const DeviceFactor &D, const std::vector<L
             continue;
         }
         e = run_level(fgroups, f0, f1, st, fj, true, [&](const LaunchGroup &g, hipStream_t s) {
-            return (D.kind == CS3_LU) ? launch_front_group<CS3_LU>(D, g, inv_tol, s)
-                                      : launch_front_group<CS3_CHOLESKY>(D, g, inv_tol, s);
+            return with_kind(D.kind, [&](auto K) { return launch_front_group<K>(D, call, g, inv_tol, s); });
         });
         if (e != hipSuccess) return e;
         if (ready_deferred && !rootf) {            // the level above the fork has been captured: now the side branch
@@ -4394,8 +4406,7 @@ hipError_t launch_factor_with_forward(const DeviceFactor &D, const std::vector<L
     if (!rootf) return sweep(fork_level + 1, nlevels, st);
     const BigSweepPlan pl = big_sweep_plan(D, *roots, nrhs);
     for (int c = root_rest; c < pl.nchunk; ++c) {
-        e = (D.kind == CS3_LU) ? launch_fwd_big_chunk<CS3_LU>(D, *roots, X, nrhs, c, st)
-                               : launch_fwd_big_chunk<CS3_CHOLESKY>(D, *roots, X, nrhs, c, st);
+        e = with_sweep_kind(D.kind, call.trans, [&](auto K) { return launch_fwd_big_chunk<K>(D, call, *roots, X, nrhs, c, st); });
         if (e != hipSuccess) return e;
     }
     return hipSuccess;

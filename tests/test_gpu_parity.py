@@ -575,6 +575,65 @@ def test_fused_step_graphs_per_solution_buffer_survive_rotating_buffers(gpu):
             assert np.abs(A @ X - b).max() <= 1e-13 * (scale * np.abs(X).max() + np.abs(b).max())
 
 
+def test_interleaved_calls_match_fresh_handles(gpu):
+    """What one call asks for (sweep schedule, fused permutations, trans, inverses inside the sweep, the forward sweep
+    inside the forest's factor launch) never reaches the next call: on one LU handle with a bottom forest, interleaved
+    factorisations, fused steps (1 and 300 right-hand sides), transposed and plain solves, fused-permutation solves on two
+    rotating buffers and lsolve / usolve, with tol going 1e-3 -> 0 -> 1e-3, each return what a fresh handle returns for
+    that single call, bit for bit."""
+    import torch
+    m, n, Ap, Ai, Ax = synth.grid_jacobian(n=20000, seed=21)
+    dev = torch.device("cuda", 0)
+    sh = torch.cuda.current_stream().cuda_stream
+    ax = torch.from_numpy(Ax).to(dev)
+    rng = np.random.default_rng(21)
+    B1, B300, B256 = rng.standard_normal(n), rng.standard_normal((n, 300)), rng.standard_normal((n, 256))
+    x1 = torch.empty(n, dtype=torch.float64, device=dev)               # one X for every 1-RHS fused step: its own graph
+    rot = [torch.empty((n, 256), dtype=torch.float64, device=dev) for _ in range(2)]
+
+    def fused(F, B, tol, x=None):
+        b = torch.from_numpy(B).to(dev)
+        x = torch.empty_like(b) if x is None else x
+        F.factor_solve_bx_dev(ax.data_ptr(), b.data_ptr(), x.data_ptr(), B.size // n, tol, sh)
+        torch.cuda.synchronize()
+        return x.cpu().numpy()
+
+    def solve_dev(F, x):
+        x.copy_(torch.from_numpy(B256))
+        F.solve_dev(x.data_ptr(), 256, sh)
+        torch.cuda.synchronize()
+        return x.cpu().numpy()
+
+    ops = {                                                              # name: (needs a factorisation first, the call)
+        "fused1": (False, lambda F, tol: fused(F, B1, tol, x1)),
+        "fused300": (False, lambda F, tol: fused(F, B300, tol)),
+        "plain1": (True, lambda F, tol: F.solve(B1)),
+        "trans1": (True, lambda F, tol: F.solve(B1, trans=True)),
+        "solve256": (True, lambda F, tol: solve_dev(F, rot[0])),
+        "lsolve1": (True, lambda F, tol: F.lsolve(B1)),
+        "usolve1": (True, lambda F, tol: F.usolve(B1)),
+    }
+    ref = {}
+    for tol in (1e-3, 0.0):
+        for name, (factor_first, call) in ops.items():
+            with gpu.Factorization(m, n, Ap, Ai) as G:
+                if factor_first:
+                    G.factor(Ax, tol)
+                ref[name, tol] = call(G, tol)
+    with gpu.Factorization(m, n, Ap, Ai) as F:
+        for tol in (1e-3, 0.0, 1e-3):
+            F.factor(Ax, tol)
+            assert np.array_equal(F.solve(B1), ref["plain1", tol])
+            for _ in range(3):                                           # the third call in a row replays the per-X graph
+                assert np.array_equal(ops["fused1"][1](F, tol), ref["fused1", tol])
+            for name in ("trans1", "plain1", "fused300"):
+                assert np.array_equal(ops[name][1](F, tol), ref[name, tol]), (name, tol)
+            for x in rot + rot:
+                assert np.array_equal(solve_dev(F, x), ref["solve256", tol]), tol
+            for name in ("lsolve1", "usolve1", "trans1", "fused1"):
+                assert np.array_equal(ops[name][1](F, tol), ref[name, tol]), (name, tol)
+
+
 # ------------------------------------------------------------- edge cases ----
 
 def _arrow_with_dense_row(n=400, seed=0):
