@@ -193,6 +193,16 @@ class CscMat:
         """x = A \\ b by LU (factorises if needed); trans: A' x = b on the same factors."""
         return self.lu(tol).solve(b, trans=trans)
 
+    def condest(self, tol=0.0):
+        """1-norm condition estimate ||A||_1 * est(||A^-1||_1) from the LU factors (factorises as solve does)."""
+        cond, _ = self.lu(tol).condest(self.data)
+        return float(cond[0])
+
+    def slogdet(self, tol=0.0):
+        """(sign, log|det A|) from the LU factors (factorises as solve does)."""
+        sign, logabs = self.lu(tol).slogdet()
+        return float(sign[0]), float(logabs[0])
+
 
 def _sub_matrix_cols(Ap, Ai, Ax, cols):
     """Whole columns `cols` of a CSC matrix with their original row indices (csc_sub_matrix_cols, csc_numba.py:505-538):

@@ -114,6 +114,10 @@ def lib():
             f.argtypes = [vp, vp, vp, vp, I64, vp]
         for f in (L.cs3_refine_dev, L.cs3_refine_t_dev):
             f.argtypes = [vp, vp, vp, vp, I64, I64, C.POINTER(C.c_double), vp]
+        L.cs3_condest_dev.argtypes = [vp, vp, vp, vp, vp]
+        L.cs3_condest.argtypes = [vp, _f64p, _f64p, _f64p]
+        L.cs3_slogdet_dev.argtypes = [vp, vp, vp, vp]
+        L.cs3_slogdet.argtypes = [vp, _f64p, _f64p]
         L.cs3_export_factor_dev.argtypes = [vp, vp, vp]
         L.cs3_import_factor_dev.argtypes = [vp, vp, vp]
         L.cs3_get_factors.argtypes = [vp, I64, _i32p, _i32p, _f64p, _i32p, _i32p, _f64p]
@@ -351,6 +355,36 @@ class Factorization:
         _check(fn(self._h, C.c_void_p(ax_ptr), C.c_void_p(b_ptr), C.c_void_p(x_ptr), k, steps,
                   C.byref(out) if want_correction else None, C.c_void_p(stream)))
         return float(out.value)
+
+    # -- reliability of the held factors
+    def condest(self, Ax):
+        """1-norm condition estimates of every matrix of the batch from the held factors (LAPACK dlacn2, ITMAX 5):
+        -> (cond, inv_norm), float64[batch] each.  inv_norm estimates ||A^-1||_1; cond = ||A||_1 * inv_norm with ||A||_1
+        summed from Ax ([batch, nnz] in the analysed entry order) as csc_norm sums it.  Runs only the solves some matrix
+        still needs, synchronising after each."""
+        Ax = _f64(Ax)
+        assert Ax.size >= self.batch * self.nnz
+        cond = np.empty(self.batch)
+        inv_norm = np.empty(self.batch)
+        _check(lib().cs3_condest(self._h, _pf(Ax), _pf(cond), _pf(inv_norm)))
+        return cond, inv_norm
+
+    def condest_dev(self, ax_ptr, cond_ptr, inv_norm_ptr=0, stream=0):
+        """condest on device pointers, asynchronous on `stream` (a fixed sequence of 11 solves, no synchronisation); the
+        same bits as condest().  inv_norm_ptr = 0: not written."""
+        _check(lib().cs3_condest_dev(self._h, C.c_void_p(ax_ptr), C.c_void_p(cond_ptr), C.c_void_p(inv_norm_ptr),
+                                     C.c_void_p(stream)))
+
+    def slogdet(self):
+        """(sign, log|det A|) of every matrix of the batch from the pivots of the held factors, float64[batch] each
+        (numpy.linalg.slogdet's convention: a zero pivot gives (0, -inf))."""
+        sign = np.empty(self.batch)
+        logabs = np.empty(self.batch)
+        _check(lib().cs3_slogdet(self._h, _pf(sign), _pf(logabs)))
+        return sign, logabs
+
+    def slogdet_dev(self, sign_ptr, logabs_ptr, stream=0):
+        _check(lib().cs3_slogdet_dev(self._h, C.c_void_p(sign_ptr), C.c_void_p(logabs_ptr), C.c_void_p(stream)))
 
     def export_factor_dev(self, dst_ptr, stream=0):
         """Copy the factor panels (info.factor_bytes per matrix) into an HBM buffer."""

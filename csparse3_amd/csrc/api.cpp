@@ -68,6 +68,16 @@ struct cs3_handle_s {
     double *d_res = nullptr;
     long long res_cap = 0;
     unsigned long long *d_maxbits = nullptr;
+    // condition estimates (estimate.hip), allocated on first use: X [batch][n] (stable address: the solves on it replay the
+    // cached graphs), the sign vectors [2][batch][n], one state per matrix, the chunks of the partial reductions, the two
+    // "wants" counters; the host forms' buffers; the virtual pool offset of every pivot's diagonal (log-determinants)
+    double *d_est_x = nullptr;
+    signed char *d_est_s = nullptr;
+    EstState *d_est_state = nullptr;
+    EstPart *d_est_parts = nullptr;
+    unsigned *d_est_cnt = nullptr;
+    double *d_est_ax = nullptr, *d_est_out = nullptr;
+    i64 *d_diag = nullptr;
 };
 
 namespace {
@@ -114,7 +124,9 @@ void release_device(cs3_handle h)
                      (void **) &D.ax, (void **) &D.pool, (void **) &D.dbuf, (void **) &D.tbuf, (void **) &D.bigv,
                      (void **) &D.cv, (void **) &D.xp, (void **) &D.status, (void **) &h->d_lmap, (void **) &h->d_umap,
                      (void **) &h->d_lx, (void **) &h->d_ux, (void **) &h->d_rp, (void **) &h->d_rj, (void **) &h->d_rmap,
-                     (void **) &h->d_cp, (void **) &h->d_ci, (void **) &h->d_cmap, (void **) &h->d_res, (void **) &h->d_maxbits};
+                     (void **) &h->d_cp, (void **) &h->d_ci, (void **) &h->d_cmap, (void **) &h->d_res, (void **) &h->d_maxbits,
+                     (void **) &h->d_est_x, (void **) &h->d_est_s, (void **) &h->d_est_state, (void **) &h->d_est_parts, (void **) &h->d_est_cnt,
+                     (void **) &h->d_est_ax, (void **) &h->d_est_out, (void **) &h->d_diag};
     h->res_cap = 0;
     for (void **p : ptrs) if (*p) { (void) hipFree(*p); *p = nullptr; }
     D.nrhs_cap = 0;
@@ -1104,6 +1116,149 @@ int cs3_refine_t_dev(cs3_handle h, const double *Ax_dev, const double *B_dev, do
                      double *last_correction, void *stream)
 {
     return refine(h, Ax_dev, B_dev, X_dev, k, steps, last_correction, stream, true);
+}
+
+// ---- condition estimates and log-determinants from the held factors --------------------------------------------------
+static int ensure_estimator(cs3_handle h)
+{
+    int rc = ensure_col_view(h, 0);
+    if (rc) return rc;
+    const size_t bn = std::max<size_t>(1, (size_t) (h->batch * h->S.n));
+    if (!h->d_est_x) CS3_HIP(hipMalloc((void **) &h->d_est_x, bn * sizeof(double)));
+    if (!h->d_est_s) CS3_HIP(hipMalloc((void **) &h->d_est_s, 2 * bn));
+    if (!h->d_est_state) CS3_HIP(hipMalloc((void **) &h->d_est_state, (size_t) h->batch * sizeof(EstState)));
+    const long long nparts = std::max(est_chunks(h->S.n), norm_chunks(h->S.n));
+    if (!h->d_est_parts) CS3_HIP(hipMalloc((void **) &h->d_est_parts, (size_t) (h->batch * nparts) * sizeof(EstPart)));
+    if (!h->d_est_cnt) CS3_HIP(hipMalloc((void **) &h->d_est_cnt, 2 * sizeof(unsigned)));
+    return CS3_OK;
+}
+
+// dlacn2 for every matrix of the batch in SLOTS (estimate.hip): prepare(kind), the handle's own solve of that kind on the
+// work buffer (k = 1, run_solve mode 0: the cached graphs), consume(kind).  adaptive (cs3_condest): after every slot the
+// two counters come back (8 bytes and a sync) and only a wanted kind runs, alternating when both are wanted -- one matrix
+// gets exactly dlacn2's call sequence.  Otherwise (cs3_condest_dev) the fixed sequence F T F T F T F T F T F: enough for
+// every path (J1, J2, four J3/J4 pairs, J5; a matrix that leaves J3 for J5 waits one slot at most), no synchronisation.
+// A Cholesky slot serves both kinds (A' = A).  Both drivers give the same bits: a solve of the batch computes every matrix
+// on its own, an idle matrix gets zeros and keeps its state.
+static int condest_run(cs3_handle h, const double *Ax_dev, double *cond_dev, double *inv_dev, hipStream_t st, bool adaptive)
+{
+    int rc = ensure_estimator(h);
+    if (rc) return rc;
+    const i64 n = h->S.n, batch = h->batch;
+    const bool chol = h->S.kind == CS3_CHOLESKY;
+    CS3_HIP(launch_est_start(h->d_cp, h->d_cmap, Ax_dev, n, h->S.nnzA, batch, h->d_est_parts, h->d_est_state, st));
+    constexpr int FIXED_SLOTS = 11;
+    unsigned want[2] = {1u, 0u};                             // before the first slot: J1 wants A^-1
+    int last = 1;
+    // (adaptive: a wanted kind runs at most one slot late, so 2 * 11 slots bound every matrix's 11 steps)
+    for (int slot = 0; slot < (adaptive ? 2 * FIXED_SLOTS : FIXED_SLOTS); ++slot) {
+        int kind = slot & 1;                                 // 0: x = A^-1 b (F), 1: x = A^-T b (T)
+        if (adaptive) {
+            if (slot > 0) {
+                CS3_HIP(hipMemcpyAsync(want, h->d_est_cnt, sizeof(want), hipMemcpyDeviceToHost, st));
+                CS3_HIP(hipStreamSynchronize(st));
+            }
+            if (!want[0] && !want[1]) break;
+            kind = (want[0] && want[1]) ? 1 - last : (want[0] ? 0 : 1);
+        }
+        if (chol) kind = 0;
+        const int kmask = chol ? 3 : 1 << kind;
+        CS3_HIP(launch_est_prepare(h->d_est_state, h->d_est_s, h->d_est_x, n, batch, kmask, h->d_est_cnt, st));
+        if ((rc = run_solve(h, h->d_est_x, 1, 0, st, kind == 1))) return rc;
+        CS3_HIP(launch_est_consume(h->d_est_state, h->d_est_s, h->d_est_x, n, batch, kmask, h->d_est_parts, h->d_est_cnt, st));
+        last = kind;
+    }
+    CS3_HIP(launch_est_finalize(h->d_est_state, batch, cond_dev, inv_dev, st));
+    return CS3_OK;
+}
+
+static int condest_check(const char *who, cs3_handle h, const double *Ax, const double *cond)
+{
+    int rc = guard(h); if (rc) return rc;
+    if (!Ax || !cond) { set_error(std::string(who) + ": null argument"); return CS3_ERR_ARG; }
+    if (!h->factored) { set_error(std::string(who) + ": no successful factorisation"); return CS3_ERR_STATE; }
+    return CS3_OK;
+}
+
+int cs3_condest_dev(cs3_handle h, const double *Ax_dev, double *cond_dev, double *inv_norm_dev, void *stream)
+{
+    int rc = condest_check("cs3_condest_dev", h, Ax_dev, cond_dev);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t) stream;
+    if (h->S.n == 0) {
+        CS3_HIP(hipMemsetAsync(cond_dev, 0, (size_t) h->batch * sizeof(double), st));
+        if (inv_norm_dev) CS3_HIP(hipMemsetAsync(inv_norm_dev, 0, (size_t) h->batch * sizeof(double), st));
+        return CS3_OK;
+    }
+    return condest_run(h, Ax_dev, cond_dev, inv_norm_dev, st, false);
+}
+
+// The host forms stage through buffers the handle keeps (allocated on first use), on the null stream.
+static int ensure_host_out(cs3_handle h)
+{
+    if (!h->d_est_out) CS3_HIP(hipMalloc((void **) &h->d_est_out, (size_t) (2 * h->batch) * sizeof(double)));
+    return CS3_OK;
+}
+
+int cs3_condest(cs3_handle h, const double *Ax, double *cond, double *inv_norm)
+{
+    int rc = condest_check("cs3_condest", h, Ax, cond);
+    if (rc) return rc;
+    const long long batch = h->batch;
+    if (h->S.n == 0) {
+        for (long long b = 0; b < batch; ++b) { cond[b] = 0.0; if (inv_norm) inv_norm[b] = 0.0; }
+        return CS3_OK;
+    }
+    if ((rc = ensure_host_out(h))) return rc;
+    const size_t ax_bytes = (size_t) (batch * h->S.nnzA) * sizeof(double);
+    if (!h->d_est_ax) CS3_HIP(hipMalloc((void **) &h->d_est_ax, std::max<size_t>(ax_bytes, 8)));
+    if (ax_bytes) CS3_HIP(hipMemcpy(h->d_est_ax, Ax, ax_bytes, hipMemcpyHostToDevice));
+    if ((rc = condest_run(h, h->d_est_ax, h->d_est_out, h->d_est_out + batch, nullptr, true))) return rc;
+    std::vector<double> out((size_t) (2 * batch));
+    CS3_HIP(hipMemcpy(out.data(), h->d_est_out, out.size() * sizeof(double), hipMemcpyDeviceToHost));
+    std::memcpy(cond, out.data(), (size_t) batch * sizeof(double));
+    if (inv_norm) std::memcpy(inv_norm, out.data() + batch, (size_t) batch * sizeof(double));
+    return CS3_OK;
+}
+
+// sign and log|det| from the diagonal of the held factors: pivot j's diagonal sits at virtual pool offset
+// lpan_off[s] + jj (r + 1), s = col2sn[j], jj = j - sn_ptr[s], r = the front order (build_csc_factors' rule); the map is
+// built once per handle, without the CSC view of the factors.
+static int ensure_diag_map(cs3_handle h)
+{
+    if (h->d_diag) return CS3_OK;
+    const Symbolic &S = h->S;
+    std::vector<i64> diag((size_t) S.n);
+    for (i64 j = 0; j < S.n; ++j) {
+        const i32 s = S.col2sn[j];
+        diag[j] = S.lpan_off[s] + (j - S.sn_ptr[s]) * (S.st_ptr[s + 1] - S.st_ptr[s] + 1);
+    }
+    return upload(&h->d_diag, diag);
+}
+
+int cs3_slogdet_dev(cs3_handle h, double *sign_dev, double *logabs_dev, void *stream)
+{
+    int rc = guard(h); if (rc) return rc;
+    if (!sign_dev || !logabs_dev) { set_error("cs3_slogdet_dev: null argument"); return CS3_ERR_ARG; }
+    if (!h->factored) { set_error("cs3_slogdet_dev: no successful factorisation"); return CS3_ERR_STATE; }
+    if ((rc = ensure_diag_map(h))) return rc;
+    CS3_HIP(launch_slogdet(h->D, (const long long *) h->d_diag, sign_dev, logabs_dev, (hipStream_t) stream));
+    return CS3_OK;
+}
+
+int cs3_slogdet(cs3_handle h, double *sign, double *logabs)
+{
+    int rc = guard(h); if (rc) return rc;
+    if (!sign || !logabs) { set_error("cs3_slogdet: null argument"); return CS3_ERR_ARG; }
+    if (!h->factored) { set_error("cs3_slogdet: no successful factorisation"); return CS3_ERR_STATE; }
+    if ((rc = ensure_host_out(h))) return rc;
+    const long long batch = h->batch;
+    if ((rc = cs3_slogdet_dev(h, h->d_est_out, h->d_est_out + batch, nullptr))) return rc;
+    std::vector<double> out((size_t) (2 * batch));
+    CS3_HIP(hipMemcpy(out.data(), h->d_est_out, out.size() * sizeof(double), hipMemcpyDeviceToHost));
+    std::memcpy(sign, out.data(), (size_t) batch * sizeof(double));
+    std::memcpy(logabs, out.data() + batch, (size_t) batch * sizeof(double));
+    return CS3_OK;
 }
 
 // The same on data that already lives in HBM: nothing crosses PCIe and nothing synchronises.  The caller knows the

@@ -182,4 +182,34 @@ hipError_t launch_axpy_max(double *X, const double *D, long long total, unsigned
 hipError_t launch_matvec_rows(const int *Rp, const int *Rj, const double *Rx, const double *X, double *Y,
                               long long m, int nrhs, hipStream_t st);
 
+// estimate.hip: condition estimates (LAPACK dlacn2, one state machine per matrix of a batch) and log-determinants.
+// The state of one matrix: step = what the next solve's result is for (1..5: dlacn2's J1..J5; J1, J3, J5 consume
+// x = A^-1 b, J2 and J4 x = A^-T b), 0 = DONE; j = the current column, iter = dlacn2's iteration count; sbuf = which half
+// of the sign buffer S [2][batch][n] (int8) holds the current sign vector s.
+struct EstState {
+    double est, anorm;            // the estimate of ||A^-1||_1 so far, ||A||_1
+    int step, j, iter, sbuf;
+};
+// The reductions over a vector of n entries run on a FIXED partition (chunks of EST_CHUNK entries, one workgroup each) and
+// a second stage that combines the chunks in index order: the same sums on every run, whatever the batch.
+constexpr long long EST_CHUNK = 2048;
+inline long long est_chunks(long long n) { return n > 0 ? (n + EST_CHUNK - 1) / EST_CHUNK : 1; }
+constexpr long long EST_NORM_COLS = 256;       // ||A||_1: columns per workgroup (a max: any partition gives the same value)
+inline long long norm_chunks(long long n) { return n > 0 ? (n + EST_NORM_COLS - 1) / EST_NORM_COLS : 1; }
+struct EstPart {                  // one chunk: sum |x_i|, max |x_i| and its first index, flags (1: non-finite, 2: a sign changed)
+    double sum, max;
+    int idx, flags;
+};
+// ||A_b||_1 over the column view (Cp, Cmap: entry of Ax) and the initial states; parts [batch][norm_chunks(n)]
+hipError_t launch_est_start(const int *Cp, const int *Cmap, const double *Ax, long long n, long long nnz_a, long long batch,
+                            EstPart *parts, EstState *state, hipStream_t st);
+// kmask: bit 0 = this slot solves with A^-1, bit 1 = with A^-T (a Cholesky slot serves both)
+hipError_t launch_est_prepare(const EstState *state, const signed char *S, double *X, long long n, long long batch, int kmask,
+                              unsigned *cnt, hipStream_t st);
+hipError_t launch_est_consume(EstState *state, signed char *S, const double *X, long long n, long long batch, int kmask,
+                              EstPart *parts, unsigned *cnt, hipStream_t st);
+hipError_t launch_est_finalize(const EstState *state, long long batch, double *cond, double *inv_norm, hipStream_t st);
+// diag[n]: virtual pool offset of every pivot's diagonal
+hipError_t launch_slogdet(const DeviceFactor &D, const long long *diag, double *sign, double *logabs, hipStream_t st);
+
 }  // namespace cs3

@@ -163,6 +163,31 @@ int cs3_matvec_t_dev(cs3_handle h, const double *Ax_dev, const double *X_dev, do
 int cs3_refine_t_dev(cs3_handle h, const double *Ax_dev, const double *B_dev, double *X_dev, int64_t k, int64_t steps,
                      double *last_correction, void *stream);
 
+/* ---- condition estimates and log-determinants from the held factors -----
+ * Static diagonal pivots say nothing about how far a solution can be trusted; these are the cheap reliability signal
+ * next to the factors (klu_condest, LAPACK xGECON, MATLAB condest).  Results are per matrix of the batch, [batch] each.
+ * After a cs3_factor_dev / cs3_factor_solve_dev whose status has not been polled (cs3_factor_status) they carry the same
+ * caveat as a solve: they are only meaningful if that factorisation succeeded.
+ * Checks, in this order: a null Ax / cond (sign, logabs) gives CS3_ERR_ARG; no successful factorisation CS3_ERR_STATE.
+ *
+ * cs3_condest_dev: inv_norm[b] = LAPACK dlacn2's estimate of ||A_b^-1||_1 (ITMAX 5, every A^-1 a full solve, every A^-T a
+ *   transposed solve on the same factors; Cholesky: both the plain solve), cond[b] = ||A_b||_1 * inv_norm[b] with
+ *   ||A_b||_1 from Ax_dev [batch][nnz_a] (the analysed entry order, as for cs3_residual_dev) summed exactly as
+ *   cs3_csc_norm sums it: the STORED entries, so on a Cholesky handle analysed from one triangle cond is ||tril(A)||_1 *
+ *   inv_norm, not kappa_1 of the symmetric matrix (inv_norm is unaffected).  inv_norm may be NULL.  A non-finite value in a solution gives +inf.  Asynchronous on `stream`:
+ *   a fixed sequence of 11 solves (A^-1, A^-T alternating), no synchronisation after the first call's allocations.
+ * cs3_condest: the same from host arrays; synchronises after every solve (one 8-byte read) and runs only the solves some
+ *   matrix still needs (4 or 5 for most matrices).  Both forms give the same bits.
+ * cs3_slogdet_dev: sign[b] and logabs[b] = log|det A_b| from the pivots (LU: det A = prod u_jj since P = Q'; Cholesky:
+ *   sign +1, 2 sum log l_jj).  Pivots that only imported factors can hold follow numpy.linalg.slogdet: a zero pivot
+ *   gives (0, -inf); an infinite one log|det| = +inf; a NaN one log|det| = NaN with the sign of the other pivots.
+ *   Asynchronous.
+ * cs3_slogdet: the same into host arrays (synchronises). */
+int cs3_condest_dev(cs3_handle h, const double *Ax_dev, double *cond_dev, double *inv_norm_dev, void *stream);
+int cs3_condest(cs3_handle h, const double *Ax, double *cond, double *inv_norm);
+int cs3_slogdet_dev(cs3_handle h, double *sign_dev, double *logabs_dev, void *stream);
+int cs3_slogdet(cs3_handle h, double *sign, double *logabs);
+
 /* ---- factors back to the host in CSparse's CSC form ---------------------
  * L: diagonal FIRST in each column (unit for LU); U: diagonal LAST; row
  * indices sorted otherwise.  Sizes from cs3_info.nnz_l / nnz_u.  NumPy-style
