@@ -193,6 +193,16 @@ class CscMat:
         """x = A \\ b by LU (factorises if needed); trans: A' x = b on the same factors."""
         return self.lu(tol).solve(b, trans=trans)
 
+    def solve_modified(self, b, deltas, tol=0.0, sing_tol=0.0):
+        """x_c = (A + dA_c) \\ b for a list of sparse modifications, `deltas` = [(rows, cols, vals), ...] (triplets of dA_c;
+        duplicates add), from ONE LU factorisation of A (factorises as solve does).  -> (X [n, len(deltas)], rpiv); a
+        case whose modified matrix is singular (rpiv <= sing_tol, or an exactly zero pivot) has a NaN column."""
+        F = self.lu(tol)
+        with F.updates_plan([(d[0], d[1]) for d in deltas]) as plan:
+            vals = [np.atleast_1d(np.asarray(d[2], dtype=np.float64)) for d in deltas]
+            cx = np.concatenate(vals) if vals else np.zeros(0)
+            return F.solve_updates(plan, cx, b, sing_tol)
+
     def condest(self, tol=0.0):
         """1-norm condition estimate ||A||_1 * est(||A^-1||_1) from the LU factors (factorises as solve does)."""
         cond, _ = self.lu(tol).condest(self.data)

@@ -118,6 +118,14 @@ def lib():
         L.cs3_condest.argtypes = [vp, _f64p, _f64p, _f64p]
         L.cs3_slogdet_dev.argtypes = [vp, vp, vp, vp]
         L.cs3_slogdet.argtypes = [vp, _f64p, _f64p]
+        L.cs3_updates_plan.argtypes = [vp, I64, _i32p, _i32p, _i32p, C.POINTER(vp)]
+        L.cs3_updates_free.argtypes = [vp]
+        L.cs3_updates_info.argtypes = [vp] + [C.POINTER(I64)] * 4
+        L.cs3_updates_solve_dev.argtypes = [vp, vp, vp, vp, C.c_double, vp, vp, vp]
+        L.cs3_updates_solve.argtypes = [vp, vp, _f64p, _f64p, C.c_double, _f64p, _f64p]
+        L.cs3_debug_updates_tiles.argtypes = [vp] + [_i32p] * 4
+        L.cs3_debug_updates_tiles.restype = I64
+        L.cs3_debug_alloc_counters.argtypes = [vp, C.POINTER(I64), C.POINTER(I64)]
         L.cs3_export_factor_dev.argtypes = [vp, vp, vp]
         L.cs3_import_factor_dev.argtypes = [vp, vp, vp]
         L.cs3_get_factors.argtypes = [vp, I64, _i32p, _i32p, _f64p, _i32p, _i32p, _f64p]
@@ -207,6 +215,74 @@ def csc_counts_f(n, Ap, Ai, parent, post):
 
 
 # ------------------------------------------------------------------ handle --
+
+class UpdatesInfo:
+    """What cs3_updates_info reports: cases, distinct touched rows over all cases, largest rank, tiles."""
+
+    def __init__(self, ncases, nrows_unique, max_rank, ntiles):
+        self.ncases, self.nrows_unique, self.max_rank, self.ntiles = ncases, nrows_unique, max_rank, ntiles
+
+    def __repr__(self):
+        return "UpdatesInfo(ncases=%d, nrows_unique=%d, max_rank=%d, ntiles=%d)" % (
+            self.ncases, self.nrows_unique, self.max_rank, self.ntiles)
+
+
+def _flat_cases(cases):
+    """(cp, ci, cj) from a list of (rows, cols) index arrays per case, or the flat triple itself."""
+    if isinstance(cases, tuple) and len(cases) == 3 and np.ndim(cases[0]) == 1 and not isinstance(cases[0], tuple):
+        cp, ci, cj = (_i32(a) for a in cases)
+        return cp, ci, cj
+    rows = [_i32(np.atleast_1d(c[0])) for c in cases]
+    cols = [_i32(np.atleast_1d(c[1])) for c in cases]
+    for r, c in zip(rows, cols):
+        assert r.shape == c.shape and r.ndim == 1, "a case is (rows, cols) of equal length"
+    cp = np.zeros(len(rows) + 1, dtype=np.int32)
+    np.cumsum([len(r) for r in rows], out=cp[1:])
+    cat = lambda parts: np.concatenate(parts).astype(np.int32) if parts else np.zeros(0, dtype=np.int32)   # noqa: E731
+    return cp, cat(rows), cat(cols)
+
+
+class UpdatesPlan:
+    """The pattern of a list of sparse modifications dA_c of a handle's matrix (Factorization.updates_plan): made once on
+    the host, used by every solve_updates of that handle, across refactorisations."""
+
+    def __init__(self, factorization, cases):
+        self._u = C.c_void_p()
+        self.cp, self.ci, self.cj = _flat_cases(cases)
+        self.ncases = len(self.cp) - 1
+        _check(lib().cs3_updates_plan(factorization._h, self.ncases, _pi(self.cp), _pi(self.ci), _pi(self.cj),
+                                      C.byref(self._u)))
+
+    def close(self):
+        if self._u:
+            lib().cs3_updates_free(self._u)
+            self._u = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    @property
+    def info(self):
+        out = [I64() for _ in range(4)]
+        _check(lib().cs3_updates_info(self._u, *[C.byref(o) for o in out]))
+        return UpdatesInfo(*[int(o.value) for o in out])
+
+    def tiles(self):
+        """-> int32 [ntiles, 4]: first case, cases, touched rows and solve width of every tile (diagnostic)."""
+        nt = self.info.ntiles
+        arrs = [np.empty(nt, dtype=np.int32) for _ in range(4)]
+        assert lib().cs3_debug_updates_tiles(self._u, *[_pi(a) for a in arrs]) == nt
+        return np.stack(arrs, axis=1)
+
 
 class Factorization:
     """Device-resident factorisation handle: analyze once, (re)factor, solve.
@@ -385,6 +461,37 @@ class Factorization:
 
     def slogdet_dev(self, sign_ptr, logabs_ptr, stream=0):
         _check(lib().cs3_slogdet_dev(self._h, C.c_void_p(sign_ptr), C.c_void_p(logabs_ptr), C.c_void_p(stream)))
+
+    # -- many low-rank-modified systems on the held factors
+    def updates_plan(self, cases):
+        """Plan for solving (A + dA_c) x = b for a list of sparse modifications: `cases` is a list of (rows, cols) index
+        arrays (the positions of each case's triplets; duplicates add) or the flat (cp, ci, cj).  Needs no GPU.
+        -> UpdatesPlan (.info, .close(), context manager)."""
+        return UpdatesPlan(self, cases)
+
+    def solve_updates(self, plan, cx, b, sing_tol=0.0):
+        """x_c = (A + dA_c)^-1 b for every case of `plan` from the held factors (Sherman-Morrison-Woodbury, no
+        refactorisation): cx the values of all triplets in the plan's order, b [n].  -> (X [n, ncases], rpiv [ncases]);
+        rpiv is the smallest pivot of the case's capacitance matrix relative to its largest entry, and a case with
+        rpiv <= sing_tol (A + dA_c singular) has a NaN column."""
+        cx, b = _f64(cx).reshape(-1), _f64(b).reshape(-1)
+        assert cx.size == int(plan.cp[-1]) and b.size == self.n
+        X = np.empty((self.n, plan.ncases))
+        rpiv = np.empty(plan.ncases)
+        _check(lib().cs3_updates_solve(self._h, plan._u, _pf(cx), _pf(b), sing_tol, _pf(X), _pf(rpiv)))
+        return X, rpiv
+
+    def solve_updates_dev(self, plan, cx_ptr, b_ptr, x_ptr, rpiv_ptr=0, sing_tol=0.0, stream=0):
+        """solve_updates on device pointers, asynchronous on `stream`; X [n, ncases] row-major.  After the first call
+        with a plan nothing is allocated and nothing synchronises.  The same bits as solve_updates()."""
+        _check(lib().cs3_updates_solve_dev(self._h, plan._u, C.c_void_p(cx_ptr), C.c_void_p(b_ptr), sing_tol,
+                                           C.c_void_p(x_ptr), C.c_void_p(rpiv_ptr), C.c_void_p(stream)))
+
+    def debug_alloc_counters(self):
+        """(device allocations incl. graph instantiations, host synchronisations) the handle's solves have made so far."""
+        a, s = I64(), I64()
+        _check(lib().cs3_debug_alloc_counters(self._h, C.byref(a), C.byref(s)))
+        return int(a.value), int(s.value)
 
     def export_factor_dev(self, dst_ptr, stream=0):
         """Copy the factor panels (info.factor_bytes per matrix) into an HBM buffer."""

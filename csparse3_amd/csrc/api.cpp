@@ -78,6 +78,39 @@ struct cs3_handle_s {
     unsigned *d_est_cnt = nullptr;
     double *d_est_ax = nullptr, *d_est_out = nullptr;
     i64 *d_diag = nullptr;
+    // low-rank-modified solves (updates.hip): the plans made for this handle, the tile of A^-1 columns Z [n][upd_z_cols] and
+    // x0 [n] (stable addresses: the solves on them replay the cached graphs), allocated on first use
+    std::vector<cs3_updates_s *> plans;
+    double *d_upd_z = nullptr, *d_upd_x0 = nullptr;
+    long long upd_z_cols = 0;
+    // diagnostics (cs3_debug_alloc_counters): device allocations / graph instantiations and host synchronisations made by the
+    // solves and the paths on top of them
+    long long dbg_allocs = 0, dbg_syncs = 0;
+};
+
+// One list of sparse modifications dA_c of a handle's matrix, pattern only (cs3_updates_plan).  Cases are grouped into
+// TILES: consecutive cases whose union of touched rows fits the tile width; a tile is one many-RHS solve.
+struct cs3_updates_s {
+    cs3_handle h = nullptr;                   // null once the handle has been freed: the plan can then only be freed
+    i64 n = 0, ncases = 0, ntrip = 0, nrows_unique = 0, max_rank = 0;
+    int tile_cap = UPD_MAX_TILE;
+    std::vector<UpdCase> cases;
+    std::vector<i32> cp;
+    std::vector<unsigned char> tpos;
+    struct Tile {
+        int c0, nc;                           // its cases
+        int t, t_solve;                       // touched rows, and the width it is solved at (t rounded up; zero columns behind t)
+        int rmax;                             // largest rank among its cases
+        i64 unit0;                            // its slice of unit_row (t_solve entries)
+    };
+    std::vector<Tile> tiles;
+    std::vector<i32> unit_row;                // row of the unit entry of every tile column, -1: a zero column
+    // device copies (uploaded by the first solve) and per-case results
+    UpdCase *d_cases = nullptr;
+    int *d_cp = nullptr, *d_unit = nullptr, *d_flag = nullptr;
+    unsigned char *d_tpos = nullptr;
+    double *d_y = nullptr, *d_rpiv = nullptr, *d_cx = nullptr;
+    bool on_device = false;
 };
 
 namespace {
@@ -99,7 +132,7 @@ int drop_graphs(cs3_handle h, Pred drop, bool synced = false)
     bool any = false;
     for (const auto &kv : h->graphs) any = any || drop(kv.first);
     if (!any) return CS3_OK;
-    if (!synced) CS3_HIP(hipDeviceSynchronize());
+    if (!synced) { CS3_HIP(hipDeviceSynchronize()); h->dbg_syncs += 1; }
     for (auto it = h->graphs.begin(); it != h->graphs.end(); ) {
         if (drop(it->first)) { (void) hipGraphExecDestroy(it->second); it = h->graphs.erase(it); }
         else ++it;
@@ -109,10 +142,20 @@ int drop_graphs(cs3_handle h, Pred drop, bool synced = false)
 
 bool graph_op_is(const GraphKey &k, int op) { return std::get<0>(k) == op; }
 
+void release_plan_device(cs3_updates_s *u)
+{
+    void **ptrs[] = {(void **) &u->d_cases, (void **) &u->d_cp, (void **) &u->d_unit, (void **) &u->d_flag, (void **) &u->d_tpos,
+                     (void **) &u->d_y, (void **) &u->d_rpiv, (void **) &u->d_cx};
+    for (void **p : ptrs) if (*p) { (void) hipFree(*p); *p = nullptr; }
+    u->on_device = false;
+}
+
 // Frees every HBM allocation of the handle (ensure_device's error path and cs3_free).
 void release_device(cs3_handle h)
 {
     DeviceFactor &D = h->D;
+    for (cs3_updates_s *u : h->plans) release_plan_device(u);
+    h->upd_z_cols = 0;
     (void) drop_graphs(h, [](const GraphKey &) { return true; }, true);     // (cs3_free has synchronised)
     if (h->cap_stream) { (void) hipStreamDestroy(h->cap_stream); h->cap_stream = nullptr; }
     h->fj.destroy();
@@ -126,7 +169,7 @@ void release_device(cs3_handle h)
                      (void **) &h->d_lx, (void **) &h->d_ux, (void **) &h->d_rp, (void **) &h->d_rj, (void **) &h->d_rmap,
                      (void **) &h->d_cp, (void **) &h->d_ci, (void **) &h->d_cmap, (void **) &h->d_res, (void **) &h->d_maxbits,
                      (void **) &h->d_est_x, (void **) &h->d_est_s, (void **) &h->d_est_state, (void **) &h->d_est_parts, (void **) &h->d_est_cnt,
-                     (void **) &h->d_est_ax, (void **) &h->d_est_out, (void **) &h->d_diag};
+                     (void **) &h->d_est_ax, (void **) &h->d_est_out, (void **) &h->d_diag, (void **) &h->d_upd_z, (void **) &h->d_upd_x0};
     h->res_cap = 0;
     for (void **p : ptrs) if (*p) { (void) hipFree(*p); *p = nullptr; }
     D.nrhs_cap = 0;
@@ -270,6 +313,8 @@ int ensure_rhs_capacity(cs3_handle h, long long nrhs)
     DeviceFactor &D = h->D;
     if (nrhs <= D.nrhs_cap) return CS3_OK;
     CS3_HIP(hipDeviceSynchronize());
+    h->dbg_syncs += 1;
+    h->dbg_allocs += 4;
     if (int rc = drop_graphs(h, [](const GraphKey &k) { return !graph_op_is(k, GRAPH_FACTOR); }, true)) return rc;
     if (D.cv) (void) hipFree(D.cv);
     if (D.xp) (void) hipFree(D.xp);
@@ -290,6 +335,7 @@ template <class Body>
 int capture(cs3_handle h, hipGraphExec_t *exec, Body body)
 {
     hipGraph_t graph = nullptr;
+    h->dbg_allocs += 1;
     CS3_HIP(hipStreamBeginCapture(h->cap_stream, hipStreamCaptureModeThreadLocal));
     hipError_t e = body(h->cap_stream);
     hipError_t e2 = hipStreamEndCapture(h->cap_stream, &graph);
@@ -572,6 +618,7 @@ int cs3_free(cs3_handle h)
         (void) hipDeviceSynchronize();
         release_device(h);
     }
+    for (cs3_updates_s *u : h->plans) u->h = nullptr;      // (their device arrays went with release_device)
     delete h;
     return CS3_OK;
 }
@@ -1258,6 +1305,258 @@ int cs3_slogdet(cs3_handle h, double *sign, double *logabs)
     CS3_HIP(hipMemcpy(out.data(), h->d_est_out, out.size() * sizeof(double), hipMemcpyDeviceToHost));
     std::memcpy(sign, out.data(), (size_t) batch * sizeof(double));
     std::memcpy(logabs, out.data() + batch, (size_t) batch * sizeof(double));
+    return CS3_OK;
+}
+
+// ---- many low-rank-modified systems (A + dA_c) x = b on the held factors (updates.hip) ---------------------------------
+// Plan: per case its distinct rows R_c and columns C_c (ascending) and the entry of D_c every triplet adds to; the cases
+// in their order cut into tiles (a case joins the current tile unless the union of touched rows would pass the tile
+// width, or the tile already has UPD_MAX_TILE_CASES cases); per tile the touched rows in order of first use = the columns
+// of its Z.  A row that cases of two tiles touch is a column of both.
+static int updates_build(cs3_updates_s &u, int64_t n, int64_t ncases, const int32_t *cp, const int32_t *ci, const int32_t *cj)
+{
+    u.n = n; u.ncases = ncases; u.ntrip = cp[ncases];
+    u.cp.assign(cp, cp + ncases + 1);
+    u.cases.assign((size_t) ncases, UpdCase());
+    u.tpos.assign((size_t) u.ntrip, 0);
+    std::vector<i32> rows, cols;
+    std::vector<char> seen((size_t) n, 0);
+    for (int64_t c = 0; c < ncases; ++c) {
+        rows.assign(ci + cp[c], ci + cp[c + 1]);
+        cols.assign(cj + cp[c], cj + cp[c + 1]);
+        std::sort(rows.begin(), rows.end()); rows.erase(std::unique(rows.begin(), rows.end()), rows.end());
+        std::sort(cols.begin(), cols.end()); cols.erase(std::unique(cols.begin(), cols.end()), cols.end());
+        if (rows.size() > (size_t) UPD_MAX_RANK || cols.size() > (size_t) UPD_MAX_RANK) {
+            set_error("cs3_updates_plan: case " + std::to_string(c) + " touches " + std::to_string(rows.size()) + " rows and " +
+                      std::to_string(cols.size()) + " columns (at most 16 of each)");
+            return CS3_ERR_ARG;
+        }
+        UpdCase &uc = u.cases[(size_t) c];
+        std::memset(&uc, 0, sizeof(uc));
+        uc.r = (int) rows.size(); uc.s = (int) cols.size();
+        for (size_t a = 0; a < cols.size(); ++a) uc.col[a] = cols[a];
+        for (int p = cp[c]; p < cp[c + 1]; ++p) {
+            const int ri = (int) (std::lower_bound(rows.begin(), rows.end(), ci[p]) - rows.begin());
+            const int cc = (int) (std::lower_bound(cols.begin(), cols.end(), cj[p]) - cols.begin());
+            u.tpos[(size_t) p] = (unsigned char) (ri * UPD_MAX_RANK + cc);
+        }
+        u.max_rank = std::max<i64>(u.max_rank, std::max(uc.r, uc.s));
+        for (i32 r : rows) if (!seen[(size_t) r]) { seen[(size_t) r] = 1; u.nrows_unique += 1; }
+    }
+    int tile = UPD_MAX_TILE;
+    if (const char *e = std::getenv("CS3_UPD_TILE")) tile = (int) std::min<long long>(UPD_MAX_TILE, std::max<long long>(1, std::atoll(e)));
+    u.tile_cap = std::max<int>(tile, (int) u.max_rank);           // every case fits a tile of its own
+    std::vector<i32> pos((size_t) n, -1);                          // column of a row in the current tile
+    std::vector<i32> cur;                                          // the current tile's rows
+    cs3_updates_s::Tile t{0, 0, 0, 0, 0, 0};
+    auto close_tile = [&]() {
+        t.t = (int) cur.size();
+        t.t_solve = std::min(u.tile_cap, (t.t + 63) / 64 * 64);   // few distinct widths: one captured graph per width
+        t.unit0 = (i64) u.unit_row.size();
+        u.unit_row.insert(u.unit_row.end(), cur.begin(), cur.end());
+        u.unit_row.insert(u.unit_row.end(), (size_t) (t.t_solve - t.t), -1);
+        u.tiles.push_back(t);
+        for (i32 r : cur) pos[(size_t) r] = -1;
+        cur.clear();
+    };
+    for (int64_t c = 0; c < ncases; ++c) {
+        rows.assign(ci + cp[c], ci + cp[c + 1]);
+        std::sort(rows.begin(), rows.end()); rows.erase(std::unique(rows.begin(), rows.end()), rows.end());
+        int fresh = 0;
+        for (i32 r : rows) fresh += pos[(size_t) r] < 0;
+        if (t.nc > 0 && ((int) cur.size() + fresh > u.tile_cap || t.nc == UPD_MAX_TILE_CASES)) {
+            close_tile();
+            t = cs3_updates_s::Tile{(int) c, 0, 0, 0, 0, 0};
+        }
+        UpdCase &uc = u.cases[(size_t) c];
+        for (size_t k = 0; k < rows.size(); ++k) {
+            i32 &p = pos[(size_t) rows[k]];
+            if (p < 0) { p = (i32) cur.size(); cur.push_back(rows[k]); }
+            uc.zcol[k] = (unsigned short) p;
+        }
+        t.nc += 1;
+        t.rmax = std::max(t.rmax, uc.r);
+    }
+    close_tile();
+    return CS3_OK;
+}
+
+int cs3_updates_plan(cs3_handle h, int64_t ncases, const int32_t *cp, const int32_t *ci, const int32_t *cj, cs3_updates *out)
+{
+    int rc = guard(h); if (rc) return rc;
+    if (!out) { set_error("cs3_updates_plan: null output"); return CS3_ERR_ARG; }
+    *out = nullptr;
+    if (!cp) { set_error("cs3_updates_plan: null case pointers"); return CS3_ERR_ARG; }
+    if (ncases < 1 || ncases > INT_MAX / 2) { set_error("cs3_updates_plan: ncases must be >= 1"); return CS3_ERR_ARG; }
+    if (cp[0] != 0) { set_error("cs3_updates_plan: cp[0] != 0"); return CS3_ERR_ARG; }
+    for (int64_t c = 0; c < ncases; ++c)
+        if (cp[c + 1] < cp[c]) { set_error("cs3_updates_plan: cp not monotone at case " + std::to_string(c)); return CS3_ERR_ARG; }
+    if (cp[ncases] > 0 && (!ci || !cj)) { set_error("cs3_updates_plan: null index arrays"); return CS3_ERR_ARG; }
+    const int64_t n = h->S.n;
+    for (int64_t c = 0; c < ncases; ++c)
+        for (int p = cp[c]; p < cp[c + 1]; ++p)
+            if (ci[p] < 0 || ci[p] >= n || cj[p] < 0 || cj[p] >= n) {
+                set_error("cs3_updates_plan: index out of range in case " + std::to_string(c));
+                return CS3_ERR_ARG;
+            }
+    cs3_updates_s *u = nullptr;
+    try {
+        u = new cs3_updates_s();
+        if ((rc = updates_build(*u, n, ncases, cp, ci, cj))) { delete u; return rc; }
+        if (h->batch > 1) {
+            delete u;
+            set_error("cs3_updates_plan: handles with batch > 1 are not supported");
+            return CS3_ERR_ARG;
+        }
+        h->plans.push_back(u);
+    } catch (const std::bad_alloc &) {
+        delete u; set_error("cs3_updates_plan: out of memory"); return CS3_ERR_ALLOC;
+    }
+    u->h = h;
+    *out = u;
+    return CS3_OK;
+}
+
+int cs3_updates_free(cs3_updates u)
+{
+    if (!u) return CS3_OK;
+    if (u->h) {
+        if (u->on_device) { (void) hipDeviceSynchronize(); release_plan_device(u); }
+        auto &pl = u->h->plans;
+        pl.erase(std::remove(pl.begin(), pl.end(), u), pl.end());
+    }
+    delete u;
+    return CS3_OK;
+}
+
+int cs3_updates_info(cs3_updates u, int64_t *ncases, int64_t *nrows_unique, int64_t *max_rank, int64_t *ntiles)
+{
+    if (!u) { set_error("cs3_updates_info: null plan"); return CS3_ERR_ARG; }
+    if (ncases) *ncases = u->ncases;
+    if (nrows_unique) *nrows_unique = u->nrows_unique;
+    if (max_rank) *max_rank = u->max_rank;
+    if (ntiles) *ntiles = (int64_t) u->tiles.size();
+    return CS3_OK;
+}
+
+int64_t cs3_debug_updates_tiles(cs3_updates u, int32_t *first_case, int32_t *ncases, int32_t *nrows, int32_t *width)
+{
+    if (!u) { set_error("cs3_debug_updates_tiles: null plan"); return CS3_ERR_ARG; }
+    for (size_t k = 0; k < u->tiles.size(); ++k) {
+        const auto &t = u->tiles[k];
+        if (first_case) first_case[k] = t.c0;
+        if (ncases) ncases[k] = t.nc;
+        if (nrows) nrows[k] = t.t;
+        if (width) width[k] = t.t_solve;
+    }
+    return (int64_t) u->tiles.size();
+}
+
+int cs3_debug_alloc_counters(cs3_handle h, int64_t *allocs, int64_t *syncs)
+{
+    int rc = guard(h); if (rc) return rc;
+    if (allocs) *allocs = h->dbg_allocs;
+    if (syncs) *syncs = h->dbg_syncs;
+    return CS3_OK;
+}
+
+static int updates_check(const char *who, cs3_handle h, cs3_updates u, const double *cx, const double *b, const double *X)
+{
+    int rc = guard(h); if (rc) return rc;
+    if (!u) { set_error(std::string(who) + ": null plan"); return CS3_ERR_ARG; }
+    if (!b || !X || (u->ntrip > 0 && !cx)) { set_error(std::string(who) + ": null argument"); return CS3_ERR_ARG; }
+    if (u->h != h) { set_error(std::string(who) + ": the plan was made for another handle"); return CS3_ERR_ARG; }
+    if (!h->factored) { set_error(std::string(who) + ": no successful factorisation"); return CS3_ERR_STATE; }
+    return CS3_OK;
+}
+
+// Tables of the plan in HBM, the handle's Z and x0, room for the widest tile in the sweep buffers: everything a call
+// needs, so that later calls neither allocate nor synchronise.
+static int ensure_updates(cs3_handle h, cs3_updates_s *u)
+{
+    int wmax = 1;
+    for (const auto &t : u->tiles) wmax = std::max(wmax, t.t_solve);
+    if (!u->on_device) {
+        static bool prepared = false;
+        if (!prepared) { CS3_HIP(prepare_updates_kernels()); prepared = true; }
+        int rc;
+        if ((rc = upload(&u->d_cases, u->cases))) return rc;
+        if ((rc = upload(&u->d_cp, u->cp))) return rc;
+        if ((rc = upload(&u->d_tpos, u->tpos))) return rc;
+        if ((rc = upload(&u->d_unit, u->unit_row))) return rc;
+        CS3_HIP(hipMalloc((void **) &u->d_y, (size_t) u->ncases * UPD_MAX_RANK * sizeof(double)));
+        CS3_HIP(hipMalloc((void **) &u->d_flag, (size_t) u->ncases * sizeof(int)));
+        CS3_HIP(hipMalloc((void **) &u->d_rpiv, (size_t) u->ncases * sizeof(double)));
+        h->dbg_allocs += 7;
+        u->on_device = true;
+    }
+    const size_t n1 = std::max<size_t>(1, (size_t) h->S.n);
+    if (!h->d_upd_x0) { CS3_HIP(hipMalloc((void **) &h->d_upd_x0, n1 * sizeof(double))); h->dbg_allocs += 1; }
+    if (h->upd_z_cols < wmax) {
+        if (h->d_upd_z) {                                  // a wider plan than any before: the old tile may still be in use
+            CS3_HIP(hipDeviceSynchronize());
+            h->dbg_syncs += 1;
+            (void) hipFree(h->d_upd_z);
+            h->d_upd_z = nullptr; h->upd_z_cols = 0;
+        }
+        CS3_HIP(hipMalloc((void **) &h->d_upd_z, n1 * (size_t) wmax * sizeof(double)));
+        h->dbg_allocs += 1;
+        h->upd_z_cols = wmax;
+    }
+    return ensure_rhs_capacity(h, wmax);
+}
+
+static int updates_run(cs3_handle h, cs3_updates_s *u, const double *cx_dev, const double *b_dev, double sing_tol, double *X_dev,
+                       double *rpiv_dev, hipStream_t st)
+{
+    int rc = ensure_updates(h, u);
+    if (rc) return rc;
+    const i64 n = h->S.n;
+    const UpdTables T{u->d_cases, u->d_cp, u->d_tpos, u->d_y, u->d_flag};
+    double *rpiv = rpiv_dev ? rpiv_dev : u->d_rpiv;
+    if (n > 0) {
+        CS3_HIP(hipMemcpyAsync(h->d_upd_x0, b_dev, (size_t) n * sizeof(double), hipMemcpyDeviceToDevice, st));
+        if ((rc = run_solve(h, h->d_upd_x0, 1, 0, st))) return rc;
+    }
+    for (const auto &t : u->tiles) {
+        if (n > 0 && t.t > 0) {
+            CS3_HIP(launch_upd_units(h->d_upd_z, n, t.t_solve, u->d_unit + t.unit0, st));
+            if ((rc = run_solve(h, h->d_upd_z, t.t_solve, 0, st))) return rc;
+        }
+        CS3_HIP(launch_upd_capacitance(T, cx_dev, h->d_upd_z, t.t_solve, h->d_upd_x0, t.c0, t.nc, sing_tol, rpiv, st));
+        CS3_HIP(launch_upd_apply(T, h->d_upd_z, t.t_solve, h->d_upd_x0, n, t.c0, t.nc, t.rmax, u->ncases, X_dev, st));
+    }
+    return CS3_OK;
+}
+
+int cs3_updates_solve_dev(cs3_handle h, cs3_updates u, const double *cx_dev, const double *b_dev, double sing_tol, double *X_dev,
+                          double *rpiv_dev, void *stream)
+{
+    int rc = updates_check("cs3_updates_solve_dev", h, u, cx_dev, b_dev, X_dev);
+    if (rc) return rc;
+    return updates_run(h, u, cx_dev, b_dev, sing_tol, X_dev, rpiv_dev, (hipStream_t) stream);
+}
+
+int cs3_updates_solve(cs3_handle h, cs3_updates u, const double *cx, const double *b, double sing_tol, double *X, double *rpiv)
+{
+    int rc = updates_check("cs3_updates_solve", h, u, cx, b, X);
+    if (rc) return rc;
+    const size_t n = (size_t) h->S.n, nc = (size_t) u->ncases, nt = (size_t) u->ntrip;
+    if (!u->d_cx) CS3_HIP(hipMalloc((void **) &u->d_cx, std::max<size_t>(nt, 1) * sizeof(double)));
+    double *d_b = nullptr, *d_x = nullptr;                 // [n] and [n, ncases], for this call
+    CS3_HIP(hipMalloc((void **) &d_b, std::max<size_t>(n * (nc + 1), 1) * sizeof(double)));
+    d_x = d_b + n;
+    hipError_t e = nt ? hipMemcpy(u->d_cx, cx, nt * sizeof(double), hipMemcpyHostToDevice) : hipSuccess;
+    if (e == hipSuccess && n) e = hipMemcpy(d_b, b, n * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        rc = updates_run(h, u, u->d_cx, d_b, sing_tol, d_x, nullptr, nullptr);
+        if (rc == CS3_OK && n) e = hipMemcpy(X, d_x, n * nc * sizeof(double), hipMemcpyDeviceToHost);
+        if (rc == CS3_OK && e == hipSuccess && rpiv) e = hipMemcpy(rpiv, u->d_rpiv, nc * sizeof(double), hipMemcpyDeviceToHost);
+        if (rc == CS3_OK && e == hipSuccess) e = hipDeviceSynchronize();
+    }
+    (void) hipFree(d_b);
+    if (rc) return rc;
+    CS3_HIP(e);
     return CS3_OK;
 }
 

@@ -212,4 +212,30 @@ hipError_t launch_est_finalize(const EstState *state, long long batch, double *c
 // diag[n]: virtual pool offset of every pivot's diagonal
 hipError_t launch_slogdet(const DeviceFactor &D, const long long *diag, double *sign, double *logabs, hipStream_t st);
 
+// updates.hip: many low-rank-modified systems (A + dA_c) x = b on the held factors (cs3_updates_*).
+constexpr int UPD_MAX_RANK = 16;               // distinct rows / columns of one case
+constexpr int UPD_MAX_TILE = 1024;             // columns of A^-1 solved for at a time (the width the many-RHS path is tuned at)
+constexpr int UPD_MAX_TILE_CASES = 1024;       // cases of one tile: lanes of one k_upd_apply workgroup
+struct UpdCase {                  // one case as the kernels read it
+    int r, s;                     // distinct rows / columns
+    int col[UPD_MAX_RANK];        // its columns C_c, ascending (rows of Z and of x0 to gather)
+    unsigned short zcol[UPD_MAX_RANK];    // where its rows R_c, ascending, sit among the columns of its tile of Z
+};
+struct UpdTables {                // device arrays of one plan
+    const UpdCase *cases;         // [ncases]
+    const int *cp;                // [ncases + 1] triplets of each case
+    const unsigned char *tpos;    // [cp[ncases]] entry of D_c (16 x 16, row-major) each triplet adds to
+    double *y;                    // [ncases][16] S_c^-1 D_c x0[C_c], zero-padded
+    int *flag;                    // [ncases] 1: singular, its column of X is NaN
+};
+hipError_t prepare_updates_kernels();
+// Z [n, t] = the unit vectors e_{unit_row[j]} (a negative row: a zero column)
+hipError_t launch_upd_units(double *Z, long long n, int t, const int *unit_row, hipStream_t st);
+// the cases c0 .. c0 + nc - 1 of one tile: y, rpiv, flag from the solved tile Z [n, t] and x0
+hipError_t launch_upd_capacitance(const UpdTables &T, const double *cx, const double *Z, int t, const double *x0, int c0, int nc,
+                                  double sing_tol, double *rpiv, hipStream_t st);
+// columns c0 .. c0 + nc - 1 of X [n, ldx]; rmax = the largest rank among them
+hipError_t launch_upd_apply(const UpdTables &T, const double *Z, int t, const double *x0, long long n, int c0, int nc, int rmax,
+                            long long ldx, double *X, hipStream_t st);
+
 }  // namespace cs3

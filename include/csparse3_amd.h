@@ -28,6 +28,7 @@ extern "C" {
 #endif
 
 typedef struct cs3_handle_s *cs3_handle;
+typedef struct cs3_updates_s *cs3_updates;     /* a list of sparse modifications of a handle's matrix (below) */
 
 enum cs3_status {
     CS3_OK = 0,
@@ -188,6 +189,56 @@ int cs3_condest(cs3_handle h, const double *Ax, double *cond, double *inv_norm);
 int cs3_slogdet_dev(cs3_handle h, double *sign_dev, double *logabs_dev, void *stream);
 int cs3_slogdet(cs3_handle h, double *sign, double *logabs);
 
+/* ---- many low-rank-modified systems (A + dA_c) x = b on the held factors -
+ * Contingency screening ("compensation" in the power-systems literature): the factors of A are held, case c changes a
+ * handful of entries, and x_c is wanted for a thousand cases.  Nothing is refactorised (so a modified matrix that would
+ * fail the static pivot test is no obstacle): Sherman-Morrison-Woodbury on the base factors, one small dense system
+ * per case, all on the device.
+ *
+ * Case c is a sparse matrix dA_c given as triplets (i, j, v); duplicates of one (i, j) inside a case ADD.  With R_c its
+ * distinct rows (r of them, ascending), C_c its distinct columns (s, ascending), D_c the dense r x s block,
+ * x0 = A^-1 b and Z = A^-1 E_R (the columns of A^-1 of the touched rows):
+ *     G_c = Z[C_c, R_c]   S_c = I_r + D_c G_c   y_c = S_c^-1 (D_c x0[C_c])   x_c = x0 - Z[:, R_c] y_c
+ * S_c is eliminated with partial pivoting (largest |.|, ties to the lowest row).  A case without entries gives x0, bit for
+ * bit what cs3_solve_dev gives for b.  S_c singular means A + dA_c is singular (an outage that islands the network):
+ * an answer, not an error.  rpiv[c] = min_k |pivot_k| / max(1, max |S_c|) (1.0 for an empty case): the smallest pivot on
+ * the scale of the identity that S_c perturbs -- normalising by max |S_c| alone would give 1.0 for EVERY case of rank 1,
+ * singular or not.  A case with rpiv[c] <= sing_tol has its column of X filled with NaN (sing_tol <= 0 disables the test;
+ * an exactly zero pivot always counts); the other cases of the call are unaffected.
+ *
+ * Two phases, as analysis and factorisation are: the case list of a screening run is fixed while values change.
+ * cs3_updates_plan: host, pattern only, needs no GPU.  cp[ncases + 1] (cp[0] = 0), ci / cj[cp[ncases]] rows and columns
+ *   of the triplets of each case.  Checks, in this order: null pointers, ncases < 1, cp not monotone, an index outside
+ *   [0, n), a case with more than 16 distinct rows or more than 16 distinct columns (the message names the case), a
+ *   handle with batch > 1 (not supported): CS3_ERR_ARG.
+ *   Cases are grouped, in their order, into TILES whose union of touched rows is at most 1024 columns of A^-1 (and at
+ *   most 1024 cases); a tile is one many-right-hand-side solve, and a row that cases of two tiles touch is solved for in
+ *   both.  CS3_UPD_TILE in the environment, read by this call, lowers the width (for tests that must cross tile
+ *   boundaries; a case always fits a tile of its own).
+ * cs3_updates_info: number of cases, distinct touched rows over all cases, largest r or s, number of tiles.  Any pointer
+ *   may be NULL.
+ * cs3_updates_solve_dev: cx_dev[cp[ncases]] the values in the plan's triplet order; b_dev[n]; X_dev [n, ncases] row-major
+ *   (the library's multi-vector layout: case c is column c); rpiv_dev[ncases] may be NULL.  Asynchronous on `stream`.
+ *   Checks, in this order: null arguments, a plan made for another handle: CS3_ERR_ARG; no successful factorisation:
+ *   CS3_ERR_STATE.  LU and Cholesky handles both work, and dA_c need not be symmetric on a Cholesky handle.
+ *   Workspace: n x 1024 doubles (less when every tile is narrower) + n doubles on the handle, a few hundred bytes per case
+ *   on the plan, allocated by the first call; later calls neither allocate nor synchronise.
+ * cs3_updates_solve: the same from host arrays (synchronises); the same bits.
+ * A plan survives refactorisations of its handle.  Plans and handle may be freed in either order: freeing the handle
+ * releases the device memory of its plans, which can then only be freed (a solve with one is CS3_ERR_ARG).
+ *
+ * Out of scope: batched handles; transposed systems; several base right-hand sides per call; more than 16 distinct rows
+ * or columns per case; exploiting the sparsity of the unit right-hand sides inside the sweeps; solving with A^-T E_C
+ * instead of A^-1 E_R when a list has fewer distinct columns than rows. */
+int cs3_updates_plan(cs3_handle h, int64_t ncases, const int32_t *cp, const int32_t *ci, const int32_t *cj,
+                     cs3_updates *out);
+int cs3_updates_free(cs3_updates u);
+int cs3_updates_info(cs3_updates u, int64_t *ncases, int64_t *nrows_unique, int64_t *max_rank, int64_t *ntiles);
+int cs3_updates_solve_dev(cs3_handle h, cs3_updates u, const double *cx_dev, const double *b_dev,
+                          double sing_tol, double *X_dev, double *rpiv_dev, void *stream);
+int cs3_updates_solve(cs3_handle h, cs3_updates u, const double *cx, const double *b,
+                      double sing_tol, double *X, double *rpiv);
+
 /* ---- factors back to the host in CSparse's CSC form ---------------------
  * L: diagonal FIRST in each column (unit for LU); U: diagonal LAST; row
  * indices sorted otherwise.  Sizes from cs3_info.nnz_l / nnz_u.  NumPy-style
@@ -219,6 +270,14 @@ int cs3_debug_poison_lds(void *stream);
  * wait and gives up: the step must then be reported as failed by cs3_factor_status (CS3_ERR_STATE), never pass silently.
  * Process-wide; on = 0 restores the normal path.  For the test of that path. */
 int cs3_debug_withhold_handover(int on);
+/* Diagnostic, for the tests of the "no allocation, no synchronisation" contracts: how many device allocations (graph
+ * instantiations included) and host synchronisations the handle has made so far in its solves and in the paths built on
+ * them (the low-rank-modified solves).  Either pointer may be NULL. */
+int cs3_debug_alloc_counters(cs3_handle h, int64_t *allocs, int64_t *syncs);
+/* The tiles of a plan of low-rank-modified solves: returns their number and, for arrays that are not null, per tile its
+ * first case, its number of cases, its touched rows and the number of right-hand sides it is solved with (the touched rows
+ * rounded up to a multiple of 64, at most the tile width).  Diagnostics, tests and tools. */
+int64_t cs3_debug_updates_tiles(cs3_updates u, int32_t *first_case, int32_t *ncases, int32_t *nrows, int32_t *width);
 /* Factorisation schedule: supernode id, front order r and width w per schedule slot. */
 int cs3_debug_schedule(cs3_handle h, int32_t *sched, int32_t *front_r, int32_t *front_w);
 /* The bottom forest (subtrees of small fronts walked by one workgroup each, all in one launch): returns the
