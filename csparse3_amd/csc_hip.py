@@ -126,6 +126,8 @@ def lib():
         L.cs3_debug_updates_tiles.argtypes = [vp] + [_i32p] * 4
         L.cs3_debug_updates_tiles.restype = I64
         L.cs3_debug_alloc_counters.argtypes = [vp, C.POINTER(I64), C.POINTER(I64)]
+        L.cs3_debug_live_device_buffers.argtypes = []
+        L.cs3_debug_live_device_buffers.restype = I64
         L.cs3_export_factor_dev.argtypes = [vp, vp, vp]
         L.cs3_import_factor_dev.argtypes = [vp, vp, vp]
         L.cs3_get_factors.argtypes = [vp, I64, _i32p, _i32p, _f64p, _i32p, _i32p, _f64p]
@@ -180,6 +182,11 @@ def _pf(a):
 
 def device_count():
     return int(lib().cs3_device_count())
+
+
+def debug_live_device_buffers():
+    """Device blocks the library holds right now, over all handles, plans and calls (process-wide; 0 when all are freed)."""
+    return int(lib().cs3_debug_live_device_buffers())
 
 
 # ------------------------------------------------------ ordering / symbolic --

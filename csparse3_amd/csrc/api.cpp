@@ -12,6 +12,7 @@
 #include <tuple>
 
 #include "cs3_device.hpp"
+#include "cs3_hipmem.hpp"
 
 using namespace cs3;
 
@@ -22,15 +23,6 @@ thread_local std::string g_error;
 namespace cs3 {
 void set_error(const std::string &msg) { g_error = msg; }
 }
-
-#define CS3_HIP(call)                                                                   \
-    do {                                                                                \
-        hipError_t e_ = (call);                                                         \
-        if (e_ != hipSuccess) {                                                         \
-            set_error(std::string(#call) + ": " + hipGetErrorString(e_));               \
-            return CS3_ERR_HIP;                                                         \
-        }                                                                               \
-    } while (0)
 
 // Captured graphs, one cache per handle, keyed by what a capture bakes in: (operation, trans, nrhs, the caller's X when
 // its address is inside the graph, else null).
@@ -57,32 +49,32 @@ struct cs3_handle_s {
     double factor_inv_tol = 0.0, fused_inv_tol = 0.0;     // what the factor / fused-step graphs were captured with
     const void *fused_last_x = nullptr;
     int fused_same_x = 0;
-    i64 *d_lmap = nullptr, *d_umap = nullptr;
-    double *d_lx = nullptr, *d_ux = nullptr;
     long long fail_col = -1;
     bool inverses_valid = false;      // inverted diagonal blocks (many-RHS GEMM sweeps) match the current factors
-    // residual / refinement: the analysed pattern in row view (built on first use), a work array, a result word
     std::vector<i32> Ap_host, Ai_host;
-    int *d_rp = nullptr, *d_rj = nullptr, *d_rmap = nullptr;
-    int *d_cp = nullptr, *d_ci = nullptr, *d_cmap = nullptr;       // the same pattern in column view (transposed products)
-    double *d_res = nullptr;
-    long long res_cap = 0;
-    unsigned long long *d_maxbits = nullptr;
-    // condition estimates (estimate.hip), allocated on first use: X [batch][n] (stable address: the solves on it replay the
-    // cached graphs), the sign vectors [2][batch][n], one state per matrix, the chunks of the partial reductions, the two
-    // "wants" counters; the host forms' buffers; the virtual pool offset of every pivot's diagonal (log-determinants)
-    double *d_est_x = nullptr;
-    signed char *d_est_s = nullptr;
-    EstState *d_est_state = nullptr;
-    EstPart *d_est_parts = nullptr;
-    unsigned *d_est_cnt = nullptr;
-    double *d_est_ax = nullptr, *d_est_out = nullptr;
-    i64 *d_diag = nullptr;
-    // low-rank-modified solves (updates.hip): the plans made for this handle, the tile of A^-1 columns Z [n][upd_z_cols] and
-    // x0 [n] (stable addresses: the solves on them replay the cached graphs), allocated on first use
-    std::vector<cs3_updates_s *> plans;
-    double *d_upd_z = nullptr, *d_upd_x0 = nullptr;
-    long long upd_z_cols = 0;
+    std::vector<cs3_updates_s *> plans;       // the plans made for this handle (cs3_updates_plan)
+    // Every HBM block of the handle, one group per feature that builds it; release_device drops them all at once.  A
+    // new feature declares its DevBuf in a group here and allocates it in its ensure_*: nothing else has to know.
+    struct Memory {
+        // ensure_device: the arrays behind D's pointers (allocated together, die together) ...
+        std::vector<DevBuf<unsigned char>> factor;
+        // ... but for the sweep buffers D.cv, D.xp, D.bigv, D.gv, which grow with nrhs (ensure_rhs_capacity)
+        DevBuf<double> cv, xp, bigv, gv;
+        // ensure_row_view / ensure_col_view (residuals, refinement): the analysed pattern by rows, the same by columns
+        // (transposed products), the residual R [batch][n][k] (grows), the bits of max |dx|
+        struct { DevBuf<int> rp, rj, rmap, cp, ci, cmap; DevBuf<double> res; DevBuf<unsigned long long> maxbits; } view;
+        // ensure_estimator (estimate.hip): X [batch][n] (stable address: the solves on it replay the cached graphs), the
+        // sign vectors [2][batch][n], one state per matrix, the chunks of the partial reductions, the two "wants" counters
+        struct { DevBuf<double> x; DevBuf<signed char> s; DevBuf<EstState> state; DevBuf<EstPart> parts; DevBuf<unsigned> cnt; } est;
+        // the host forms of condest / slogdet stage through these: values of A, results [2][batch]
+        struct { DevBuf<double> ax, out; } host;
+        DevBuf<i64> diag;             // ensure_diag_map (log-determinants): virtual pool offset of every pivot's diagonal
+        // cs3_get_factors: where the entries of L and U sit in the pool, and their values gathered
+        struct { DevBuf<i64> lmap, umap; DevBuf<double> lx, ux; } exp;
+        // ensure_updates (updates.hip): the tile of A^-1 columns Z [n][widest tile so far] (grows) and x0 [n] (stable
+        // addresses: the solves on them replay the cached graphs)
+        struct { DevBuf<double> z, x0; } upd;
+    } mem;
     // diagnostics (cs3_debug_alloc_counters): device allocations / graph instantiations and host synchronisations made by the
     // solves and the paths on top of them
     long long dbg_allocs = 0, dbg_syncs = 0;
@@ -105,22 +97,34 @@ struct cs3_updates_s {
     };
     std::vector<Tile> tiles;
     std::vector<i32> unit_row;                // row of the unit entry of every tile column, -1: a zero column
-    // device copies (uploaded by the first solve) and per-case results
-    UpdCase *d_cases = nullptr;
-    int *d_cp = nullptr, *d_unit = nullptr, *d_flag = nullptr;
-    unsigned char *d_tpos = nullptr;
-    double *d_y = nullptr, *d_rpiv = nullptr, *d_cx = nullptr;
+    // device copies (uploaded by the first solve), per-case results, the host form's copy of the triplet values
+    struct Memory {
+        DevBuf<UpdCase> cases;
+        DevBuf<int> cp, unit, flag;
+        DevBuf<unsigned char> tpos;
+        DevBuf<double> y, rpiv, cx;
+    } mem;
     bool on_device = false;
 };
 
 namespace {
 
+// One array of the DeviceFactor: the block joins h->mem.factor, *field points at it.
 template <class T>
-int upload(T **dst, const std::vector<T> &src)
+int factor_alloc(cs3_handle h, T **field, size_t count)
 {
-    size_t bytes = std::max<size_t>(src.size(), 1) * sizeof(T);
-    CS3_HIP(hipMalloc((void **) dst, bytes));
-    if (!src.empty()) CS3_HIP(hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
+    DevBuf<unsigned char> b;
+    CS3_HIP(b.alloc(count * sizeof(T)));
+    *field = reinterpret_cast<T *>(b.get());
+    h->mem.factor.push_back(std::move(b));
+    return CS3_OK;
+}
+
+template <class T>
+int factor_upload(cs3_handle h, T **field, const std::vector<T> &src)
+{
+    if (int rc = factor_alloc(h, field, src.size())) return rc;
+    if (!src.empty()) CS3_HIP(hipMemcpy(*field, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
     return CS3_OK;
 }
 
@@ -144,35 +148,19 @@ bool graph_op_is(const GraphKey &k, int op) { return std::get<0>(k) == op; }
 
 void release_plan_device(cs3_updates_s *u)
 {
-    void **ptrs[] = {(void **) &u->d_cases, (void **) &u->d_cp, (void **) &u->d_unit, (void **) &u->d_flag, (void **) &u->d_tpos,
-                     (void **) &u->d_y, (void **) &u->d_rpiv, (void **) &u->d_cx};
-    for (void **p : ptrs) if (*p) { (void) hipFree(*p); *p = nullptr; }
+    u->mem = cs3_updates_s::Memory();
     u->on_device = false;
 }
 
 // Frees every HBM allocation of the handle (ensure_device's error path and cs3_free).
 void release_device(cs3_handle h)
 {
-    DeviceFactor &D = h->D;
     for (cs3_updates_s *u : h->plans) release_plan_device(u);
-    h->upd_z_cols = 0;
     (void) drop_graphs(h, [](const GraphKey &) { return true; }, true);     // (cs3_free has synchronised)
     if (h->cap_stream) { (void) hipStreamDestroy(h->cap_stream); h->cap_stream = nullptr; }
     h->fj.destroy();
-    void **ptrs[] = {(void **) &D.fdesc, (void **) &D.st_idx, (void **) &D.fa_tgt, (void **) &D.fa_src, (void **) &D.ch_tab, (void **) &D.rel_idx,
-                     (void **) &D.sdesc, (void **) &D.sdesc1, (void **) &D.sub_tasks, (void **) &D.sub_fronts, (void **) &D.sub_lvl,
-                     (void **) &D.sub_rel, (void **) &D.sub_st, (void **) &D.sub_child, (void **) &D.sub_a_tgt, (void **) &D.sub_a_src,
-                     (void **) &D.axf, (void **) &D.fasm_src, (void **) &D.fasm_tgt, (void **) &D.flong_src, (void **) &D.rl_pairs,
-                     (void **) &D.sl_src,                     (void **) &D.q, (void **) &D.ila_pairs, (void **) &D.inv_tasks, (void **) &D.dinv, (void **) &D.gv,
-                     (void **) &D.ax, (void **) &D.pool, (void **) &D.dbuf, (void **) &D.tbuf, (void **) &D.bigv,
-                     (void **) &D.cv, (void **) &D.xp, (void **) &D.status, (void **) &h->d_lmap, (void **) &h->d_umap,
-                     (void **) &h->d_lx, (void **) &h->d_ux, (void **) &h->d_rp, (void **) &h->d_rj, (void **) &h->d_rmap,
-                     (void **) &h->d_cp, (void **) &h->d_ci, (void **) &h->d_cmap, (void **) &h->d_res, (void **) &h->d_maxbits,
-                     (void **) &h->d_est_x, (void **) &h->d_est_s, (void **) &h->d_est_state, (void **) &h->d_est_parts, (void **) &h->d_est_cnt,
-                     (void **) &h->d_est_ax, (void **) &h->d_est_out, (void **) &h->d_diag, (void **) &h->d_upd_z, (void **) &h->d_upd_x0};
-    h->res_cap = 0;
-    for (void **p : ptrs) if (*p) { (void) hipFree(*p); *p = nullptr; }
-    D.nrhs_cap = 0;
+    h->mem = cs3_handle_s::Memory();
+    h->D = DeviceFactor();                  // (no pointer of it outlives its block; nrhs_cap = 0)
     h->on_device = false;
 }
 
@@ -207,8 +195,7 @@ int ensure_device(cs3_handle h)
 
 int ensure_device_impl(cs3_handle h)
 {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
+    if (!device_visible()) {
         set_error("no HIP device visible: the numeric path runs on the GPU only (there is no CPU fallback)");
         return CS3_ERR_HIP;
     }
@@ -251,53 +238,54 @@ int ensure_device_impl(cs3_handle h)
     if (!S.sub_forest.empty()) {
         std::vector<SolveDesc> sdesc1(S.nsuper);
         for (i32 t = 0; t < S.nsuper; ++t) sdesc1[t] = solve_desc_of(S, S.ssched1[t]);
-        if ((rc = upload(&D.sdesc1, sdesc1))) return rc;
-        if ((rc = upload(&D.sub_tasks, S.sub_tasks))) return rc;
-        if ((rc = upload(&D.sub_fronts, S.sub_fronts))) return rc;
-        if ((rc = upload(&D.sub_lvl, S.sub_lvl))) return rc;
-        if ((rc = upload(&D.sub_rel, S.sub_rel))) return rc;
-        if ((rc = upload(&D.sub_st, S.sub_st))) return rc;
-        if ((rc = upload(&D.sub_child, S.sub_child))) return rc;
-        if ((rc = upload(&D.sub_a_tgt, S.sub_a_tgt))) return rc;
-        if ((rc = upload(&D.sub_a_src, S.sub_a_src))) return rc;
-        CS3_HIP(hipMalloc((void **) &D.axf, std::max<size_t>(1, (size_t) (D.batch * D.n_sub_a)) * sizeof(double)));
+        if ((rc = factor_upload(h, &D.sdesc1, sdesc1))) return rc;
+        if ((rc = factor_upload(h, &D.sub_tasks, S.sub_tasks))) return rc;
+        if ((rc = factor_upload(h, &D.sub_fronts, S.sub_fronts))) return rc;
+        if ((rc = factor_upload(h, &D.sub_lvl, S.sub_lvl))) return rc;
+        if ((rc = factor_upload(h, &D.sub_rel, S.sub_rel))) return rc;
+        if ((rc = factor_upload(h, &D.sub_st, S.sub_st))) return rc;
+        if ((rc = factor_upload(h, &D.sub_child, S.sub_child))) return rc;
+        if ((rc = factor_upload(h, &D.sub_a_tgt, S.sub_a_tgt))) return rc;
+        if ((rc = factor_upload(h, &D.sub_a_src, S.sub_a_src))) return rc;
+        if ((rc = factor_alloc(h, &D.axf, (size_t) (D.batch * D.n_sub_a)))) return rc;
     }
-    if ((rc = upload(&D.sdesc, sdesc))) return rc;
-    if ((rc = upload(&D.fasm_src, S.fasm_src))) return rc;
-    if ((rc = upload(&D.fasm_tgt, S.fasm_tgt))) return rc;
-    if ((rc = upload(&D.flong_src, S.flong_src))) return rc;
-    if ((rc = upload(&D.rl_pairs, S.rl_pairs))) return rc;
-    if ((rc = upload(&D.sl_src, S.sl_src))) return rc;
-    if ((rc = upload(&D.fdesc, fdesc))) return rc;
-    if ((rc = upload(&D.st_idx, S.st_idx))) return rc;
-    if ((rc = upload(&D.fa_tgt, S.fa_tgt))) return rc;
-    if ((rc = upload(&D.fa_src, S.fa_src))) return rc;
+    if ((rc = factor_upload(h, &D.sdesc, sdesc))) return rc;
+    if ((rc = factor_upload(h, &D.fasm_src, S.fasm_src))) return rc;
+    if ((rc = factor_upload(h, &D.fasm_tgt, S.fasm_tgt))) return rc;
+    if ((rc = factor_upload(h, &D.flong_src, S.flong_src))) return rc;
+    if ((rc = factor_upload(h, &D.rl_pairs, S.rl_pairs))) return rc;
+    if ((rc = factor_upload(h, &D.sl_src, S.sl_src))) return rc;
+    if ((rc = factor_upload(h, &D.fdesc, fdesc))) return rc;
+    if ((rc = factor_upload(h, &D.st_idx, S.st_idx))) return rc;
+    if ((rc = factor_upload(h, &D.fa_tgt, S.fa_tgt))) return rc;
+    if ((rc = factor_upload(h, &D.fa_src, S.fa_src))) return rc;
     {
         std::vector<i32> tab(S.ch_tab);
         tab.resize(tab.size() + 4, 0);                          // (16-byte loads of the last entry stay inside the array)
-        if ((rc = upload(&D.ch_tab, tab))) return rc;
+        if ((rc = factor_upload(h, &D.ch_tab, tab))) return rc;
     }
-    if ((rc = upload(&D.rel_idx, S.rel_idx))) return rc;
-    if ((rc = upload(&D.q, S.q))) return rc;
-    if ((rc = upload(&D.ila_pairs, S.ila_pairs))) return rc;
-    if ((rc = upload(&D.inv_tasks, S.inv_tasks))) return rc;
-    CS3_HIP(hipMalloc((void **) &D.dinv, std::max<size_t>(1, (size_t) (D.batch * D.dinv_size)) * sizeof(double)));
+    if ((rc = factor_upload(h, &D.rel_idx, S.rel_idx))) return rc;
+    if ((rc = factor_upload(h, &D.q, S.q))) return rc;
+    if ((rc = factor_upload(h, &D.ila_pairs, S.ila_pairs))) return rc;
+    if ((rc = factor_upload(h, &D.inv_tasks, S.inv_tasks))) return rc;
+    if ((rc = factor_alloc(h, &D.dinv, (size_t) (D.batch * D.dinv_size)))) return rc;
     D.il_len = S.il_len;
     D.pm_stride = S.pool_size - S.il_len;
     D.ngroups = (D.batch + 63) / 64;
     const size_t il_doubles = (size_t) (D.ngroups * 64 * D.il_len);
-    CS3_HIP(hipMalloc((void **) &D.pool, (il_doubles + (size_t) (D.batch * D.pm_stride) + POOL_SLACK) * sizeof(double)));   // slack: see k_fwd_rhs
+    if ((rc = factor_alloc(h, &D.pool, il_doubles + (size_t) (D.batch * D.pm_stride) + POOL_SLACK))) return rc;   // slack: see k_fwd_rhs
     D.pool_il = D.pool;
     D.pool_pm = D.pool + il_doubles - D.il_len;            // virtual offsets >= il_len index this pointer directly
-    CS3_HIP(hipMalloc((void **) &D.dbuf, std::max<size_t>(1, (size_t) (D.batch * D.dbuf_size)) * sizeof(double)));
-    CS3_HIP(hipMalloc((void **) &D.ax, std::max<size_t>(1, (size_t) (D.batch * D.nnz_a)) * sizeof(double)));
-    CS3_HIP(hipMalloc((void **) &D.status, 4 * sizeof(int)));    // [0] the status word, [1], [2] unused, [3] a hand-over between waves timed out
+    if ((rc = factor_alloc(h, &D.dbuf, (size_t) (D.batch * D.dbuf_size)))) return rc;
+    if ((rc = factor_alloc(h, &D.ax, (size_t) (D.batch * D.nnz_a)))) return rc;
+    if ((rc = factor_alloc(h, &D.status, 4))) return rc;    // [0] the status word, [1], [2] unused, [3] a hand-over between waves timed out
     CS3_HIP(hipMemset(D.status, 0, 4 * sizeof(int)));
     CS3_HIP(hipMemset(D.status, 0x7f, sizeof(int)));      // "clean": a handle that only imports factors never runs a prologue
     if (const char *pf = std::getenv("CS3_PROFILE")) {
         if (pf[0] == '1') {
-            CS3_HIP(hipMalloc((void **) &D.tbuf, std::max<size_t>(1, (size_t) S.nsuper) * 8 * sizeof(long long)));
-            CS3_HIP(hipMemset(D.tbuf, 0, std::max<size_t>(1, (size_t) S.nsuper) * 8 * sizeof(long long)));
+            const size_t stamps = std::max<size_t>(1, (size_t) S.nsuper) * 8;
+            if ((rc = factor_alloc(h, &D.tbuf, stamps))) return rc;
+            CS3_HIP(hipMemset(D.tbuf, 0, stamps * sizeof(long long)));
         }
     }
     CS3_HIP(hipStreamCreateWithFlags(&h->cap_stream, hipStreamNonBlocking));
@@ -316,16 +304,15 @@ int ensure_rhs_capacity(cs3_handle h, long long nrhs)
     h->dbg_syncs += 1;
     h->dbg_allocs += 4;
     if (int rc = drop_graphs(h, [](const GraphKey &k) { return !graph_op_is(k, GRAPH_FACTOR); }, true)) return rc;
-    if (D.cv) (void) hipFree(D.cv);
-    if (D.xp) (void) hipFree(D.xp);
-    if (D.bigv) (void) hipFree(D.bigv);
-    if (D.gv) (void) hipFree(D.gv);
+    auto &M = h->mem;
+    M.cv.reset(); M.xp.reset(); M.bigv.reset(); M.gv.reset();
     D.cv = D.xp = D.bigv = D.gv = nullptr;
-    D.nrhs_cap = 0;                           // nothing usable until all three are back
-    CS3_HIP(hipMalloc((void **) &D.cv, std::max<size_t>(1, (size_t) (D.batch * D.cv_size * nrhs)) * sizeof(double)));
-    CS3_HIP(hipMalloc((void **) &D.xp, std::max<size_t>(1, (size_t) (D.batch * D.n * nrhs)) * sizeof(double)));
-    CS3_HIP(hipMalloc((void **) &D.bigv, std::max<size_t>(1, (size_t) (D.batch * D.bv_size * nrhs)) * sizeof(double)));
-    CS3_HIP(hipMalloc((void **) &D.gv, std::max<size_t>(1, (size_t) (D.batch * D.gv_size * nrhs)) * sizeof(double)));
+    D.nrhs_cap = 0;                           // nothing usable until all four are back
+    CS3_HIP(M.cv.alloc((size_t) (D.batch * D.cv_size * nrhs)));
+    CS3_HIP(M.xp.alloc((size_t) (D.batch * D.n * nrhs)));
+    CS3_HIP(M.bigv.alloc((size_t) (D.batch * D.bv_size * nrhs)));
+    CS3_HIP(M.gv.alloc((size_t) (D.batch * D.gv_size * nrhs)));
+    D.cv = M.cv.get(); D.xp = M.xp.get(); D.bigv = M.bigv.get(); D.gv = M.gv.get();
     D.nrhs_cap = nrhs;
     return CS3_OK;
 }
@@ -759,17 +746,12 @@ static int solve_host(cs3_handle h, double *X, int64_t k, int mode, bool trans =
     if (!X) { set_error("solve: null right-hand side"); return CS3_ERR_ARG; }
     if (trans && mode == 1 && h->S.kind != CS3_LU) { set_error("utsolve: a Cholesky factorisation has no U"); return CS3_ERR_ARG; }
     if (!h->factored) { set_error("solve before a successful factorisation"); return CS3_ERR_STATE; }
-    const size_t bytes = (size_t) (h->batch * h->S.n * k) * sizeof(double);
-    double *d_x = nullptr;
-    CS3_HIP(hipMalloc((void **) &d_x, std::max<size_t>(bytes, 8)));
-    hipError_t e = hipMemcpy(d_x, X, bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        rc = trans ? run_solve_t(h, d_x, k, mode, nullptr) : run_solve(h, d_x, k, mode, nullptr);
-        if (rc == CS3_OK) e = hipMemcpy(X, d_x, bytes, hipMemcpyDeviceToHost);
-    }
-    (void) hipFree(d_x);
-    if (rc) return rc;
-    CS3_HIP(e);
+    const size_t count = (size_t) (h->batch * h->S.n * k);
+    DevBuf<double> x;
+    CS3_HIP(x.alloc(count));
+    CS3_HIP(hipMemcpy(x.get(), X, count * sizeof(double), hipMemcpyHostToDevice));
+    if ((rc = trans ? run_solve_t(h, x.get(), k, mode, nullptr) : run_solve(h, x.get(), k, mode, nullptr))) return rc;
+    CS3_HIP(hipMemcpy(X, x.get(), count * sizeof(double), hipMemcpyDeviceToHost));
     return CS3_OK;
 }
 
@@ -849,8 +831,7 @@ int64_t cs3_debug_forest(cs3_handle h, int32_t *supernode, int32_t *task, int32_
 
 int cs3_debug_withhold_handover(int on)
 {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { set_error("cs3_debug_withhold_handover: no HIP device"); return CS3_ERR_HIP; }
+    if (!device_visible()) { set_error("cs3_debug_withhold_handover: no HIP device"); return CS3_ERR_HIP; }
     CS3_HIP(hipDeviceSynchronize());
     CS3_HIP(set_withhold_handover(on ? 1 : 0));
     return CS3_OK;
@@ -885,17 +866,18 @@ int cs3_get_factors(cs3_handle h, int64_t b, int32_t *Lp, int32_t *Li, double *L
     const DeviceFactor &DD = h->D;
     const double *vals = DD.pool_pm + b * DD.pm_stride;                                   // per-matrix part (virtual offsets)
     const double *vals_il = DD.pool_il + (b / 64) * 64 * DD.il_len + (b % 64);          // interleaved part, stride 64
+    auto &E = h->mem.exp;
     if (Lx) {
-        if (!h->d_lmap) { if ((rc = upload(&h->d_lmap, S.Lmap))) return rc; }
-        if (!h->d_lx) CS3_HIP(hipMalloc((void **) &h->d_lx, std::max<size_t>(1, (size_t) lnz) * sizeof(double)));
-        CS3_HIP(launch_extract(vals, vals_il, DD.il_len, (const long long *) h->d_lmap, h->d_lx, lnz, nullptr));
-        CS3_HIP(hipMemcpy(Lx, h->d_lx, (size_t) lnz * sizeof(double), hipMemcpyDeviceToHost));
+        if (!E.lmap.get()) CS3_HIP(E.lmap.upload(S.Lmap));
+        CS3_HIP(E.lx.reserve((size_t) lnz));
+        CS3_HIP(launch_extract(vals, vals_il, DD.il_len, (const long long *) E.lmap.get(), E.lx.get(), lnz, nullptr));
+        CS3_HIP(hipMemcpy(Lx, E.lx.get(), (size_t) lnz * sizeof(double), hipMemcpyDeviceToHost));
     }
     if (Ux) {
-        if (!h->d_umap) { if ((rc = upload(&h->d_umap, S.Umap))) return rc; }
-        if (!h->d_ux) CS3_HIP(hipMalloc((void **) &h->d_ux, std::max<size_t>(1, (size_t) unz) * sizeof(double)));
-        CS3_HIP(launch_extract(vals, vals_il, DD.il_len, (const long long *) h->d_umap, h->d_ux, unz, nullptr));
-        CS3_HIP(hipMemcpy(Ux, h->d_ux, (size_t) unz * sizeof(double), hipMemcpyDeviceToHost));
+        if (!E.umap.get()) CS3_HIP(E.umap.upload(S.Umap));
+        CS3_HIP(E.ux.reserve((size_t) unz));
+        CS3_HIP(launch_extract(vals, vals_il, DD.il_len, (const long long *) E.umap.get(), E.ux.get(), unz, nullptr));
+        CS3_HIP(hipMemcpy(Ux, E.ux.get(), (size_t) unz * sizeof(double), hipMemcpyDeviceToHost));
     }
     return CS3_OK;
 }
@@ -912,33 +894,18 @@ static int csc_trisolve(int64_t n, const int32_t *Gp, const int32_t *Gi, const d
     try { tri_schedule(n, Gp, Gi, lower, T, trans); }
     catch (const std::bad_alloc &) { set_error("triangular solve: out of memory"); return CS3_ERR_ALLOC; }
     catch (const std::exception &e) { set_error(e.what()); return CS3_ERR_ARG; }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-        set_error("no HIP device visible: triangular solves run on the GPU only"); return CS3_ERR_HIP;
-    }
-    int *d_rows = nullptr, *d_rp = nullptr, *d_rj = nullptr;
-    long long *d_rmap = nullptr, *d_diag = nullptr;
-    double *d_gx = nullptr, *d_x = nullptr;
-    int rc = CS3_OK;
-    auto cleanup = [&]() {
-        void *ptrs[] = {d_rows, d_rp, d_rj, d_rmap, d_diag, d_gx, d_x};
-        for (void *p : ptrs) if (p) (void) hipFree(p);
-    };
+    if (!device_visible()) { set_error("no HIP device visible: triangular solves run on the GPU only"); return CS3_ERR_HIP; }
+    DevBuf<int> d_rows, d_rp, d_rj;
+    DevBuf<long long> d_rmap, d_diag;
+    DevBuf<double> d_gx, d_x;
     std::vector<long long> rmap(T.Rmap.begin(), T.Rmap.end()), diag(T.diag.begin(), T.diag.end());
-    std::vector<double> gx(Gx, Gx + Gp[n]);
-    if ((rc = upload(&d_rows, T.level_rows)) || (rc = upload(&d_rp, T.Rp)) || (rc = upload(&d_rj, T.Rj)) ||
-        (rc = upload(&d_rmap, rmap)) || (rc = upload(&d_diag, diag)) || (rc = upload(&d_gx, gx))) {
-        cleanup(); return rc;
-    }
-    const size_t xbytes = (size_t) (n * k) * sizeof(double);
-    hipError_t e = hipMalloc((void **) &d_x, xbytes);
-    if (e == hipSuccess) e = hipMemcpy(d_x, x, xbytes, hipMemcpyHostToDevice);
-    for (i32 l = 0; l < T.nlevels && e == hipSuccess; ++l)
-        e = launch_tri_level(d_rows + T.level_ptr[l], T.level_ptr[l + 1] - T.level_ptr[l], d_rp, d_rj, d_rmap,
-                             d_diag, d_gx, d_x, (int) k, nullptr);
-    if (e == hipSuccess) e = hipMemcpy(x, d_x, xbytes, hipMemcpyDeviceToHost);
-    cleanup();
-    CS3_HIP(e);
+    CS3_HIP(d_rows.upload(T.level_rows)); CS3_HIP(d_rp.upload(T.Rp)); CS3_HIP(d_rj.upload(T.Rj));
+    CS3_HIP(d_rmap.upload(rmap)); CS3_HIP(d_diag.upload(diag)); CS3_HIP(d_gx.upload(Gx, (size_t) Gp[n]));
+    CS3_HIP(d_x.upload(x, (size_t) (n * k)));
+    for (i32 l = 0; l < T.nlevels; ++l)
+        CS3_HIP(launch_tri_level(d_rows.get() + T.level_ptr[l], T.level_ptr[l + 1] - T.level_ptr[l], d_rp.get(), d_rj.get(),
+                                 d_rmap.get(), d_diag.get(), d_gx.get(), d_x.get(), (int) k, nullptr));
+    CS3_HIP(hipMemcpy(x, d_x.get(), (size_t) (n * k) * sizeof(double), hipMemcpyDeviceToHost));
     return CS3_OK;
 }
 
@@ -966,10 +933,7 @@ int cs3_csc_matvec(int64_t m, int64_t n, const int32_t *Ap, const int32_t *Ai, c
                    const double *X, double *Y, int64_t k)
 {
     if (m < 0 || n < 0 || k < 1 || k > INT_MAX || !Ap || !X || !Y) { set_error("cs3_csc_matvec: bad argument"); return CS3_ERR_ARG; }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-        set_error("no HIP device visible: cs3_csc_matvec runs on the GPU only"); return CS3_ERR_HIP;
-    }
+    if (no_device("cs3_csc_matvec")) return CS3_ERR_HIP;
     const i64 nnz = Ap[n];
     // row view with ascending columns: the summation order of the column scatter loop
     std::vector<int> Rp(m + 1, 0), Rj(nnz);
@@ -984,21 +948,14 @@ int cs3_csc_matvec(int64_t m, int64_t n, const int32_t *Ap, const int32_t *Ai, c
         for (i64 j = 0; j < n; ++j)
             for (i64 p = Ap[j]; p < Ap[j + 1]; ++p) { int q = fill[Ai[p]]++; Rj[q] = (int) j; Rx[q] = Ax[p]; }
     }
-    int *d_rp = nullptr, *d_rj = nullptr;
-    double *d_rx = nullptr, *d_x = nullptr, *d_y = nullptr;
-    auto cleanup = [&]() {
-        void *ptrs[] = {d_rp, d_rj, d_rx, d_x, d_y};
-        for (void *p : ptrs) if (p) (void) hipFree(p);
-    };
-    int rc;
-    if ((rc = upload(&d_rp, Rp)) || (rc = upload(&d_rj, Rj)) || (rc = upload(&d_rx, Rx))) { cleanup(); return rc; }
-    hipError_t e = hipMalloc((void **) &d_x, std::max<size_t>(8, (size_t) (n * k) * sizeof(double)));
-    if (e == hipSuccess) e = hipMalloc((void **) &d_y, std::max<size_t>(8, (size_t) (m * k) * sizeof(double)));
-    if (e == hipSuccess) e = hipMemcpy(d_x, X, (size_t) (n * k) * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = launch_matvec_rows(d_rp, d_rj, d_rx, d_x, d_y, m, (int) k, nullptr);
-    if (e == hipSuccess) e = hipMemcpy(Y, d_y, (size_t) (m * k) * sizeof(double), hipMemcpyDeviceToHost);
-    cleanup();
-    CS3_HIP(e);
+    DevBuf<int> d_rp, d_rj;
+    DevBuf<double> d_rx, d_x, d_y;
+    CS3_HIP(d_rp.upload(Rp)); CS3_HIP(d_rj.upload(Rj)); CS3_HIP(d_rx.upload(Rx));
+    CS3_HIP(d_x.alloc((size_t) (n * k)));
+    CS3_HIP(d_y.alloc((size_t) (m * k)));
+    CS3_HIP(hipMemcpy(d_x.get(), X, (size_t) (n * k) * sizeof(double), hipMemcpyHostToDevice));
+    CS3_HIP(launch_matvec_rows(d_rp.get(), d_rj.get(), d_rx.get(), d_x.get(), d_y.get(), m, (int) k, nullptr));
+    CS3_HIP(hipMemcpy(Y, d_y.get(), (size_t) (m * k) * sizeof(double), hipMemcpyDeviceToHost));
     return CS3_OK;
 }
 
@@ -1011,42 +968,32 @@ int cs3_csc_stack_4_by_4(int64_t am, int64_t an, const int32_t *Ai, const int32_
     // the reference asserts these (csc_numba.py:679-682)
     if (am != bm || cm != dm || an != cn || bn != dn) { set_error("cs3_csc_stack_4_by_4: incompatible block shapes"); return CS3_ERR_ARG; }
     if (!Ap || !Bp || !Cp || !Dp || !Pp) { set_error("cs3_csc_stack_4_by_4: null argument"); return CS3_ERR_ARG; }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-        set_error("no HIP device visible: cs3_csc_stack_4_by_4 runs on the GPU only"); return CS3_ERR_HIP;
-    }
+    if (no_device("cs3_csc_stack_4_by_4")) return CS3_ERR_HIP;
     const i64 nnz = (i64) Ap[an] + Bp[bn] + Cp[cn] + Dp[dn];
-    struct Blk { const int32_t *p, *i; const double *x; i64 n; int *dp = nullptr, *di = nullptr; double *dx = nullptr; };
+    struct Blk { const int32_t *p, *i; const double *x; i64 n; DevBuf<int> dp, di; DevBuf<double> dx; };
     Blk blk[4] = {{Ap, Ai, Ax, an}, {Bp, Bi, Bx, bn}, {Cp, Ci, Cx, cn}, {Dp, Di, Dx, dn}};
-    int *d_pp = nullptr, *d_pi = nullptr; double *d_px = nullptr;
-    auto cleanup = [&]() {
-        for (Blk &b : blk) { if (b.dp) (void) hipFree(b.dp); if (b.di) (void) hipFree(b.di); if (b.dx) (void) hipFree(b.dx); }
-        if (d_pp) (void) hipFree(d_pp); if (d_pi) (void) hipFree(d_pi); if (d_px) (void) hipFree(d_px);
-    };
-    hipError_t e = hipSuccess;
     for (Blk &b : blk) {
         const size_t bn_ = (size_t) b.p[b.n];
-        if (e == hipSuccess) e = hipMalloc((void **) &b.dp, (size_t) (b.n + 1) * sizeof(int));
-        if (e == hipSuccess) e = hipMalloc((void **) &b.di, std::max<size_t>(1, bn_) * sizeof(int));
-        if (e == hipSuccess) e = hipMalloc((void **) &b.dx, std::max<size_t>(1, bn_) * sizeof(double));
-        if (e == hipSuccess) e = hipMemcpy(b.dp, b.p, (size_t) (b.n + 1) * sizeof(int), hipMemcpyHostToDevice);
-        if (e == hipSuccess && bn_) e = hipMemcpy(b.di, b.i, bn_ * sizeof(int), hipMemcpyHostToDevice);
-        if (e == hipSuccess && bn_) e = hipMemcpy(b.dx, b.x, bn_ * sizeof(double), hipMemcpyHostToDevice);
+        CS3_HIP(b.dp.alloc((size_t) (b.n + 1)));
+        CS3_HIP(b.di.alloc(bn_));
+        CS3_HIP(b.dx.alloc(bn_));
+        CS3_HIP(hipMemcpy(b.dp.get(), b.p, (size_t) (b.n + 1) * sizeof(int), hipMemcpyHostToDevice));
+        if (bn_) CS3_HIP(hipMemcpy(b.di.get(), b.i, bn_ * sizeof(int), hipMemcpyHostToDevice));
+        if (bn_) CS3_HIP(hipMemcpy(b.dx.get(), b.x, bn_ * sizeof(double), hipMemcpyHostToDevice));
     }
     const i64 ncol = an + bn;
-    if (e == hipSuccess) e = hipMalloc((void **) &d_pp, (size_t) (ncol + 1) * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void **) &d_pi, std::max<size_t>(1, (size_t) nnz) * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void **) &d_px, std::max<size_t>(1, (size_t) nnz) * sizeof(double));
-    if (e == hipSuccess) e = hipMemset(d_pp, 0, (size_t) (ncol + 1) * sizeof(int));
-    if (e == hipSuccess)
-        e = launch_stack_4_by_4((int) an, (int) bn, (int) am, (int) bm, blk[0].dp, blk[0].di, blk[0].dx, blk[1].dp, blk[1].di,
-                                blk[1].dx, blk[2].dp, blk[2].di, blk[2].dx, blk[3].dp, blk[3].di, blk[3].dx, d_pp, d_pi, d_px,
-                                nullptr, nullptr);
-    if (e == hipSuccess) e = hipMemcpy(Pp, d_pp, (size_t) (ncol + 1) * sizeof(int), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && nnz) e = hipMemcpy(Pi, d_pi, (size_t) nnz * sizeof(int), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && nnz) e = hipMemcpy(Px, d_px, (size_t) nnz * sizeof(double), hipMemcpyDeviceToHost);
-    cleanup();
-    CS3_HIP(e);
+    DevBuf<int> d_pp, d_pi;
+    DevBuf<double> d_px;
+    CS3_HIP(d_pp.alloc((size_t) (ncol + 1)));
+    CS3_HIP(d_pi.alloc((size_t) nnz));
+    CS3_HIP(d_px.alloc((size_t) nnz));
+    CS3_HIP(hipMemset(d_pp.get(), 0, (size_t) (ncol + 1) * sizeof(int)));
+    CS3_HIP(launch_stack_4_by_4((int) an, (int) bn, (int) am, (int) bm, blk[0].dp.get(), blk[0].di.get(), blk[0].dx.get(),
+                                blk[1].dp.get(), blk[1].di.get(), blk[1].dx.get(), blk[2].dp.get(), blk[2].di.get(), blk[2].dx.get(),
+                                blk[3].dp.get(), blk[3].di.get(), blk[3].dx.get(), d_pp.get(), d_pi.get(), d_px.get(), nullptr, nullptr));
+    CS3_HIP(hipMemcpy(Pp, d_pp.get(), (size_t) (ncol + 1) * sizeof(int), hipMemcpyDeviceToHost));
+    if (nnz) CS3_HIP(hipMemcpy(Pi, d_pi.get(), (size_t) nnz * sizeof(int), hipMemcpyDeviceToHost));
+    if (nnz) CS3_HIP(hipMemcpy(Px, d_px.get(), (size_t) nnz * sizeof(double), hipMemcpyDeviceToHost));
     return CS3_OK;
 }
 
@@ -1056,7 +1003,8 @@ static int ensure_row_view(cs3_handle h, long long k)
     int rc = ensure_device(h);
     if (rc) return rc;
     const Symbolic &S = h->S;
-    if (!h->d_rp) {
+    auto &V = h->mem.view;
+    if (!V.rp.get()) {
         const i64 n = S.n, nnz = S.nnzA;
         std::vector<int> Rp(n + 1, 0), Rj(nnz), Rmap(nnz);
         const i32 *Ap = h->Ap_host.data(), *Ai = h->Ai_host.data();
@@ -1065,16 +1013,13 @@ static int ensure_row_view(cs3_handle h, long long k)
         std::vector<int> fill(Rp.begin(), Rp.end() - 1);
         for (i64 j = 0; j < n; ++j)                      // ascending column inside every row: csc_mat_vec_ff's summation order
             for (i64 p = Ap[j]; p < Ap[j + 1]; ++p) { const int q = fill[Ai[p]]++; Rj[q] = (int) j; Rmap[q] = (int) p; }
-        if ((rc = upload(&h->d_rp, Rp)) || (rc = upload(&h->d_rj, Rj)) || (rc = upload(&h->d_rmap, Rmap))) return rc;
-        CS3_HIP(hipMalloc((void **) &h->d_maxbits, sizeof(unsigned long long)));
+        CS3_HIP(V.rp.upload(Rp)); CS3_HIP(V.rj.upload(Rj)); CS3_HIP(V.rmap.upload(Rmap));
+        CS3_HIP(V.maxbits.alloc(1));
     }
-    const long long need = h->batch * S.n * k;
-    if (need > h->res_cap) {
-        CS3_HIP(hipDeviceSynchronize());
-        if (h->d_res) (void) hipFree(h->d_res);
-        h->d_res = nullptr; h->res_cap = 0;
-        CS3_HIP(hipMalloc((void **) &h->d_res, std::max<size_t>(8, (size_t) need * sizeof(double))));
-        h->res_cap = need;
+    const size_t need = (size_t) (h->batch * S.n * k);
+    if (need > V.res.count()) {
+        CS3_HIP(hipDeviceSynchronize());              // (the old block may still be in use)
+        CS3_HIP(V.res.alloc(need));
     }
     return CS3_OK;
 }
@@ -1084,10 +1029,11 @@ static int ensure_col_view(cs3_handle h, long long k)
 {
     int rc = ensure_row_view(h, k);
     if (rc) return rc;
-    if (!h->d_cp) {
+    auto &V = h->mem.view;
+    if (!V.cp.get()) {
         std::vector<int> Cmap(h->S.nnzA);
         for (i64 p = 0; p < h->S.nnzA; ++p) Cmap[p] = (int) p;
-        if ((rc = upload(&h->d_cp, h->Ap_host)) || (rc = upload(&h->d_ci, h->Ai_host)) || (rc = upload(&h->d_cmap, Cmap))) return rc;
+        CS3_HIP(V.cp.upload(h->Ap_host)); CS3_HIP(V.ci.upload(h->Ai_host)); CS3_HIP(V.cmap.upload(Cmap));
     }
     return CS3_OK;
 }
@@ -1100,7 +1046,8 @@ static int product(const char *who, cs3_handle h, const double *Ax_dev, const do
     int rc = guard(h); if (rc) return rc;
     if (!Ax_dev || (with_b && !B_dev) || !X_dev || !R_dev || k < 1 || k > INT_MAX) { set_error(std::string(who) + ": bad argument"); return CS3_ERR_ARG; }
     if ((rc = trans ? ensure_col_view(h, 0) : ensure_row_view(h, 0))) return rc;
-    const int *vp = trans ? h->d_cp : h->d_rp, *vj = trans ? h->d_ci : h->d_rj, *vmap = trans ? h->d_cmap : h->d_rmap;
+    const auto &V = h->mem.view;
+    const int *vp = (trans ? V.cp : V.rp).get(), *vj = (trans ? V.ci : V.rj).get(), *vmap = (trans ? V.cmap : V.rmap).get();
     CS3_HIP(launch_residual(vp, vj, vmap, Ax_dev, X_dev, B_dev, R_dev, h->S.n, (int) k, h->S.nnzA, h->batch, (hipStream_t) stream));
     return CS3_OK;
 }
@@ -1135,16 +1082,17 @@ static int refine(cs3_handle h, const double *Ax_dev, const double *B_dev, doubl
     if ((rc = trans ? ensure_col_view(h, k) : ensure_row_view(h, k))) return rc;
     hipStream_t st = (hipStream_t) stream;
     const long long total = h->batch * h->S.n * k;
-    const int *vp = trans ? h->d_cp : h->d_rp, *vj = trans ? h->d_ci : h->d_rj, *vmap = trans ? h->d_cmap : h->d_rmap;
+    const auto &V = h->mem.view;
+    const int *vp = (trans ? V.cp : V.rp).get(), *vj = (trans ? V.ci : V.rj).get(), *vmap = (trans ? V.cmap : V.rmap).get();
     for (int64_t s = 0; s < steps; ++s) {
-        CS3_HIP(launch_residual(vp, vj, vmap, Ax_dev, X_dev, B_dev, h->d_res, h->S.n, (int) k, h->S.nnzA, h->batch, st));
-        if ((rc = run_solve(h, h->d_res, k, 0, st, trans))) return rc;    // d = A \ r (A' \ r) with the factors at hand
+        CS3_HIP(launch_residual(vp, vj, vmap, Ax_dev, X_dev, B_dev, V.res.get(), h->S.n, (int) k, h->S.nnzA, h->batch, st));
+        if ((rc = run_solve(h, V.res.get(), k, 0, st, trans))) return rc;    // d = A \ r (A' \ r) with the factors at hand
         const bool want = last_correction && s + 1 == steps;
-        if (want) CS3_HIP(hipMemsetAsync(h->d_maxbits, 0, sizeof(unsigned long long), st));
-        CS3_HIP(launch_axpy_max(X_dev, h->d_res, total, want ? h->d_maxbits : nullptr, st));      // x += d
+        if (want) CS3_HIP(hipMemsetAsync(V.maxbits.get(), 0, sizeof(unsigned long long), st));
+        CS3_HIP(launch_axpy_max(X_dev, V.res.get(), total, want ? V.maxbits.get() : nullptr, st));      // x += d
         if (want) {
             unsigned long long bits = 0;
-            CS3_HIP(hipMemcpyAsync(&bits, h->d_maxbits, sizeof(bits), hipMemcpyDeviceToHost, st));
+            CS3_HIP(hipMemcpyAsync(&bits, V.maxbits.get(), sizeof(bits), hipMemcpyDeviceToHost, st));
             CS3_HIP(hipStreamSynchronize(st));
             std::memcpy(last_correction, &bits, sizeof(double));
         }
@@ -1170,13 +1118,14 @@ static int ensure_estimator(cs3_handle h)
 {
     int rc = ensure_col_view(h, 0);
     if (rc) return rc;
-    const size_t bn = std::max<size_t>(1, (size_t) (h->batch * h->S.n));
-    if (!h->d_est_x) CS3_HIP(hipMalloc((void **) &h->d_est_x, bn * sizeof(double)));
-    if (!h->d_est_s) CS3_HIP(hipMalloc((void **) &h->d_est_s, 2 * bn));
-    if (!h->d_est_state) CS3_HIP(hipMalloc((void **) &h->d_est_state, (size_t) h->batch * sizeof(EstState)));
+    auto &E = h->mem.est;
+    const size_t bn = (size_t) (h->batch * h->S.n);
     const long long nparts = std::max(est_chunks(h->S.n), norm_chunks(h->S.n));
-    if (!h->d_est_parts) CS3_HIP(hipMalloc((void **) &h->d_est_parts, (size_t) (h->batch * nparts) * sizeof(EstPart)));
-    if (!h->d_est_cnt) CS3_HIP(hipMalloc((void **) &h->d_est_cnt, 2 * sizeof(unsigned)));
+    CS3_HIP(E.x.reserve(bn));
+    CS3_HIP(E.s.reserve(2 * bn));
+    CS3_HIP(E.state.reserve((size_t) h->batch));
+    CS3_HIP(E.parts.reserve((size_t) (h->batch * nparts)));
+    CS3_HIP(E.cnt.reserve(2));
     return CS3_OK;
 }
 
@@ -1193,7 +1142,8 @@ static int condest_run(cs3_handle h, const double *Ax_dev, double *cond_dev, dou
     if (rc) return rc;
     const i64 n = h->S.n, batch = h->batch;
     const bool chol = h->S.kind == CS3_CHOLESKY;
-    CS3_HIP(launch_est_start(h->d_cp, h->d_cmap, Ax_dev, n, h->S.nnzA, batch, h->d_est_parts, h->d_est_state, st));
+    const auto &E = h->mem.est;
+    CS3_HIP(launch_est_start(h->mem.view.cp.get(), h->mem.view.cmap.get(), Ax_dev, n, h->S.nnzA, batch, E.parts.get(), E.state.get(), st));
     constexpr int FIXED_SLOTS = 11;
     unsigned want[2] = {1u, 0u};                             // before the first slot: J1 wants A^-1
     int last = 1;
@@ -1202,7 +1152,7 @@ static int condest_run(cs3_handle h, const double *Ax_dev, double *cond_dev, dou
         int kind = slot & 1;                                 // 0: x = A^-1 b (F), 1: x = A^-T b (T)
         if (adaptive) {
             if (slot > 0) {
-                CS3_HIP(hipMemcpyAsync(want, h->d_est_cnt, sizeof(want), hipMemcpyDeviceToHost, st));
+                CS3_HIP(hipMemcpyAsync(want, E.cnt.get(), sizeof(want), hipMemcpyDeviceToHost, st));
                 CS3_HIP(hipStreamSynchronize(st));
             }
             if (!want[0] && !want[1]) break;
@@ -1210,12 +1160,12 @@ static int condest_run(cs3_handle h, const double *Ax_dev, double *cond_dev, dou
         }
         if (chol) kind = 0;
         const int kmask = chol ? 3 : 1 << kind;
-        CS3_HIP(launch_est_prepare(h->d_est_state, h->d_est_s, h->d_est_x, n, batch, kmask, h->d_est_cnt, st));
-        if ((rc = run_solve(h, h->d_est_x, 1, 0, st, kind == 1))) return rc;
-        CS3_HIP(launch_est_consume(h->d_est_state, h->d_est_s, h->d_est_x, n, batch, kmask, h->d_est_parts, h->d_est_cnt, st));
+        CS3_HIP(launch_est_prepare(E.state.get(), E.s.get(), E.x.get(), n, batch, kmask, E.cnt.get(), st));
+        if ((rc = run_solve(h, E.x.get(), 1, 0, st, kind == 1))) return rc;
+        CS3_HIP(launch_est_consume(E.state.get(), E.s.get(), E.x.get(), n, batch, kmask, E.parts.get(), E.cnt.get(), st));
         last = kind;
     }
-    CS3_HIP(launch_est_finalize(h->d_est_state, batch, cond_dev, inv_dev, st));
+    CS3_HIP(launch_est_finalize(E.state.get(), batch, cond_dev, inv_dev, st));
     return CS3_OK;
 }
 
@@ -1243,7 +1193,7 @@ int cs3_condest_dev(cs3_handle h, const double *Ax_dev, double *cond_dev, double
 // The host forms stage through buffers the handle keeps (allocated on first use), on the null stream.
 static int ensure_host_out(cs3_handle h)
 {
-    if (!h->d_est_out) CS3_HIP(hipMalloc((void **) &h->d_est_out, (size_t) (2 * h->batch) * sizeof(double)));
+    CS3_HIP(h->mem.host.out.reserve((size_t) (2 * h->batch)));
     return CS3_OK;
 }
 
@@ -1257,12 +1207,13 @@ int cs3_condest(cs3_handle h, const double *Ax, double *cond, double *inv_norm)
         return CS3_OK;
     }
     if ((rc = ensure_host_out(h))) return rc;
-    const size_t ax_bytes = (size_t) (batch * h->S.nnzA) * sizeof(double);
-    if (!h->d_est_ax) CS3_HIP(hipMalloc((void **) &h->d_est_ax, std::max<size_t>(ax_bytes, 8)));
-    if (ax_bytes) CS3_HIP(hipMemcpy(h->d_est_ax, Ax, ax_bytes, hipMemcpyHostToDevice));
-    if ((rc = condest_run(h, h->d_est_ax, h->d_est_out, h->d_est_out + batch, nullptr, true))) return rc;
+    auto &H = h->mem.host;
+    const size_t ax_count = (size_t) (batch * h->S.nnzA);
+    CS3_HIP(H.ax.reserve(ax_count));
+    if (ax_count) CS3_HIP(hipMemcpy(H.ax.get(), Ax, ax_count * sizeof(double), hipMemcpyHostToDevice));
+    if ((rc = condest_run(h, H.ax.get(), H.out.get(), H.out.get() + batch, nullptr, true))) return rc;
     std::vector<double> out((size_t) (2 * batch));
-    CS3_HIP(hipMemcpy(out.data(), h->d_est_out, out.size() * sizeof(double), hipMemcpyDeviceToHost));
+    CS3_HIP(hipMemcpy(out.data(), H.out.get(), out.size() * sizeof(double), hipMemcpyDeviceToHost));
     std::memcpy(cond, out.data(), (size_t) batch * sizeof(double));
     if (inv_norm) std::memcpy(inv_norm, out.data() + batch, (size_t) batch * sizeof(double));
     return CS3_OK;
@@ -1273,14 +1224,15 @@ int cs3_condest(cs3_handle h, const double *Ax, double *cond, double *inv_norm)
 // built once per handle, without the CSC view of the factors.
 static int ensure_diag_map(cs3_handle h)
 {
-    if (h->d_diag) return CS3_OK;
+    if (h->mem.diag.get()) return CS3_OK;
     const Symbolic &S = h->S;
     std::vector<i64> diag((size_t) S.n);
     for (i64 j = 0; j < S.n; ++j) {
         const i32 s = S.col2sn[j];
         diag[j] = S.lpan_off[s] + (j - S.sn_ptr[s]) * (S.st_ptr[s + 1] - S.st_ptr[s] + 1);
     }
-    return upload(&h->d_diag, diag);
+    CS3_HIP(h->mem.diag.upload(diag));
+    return CS3_OK;
 }
 
 int cs3_slogdet_dev(cs3_handle h, double *sign_dev, double *logabs_dev, void *stream)
@@ -1289,7 +1241,7 @@ int cs3_slogdet_dev(cs3_handle h, double *sign_dev, double *logabs_dev, void *st
     if (!sign_dev || !logabs_dev) { set_error("cs3_slogdet_dev: null argument"); return CS3_ERR_ARG; }
     if (!h->factored) { set_error("cs3_slogdet_dev: no successful factorisation"); return CS3_ERR_STATE; }
     if ((rc = ensure_diag_map(h))) return rc;
-    CS3_HIP(launch_slogdet(h->D, (const long long *) h->d_diag, sign_dev, logabs_dev, (hipStream_t) stream));
+    CS3_HIP(launch_slogdet(h->D, (const long long *) h->mem.diag.get(), sign_dev, logabs_dev, (hipStream_t) stream));
     return CS3_OK;
 }
 
@@ -1300,9 +1252,10 @@ int cs3_slogdet(cs3_handle h, double *sign, double *logabs)
     if (!h->factored) { set_error("cs3_slogdet: no successful factorisation"); return CS3_ERR_STATE; }
     if ((rc = ensure_host_out(h))) return rc;
     const long long batch = h->batch;
-    if ((rc = cs3_slogdet_dev(h, h->d_est_out, h->d_est_out + batch, nullptr))) return rc;
+    double *d_out = h->mem.host.out.get();
+    if ((rc = cs3_slogdet_dev(h, d_out, d_out + batch, nullptr))) return rc;
     std::vector<double> out((size_t) (2 * batch));
-    CS3_HIP(hipMemcpy(out.data(), h->d_est_out, out.size() * sizeof(double), hipMemcpyDeviceToHost));
+    CS3_HIP(hipMemcpy(out.data(), d_out, out.size() * sizeof(double), hipMemcpyDeviceToHost));
     std::memcpy(sign, out.data(), (size_t) batch * sizeof(double));
     std::memcpy(logabs, out.data() + batch, (size_t) batch * sizeof(double));
     return CS3_OK;
@@ -1452,6 +1405,8 @@ int64_t cs3_debug_updates_tiles(cs3_updates u, int32_t *first_case, int32_t *nca
     return (int64_t) u->tiles.size();
 }
 
+int64_t cs3_debug_live_device_buffers(void) { return (int64_t) g_live_device_buffers.load(); }
+
 int cs3_debug_alloc_counters(cs3_handle h, int64_t *allocs, int64_t *syncs)
 {
     int rc = guard(h); if (rc) return rc;
@@ -1479,29 +1434,27 @@ static int ensure_updates(cs3_handle h, cs3_updates_s *u)
     if (!u->on_device) {
         static bool prepared = false;
         if (!prepared) { CS3_HIP(prepare_updates_kernels()); prepared = true; }
-        int rc;
-        if ((rc = upload(&u->d_cases, u->cases))) return rc;
-        if ((rc = upload(&u->d_cp, u->cp))) return rc;
-        if ((rc = upload(&u->d_tpos, u->tpos))) return rc;
-        if ((rc = upload(&u->d_unit, u->unit_row))) return rc;
-        CS3_HIP(hipMalloc((void **) &u->d_y, (size_t) u->ncases * UPD_MAX_RANK * sizeof(double)));
-        CS3_HIP(hipMalloc((void **) &u->d_flag, (size_t) u->ncases * sizeof(int)));
-        CS3_HIP(hipMalloc((void **) &u->d_rpiv, (size_t) u->ncases * sizeof(double)));
+        auto &P = u->mem;
+        CS3_HIP(P.cases.upload(u->cases));
+        CS3_HIP(P.cp.upload(u->cp));
+        CS3_HIP(P.tpos.upload(u->tpos));
+        CS3_HIP(P.unit.upload(u->unit_row));
+        CS3_HIP(P.y.alloc((size_t) u->ncases * UPD_MAX_RANK));
+        CS3_HIP(P.flag.alloc((size_t) u->ncases));
+        CS3_HIP(P.rpiv.alloc((size_t) u->ncases));
         h->dbg_allocs += 7;
         u->on_device = true;
     }
+    auto &U = h->mem.upd;
     const size_t n1 = std::max<size_t>(1, (size_t) h->S.n);
-    if (!h->d_upd_x0) { CS3_HIP(hipMalloc((void **) &h->d_upd_x0, n1 * sizeof(double))); h->dbg_allocs += 1; }
-    if (h->upd_z_cols < wmax) {
-        if (h->d_upd_z) {                                  // a wider plan than any before: the old tile may still be in use
+    if (!U.x0.get()) { CS3_HIP(U.x0.alloc(n1)); h->dbg_allocs += 1; }
+    if (U.z.count() < n1 * (size_t) wmax) {
+        if (U.z.get()) {                                   // a wider plan than any before: the old tile may still be in use
             CS3_HIP(hipDeviceSynchronize());
             h->dbg_syncs += 1;
-            (void) hipFree(h->d_upd_z);
-            h->d_upd_z = nullptr; h->upd_z_cols = 0;
         }
-        CS3_HIP(hipMalloc((void **) &h->d_upd_z, n1 * (size_t) wmax * sizeof(double)));
+        CS3_HIP(U.z.alloc(n1 * (size_t) wmax));
         h->dbg_allocs += 1;
-        h->upd_z_cols = wmax;
     }
     return ensure_rhs_capacity(h, wmax);
 }
@@ -1512,19 +1465,21 @@ static int updates_run(cs3_handle h, cs3_updates_s *u, const double *cx_dev, con
     int rc = ensure_updates(h, u);
     if (rc) return rc;
     const i64 n = h->S.n;
-    const UpdTables T{u->d_cases, u->d_cp, u->d_tpos, u->d_y, u->d_flag};
-    double *rpiv = rpiv_dev ? rpiv_dev : u->d_rpiv;
+    const auto &P = u->mem;
+    const UpdTables T{P.cases.get(), P.cp.get(), P.tpos.get(), P.y.get(), P.flag.get()};
+    double *rpiv = rpiv_dev ? rpiv_dev : P.rpiv.get();
+    double *Z = h->mem.upd.z.get(), *x0 = h->mem.upd.x0.get();
     if (n > 0) {
-        CS3_HIP(hipMemcpyAsync(h->d_upd_x0, b_dev, (size_t) n * sizeof(double), hipMemcpyDeviceToDevice, st));
-        if ((rc = run_solve(h, h->d_upd_x0, 1, 0, st))) return rc;
+        CS3_HIP(hipMemcpyAsync(x0, b_dev, (size_t) n * sizeof(double), hipMemcpyDeviceToDevice, st));
+        if ((rc = run_solve(h, x0, 1, 0, st))) return rc;
     }
     for (const auto &t : u->tiles) {
         if (n > 0 && t.t > 0) {
-            CS3_HIP(launch_upd_units(h->d_upd_z, n, t.t_solve, u->d_unit + t.unit0, st));
-            if ((rc = run_solve(h, h->d_upd_z, t.t_solve, 0, st))) return rc;
+            CS3_HIP(launch_upd_units(Z, n, t.t_solve, P.unit.get() + t.unit0, st));
+            if ((rc = run_solve(h, Z, t.t_solve, 0, st))) return rc;
         }
-        CS3_HIP(launch_upd_capacitance(T, cx_dev, h->d_upd_z, t.t_solve, h->d_upd_x0, t.c0, t.nc, sing_tol, rpiv, st));
-        CS3_HIP(launch_upd_apply(T, h->d_upd_z, t.t_solve, h->d_upd_x0, n, t.c0, t.nc, t.rmax, u->ncases, X_dev, st));
+        CS3_HIP(launch_upd_capacitance(T, cx_dev, Z, t.t_solve, x0, t.c0, t.nc, sing_tol, rpiv, st));
+        CS3_HIP(launch_upd_apply(T, Z, t.t_solve, x0, n, t.c0, t.nc, t.rmax, u->ncases, X_dev, st));
     }
     return CS3_OK;
 }
@@ -1542,21 +1497,16 @@ int cs3_updates_solve(cs3_handle h, cs3_updates u, const double *cx, const doubl
     int rc = updates_check("cs3_updates_solve", h, u, cx, b, X);
     if (rc) return rc;
     const size_t n = (size_t) h->S.n, nc = (size_t) u->ncases, nt = (size_t) u->ntrip;
-    if (!u->d_cx) CS3_HIP(hipMalloc((void **) &u->d_cx, std::max<size_t>(nt, 1) * sizeof(double)));
-    double *d_b = nullptr, *d_x = nullptr;                 // [n] and [n, ncases], for this call
-    CS3_HIP(hipMalloc((void **) &d_b, std::max<size_t>(n * (nc + 1), 1) * sizeof(double)));
-    d_x = d_b + n;
-    hipError_t e = nt ? hipMemcpy(u->d_cx, cx, nt * sizeof(double), hipMemcpyHostToDevice) : hipSuccess;
-    if (e == hipSuccess && n) e = hipMemcpy(d_b, b, n * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        rc = updates_run(h, u, u->d_cx, d_b, sing_tol, d_x, nullptr, nullptr);
-        if (rc == CS3_OK && n) e = hipMemcpy(X, d_x, n * nc * sizeof(double), hipMemcpyDeviceToHost);
-        if (rc == CS3_OK && e == hipSuccess && rpiv) e = hipMemcpy(rpiv, u->d_rpiv, nc * sizeof(double), hipMemcpyDeviceToHost);
-        if (rc == CS3_OK && e == hipSuccess) e = hipDeviceSynchronize();
-    }
-    (void) hipFree(d_b);
-    if (rc) return rc;
-    CS3_HIP(e);
+    CS3_HIP(u->mem.cx.reserve(nt));
+    DevBuf<double> bx;                                     // b [n], then X [n, ncases], for this call
+    CS3_HIP(bx.alloc(n * (nc + 1)));
+    double *d_b = bx.get(), *d_x = d_b + n;
+    if (nt) CS3_HIP(hipMemcpy(u->mem.cx.get(), cx, nt * sizeof(double), hipMemcpyHostToDevice));
+    if (n) CS3_HIP(hipMemcpy(d_b, b, n * sizeof(double), hipMemcpyHostToDevice));
+    if ((rc = updates_run(h, u, u->mem.cx.get(), d_b, sing_tol, d_x, nullptr, nullptr))) return rc;
+    if (n) CS3_HIP(hipMemcpy(X, d_x, n * nc * sizeof(double), hipMemcpyDeviceToHost));
+    if (rpiv) CS3_HIP(hipMemcpy(rpiv, u->mem.rpiv.get(), nc * sizeof(double), hipMemcpyDeviceToHost));
+    CS3_HIP(hipDeviceSynchronize());
     return CS3_OK;
 }
 
@@ -1573,10 +1523,7 @@ int cs3_csc_stack_4_by_4_dev(int64_t am, int64_t an, int64_t nnz_a, const int32_
     const int64_t nnz = nnz_a + nnz_b + nnz_c + nnz_d;
     if (nnz_a < 0 || nnz_b < 0 || nnz_c < 0 || nnz_d < 0 || nnz > INT_MAX || an + bn > INT_MAX) { set_error("cs3_csc_stack_4_by_4_dev: bad sizes"); return CS3_ERR_ARG; }
     if (nnz > 0 && (!Pi || !Px)) { set_error("cs3_csc_stack_4_by_4_dev: null output"); return CS3_ERR_ARG; }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-        set_error("no HIP device visible: cs3_csc_stack_4_by_4_dev runs on the GPU only"); return CS3_ERR_HIP;
-    }
+    if (no_device("cs3_csc_stack_4_by_4_dev")) return CS3_ERR_HIP;
     CS3_HIP(launch_stack_4_by_4((int) an, (int) bn, (int) am, (int) bm, Ap, Ai, Ax, Bp, Bi, Bx, Cp, Ci, Cx, Dp, Di, Dx, Pp, Pi, Px,
                                 map, (hipStream_t) stream));
     return CS3_OK;
@@ -1586,10 +1533,7 @@ int cs3_restack_values_dev(int64_t nnz, const int32_t *map, int64_t nnz_a, int64
                            const double *Ax, const double *Bx, const double *Cx, const double *Dx, double *Px, void *stream)
 {
     if (nnz < 0 || nnz_a < 0 || nnz_b < 0 || nnz_c < 0 || (nnz > 0 && (!map || !Px))) { set_error("cs3_restack_values_dev: bad argument"); return CS3_ERR_ARG; }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-        set_error("no HIP device visible: cs3_restack_values_dev runs on the GPU only"); return CS3_ERR_HIP;
-    }
+    if (no_device("cs3_restack_values_dev")) return CS3_ERR_HIP;
     CS3_HIP(launch_restack_values(nnz, map, nnz_a, nnz_b, nnz_c, Ax, Bx, Cx, Dx, Px, (hipStream_t) stream));
     return CS3_OK;
 }

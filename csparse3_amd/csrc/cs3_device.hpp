@@ -1,4 +1,4 @@
-// Device-side descriptors shared by kernels.hip and api.hip.
+// Device-side descriptors shared by kernels.hip and api.cpp.
 #pragma once
 #include <hip/hip_runtime_api.h>
 

@@ -17,6 +17,7 @@
 
 #include "../../include/csparse3_amd.h"
 #include "cs3_internal.hpp"
+#include "cs3_hipmem.hpp"
 
 #pragma clang fp contract(off)          // a * b + c stays two roundings, as in the reference's interpreter / JIT
 
@@ -326,52 +327,25 @@ using namespace cs3;
 
 namespace {
 
-// device scratch that frees itself
-struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf() { if (p) (void) hipFree(p); }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, std::max<size_t>(bytes, 8)); }
-    template <class T> T *as() { return static_cast<T *>(p); }
-};
-
-int no_device(const char *who)
-{
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-        set_error(std::string("no HIP device visible: ") + who + " runs on the GPU only");
-        return 1;
-    }
-    return 0;
-}
-
-#define SUB_HIP(call)                                                                   \
-    do {                                                                                \
-        hipError_t e_ = (call);                                                         \
-        if (e_ != hipSuccess) {                                                         \
-            set_error(std::string(#call) + ": " + hipGetErrorString(e_));               \
-            return CS3_ERR_HIP;                                                         \
-        }                                                                               \
-    } while (0)
-
 // buckets[key[p]] gets p, every bucket in ascending p: ptr[nbucket + 1] and slot[count] on the device
 int bucket_by_key(const int *d_key, long long count, int nbucket, int *d_ptr, int *d_slot, const char *who)
 {
-    DevBuf cursor, bad;
-    SUB_HIP(cursor.alloc((size_t) nbucket * sizeof(int)));
-    SUB_HIP(bad.alloc(sizeof(int)));
-    SUB_HIP(hipMemset(cursor.p, 0, std::max<size_t>((size_t) nbucket * sizeof(int), 8)));
-    SUB_HIP(hipMemset(bad.p, 0, sizeof(int)));
-    SUB_HIP(hipMemset(d_ptr, 0, (size_t) (nbucket + 1) * sizeof(int)));
-    if (count) hipLaunchKernelGGL(k_histogram, dim3(blocks_for(count, 256)), dim3(256), 0, 0, d_key, count, nbucket, d_ptr, bad.as<int>());
+    DevBuf<int> cursor, bad;
+    CS3_HIP(cursor.alloc((size_t) nbucket));
+    CS3_HIP(bad.alloc(1));
+    CS3_HIP(hipMemset(cursor.get(), 0, std::max<size_t>((size_t) nbucket * sizeof(int), 8)));
+    CS3_HIP(hipMemset(bad.get(), 0, sizeof(int)));
+    CS3_HIP(hipMemset(d_ptr, 0, (size_t) (nbucket + 1) * sizeof(int)));
+    if (count) hipLaunchKernelGGL(k_histogram, dim3(blocks_for(count, 256)), dim3(256), 0, 0, d_key, count, nbucket, d_ptr, bad.get());
     int h_bad = 0;
-    SUB_HIP(hipMemcpy(&h_bad, bad.p, sizeof(int), hipMemcpyDeviceToHost));
+    CS3_HIP(hipMemcpy(&h_bad, bad.get(), sizeof(int), hipMemcpyDeviceToHost));
     if (h_bad) { set_error(std::string(who) + ": index out of range"); return CS3_ERR_ARG; }
     hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, 0, d_ptr, (long long) nbucket);
     if (count) {
-        hipLaunchKernelGGL(k_bucket_fill, dim3(blocks_for(count, 256)), dim3(256), 0, 0, d_key, count, d_ptr, cursor.as<int>(), d_slot);
+        hipLaunchKernelGGL(k_bucket_fill, dim3(blocks_for(count, 256)), dim3(256), 0, 0, d_key, count, d_ptr, cursor.get(), d_slot);
         hipLaunchKernelGGL(k_bucket_sort, dim3(blocks_for(nbucket, 256)), dim3(256), 0, 0, d_ptr, nbucket, d_slot);
     }
-    SUB_HIP(hipGetLastError());
+    CS3_HIP(hipGetLastError());
     return CS3_OK;
 }
 
@@ -388,26 +362,22 @@ int cs3_csc_transpose(int64_t m, int64_t n, const int32_t *Ap, const int32_t *Ai
     if (no_device("cs3_csc_transpose")) return CS3_ERR_HIP;
     const long long nnz = Ap[n];
     if (nnz < 0 || (nnz > 0 && (!Ai || !Ax || !Ci || !Cx))) { set_error("cs3_csc_transpose: bad argument"); return CS3_ERR_ARG; }
-    DevBuf ap, ai, ax, col, ptr, slot, ci, cx;
-    SUB_HIP(ap.alloc((size_t) (n + 1) * 4)); SUB_HIP(ai.alloc((size_t) nnz * 4)); SUB_HIP(ax.alloc((size_t) nnz * 8));
-    SUB_HIP(col.alloc((size_t) nnz * 4)); SUB_HIP(ptr.alloc((size_t) (m + 1) * 4)); SUB_HIP(slot.alloc((size_t) nnz * 4));
-    SUB_HIP(ci.alloc((size_t) nnz * 4)); SUB_HIP(cx.alloc((size_t) nnz * 8));
-    SUB_HIP(hipMemcpy(ap.p, Ap, (size_t) (n + 1) * 4, hipMemcpyHostToDevice));
-    if (nnz) {
-        SUB_HIP(hipMemcpy(ai.p, Ai, (size_t) nnz * 4, hipMemcpyHostToDevice));
-        SUB_HIP(hipMemcpy(ax.p, Ax, (size_t) nnz * 8, hipMemcpyHostToDevice));
-    }
-    int rc = bucket_by_key(ai.as<int>(), nnz, (int) m, ptr.as<int>(), slot.as<int>(), "cs3_csc_transpose");
+    DevBuf<int> ap, ai, col, ptr, slot, ci;
+    DevBuf<double> ax, cx;
+    CS3_HIP(ap.upload(Ap, (size_t) (n + 1))); CS3_HIP(ai.upload(Ai, (size_t) nnz)); CS3_HIP(ax.upload(Ax, (size_t) nnz));
+    CS3_HIP(col.alloc((size_t) nnz)); CS3_HIP(ptr.alloc((size_t) (m + 1))); CS3_HIP(slot.alloc((size_t) nnz));
+    CS3_HIP(ci.alloc((size_t) nnz)); CS3_HIP(cx.alloc((size_t) nnz));
+    int rc = bucket_by_key(ai.get(), nnz, (int) m, ptr.get(), slot.get(), "cs3_csc_transpose");
     if (rc) return rc;
     if (nnz) {
-        hipLaunchKernelGGL(k_expand_columns, dim3(blocks_for(n, 256)), dim3(256), 0, 0, ap.as<int>(), (int) n, col.as<int>());
-        hipLaunchKernelGGL(k_gather_pairs, dim3(blocks_for(nnz, 256)), dim3(256), 0, 0, slot.as<int>(), nnz, col.as<int>(),
-                           ax.as<double>(), ci.as<int>(), cx.as<double>());
-        SUB_HIP(hipGetLastError());
-        SUB_HIP(hipMemcpy(Ci, ci.p, (size_t) nnz * 4, hipMemcpyDeviceToHost));
-        SUB_HIP(hipMemcpy(Cx, cx.p, (size_t) nnz * 8, hipMemcpyDeviceToHost));
+        hipLaunchKernelGGL(k_expand_columns, dim3(blocks_for(n, 256)), dim3(256), 0, 0, ap.get(), (int) n, col.get());
+        hipLaunchKernelGGL(k_gather_pairs, dim3(blocks_for(nnz, 256)), dim3(256), 0, 0, slot.get(), nnz, col.get(),
+                           ax.get(), ci.get(), cx.get());
+        CS3_HIP(hipGetLastError());
+        CS3_HIP(hipMemcpy(Ci, ci.get(), (size_t) nnz * 4, hipMemcpyDeviceToHost));
+        CS3_HIP(hipMemcpy(Cx, cx.get(), (size_t) nnz * 8, hipMemcpyDeviceToHost));
     }
-    SUB_HIP(hipMemcpy(Cp, ptr.p, (size_t) (m + 1) * 4, hipMemcpyDeviceToHost));
+    CS3_HIP(hipMemcpy(Cp, ptr.get(), (size_t) (m + 1) * 4, hipMemcpyDeviceToHost));
     return CS3_OK;
 }
 
@@ -419,25 +389,21 @@ int cs3_coo_to_csc(int64_t m, int64_t n, int64_t nz, const int32_t *Ti, const in
         set_error("cs3_coo_to_csc: bad argument"); return CS3_ERR_ARG;
     }
     if (no_device("cs3_coo_to_csc")) return CS3_ERR_HIP;
-    DevBuf ti, tj, tx, ptr, slot, ci, cx;
-    SUB_HIP(ti.alloc((size_t) nz * 4)); SUB_HIP(tj.alloc((size_t) nz * 4)); SUB_HIP(tx.alloc((size_t) nz * 8));
-    SUB_HIP(ptr.alloc((size_t) (n + 1) * 4)); SUB_HIP(slot.alloc((size_t) nz * 4));
-    SUB_HIP(ci.alloc((size_t) nz * 4)); SUB_HIP(cx.alloc((size_t) nz * 8));
-    if (nz) {
-        SUB_HIP(hipMemcpy(ti.p, Ti, (size_t) nz * 4, hipMemcpyHostToDevice));
-        SUB_HIP(hipMemcpy(tj.p, Tj, (size_t) nz * 4, hipMemcpyHostToDevice));
-        SUB_HIP(hipMemcpy(tx.p, Tx, (size_t) nz * 8, hipMemcpyHostToDevice));
-    }
-    int rc = bucket_by_key(tj.as<int>(), nz, (int) n, ptr.as<int>(), slot.as<int>(), "cs3_coo_to_csc");
+    DevBuf<int> ti, tj, ptr, slot, ci;
+    DevBuf<double> tx, cx;
+    CS3_HIP(ti.upload(Ti, (size_t) nz)); CS3_HIP(tj.upload(Tj, (size_t) nz)); CS3_HIP(tx.upload(Tx, (size_t) nz));
+    CS3_HIP(ptr.alloc((size_t) (n + 1))); CS3_HIP(slot.alloc((size_t) nz));
+    CS3_HIP(ci.alloc((size_t) nz)); CS3_HIP(cx.alloc((size_t) nz));
+    int rc = bucket_by_key(tj.get(), nz, (int) n, ptr.get(), slot.get(), "cs3_coo_to_csc");
     if (rc) return rc;
     if (nz) {
-        hipLaunchKernelGGL(k_gather_pairs, dim3(blocks_for(nz, 256)), dim3(256), 0, 0, slot.as<int>(), (long long) nz, ti.as<int>(),
-                           tx.as<double>(), ci.as<int>(), cx.as<double>());
-        SUB_HIP(hipGetLastError());
-        SUB_HIP(hipMemcpy(Ci, ci.p, (size_t) nz * 4, hipMemcpyDeviceToHost));
-        SUB_HIP(hipMemcpy(Cx, cx.p, (size_t) nz * 8, hipMemcpyDeviceToHost));
+        hipLaunchKernelGGL(k_gather_pairs, dim3(blocks_for(nz, 256)), dim3(256), 0, 0, slot.get(), (long long) nz, ti.get(),
+                           tx.get(), ci.get(), cx.get());
+        CS3_HIP(hipGetLastError());
+        CS3_HIP(hipMemcpy(Ci, ci.get(), (size_t) nz * 4, hipMemcpyDeviceToHost));
+        CS3_HIP(hipMemcpy(Cx, cx.get(), (size_t) nz * 8, hipMemcpyDeviceToHost));
     }
-    SUB_HIP(hipMemcpy(Cp, ptr.p, (size_t) (n + 1) * 4, hipMemcpyDeviceToHost));
+    CS3_HIP(hipMemcpy(Cp, ptr.get(), (size_t) (n + 1) * 4, hipMemcpyDeviceToHost));
     return CS3_OK;
 }
 
@@ -448,14 +414,14 @@ int cs3_csc_norm(int64_t n, const int32_t *Ap, const double *Ax, double *norm)
     if (no_device("cs3_csc_norm")) return CS3_ERR_HIP;
     const long long nnz = Ap[n];
     if (nnz > 0 && !Ax) { set_error("cs3_csc_norm: bad argument"); return CS3_ERR_ARG; }
-    DevBuf ap, ax, sums, out;
-    SUB_HIP(ap.alloc((size_t) (n + 1) * 4)); SUB_HIP(ax.alloc((size_t) nnz * 8)); SUB_HIP(sums.alloc((size_t) n * 8)); SUB_HIP(out.alloc(8));
-    SUB_HIP(hipMemcpy(ap.p, Ap, (size_t) (n + 1) * 4, hipMemcpyHostToDevice));
-    if (nnz) SUB_HIP(hipMemcpy(ax.p, Ax, (size_t) nnz * 8, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_col_abs_sums, dim3(blocks_for(n, 256)), dim3(256), 0, 0, ap.as<int>(), ax.as<double>(), (int) n, sums.as<double>());
-    hipLaunchKernelGGL(k_max_reduce, dim3(1), dim3(1024), 0, 0, sums.as<double>(), (int) n, out.as<double>());
-    SUB_HIP(hipGetLastError());
-    SUB_HIP(hipMemcpy(norm, out.p, 8, hipMemcpyDeviceToHost));
+    DevBuf<int> ap;
+    DevBuf<double> ax, sums, out;
+    CS3_HIP(ap.upload(Ap, (size_t) (n + 1))); CS3_HIP(ax.upload(Ax, (size_t) nnz));
+    CS3_HIP(sums.alloc((size_t) n)); CS3_HIP(out.alloc(1));
+    hipLaunchKernelGGL(k_col_abs_sums, dim3(blocks_for(n, 256)), dim3(256), 0, 0, ap.get(), ax.get(), (int) n, sums.get());
+    hipLaunchKernelGGL(k_max_reduce, dim3(1), dim3(1024), 0, 0, sums.get(), (int) n, out.get());
+    CS3_HIP(hipGetLastError());
+    CS3_HIP(hipMemcpy(norm, out.get(), 8, hipMemcpyDeviceToHost));
     return CS3_OK;
 }
 
@@ -469,30 +435,26 @@ int cs3_csc_add(int64_t m, int64_t n, const int32_t *Ap, const int32_t *Ai, cons
     if (no_device("cs3_csc_add")) return CS3_ERR_HIP;
     const long long na = Ap[n], nb = Bp[n];
     if ((na > 0 && (!Ai || !Ax)) || (nb > 0 && (!Bi || !Bx)) || (na + nb > 0 && (!Ci || !Cx))) { set_error("cs3_csc_add: bad argument"); return CS3_ERR_ARG; }
-    DevBuf ap, ai, ax, bp, bi, bx, cp, ci, cx;
-    SUB_HIP(ap.alloc((size_t) (n + 1) * 4)); SUB_HIP(ai.alloc((size_t) na * 4)); SUB_HIP(ax.alloc((size_t) na * 8));
-    SUB_HIP(bp.alloc((size_t) (n + 1) * 4)); SUB_HIP(bi.alloc((size_t) nb * 4)); SUB_HIP(bx.alloc((size_t) nb * 8));
-    SUB_HIP(cp.alloc((size_t) (n + 1) * 4));
-    SUB_HIP(hipMemcpy(ap.p, Ap, (size_t) (n + 1) * 4, hipMemcpyHostToDevice));
-    SUB_HIP(hipMemcpy(bp.p, Bp, (size_t) (n + 1) * 4, hipMemcpyHostToDevice));
-    if (na) { SUB_HIP(hipMemcpy(ai.p, Ai, (size_t) na * 4, hipMemcpyHostToDevice)); SUB_HIP(hipMemcpy(ax.p, Ax, (size_t) na * 8, hipMemcpyHostToDevice)); }
-    if (nb) { SUB_HIP(hipMemcpy(bi.p, Bi, (size_t) nb * 4, hipMemcpyHostToDevice)); SUB_HIP(hipMemcpy(bx.p, Bx, (size_t) nb * 8, hipMemcpyHostToDevice)); }
-    SUB_HIP(hipMemset(cp.p, 0, (size_t) (n + 1) * 4));
-    hipLaunchKernelGGL(k_add_columns, dim3(blocks_for(n, 128)), dim3(128), 0, 0, (int) n, ap.as<int>(), ai.as<int>(), ax.as<double>(),
-                       bp.as<int>(), bi.as<int>(), bx.as<double>(), alpha, beta, (const int *) nullptr, (int *) nullptr,
-                       (double *) nullptr, cp.as<int>());
-    hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, 0, cp.as<int>(), (long long) n);
-    SUB_HIP(hipGetLastError());
-    SUB_HIP(hipMemcpy(Cp, cp.p, (size_t) (n + 1) * 4, hipMemcpyDeviceToHost));
+    DevBuf<int> ap, ai, bp, bi, cp, ci;
+    DevBuf<double> ax, bx, cx;
+    CS3_HIP(ap.upload(Ap, (size_t) (n + 1))); CS3_HIP(ai.upload(Ai, (size_t) na)); CS3_HIP(ax.upload(Ax, (size_t) na));
+    CS3_HIP(bp.upload(Bp, (size_t) (n + 1))); CS3_HIP(bi.upload(Bi, (size_t) nb)); CS3_HIP(bx.upload(Bx, (size_t) nb));
+    CS3_HIP(cp.alloc((size_t) (n + 1)));
+    CS3_HIP(hipMemset(cp.get(), 0, (size_t) (n + 1) * 4));
+    hipLaunchKernelGGL(k_add_columns, dim3(blocks_for(n, 128)), dim3(128), 0, 0, (int) n, ap.get(), ai.get(), ax.get(),
+                       bp.get(), bi.get(), bx.get(), alpha, beta, (const int *) nullptr, (int *) nullptr,
+                       (double *) nullptr, cp.get());
+    hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, 0, cp.get(), (long long) n);
+    CS3_HIP(hipGetLastError());
+    CS3_HIP(hipMemcpy(Cp, cp.get(), (size_t) (n + 1) * 4, hipMemcpyDeviceToHost));
     const long long nc = Cp[n];
-    SUB_HIP(ci.alloc((size_t) nc * 4)); SUB_HIP(cx.alloc((size_t) nc * 8));
-    hipLaunchKernelGGL(k_add_columns, dim3(blocks_for(n, 128)), dim3(128), 0, 0, (int) n, ap.as<int>(), ai.as<int>(), ax.as<double>(),
-                       bp.as<int>(), bi.as<int>(), bx.as<double>(), alpha, beta, cp.as<int>(), ci.as<int>(), cx.as<double>(),
-                       (int *) nullptr);
-    SUB_HIP(hipGetLastError());
+    CS3_HIP(ci.alloc((size_t) nc)); CS3_HIP(cx.alloc((size_t) nc));
+    hipLaunchKernelGGL(k_add_columns, dim3(blocks_for(n, 128)), dim3(128), 0, 0, (int) n, ap.get(), ai.get(), ax.get(),
+                       bp.get(), bi.get(), bx.get(), alpha, beta, cp.get(), ci.get(), cx.get(), (int *) nullptr);
+    CS3_HIP(hipGetLastError());
     if (nc) {
-        SUB_HIP(hipMemcpy(Ci, ci.p, (size_t) nc * 4, hipMemcpyDeviceToHost));
-        SUB_HIP(hipMemcpy(Cx, cx.p, (size_t) nc * 8, hipMemcpyDeviceToHost));
+        CS3_HIP(hipMemcpy(Ci, ci.get(), (size_t) nc * 4, hipMemcpyDeviceToHost));
+        CS3_HIP(hipMemcpy(Cx, cx.get(), (size_t) nc * 8, hipMemcpyDeviceToHost));
     }
     return CS3_OK;
 }
@@ -511,34 +473,31 @@ int cs3_csc_sub_matrix(int64_t n, const int32_t *Ap, const int32_t *Ai, const do
         if (cols[c] < 0 || cols[c] >= n) { set_error("cs3_csc_sub_matrix: column index out of range"); return CS3_ERR_ARG; }
     if (no_device("cs3_csc_sub_matrix")) return CS3_ERR_HIP;
     const long long nnz = Ap[n];
-    DevBuf ap, ai, ax, dr, dc, bp, bi, bx;
-    SUB_HIP(ap.alloc((size_t) (n + 1) * 4)); SUB_HIP(ai.alloc((size_t) nnz * 4)); SUB_HIP(ax.alloc((size_t) nnz * 8));
-    SUB_HIP(dr.alloc((size_t) nrows * 4)); SUB_HIP(dc.alloc((size_t) ncols * 4)); SUB_HIP(bp.alloc((size_t) (ncols + 1) * 4));
-    SUB_HIP(hipMemcpy(ap.p, Ap, (size_t) (n + 1) * 4, hipMemcpyHostToDevice));
-    if (nnz) { SUB_HIP(hipMemcpy(ai.p, Ai, (size_t) nnz * 4, hipMemcpyHostToDevice)); SUB_HIP(hipMemcpy(ax.p, Ax, (size_t) nnz * 8, hipMemcpyHostToDevice)); }
-    if (nrows) SUB_HIP(hipMemcpy(dr.p, rows, (size_t) nrows * 4, hipMemcpyHostToDevice));
-    if (ncols) SUB_HIP(hipMemcpy(dc.p, cols, (size_t) ncols * 4, hipMemcpyHostToDevice));
-    SUB_HIP(hipMemset(bp.p, 0, (size_t) (ncols + 1) * 4));
-    hipLaunchKernelGGL(k_sub_matrix, dim3(blocks_for((long long) ncols * 64, 256)), dim3(256), 0, 0, ap.as<int>(), ai.as<int>(), ax.as<double>(),
-                       dr.as<int>(), (int) nrows, dc.as<int>(), (int) ncols, (const int *) nullptr, (int *) nullptr,
-                       (double *) nullptr, bp.as<int>());
-    hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, 0, bp.as<int>(), (long long) ncols);
-    SUB_HIP(hipGetLastError());
-    SUB_HIP(hipMemcpy(Bp, bp.p, (size_t) (ncols + 1) * 4, hipMemcpyDeviceToHost));
+    DevBuf<int> ap, ai, dr, dc, bp, bi;
+    DevBuf<double> ax, bx;
+    CS3_HIP(ap.upload(Ap, (size_t) (n + 1))); CS3_HIP(ai.upload(Ai, (size_t) nnz)); CS3_HIP(ax.upload(Ax, (size_t) nnz));
+    CS3_HIP(dr.upload(rows, (size_t) nrows)); CS3_HIP(dc.upload(cols, (size_t) ncols));
+    CS3_HIP(bp.alloc((size_t) (ncols + 1)));
+    CS3_HIP(hipMemset(bp.get(), 0, (size_t) (ncols + 1) * 4));
+    hipLaunchKernelGGL(k_sub_matrix, dim3(blocks_for((long long) ncols * 64, 256)), dim3(256), 0, 0, ap.get(), ai.get(), ax.get(),
+                       dr.get(), (int) nrows, dc.get(), (int) ncols, (const int *) nullptr, (int *) nullptr,
+                       (double *) nullptr, bp.get());
+    hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, 0, bp.get(), (long long) ncols);
+    CS3_HIP(hipGetLastError());
+    CS3_HIP(hipMemcpy(Bp, bp.get(), (size_t) (ncols + 1) * 4, hipMemcpyDeviceToHost));
     const long long nb = Bp[ncols];
     if (nb > b_cap || (nb > 0 && (!Bi || !Bx))) {
         set_error("cs3_csc_sub_matrix: result has " + std::to_string(nb) + " entries, room for " + std::to_string(b_cap) +
                   " (repeated rows / columns?)");
         return CS3_ERR_ARG;
     }
-    SUB_HIP(bi.alloc((size_t) nb * 4)); SUB_HIP(bx.alloc((size_t) nb * 8));
-    hipLaunchKernelGGL(k_sub_matrix, dim3(blocks_for((long long) ncols * 64, 256)), dim3(256), 0, 0, ap.as<int>(), ai.as<int>(), ax.as<double>(),
-                       dr.as<int>(), (int) nrows, dc.as<int>(), (int) ncols, bp.as<int>(), bi.as<int>(), bx.as<double>(),
-                       (int *) nullptr);
-    SUB_HIP(hipGetLastError());
+    CS3_HIP(bi.alloc((size_t) nb)); CS3_HIP(bx.alloc((size_t) nb));
+    hipLaunchKernelGGL(k_sub_matrix, dim3(blocks_for((long long) ncols * 64, 256)), dim3(256), 0, 0, ap.get(), ai.get(), ax.get(),
+                       dr.get(), (int) nrows, dc.get(), (int) ncols, bp.get(), bi.get(), bx.get(), (int *) nullptr);
+    CS3_HIP(hipGetLastError());
     if (nb) {
-        SUB_HIP(hipMemcpy(Bi, bi.p, (size_t) nb * 4, hipMemcpyDeviceToHost));
-        SUB_HIP(hipMemcpy(Bx, bx.p, (size_t) nb * 8, hipMemcpyDeviceToHost));
+        CS3_HIP(hipMemcpy(Bi, bi.get(), (size_t) nb * 4, hipMemcpyDeviceToHost));
+        CS3_HIP(hipMemcpy(Bx, bx.get(), (size_t) nb * 8, hipMemcpyDeviceToHost));
     }
     return CS3_OK;
 }
@@ -551,30 +510,29 @@ int cs3_find_islands(int64_t n, const int32_t *Ap, const int32_t *Ai, int32_t *l
     if (no_device("cs3_find_islands")) return CS3_ERR_HIP;
     if (n == 0) return CS3_OK;
     const long long nnz = Ap[n];
-    DevBuf ap, ai, lab, chg;
-    SUB_HIP(ap.alloc((size_t) (n + 1) * 4)); SUB_HIP(ai.alloc((size_t) nnz * 4)); SUB_HIP(lab.alloc((size_t) n * 4)); SUB_HIP(chg.alloc(4));
-    SUB_HIP(hipMemcpy(ap.p, Ap, (size_t) (n + 1) * 4, hipMemcpyHostToDevice));
-    if (nnz) SUB_HIP(hipMemcpy(ai.p, Ai, (size_t) nnz * 4, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_label_init, dim3(blocks_for(n, 256)), dim3(256), 0, 0, lab.as<int>(), (int) n);
+    DevBuf<int> ap, ai, lab, chg;
+    CS3_HIP(ap.upload(Ap, (size_t) (n + 1))); CS3_HIP(ai.upload(Ai, (size_t) nnz));
+    CS3_HIP(lab.alloc((size_t) n)); CS3_HIP(chg.alloc(1));
+    hipLaunchKernelGGL(k_label_init, dim3(blocks_for(n, 256)), dim3(256), 0, 0, lab.get(), (int) n);
     int unsym = 0;
-    SUB_HIP(hipMemset(chg.p, 0, 4));
-    hipLaunchKernelGGL(k_pattern_symmetric, dim3(blocks_for(n, 256)), dim3(256), 0, 0, ap.as<int>(), ai.as<int>(), (int) n, chg.as<int>());
-    SUB_HIP(hipMemcpy(&unsym, chg.p, 4, hipMemcpyDeviceToHost));
+    CS3_HIP(hipMemset(chg.get(), 0, 4));
+    hipLaunchKernelGGL(k_pattern_symmetric, dim3(blocks_for(n, 256)), dim3(256), 0, 0, ap.get(), ai.get(), (int) n, chg.get());
+    CS3_HIP(hipMemcpy(&unsym, chg.get(), 4, hipMemcpyDeviceToHost));
     for (int64_t round = 0; round <= n; ++round) {
         int changed = 0;
-        SUB_HIP(hipMemset(chg.p, 0, 4));
+        CS3_HIP(hipMemset(chg.get(), 0, 4));
         if (!unsym) {               // structurally symmetric: root hooking + full compression, O(log n) rounds in practice
-            hipLaunchKernelGGL(k_label_hook, dim3(blocks_for(n, 256)), dim3(256), 0, 0, ap.as<int>(), ai.as<int>(), (int) n, lab.as<int>(), chg.as<int>());
-            hipLaunchKernelGGL(k_label_jump, dim3(blocks_for(n, 256)), dim3(256), 0, 0, lab.as<int>(), (int) n);
+            hipLaunchKernelGGL(k_label_hook, dim3(blocks_for(n, 256)), dim3(256), 0, 0, ap.get(), ai.get(), (int) n, lab.get(), chg.get());
+            hipLaunchKernelGGL(k_label_jump, dim3(blocks_for(n, 256)), dim3(256), 0, 0, lab.get(), (int) n);
         } else {                    // directed reachability, the reference's exact semantics
-            hipLaunchKernelGGL(k_reach_hook, dim3(blocks_for(n, 256)), dim3(256), 0, 0, ap.as<int>(), ai.as<int>(), (int) n, lab.as<int>(), chg.as<int>());
-            hipLaunchKernelGGL(k_reach_jump, dim3(blocks_for(n, 256)), dim3(256), 0, 0, lab.as<int>(), (int) n, chg.as<int>());
+            hipLaunchKernelGGL(k_reach_hook, dim3(blocks_for(n, 256)), dim3(256), 0, 0, ap.get(), ai.get(), (int) n, lab.get(), chg.get());
+            hipLaunchKernelGGL(k_reach_jump, dim3(blocks_for(n, 256)), dim3(256), 0, 0, lab.get(), (int) n, chg.get());
         }
-        SUB_HIP(hipMemcpy(&changed, chg.p, 4, hipMemcpyDeviceToHost));
+        CS3_HIP(hipMemcpy(&changed, chg.get(), 4, hipMemcpyDeviceToHost));
         if (!changed) break;
     }
-    SUB_HIP(hipGetLastError());
-    SUB_HIP(hipMemcpy(label, lab.p, (size_t) n * 4, hipMemcpyDeviceToHost));
+    CS3_HIP(hipGetLastError());
+    CS3_HIP(hipMemcpy(label, lab.get(), (size_t) n * 4, hipMemcpyDeviceToHost));
     return CS3_OK;
 }
 

@@ -274,6 +274,9 @@ int cs3_debug_withhold_handover(int on);
  * instantiations included) and host synchronisations the handle has made so far in its solves and in the paths built on
  * them (the low-rank-modified solves).  Either pointer may be NULL. */
 int cs3_debug_alloc_counters(cs3_handle h, int64_t *allocs, int64_t *syncs);
+/* Diagnostic, for the test of device-memory lifetime: the number of device blocks the library holds right now, over all
+ * handles, plans and calls in flight (process-wide, needs no handle and no device).  0 once everything has been freed. */
+int64_t cs3_debug_live_device_buffers(void);
 /* The tiles of a plan of low-rank-modified solves: returns their number and, for arrays that are not null, per tile its
  * first case, its number of cases, its touched rows and the number of right-hand sides it is solved with (the touched rows
  * rounded up to a multiple of 64, at most the tile width).  Diagnostics, tests and tools. */

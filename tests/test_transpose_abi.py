@@ -80,3 +80,20 @@ def test_trans_defaults_to_false_everywhere(hip):
                hip.Factorization.residual_dev, hip.Factorization.refine_dev, csc_mod.CscMat.solve):
         assert inspect.signature(fn).parameters["trans"].default is False, fn.__qualname__
     assert callable(csc_mod.ltsolve) and callable(csc_mod.utsolve)
+
+
+def test_live_device_buffers_stays_zero_without_a_device(hip):
+    """cs3_debug_live_device_buffers counts the device blocks held: none before and after the no-device error returns."""
+    if hip.device_count() > 0:
+        return                                                    # (tests/test_gpu_lifetime.py covers a process with a device)
+    assert hip.debug_live_device_buffers() == 0
+    test_general_transposed_triangular_solves(hip)
+    m, n, Ap, Ai, Ax, F = _toy(hip)
+    with F:
+        with pytest.raises(hip.Cs3Error) as e:
+            F.factor(Ax)
+        assert e.value.code == hip.CS3_ERR_HIP
+    with pytest.raises(hip.Cs3Error) as e:
+        hip.csc_transpose(m, n, Ap, Ai, Ax)
+    assert e.value.code == hip.CS3_ERR_HIP
+    assert hip.debug_live_device_buffers() == 0
