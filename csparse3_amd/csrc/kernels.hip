@@ -2720,7 +2720,7 @@ k_front_il(const FrontDesc *__restrict__ fdesc, int first, const int *__restrict
                 dd[kk][ii] *= rd[kk];
                 if (KIND == CS3_LU) rej = rej || (ii < kb && !(fabs(dd[kk][ii]) <= inv_tol));
             }
-            if (rej && kk < kb && !bad) { bad = true; bad_col = k0 + kk; }
+            if (rej && kk < kb) { bad_col = bad ? min(bad_col, k0 + kk) : k0 + kk; bad = true; }
 #pragma unroll
             for (int jj = kk + 1; jj < IL_KB; ++jj)
 #pragma unroll
@@ -2752,7 +2752,8 @@ k_front_il(const FrontDesc *__restrict__ fdesc, int first, const int *__restrict
                     for (int kk = 0; kk < jj; ++kk) x -= t[a][kk] * ((KIND == CS3_LU) ? dd[jj][kk] : dd[kk][jj]);
                     x *= rd[jj];
                     t[a][jj] = x;
-                    if (KIND == CS3_LU && jj < kb && i0 + a < r && !(fabs(x) <= inv_tol) && !bad) { bad = true; bad_col = k0 + jj; }
+                    // (a column may fail only here, after a later column of the block has failed in step 1: the smallest is reported)
+                    if (KIND == CS3_LU && jj < kb && i0 + a < r && !(fabs(x) <= inv_tol)) { bad_col = bad ? min(bad_col, k0 + jj) : k0 + jj; bad = true; }
                 }
 #pragma unroll
             for (int a = 0; a < IL_T; ++a)
