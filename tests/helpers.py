@@ -82,13 +82,50 @@ def backward_error_ratio(n, A_perm, L, U):
     return ratio, nz_bad
 
 
-def assert_backward_error(n, A_perm, L, U, what="", oracle_ratio=None, bound=None):
+def _exact_pieces(A, axis, bits=21):
+    """A = sum of the returned float64 matrices, exactly; every entry of a piece is an integer multiple of its row's
+    (axis 1) or column's (axis 0) grid 2^(e - bits + 1), at most 2^(bits - 1) of them, where 2^e bounds what was left of
+    that row or column.  (fl((x + sigma) - sigma) with sigma = 1.5 2^k rounds x to a multiple of 2^(k - 52).)"""
+    pieces = []
+    R = np.array(A, dtype=np.float64, copy=True)
+    while R.any():
+        assert len(pieces) < 32, "entries too far apart to split"
+        e = np.frexp(np.abs(R).max(axis=axis, keepdims=True))[1]           # max < 2^e (0 for an empty row: its piece is 0)
+        sigma = np.ldexp(1.5, e + 52 - bits + 1)
+        P = (R + sigma) - sigma
+        R = R - P                                                           # exact: P is R rounded to the grid
+        pieces.append(P)
+    return pieces
+
+
+def backward_error_ratio_dense(n, A_perm, L, U):
+    """backward_error_ratio for factors that are nearly dense (n of a few hundred), where one term per (i, k, j) is
+    n^3 / 3 terms: L U is formed from float64 matrix products that are EXACT -- L's rows and U's columns are split into
+    pieces of 21 bits (_exact_pieces), so that a sum of n <= 2048 products of two pieces fits 53 bits in any order --
+    and the products are added up in np.longdouble, as the sparse form adds its terms.  |L||U| is a float64 product
+    (relative error n u, on a ratio that is compared with 2 n)."""
+    assert n <= 2048
+    Ld = sp.csc_matrix((np.asarray(L[2], dtype=np.float64), np.asarray(L[1]), np.asarray(L[0])), shape=(n, n)).toarray()
+    Ud = sp.csc_matrix((np.asarray(U[2], dtype=np.float64), np.asarray(U[1]), np.asarray(U[0])), shape=(n, n)).toarray()
+    S = np.zeros((n, n), dtype=np.longdouble)
+    for PL in _exact_pieces(Ld, axis=1):
+        for PU in _exact_pieces(Ud, axis=0):
+            S += PL @ PU
+    E = np.abs(S - A_perm.toarray().astype(np.longdouble))
+    W = np.abs(Ld) @ np.abs(Ud)
+    zero = W == 0
+    nz_bad = int(np.count_nonzero(E[zero] != 0))
+    ratio = float((E[~zero] / (np.longdouble(U_ROUND) * W[~zero])).max()) if (~zero).any() else 0.0
+    return ratio, nz_bad
+
+
+def assert_backward_error(n, A_perm, L, U, what="", oracle_ratio=None, bound=None, dense=False):
     """Higham's componentwise bound for any LU (or Cholesky, U = L') computed in float64, in any summation order, with
     or without FMA:  |P A Q - L U|_ij <= gamma_n (|L||U|)_ij,  asserted as 2 n u (the factor 2 covers multipliers formed
     by a reciprocal multiply: one more rounding per entry of L), and exactly zero where (|L||U|)_ij = 0.  `bound`
     (in units of u) replaces 2 n by something sharper; `oracle_ratio` only goes into the message.  Returns the ratio
-    max |E|_ij / (u (|L||U|)_ij)."""
-    ratio, nz_bad = backward_error_ratio(n, A_perm, L, U)
+    max |E|_ij / (u (|L||U|)_ij).  dense: through backward_error_ratio_dense."""
+    ratio, nz_bad = (backward_error_ratio_dense if dense else backward_error_ratio)(n, A_perm, L, U)
     lim = 2.0 * n if bound is None else bound
     note = "" if oracle_ratio is None else " (oracle %.2f)" % oracle_ratio
     assert nz_bad == 0, "%s: %d entries of P A Q outside the pattern of |L||U|" % (what, nz_bad)
