@@ -167,20 +167,23 @@ class CscMat:
         h.update(np.ascontiguousarray(self.indices[:nnz], dtype=np.int32).tobytes())
         return self.m, n, nnz, h.digest()
 
-    def _analysis(self, kind, order, q):
-        key = (kind, order, None if q is None else bytes(np.asarray(q, dtype=np.int32)), self._pattern_fingerprint())
+    def _analysis(self, kind, order, q, match=False):
+        key = (kind, order, None if q is None else bytes(np.asarray(q, dtype=np.int32)), self._pattern_fingerprint(), bool(match))
         f = self._factorization
         if f is None or f[0] != key:
             if f is not None:
                 f[1].close()
-            fac = _k.Factorization(self.m, self.n, self.indptr, self.indices, kind=kind, order=order, q=q)
+            fac = _k.Factorization(self.m, self.n, self.indptr, self.indices, kind=kind, order=order, q=q,
+                                   match_values=self.data if match else None)
             self._factorization = f = (key, fac)
         return f[1]
 
-    def lu(self, tol=0.0, order=_k.ORDER_AMD, q=None):
+    def lu(self, tol=0.0, order=_k.ORDER_AMD, q=None, match=False):
         """Numeric LU on the device; the symbolic analysis is cached on the object, so calling
-        lu() again after changing .data is a refactorisation with the pattern reused."""
-        F = self._analysis(_k.CS3_LU, order, q)
+        lu() again after changing .data is a refactorisation with the pattern reused.
+        match: permute rows by the maximum-product transversal and scale before the analysis (matrices without a strong
+        diagonal); the matching is computed from .data at the first analysis and kept across refactorisations."""
+        F = self._analysis(_k.CS3_LU, order, q, match)
         F.factor(self.data, tol)
         return F
 
@@ -189,9 +192,9 @@ class CscMat:
         F.factor(self.data)
         return F
 
-    def solve(self, b, tol=0.0, trans=False):
-        """x = A \\ b by LU (factorises if needed); trans: A' x = b on the same factors."""
-        return self.lu(tol).solve(b, trans=trans)
+    def solve(self, b, tol=0.0, trans=False, match=False):
+        """x = A \\ b by LU (factorises if needed); trans: A' x = b on the same factors; match: as in lu()."""
+        return self.lu(tol, match=match).solve(b, trans=trans)
 
     def solve_modified(self, b, deltas, tol=0.0, sing_tol=0.0):
         """x_c = (A + dA_c) \\ b for a list of sparse modifications, `deltas` = [(rows, cols, vals), ...] (triplets of dA_c;
@@ -233,9 +236,9 @@ def scipy_to_mat(scipy_mat):
     return CscMat(m, n, indptr=scipy_mat.indptr, indices=scipy_mat.indices, data=scipy_mat.data)
 
 
-def lusol(A, b, order=1, tol=0.0):
-    """x = A \\ b (cs_lusol)."""
-    return _k.csc_lusol_f(order, A.m, A.n, A.indptr, A.indices, A.data, b, tol)
+def lusol(A, b, order=1, tol=0.0, match=False):
+    """x = A \\ b (cs_lusol).  match: with the maximum-product matching and scaling in front (CscMat.lu)."""
+    return _k.csc_lusol_f(order, A.m, A.n, A.indptr, A.indices, A.data, b, tol, match=match)
 
 
 def cholsol(A, b, order=1):

@@ -95,6 +95,9 @@ def lib():
         L.cs3_last_error.restype = C.c_char_p
         vp = C.c_void_p
         L.cs3_analyze.argtypes = [I64, I64, I64, _i32p, _i32p, _i32p, I64, C.POINTER(vp)]
+        L.cs3_match_scale.argtypes = [I64, _i32p, _i32p, _f64p, _i32p, _f64p, _f64p]
+        L.cs3_analyze_matched.argtypes = [I64, I64, _i32p, _i32p, _f64p, _i32p, I64, C.POINTER(vp)]
+        L.cs3_get_matching.argtypes = [vp, _i32p, _f64p, _f64p, C.POINTER(C.c_double)]
         L.cs3_free.argtypes = [vp]
         L.cs3_get_info.argtypes = [vp, C.POINTER(Cs3Info)]
         L.cs3_get_ordering.argtypes = [vp] + [_i32p] * 6
@@ -221,6 +224,17 @@ def csc_counts_f(n, Ap, Ai, parent, post):
     return cc
 
 
+def match_scale(n, Ap, Ai, Ax):
+    """Maximum-product transversal with scalings (MC64 job 5), on the host: -> (rowperm, dr, dc) with
+    B[rowinv[i], j] = (dr[i] * A[i, j]) * dc[j], |B| <= 1 and |B[j, j]| = 1; rowperm[j] is the row of A matched to column j.
+    SingularMatrix when A has no full transversal (stored zeros count as absent)."""
+    Ap, Ai, Ax = _i32(Ap), _i32(Ai), _f64(Ax)
+    rowperm = np.empty(n, dtype=np.int32)
+    dr, dc = np.empty(n), np.empty(n)
+    _check(lib().cs3_match_scale(n, _pi(Ap), _pi(Ai), _pf(Ax), _pi(rowperm), _pf(dr), _pf(dc)))
+    return rowperm, dr, dc
+
+
 # ------------------------------------------------------------------ handle --
 
 class UpdatesInfo:
@@ -296,9 +310,13 @@ class Factorization:
 
     kind: CS3_LU or CS3_CHOLESKY.  order: ORDER_NATURAL / ORDER_AMD, or pass q.
     batch: number of matrices sharing the pattern (values [batch, nnz]).
+    match_values (LU only): values Ax[nnz] of ONE representative matrix; the handle then permutes rows by their
+    maximum-product transversal and scales (match_scale) before the analysis and factorises B = P (Dr A Dc), for matrices
+    without a strong diagonal (zero diagonals, saddle-point systems, bad scaling).  Values, right-hand sides and solutions
+    stay in terms of A; order / q, tol, factors() and ordering() refer to B.  The matching is kept across refactorisations.
     """
 
-    def __init__(self, m, n, Ap, Ai, kind=CS3_LU, order=ORDER_AMD, q=None, batch=1):
+    def __init__(self, m, n, Ap, Ai, kind=CS3_LU, order=ORDER_AMD, q=None, batch=1, match_values=None):
         assert m == n, "square matrix required"
         self._h = C.c_void_p()
         self.kind = kind
@@ -310,7 +328,14 @@ class Factorization:
         if q is not None:
             qa = _i32(q)
             order = ORDER_GIVEN
-        _check(lib().cs3_analyze(kind, order, n, _pi(Ap), _pi(Ai), _pi(qa), batch, C.byref(self._h)))
+        self.matched = match_values is not None
+        if self.matched:
+            assert kind == CS3_LU, "matching is for LU handles"
+            mv = _f64(match_values).reshape(-1)
+            assert mv.size >= self.nnz
+            _check(lib().cs3_analyze_matched(order, n, _pi(Ap), _pi(Ai), _pf(mv), _pi(qa), batch, C.byref(self._h)))
+        else:
+            _check(lib().cs3_analyze(kind, order, n, _pi(Ap), _pi(Ai), _pi(qa), batch, C.byref(self._h)))
 
     def close(self):
         if self._h:
@@ -341,6 +366,20 @@ class Factorization:
         arrs = [np.empty(self.n, dtype=np.int32) for _ in names]
         _check(lib().cs3_get_ordering(self._h, *[_pi(a) for a in arrs]))
         return dict(zip(names, arrs))
+
+    def matching(self):
+        """-> (rowperm, dr, dc) of a matched handle, as match_scale returns them (Cs3Error on a plain handle)."""
+        rowperm = np.empty(self.n, dtype=np.int32)
+        dr, dc = np.empty(self.n), np.empty(self.n)
+        _check(lib().cs3_get_matching(self._h, _pi(rowperm), _pf(dr), _pf(dc), None))
+        return rowperm, dr, dc
+
+    @property
+    def match_time(self):
+        """Host seconds the matching took (next to info.t_order_s)."""
+        t = C.c_double(0.0)
+        _check(lib().cs3_get_matching(self._h, None, None, None, C.byref(t)))
+        return float(t.value)
 
     def supernodes(self):
         ns = int(self.info.nsuper)
@@ -577,9 +616,10 @@ def csc_utsolve_f(n, Up, Ui, Ux, x):
     _tri(lib().cs3_csc_utsolve, n, Up, Ui, Ux, x)
 
 
-def csc_lusol_f(order, m, n, Ap, Ai, Ax, b, tol=0.0):
-    """x = A \\ b by LU (cs_lusol)."""
-    with Factorization(m, n, Ap, Ai, CS3_LU, order) as F:
+def csc_lusol_f(order, m, n, Ap, Ai, Ax, b, tol=0.0, match=False):
+    """x = A \\ b by LU (cs_lusol).  match: rows permuted and scaled by the maximum-product transversal first (matrices
+    without a strong diagonal)."""
+    with Factorization(m, n, Ap, Ai, CS3_LU, order, match_values=Ax if match else None) as F:
         return F.factor(Ax, tol).solve(b)
 
 

@@ -3,7 +3,9 @@
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
+#include <chrono>
 #include <climits>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <map>
@@ -52,6 +54,14 @@ struct cs3_handle_s {
     long long fail_col = -1;
     bool inverses_valid = false;      // inverted diagonal blocks (many-RHS GEMM sweeps) match the current factors
     std::vector<i32> Ap_host, Ai_host;
+    // A matched handle (cs3_analyze_matched): S analyses B = P (Dr A Dc), Ap_host / Ai_host keep the pattern of A.
+    struct Matching {
+        bool on = false;
+        std::vector<i32> rowperm;             // row of A matched to column j = row j of B
+        std::vector<double> dr, dc;
+        double t_match = 0.0;                 // host seconds of the matching
+        double parity = 1.0, log_shift = 0.0; // det A = parity det B exp(log_shift): sign of rowperm, -(sum log dr + sum log dc)
+    } match;
     std::vector<cs3_updates_s *> plans;       // the plans made for this handle (cs3_updates_plan)
     // Every HBM block of the handle, one group per feature that builds it; release_device drops them all at once.  A
     // new feature declares its DevBuf in a group here and allocates it in its ensure_*: nothing else has to know.
@@ -74,6 +84,8 @@ struct cs3_handle_s {
         // ensure_updates (updates.hip): the tile of A^-1 columns Z [n][widest tile so far] (grows) and x0 [n] (stable
         // addresses: the solves on them replay the cached graphs)
         struct { DevBuf<double> z, x0; } upd;
+        // ensure_match (matching.hip): the scalings, the row of A behind every pivot row, row and column of every entry
+        struct { DevBuf<double> dr, dc; DevBuf<int> rq, erow, ecol; } match;
     } mem;
     // diagnostics (cs3_debug_alloc_counters): device allocations / graph instantiations and host synchronisations made by the
     // solves and the paths on top of them
@@ -182,6 +194,7 @@ SolveDesc solve_desc_of(const Symbolic &S, i32 s)
 }
 
 int ensure_device_impl(cs3_handle h);
+int ensure_match(cs3_handle h);
 
 // Uploads the analysis and allocates the numeric state; a failure half way leaves nothing behind, so a
 // retry starts from scratch instead of allocating on top of the leaked buffers.
@@ -288,6 +301,8 @@ int ensure_device_impl(cs3_handle h)
             CS3_HIP(hipMemset(D.tbuf, 0, stamps * sizeof(long long)));
         }
     }
+    if (h->match.on)
+        if ((rc = ensure_match(h))) return rc;
     CS3_HIP(hipStreamCreateWithFlags(&h->cap_stream, hipStreamNonBlocking));
     CS3_HIP(h->fj.init());
     const char *ng = std::getenv("CS3_NO_GRAPH");
@@ -358,6 +373,37 @@ int replay_or_run(cs3_handle h, const GraphKey &key, hipStream_t st, Body body)
     return CS3_OK;
 }
 
+// Device arrays of a matched handle, uploaded once (they die with release_device).
+int ensure_match(cs3_handle h)
+{
+    auto &M = h->mem.match;
+    if (M.dr.get()) return CS3_OK;
+    const i64 n = h->S.n, nnz = h->S.nnzA;
+    std::vector<int> rq((size_t) n), ecol((size_t) nnz);
+    for (i64 k = 0; k < n; ++k) rq[k] = h->match.rowperm[h->S.q[k]];
+    for (i64 j = 0; j < n; ++j)
+        for (i64 p = h->Ap_host[j]; p < h->Ap_host[j + 1]; ++p) ecol[p] = (int) j;
+    CS3_HIP(M.dr.upload(h->match.dr)); CS3_HIP(M.dc.upload(h->match.dc));
+    CS3_HIP(M.rq.upload(rq)); CS3_HIP(M.erow.upload(h->Ai_host)); CS3_HIP(M.ecol.upload(ecol));
+    return CS3_OK;
+}
+
+MatchView match_view(cs3_handle h)
+{
+    const auto &M = h->mem.match;
+    return MatchView{M.dr.get(), M.dc.get(), M.rq.get(), M.erow.get(), M.ecol.get()};
+}
+
+// The row permutations of a full solve on a matched handle, scalings folded in (A x = b: x = Dc B^-1 (Dr P b);
+// A' x = b: x = P' Dr B^-T (Dc b)).  into_pivot_order: the caller's rows into D.xp; else D.xp back to the caller's rows.
+hipError_t launch_match_permute(cs3_handle h, const double *src, double *dst, int nrhs, bool into_pivot_order, bool trans, hipStream_t st)
+{
+    const DeviceFactor &D = h->D;
+    const MatchView M = match_view(h);
+    const bool rows_of_a = into_pivot_order != trans;          // this side runs over the rows of A (rq, dr), the other over its columns (q, dc)
+    return launch_match_rows(src, dst, rows_of_a ? M.rq : D.q, rows_of_a ? M.dr : M.dc, D.n, nrhs, D.batch, !into_pivot_order, st);
+}
+
 // The sweeps of one call: launch groups and their descriptors.  One right-hand side on a handle with a bottom forest
 // follows the factor schedule (the forest, then the levels above it) with descriptors of its own.  (The forest's sweeps
 // have no transposed form: a transposed solve takes the level schedule whatever nrhs is.)
@@ -375,6 +421,10 @@ int run_factor(cs3_handle h, const double *ax_dev, double tol, hipStream_t st)
 {
     const DeviceFactor &D = h->D;
     const double inv_tol = (tol > 0.0) ? 1.0 / tol : HUGE_VAL;
+    if (h->match.on) {                                          // the values of B straight into the library's copy
+        CS3_HIP(launch_match_values(match_view(h), ax_dev, D.ax, D.nnz_a, D.batch, st));
+        ax_dev = D.ax;
+    }
     CS3_HIP(launch_prologue(D, ax_dev, nullptr, 0, st));        // status 0x7f7f7f7f = clean, zeros, values
     if (h->factor_inv_tol != inv_tol) {
         if (int rc = drop_graphs(h, [](const GraphKey &k) { return graph_op_is(k, GRAPH_FACTOR); })) return rc;
@@ -440,15 +490,18 @@ int run_solve(cs3_handle h, double *x_dev, long long k, int mode, hipStream_t st
     }
     // fused permutations: the forward sweep reads row q[k] of the caller's X, the backward sweep writes the solution rows
     // back there; X's address is baked into the graph
-    const bool fused = permutation_can_fuse(D, nrhs);
+    const bool matched = h->match.on;                          // (the scalings are not folded into the XMap sweeps)
+    const bool fused = !matched && permutation_can_fuse(D, nrhs);
     if (fused) call.xm = XMap{x_dev, x_dev, D.q};
+    else if (matched) CS3_HIP(launch_match_permute(h, x_dev, D.xp, nrhs, true, trans, st));
     else CS3_HIP(launch_permute(D, x_dev, D.xp, nrhs, false, st));
     rc = replay_or_run(h, GraphKey(GRAPH_SOLVE, trans, nrhs, fused ? x_dev : nullptr), st, [&](hipStream_t s) {
         hipError_t e = launch_solve_levels(D, call, D.xp, nrhs, true, s, h->fj);
         return (e != hipSuccess) ? e : launch_solve_levels(D, call, D.xp, nrhs, false, s, h->fj);
     });
     if (rc) return rc;
-    if (!fused) CS3_HIP(launch_permute(D, D.xp, x_dev, nrhs, true, st));
+    if (matched) CS3_HIP(launch_match_permute(h, D.xp, x_dev, nrhs, false, trans, st));
+    else if (!fused) CS3_HIP(launch_permute(D, D.xp, x_dev, nrhs, true, st));
     return CS3_OK;
 }
 
@@ -464,7 +517,14 @@ int run_factor_solve(cs3_handle h, const double *ax_dev, const double *b_dev, do
     SweepCall call = select_sweep_schedule(h, nrhs);
     call.fwd_in_factor = nrhs == 1 && !h->S.sub_forest.empty();   // the forest's factor launch carries its forward sweep
     call.inverses_in_sweep = true;                                 // the forward sweep inverts group by group
-    CS3_HIP(launch_prologue(D, ax_dev, b_dev, nrhs, st));          // right-hand sides are read from b_dev, the solution goes to x_dev
+    const bool matched = h->match.on;
+    if (matched) {                                                 // scaled values, then the scaled right-hand sides into D.xp
+        CS3_HIP(launch_match_values(match_view(h), ax_dev, D.ax, D.nnz_a, D.batch, st));
+        CS3_HIP(launch_prologue(D, D.ax, nullptr, nrhs, st));
+        CS3_HIP(launch_match_permute(h, b_dev, D.xp, nrhs, true, false, st));
+    } else {
+        CS3_HIP(launch_prologue(D, ax_dev, b_dev, nrhs, st));      // right-hand sides are read from b_dev, the solution goes to x_dev
+    }
     if (h->fused_inv_tol != inv_tol) {
         if ((rc = drop_graphs(h, [](const GraphKey &g) { return graph_op_is(g, GRAPH_FUSED); }))) return rc;
         h->fused_inv_tol = inv_tol;
@@ -475,11 +535,12 @@ int run_factor_solve(cs3_handle h, const double *ax_dev, const double *b_dev, do
     rc = replay_or_run(h, GraphKey(GRAPH_FUSED, false, nrhs, per_x ? x_dev : nullptr), st, [&](hipStream_t s) {
         hipError_t e = launch_factor_with_forward(D, call, h->S.groups, inv_tol, D.xp, nrhs, s, h->fj);
         if (e == hipSuccess) e = launch_solve_levels(D, call, D.xp, nrhs, false, s, h->fj);
-        if (e == hipSuccess && per_x) e = launch_permute(D, D.xp, x_dev, nrhs, true, s);
+        if (e == hipSuccess && per_x)
+            e = matched ? launch_match_permute(h, D.xp, x_dev, nrhs, false, false, s) : launch_permute(D, D.xp, x_dev, nrhs, true, s);
         return e;
     });
     if (rc) return rc;
-    if (!per_x) CS3_HIP(launch_permute(D, D.xp, x_dev, nrhs, true, st));
+    if (!per_x) CS3_HIP(matched ? launch_match_permute(h, D.xp, x_dev, nrhs, false, false, st) : launch_permute(D, D.xp, x_dev, nrhs, true, st));
     h->factored = true;
     h->inverses_valid = nrhs >= 16;                                // a many-RHS fused call leaves them current
     return CS3_OK;
@@ -595,6 +656,89 @@ int cs3_analyze(int64_t kind, int64_t order, int64_t n, const int32_t *Ap, const
         delete h; set_error(e.what()); return CS3_ERR_ARG;
     }
     *out = h;
+    return CS3_OK;
+}
+
+// The checks of cs3_match_scale and the matching itself; `matched` columns on CS3_ERR_PIVOT.
+static int matching_of(const char *who, int64_t n, const int32_t *Ap, const int32_t *Ai, const double *Ax,
+                       int32_t *rowperm, double *dr, double *dc)
+{
+    if (!rowperm || !dr || !dc) { set_error(std::string(who) + ": null output"); return CS3_ERR_ARG; }
+    if (int rc = check_pattern(who, n, Ap, Ai)) return rc;
+    const int64_t nnz = n > 0 ? Ap[n] : 0;
+    if (nnz > 0 && !Ax) { set_error(std::string(who) + ": null values"); return CS3_ERR_ARG; }
+    for (int64_t p = 0; p < nnz; ++p)
+        if (!std::isfinite(Ax[p])) { set_error(std::string(who) + ": non-finite value at entry " + std::to_string(p)); return CS3_ERR_ARG; }
+    int64_t matched = 0;
+    try { matched = match_scale(n, Ap, Ai, Ax, rowperm, dr, dc); }
+    catch (const std::exception &e) { set_error(e.what()); return CS3_ERR_ALLOC; }
+    if (matched < n) {
+        set_error(std::string(who) + ": structurally singular, only " + std::to_string(matched) + " of " + std::to_string(n) +
+                  " columns can be matched to distinct rows (stored zeros count as absent)");
+        return CS3_ERR_PIVOT;
+    }
+    return CS3_OK;
+}
+
+int cs3_match_scale(int64_t n, const int32_t *Ap, const int32_t *Ai, const double *Ax, int32_t *rowperm, double *dr, double *dc)
+{
+    return matching_of("cs3_match_scale", n, Ap, Ai, Ax, rowperm, dr, dc);
+}
+
+int cs3_analyze_matched(int64_t order, int64_t n, const int32_t *Ap, const int32_t *Ai, const double *Ax,
+                        const int32_t *q_given, int64_t batch, cs3_handle *out)
+{
+    if (!out) { set_error("cs3_analyze_matched: null output"); return CS3_ERR_ARG; }
+    *out = nullptr;
+    if (batch < 1) { set_error("cs3_analyze_matched: batch must be >= 1"); return CS3_ERR_ARG; }
+    if (n < 0 || !Ap) { set_error("cs3_analyze_matched: bad size or null column pointers"); return CS3_ERR_ARG; }
+    cs3_handle h = nullptr;
+    try {
+        h = new cs3_handle_s();
+        h->batch = batch;
+        auto &M = h->match;
+        M.rowperm.resize((size_t) n); M.dr.resize((size_t) n); M.dc.resize((size_t) n);
+        const auto t0 = std::chrono::steady_clock::now();
+        if (int rc = matching_of("cs3_analyze_matched", n, Ap, Ai, Ax, M.rowperm.data(), M.dr.data(), M.dc.data())) { delete h; return rc; }
+        M.t_match = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        M.on = true;
+        const int64_t nnz = n > 0 ? Ap[n] : 0;
+        std::vector<i32> rowinv((size_t) n), Bi((size_t) nnz);
+        for (int64_t j = 0; j < n; ++j) rowinv[M.rowperm[j]] = (i32) j;
+        for (int64_t p = 0; p < nnz; ++p) Bi[p] = rowinv[Ai[p]];
+        // det A = parity det B / (prod dr prod dc): the two scalars of cs3_slogdet, summed in index order
+        std::vector<char> seen((size_t) n, 0);
+        for (int64_t j = 0; j < n; ++j) {
+            if (seen[j]) continue;
+            int64_t len = 0;
+            for (int64_t k = j; !seen[k]; k = M.rowperm[k]) { seen[k] = 1; ++len; }
+            if (len % 2 == 0) M.parity = -M.parity;
+        }
+        double sum = 0.0;
+        for (int64_t j = 0; j < n; ++j) sum += std::log(M.dr[j]);
+        for (int64_t j = 0; j < n; ++j) sum += std::log(M.dc[j]);
+        M.log_shift = -sum;
+        analyze(CS3_LU, (int) order, n, Ap, Bi.data(), q_given, h->S, batch);
+        h->Ap_host.assign(Ap, Ap + n + 1);
+        h->Ai_host.assign(Ai, Ai + nnz);
+    } catch (const std::bad_alloc &) {
+        delete h; set_error("cs3_analyze_matched: out of memory"); return CS3_ERR_ALLOC;
+    } catch (const std::exception &e) {
+        delete h; set_error(e.what()); return CS3_ERR_ARG;
+    }
+    *out = h;
+    return CS3_OK;
+}
+
+int cs3_get_matching(cs3_handle h, int32_t *rowperm, double *dr, double *dc, double *t_match_s)
+{
+    int rc = guard(h); if (rc) return rc;
+    if (!h->match.on) { set_error("cs3_get_matching: the handle was not analysed with a matching (cs3_analyze_matched)"); return CS3_ERR_STATE; }
+    const size_t n = (size_t) h->S.n;
+    if (rowperm) std::memcpy(rowperm, h->match.rowperm.data(), n * sizeof(int32_t));
+    if (dr) std::memcpy(dr, h->match.dr.data(), n * sizeof(double));
+    if (dc) std::memcpy(dc, h->match.dc.data(), n * sizeof(double));
+    if (t_match_s) *t_match_s = h->match.t_match;
     return CS3_OK;
 }
 
@@ -765,6 +909,7 @@ int cs3_ltsolve(cs3_handle h, double *X, int64_t k) { return solve_host(h, X, k,
 int cs3_export_factor_dev(cs3_handle h, double *dst_dev, void *stream)
 {
     int rc = guard(h); if (rc) return rc;
+    if (h->match.on) { set_error("cs3_export_factor_dev: not available for a matched handle"); return CS3_ERR_ARG; }
     if (!h->factored) { set_error("cs3_export_factor_dev: nothing factorised"); return CS3_ERR_STATE; }
     if (!dst_dev) { set_error("cs3_export_factor_dev: null buffer"); return CS3_ERR_ARG; }
     const DeviceFactor &D = h->D;
@@ -779,6 +924,7 @@ int cs3_export_factor_dev(cs3_handle h, double *dst_dev, void *stream)
 int cs3_import_factor_dev(cs3_handle h, const double *src_dev, void *stream)
 {
     int rc = guard(h); if (rc) return rc;
+    if (h->match.on) { set_error("cs3_import_factor_dev: not available for a matched handle"); return CS3_ERR_ARG; }
     if (!src_dev) { set_error("cs3_import_factor_dev: null buffer"); return CS3_ERR_ARG; }
     if ((rc = ensure_device(h))) return rc;
     const DeviceFactor &D = h->D;
@@ -1242,6 +1388,8 @@ int cs3_slogdet_dev(cs3_handle h, double *sign_dev, double *logabs_dev, void *st
     if (!h->factored) { set_error("cs3_slogdet_dev: no successful factorisation"); return CS3_ERR_STATE; }
     if ((rc = ensure_diag_map(h))) return rc;
     CS3_HIP(launch_slogdet(h->D, (const long long *) h->mem.diag.get(), sign_dev, logabs_dev, (hipStream_t) stream));
+    if (h->match.on)                                               // of A, not of B
+        CS3_HIP(launch_match_slogdet(sign_dev, logabs_dev, h->batch, h->match.parity, h->match.log_shift, (hipStream_t) stream));
     return CS3_OK;
 }
 

@@ -212,6 +212,20 @@ hipError_t launch_est_finalize(const EstState *state, long long batch, double *c
 // diag[n]: virtual pool offset of every pivot's diagonal
 hipError_t launch_slogdet(const DeviceFactor &D, const long long *diag, double *sign, double *logabs, hipStream_t st);
 
+// matching.hip: a matched handle (cs3_analyze_matched) factorises B = P (Dr A Dc); its callers speak in terms of A.
+struct MatchView {                // device arrays of the matching
+    const double *dr, *dc;        // [n] row and column scalings
+    const int *rq;                // [n] rowperm[q[k]]: the row of A behind pivot row k (D.q is the other row map)
+    const int *erow, *ecol;       // [nnz_a] row and column of every entry of A
+};
+// dst [batch][nnz] = (dr[row] * src) * dc[col], entry by entry (src may be dst)
+hipError_t launch_match_values(const MatchView &M, const double *src, double *dst, long long nnz, long long batch, hipStream_t st);
+// k_permute_rows with a scaling: gather dst[k, :] = scale[map[k]] src[map[k], :], scatter dst[map[k], :] = scale[map[k]] src[k, :]
+hipError_t launch_match_rows(const double *src, double *dst, const int *map, const double *scale, long long n, int nrhs,
+                             long long batch, bool scatter, hipStream_t st);
+// sign[b] *= parity (unless 0), logabs[b] += shift
+hipError_t launch_match_slogdet(double *sign, double *logabs, long long batch, double parity, double shift, hipStream_t st);
+
 // updates.hip: many low-rank-modified systems (A + dA_c) x = b on the held factors (cs3_updates_*).
 constexpr int UPD_MAX_RANK = 16;               // distinct rows / columns of one case
 constexpr int UPD_MAX_TILE = 1024;             // columns of A^-1 solved for at a time (the width the many-RHS path is tuned at)

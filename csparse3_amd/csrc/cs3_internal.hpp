@@ -23,6 +23,11 @@ void symmetrized_pattern(i64 n, const i32 *Ap, const i32 *Ai,
 void amd_order(i64 n, const std::vector<i64> &Cp, const std::vector<i32> &Ci,
                std::vector<i32> &perm);
 
+// ---- matching.cpp --------------------------------------------------------
+// Maximum-product transversal with scalings (include/csparse3_amd.h: cs3_match_scale).  The pattern has been checked and
+// the values are finite.  Returns the number of matched columns; rowperm, dr, dc are written only when that is n.
+i64 match_scale(i64 n, const i32 *Ap, const i32 *Ai, const double *Ax, i32 *rowperm, double *dr, double *dc);
+
 // ---- symbolic.cpp --------------------------------------------------------
 void etree_upper(i64 n, const i32 *Ap, const i32 *Ai, i32 *parent);
 void tree_postorder(i64 n, const i32 *parent, i32 *post);

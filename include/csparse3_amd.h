@@ -92,19 +92,68 @@ int cs3_get_info(cs3_handle h, cs3_info *info);
  * parent[n], post[n], colcount[n]: etree / postorder / column counts of
  *             A(q_amd,q_amd) + its transpose, as cs_schol computes them
  * q[n]:       the pivot order actually used = q_amd[post[.]]
- * pinv[n]:    row permutation of the factorisation, pinv[q[k]] = k */
+ * pinv[n]:    row permutation of the factorisation, pinv[q[k]] = k
+ * On a matched handle these are the orderings of B (cs3_get_matching has the row matching in front of them). */
 int cs3_get_ordering(cs3_handle h, int32_t *q_amd, int32_t *parent, int32_t *post,
                      int32_t *colcount, int32_t *q, int32_t *pinv);
 /* Supernode partition: sn_ptr[nsuper+1] first pivot column of each supernode,
  * sn_parent[nsuper], sn_level[nsuper]. */
 int cs3_get_supernodes(cs3_handle h, int32_t *sn_ptr, int32_t *sn_parent, int32_t *sn_level);
 
+/* ---- matching + scaling: LU for matrices without a strong diagonal ------
+ * Every pivot of cs3_factor is a diagonal entry, only checked against tol.  A row-permuted identity, a saddle-point
+ * system [[H, G'], [G, 0]] or a badly scaled Jacobian fails that check.  The step that makes static pivots safe there
+ * (Duff & Koster, MC64 job 5; the weighted relative of cs_maxtrans; what SuperLU_DIST, PARDISO and cuDSS do): before the
+ * analysis, permute the rows by a maximum-product transversal and scale rows and columns so that the diagonal is 1 and
+ * everything else at most 1 in magnitude.
+ *
+ * For A (n x n, CSC, nnz = Ap[n]) a matching is rowperm[n], dr[n] > 0, dc[n] > 0:
+ *   rowperm[j] is the row of A matched to column j; it becomes row j of B.  rowinv is its inverse.
+ *   B[rowinv[i], j] = (dr[i] * A[i, j]) * dc[j], in exactly this product order (two roundings), so a host can rebuild B bit
+ *     for bit.  Column j of B holds the entries of column j of A in the same storage order: Ax keeps its entry order, only
+ *     the row indices change.
+ *   |B| <= 1 everywhere and |B[j, j]| = 1, up to the rounding of exp / log (a few 1e-15).
+ *   Among all transversals sum_j log |A[rowperm[j], j]| is maximal.
+ * An entry whose value is exactly 0 counts as absent (entries stored twice count as two entries).  Costs
+ * c_ij = log max_i |a_ij| - log |a_ij|, shortest augmenting paths with duals u_i + v_j <= c_ij, dr_i = exp(u_i),
+ * dc_j = exp(v_j) / max_i |a_ij|; ties go to the lowest index, so the result is bitwise the same on every run.  Host
+ * code, sequential.
+ *
+ * cs3_match_scale: the matching alone; needs no GPU (like cs3_amd).  Rows inside a column need not be sorted.
+ * cs3_analyze_matched: cs3_analyze for CS3_LU with the matching computed from Ax[nnz] -- ONE representative matrix, also
+ *   when batch > 1; the matching is then fixed for the life of the handle (refactorisations keep it).  The handle
+ *   analyses the pattern of B, (Ap, rowinv[Ai]); order / q_given apply to B.
+ * cs3_get_matching: any pointer may be NULL; t_match_s = host seconds the matching took (next to cs3_info.t_order_s).
+ *   A handle made by cs3_analyze gives CS3_ERR_STATE.
+ * Checks of the first two, in this order: null pointers or a bad pattern (Ap[0] != 0, Ap not monotone, a row index
+ * outside [0, n)): CS3_ERR_ARG; a non-finite value in Ax: CS3_ERR_ARG; no full transversal (structurally singular, stored
+ * zeros absent): CS3_ERR_PIVOT, and the message says how many columns could be matched.
+ *
+ * On a MATCHED handle every entry point keeps speaking in terms of A where it takes or returns values, right-hand sides
+ * and solutions -- Ax in A's entry order, b and x in A's rows and columns -- and in terms of B where it exposes the
+ * factorisation itself:
+ *   cs3_factor, cs3_factor_dev, cs3_factor_solve_dev, cs3_factor_solve_bx_dev: factorise B; the values are scaled on the device into the
+ *     library's own copy (one more launch, no further pass over the values).  tol and fail_col refer to B in its pivot order.
+ *   cs3_solve(_dev): A x = b as x = Dc B^-1 (Dr P b).  cs3_solve_t(_dev): A' x = b as z = B^-T (Dc b),
+ *     x[i] = dr[i] z[rowinv[i]].  The scalings ride in the two row permutations of the solve.
+ *   cs3_residual / matvec / refine(_t)_dev, cs3_condest(_dev), cs3_slogdet(_dev), cs3_updates_*: of A (||A||_1 from the
+ *     caller's Ax; sign = sign(det B) * parity(rowperm), log|det A| = log|det B| - sum log dr - sum log dc).
+ *   cs3_lsolve / usolve / ltsolve / utsolve, cs3_get_factors, cs3_get_ordering, cs3_get_info: the factors and orderings of B.
+ *   cs3_export_factor_dev / cs3_import_factor_dev: CS3_ERR_ARG (not available on matched handles).
+ * A handle made by cs3_analyze behaves as before, bit for bit and launch for launch. */
+int cs3_match_scale(int64_t n, const int32_t *Ap, const int32_t *Ai, const double *Ax,
+                    int32_t *rowperm, double *dr, double *dc);
+int cs3_analyze_matched(int64_t order, int64_t n, const int32_t *Ap, const int32_t *Ai, const double *Ax,
+                        const int32_t *q_given, int64_t batch, cs3_handle *out);
+int cs3_get_matching(cs3_handle h, int32_t *rowperm, double *dr, double *dc, double *t_match_s);
+
 /* ---- numeric factorisation (cs_lu / cs_chol lineage) --------------------
  * P A Q = L U with P = Q' (static diagonal pivots in AMD order), L unit lower,
  * U upper; or P A P' = L L'.  Ax[batch][nnz_a] in the entry order of the
  * analysed (Ap, Ai).  tol as in cs_lu: a diagonal pivot is accepted when
  * |pivot| >= tol * max|column below|; rejected pivots give CS3_ERR_PIVOT
- * (there is no CPU fallback).  tol <= 0 disables the test. */
+ * (there is no CPU fallback).  tol <= 0 disables the test.  On a matched handle (cs3_analyze_matched) Ax are still the
+ * values of A; B is factorised and tol refers to B. */
 int cs3_factor(cs3_handle h, const double *Ax, double tol);
 int cs3_factor_dev(cs3_handle h, const double *Ax_dev, double tol, void *stream);
 /* cs_lusol / cs_cholsol as one call on resident data: numeric (re)factorisation of Ax AND the full
@@ -123,7 +172,9 @@ int cs3_factor_status(cs3_handle h, void *stream);
  * overwritten in place.  With batch > 1, X is [batch, n, k].
  * cs3_solve:   full solve A x = b including both permutations
  * cs3_lsolve:  x = L \ x     in the permuted (pivot-order) space
- * cs3_usolve:  x = U \ x     (for Cholesky: x = L' \ x) */
+ * cs3_usolve:  x = U \ x     (for Cholesky: x = L' \ x)
+ * On a matched handle cs3_solve solves with A (scalings and row matching included); cs3_lsolve / cs3_usolve apply the
+ * factors of B. */
 int cs3_solve(cs3_handle h, double *X, int64_t k);
 int cs3_lsolve(cs3_handle h, double *X, int64_t k);
 int cs3_usolve(cs3_handle h, double *X, int64_t k);
@@ -134,7 +185,8 @@ int cs3_usolve_dev(cs3_handle h, double *X_dev, int64_t k, void *stream);
  * cs3_solve_t:  full solve A' x = b, both permutations included (x = P' (L' \ (U' \ (Q' b))))
  * cs3_utsolve:  x = U' \ x   in pivot order (Cholesky handles: CS3_ERR_ARG, there is no U)
  * cs3_ltsolve:  x = L' \ x   in pivot order, unit diagonal for LU (Cholesky: what cs3_usolve does)
- * On a Cholesky handle A' = A: cs3_solve_t is cs3_solve, bit for bit. */
+ * On a Cholesky handle A' = A: cs3_solve_t is cs3_solve, bit for bit.  On a matched handle cs3_solve_t solves with A',
+ * cs3_utsolve / cs3_ltsolve apply the factors of B. */
 int cs3_solve_t(cs3_handle h, double *X, int64_t k);
 int cs3_utsolve(cs3_handle h, double *X, int64_t k);
 int cs3_ltsolve(cs3_handle h, double *X, int64_t k);
@@ -145,7 +197,8 @@ int cs3_ltsolve_dev(cs3_handle h, double *X_dev, int64_t k, void *stream);
 /* ---- residual and iterative refinement on resident data ----
  * R = B - A X with the handle's analysed pattern and the values Ax_dev [batch][nnz]; X, B, R [batch][n, k] row-major.
  * Every row of A X is summed as csc_mat_vec_ff sums it (csc_numba.py:309-328: ascending column, product rounded before
- * the add), so results are reproducible and A X equals the reference's matvec bit for bit. */
+ * the add), so results are reproducible and A X equals the reference's matvec bit for bit.  On a matched handle these
+ * are products with A itself (the pattern the caller passed), and refinement solves with A. */
 int cs3_residual_dev(cs3_handle h, const double *Ax_dev, const double *B_dev, const double *X_dev, double *R_dev,
                      int64_t k, void *stream);
 /* Y = A X alone, same summation (the device-resident csc_mat_vec_ff; cs3_csc_matvec is the host-pointer form). */
@@ -183,7 +236,9 @@ int cs3_refine_t_dev(cs3_handle h, const double *Ax_dev, const double *B_dev, do
  *   sign +1, 2 sum log l_jj).  Pivots that only imported factors can hold follow numpy.linalg.slogdet: a zero pivot
  *   gives (0, -inf); an infinite one log|det| = +inf; a NaN one log|det| = NaN with the sign of the other pivots.
  *   Asynchronous.
- * cs3_slogdet: the same into host arrays (synchronises). */
+ * cs3_slogdet: the same into host arrays (synchronises).
+ * On a matched handle all four are of A: kappa_1(A) through the matched solves, det A from det B, the parity of rowperm
+ * and the scalings. */
 int cs3_condest_dev(cs3_handle h, const double *Ax_dev, double *cond_dev, double *inv_norm_dev, void *stream);
 int cs3_condest(cs3_handle h, const double *Ax, double *cond, double *inv_norm);
 int cs3_slogdet_dev(cs3_handle h, double *sign_dev, double *logabs_dev, void *stream);
@@ -227,6 +282,8 @@ int cs3_slogdet(cs3_handle h, double *sign, double *logabs);
  * A plan survives refactorisations of its handle.  Plans and handle may be freed in either order: freeing the handle
  * releases the device memory of its plans, which can then only be freed (a solve with one is CS3_ERR_ARG).
  *
+ * On a matched handle the plan's indices and the solutions are in A's rows and columns, as everywhere.
+ *
  * Out of scope: batched handles; transposed systems; several base right-hand sides per call; more than 16 distinct rows
  * or columns per case; exploiting the sparsity of the unit right-hand sides inside the sweeps; solving with A^-T E_C
  * instead of A^-1 E_R when a list has fewer distinct columns than rows. */
@@ -243,7 +300,9 @@ int cs3_updates_solve(cs3_handle h, cs3_updates u, const double *cx, const doubl
  * L: diagonal FIRST in each column (unit for LU); U: diagonal LAST; row
  * indices sorted otherwise.  Sizes from cs3_info.nnz_l / nnz_u.  NumPy-style
  * ownership: the caller allocates, the library fills.  b = matrix index in
- * the batch.  For Cholesky Up/Ui/Ux must be NULL. */
+ * the batch.  For Cholesky Up/Ui/Ux must be NULL.  On a matched handle these are the factors of B.  The structure is
+ * that of the analysed pattern plus its transpose: on a structurally unsymmetric pattern (B usually is one) positions
+ * that the unsymmetric elimination never fills are stored as explicit zeros. */
 int cs3_get_factors(cs3_handle h, int64_t b, int32_t *Lp, int32_t *Li, double *Lx,
                     int32_t *Up, int32_t *Ui, double *Ux);
 
@@ -252,7 +311,7 @@ int cs3_get_factors(cs3_handle h, int64_t b, int32_t *Lp, int32_t *Li, double *L
  * per matrix, batch matrices back to back.  Export copies them into a caller
  * buffer in HBM (which RCCL then broadcasts); import installs such a buffer in
  * a handle that analysed the SAME pattern with the SAME ordering, after which
- * it solves as if it had factorised itself. */
+ * it solves as if it had factorised itself.  Matched handles: CS3_ERR_ARG. */
 int cs3_export_factor_dev(cs3_handle h, double *dst_dev, void *stream);
 int cs3_import_factor_dev(cs3_handle h, const double *src_dev, void *stream);
 
