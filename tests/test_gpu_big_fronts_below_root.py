@@ -30,6 +30,7 @@ import pytest
 import pivot_cases as pc
 import sweep_cases as sc
 from helpers import RTOL, U_ROUND, assert_backward_error, assert_factor_equal, backward_error_ratio_dense, lower_transposed, permuted
+from rhs_cases import right_hand_sides as _right_hand_sides         # (shared with tests/test_gpu_many_rhs_edges.py)
 
 pytestmark = pytest.mark.gpu
 
@@ -150,20 +151,6 @@ MODES = {"lu": {"lsolve": ((("L", True, False),), False), "usolve": ((("U", Fals
                 "solve_t": ((("U", False, True), ("L", True, True)), True)},
          "chol": {"lsolve": ((("L", True, False),), False), "usolve": ((("L", True, True),), False),
                   "solve": ((("L", True, False), ("L", True, True)), True)}}
-
-
-def _right_hand_sides(batch, n, nrhs, seed):
-    """[batch, n, nrhs] standard normal; of the batch * nrhs columns (matrix-major) the last is scaled by 2^200, the
-    second by 2^-200 (three columns or more) and the third is zero (four or more)."""
-    B = np.random.default_rng(seed).standard_normal((batch, n, nrhs))
-    cols = B.transpose(0, 2, 1).reshape(batch * nrhs, n)                   # a copy: column c = (matrix c // nrhs, column c % nrhs)
-    if len(cols) >= 2:
-        cols[-1] *= 2.0 ** 200
-    if len(cols) >= 3:
-        cols[1] *= 2.0 ** -200
-    if len(cols) >= 4:
-        cols[2] = 0.0
-    return np.ascontiguousarray(cols.reshape(batch, nrhs, n).transpose(0, 2, 1))
 
 
 def _run(F, mode, B):
