@@ -75,6 +75,16 @@ def _hub():
 TREES = {"t16": _t16, "t24": _t24, "t32": _t32, "hub": _hub}
 SEEDS = {"t16": 16000, "t24": 24000, "t32": 32000, "hub": 64000}
 
+_REGISTERED = {}               # trees of other case modules (tests/forest_cases.py): not among the cases of this one
+
+
+def register(name, tree, seed):
+    """Makes `tree` (a function -> _node) known to _pattern / tree_matrix / case_matrix / handle under `name`."""
+    assert name not in TREES and _REGISTERED.get(name, tree) is tree
+    _REGISTERED[name] = tree
+    SEEDS[name] = seed
+
+
 Pattern = collections.namedtuple("Pattern", "n Ap Ai ei ej order")
 _PATTERNS = {}
 
@@ -95,7 +105,7 @@ def _pattern(name):
             flat[c][2] = len(flat) - 1
         return len(flat) - 1
 
-    walk(TREES[name]())
+    walk((TREES[name] if name in TREES else _REGISTERED[name])())
     c0 = np.concatenate([[0], np.cumsum([f[0] for f in flat])]).astype(np.int64)
     n = int(c0[-1])
     struct = [None] * len(flat)
