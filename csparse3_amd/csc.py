@@ -178,12 +178,18 @@ class CscMat:
             self._factorization = f = (key, fac)
         return f[1]
 
-    def lu(self, tol=0.0, order=_k.ORDER_AMD, q=None, match=False):
+    def lu(self, tol=0.0, order=_k.ORDER_AMD, q=None, match=False, perturb=0.0):
         """Numeric LU on the device; the symbolic analysis is cached on the object, so calling
         lu() again after changing .data is a refactorisation with the pattern reused.
         match: permute rows by the maximum-product transversal and scale before the analysis (matrices without a strong
-        diagonal); the matching is computed from .data at the first analysis and kept across refactorisations."""
+        diagonal); the matching is computed from .data at the first analysis and kept across refactorisations.
+        perturb: static pivot perturbation -- a pivot below delta becomes +delta instead of failing the factorisation
+        (a number: delta itself; True: sqrt(eps), times max |data| when match is false).  The analysis is reused whatever
+        perturb is; F.perturbed() counts the replaced pivots and solutions then need F.refine / solve(perturb=...)."""
         F = self._analysis(_k.CS3_LU, order, q, match)
+        delta = _k.perturbation_delta(perturb, self.data, match)
+        if delta != F.perturbation:
+            F.set_perturbation(delta)
         F.factor(self.data, tol)
         return F
 
@@ -192,9 +198,15 @@ class CscMat:
         F.factor(self.data)
         return F
 
-    def solve(self, b, tol=0.0, trans=False, match=False):
-        """x = A \\ b by LU (factorises if needed); trans: A' x = b on the same factors; match: as in lu()."""
-        return self.lu(tol, match=match).solve(b, trans=trans)
+    def solve(self, b, tol=0.0, trans=False, match=False, perturb=0.0, max_refine=10):
+        """x = A \\ b by LU (factorises if needed); trans: A' x = b on the same factors; match, perturb: as in lu().
+        With perturb the solution is refined against A when pivots were replaced (Factorization.solve_refined; not
+        offered together with trans)."""
+        F = self.lu(tol, match=match, perturb=perturb)
+        if F.perturbation == 0.0:
+            return F.solve(b, trans=trans)
+        assert not trans, "perturb refines A x = b only"
+        return F.solve_refined(self.data, b, max_refine)
 
     def solve_modified(self, b, deltas, tol=0.0, sing_tol=0.0):
         """x_c = (A + dA_c) \\ b for a list of sparse modifications, `deltas` = [(rows, cols, vals), ...] (triplets of dA_c;
@@ -236,9 +248,11 @@ def scipy_to_mat(scipy_mat):
     return CscMat(m, n, indptr=scipy_mat.indptr, indices=scipy_mat.indices, data=scipy_mat.data)
 
 
-def lusol(A, b, order=1, tol=0.0, match=False):
-    """x = A \\ b (cs_lusol).  match: with the maximum-product matching and scaling in front (CscMat.lu)."""
-    return _k.csc_lusol_f(order, A.m, A.n, A.indptr, A.indices, A.data, b, tol, match=match)
+def lusol(A, b, order=1, tol=0.0, match=False, perturb=0.0, max_refine=10):
+    """x = A \\ b (cs_lusol).  match: with the maximum-product matching and scaling in front (CscMat.lu).  perturb: small
+    pivots are replaced instead of rejected and the solution is refined, at most max_refine rounds (csc_lusol_f)."""
+    return _k.csc_lusol_f(order, A.m, A.n, A.indptr, A.indices, A.data, b, tol, match=match, perturb=perturb,
+                          max_refine=max_refine)
 
 
 def cholsol(A, b, order=1):

@@ -117,6 +117,9 @@ def lib():
             f.argtypes = [vp, vp, vp, vp, I64, vp]
         for f in (L.cs3_refine_dev, L.cs3_refine_t_dev):
             f.argtypes = [vp, vp, vp, vp, I64, I64, C.POINTER(C.c_double), vp]
+        L.cs3_refine.argtypes = [vp, _f64p, _f64p, _f64p, I64, I64, C.POINTER(C.c_double)]
+        L.cs3_set_pivot_perturbation.argtypes = [vp, C.c_double]
+        L.cs3_get_perturbed.argtypes = [vp, C.POINTER(I64), vp]
         L.cs3_condest_dev.argtypes = [vp, vp, vp, vp, vp]
         L.cs3_condest.argtypes = [vp, _f64p, _f64p, _f64p]
         L.cs3_slogdet_dev.argtypes = [vp, vp, vp, vp]
@@ -314,6 +317,8 @@ class Factorization:
     maximum-product transversal and scales (match_scale) before the analysis and factorises B = P (Dr A Dc), for matrices
     without a strong diagonal (zero diagonals, saddle-point systems, bad scaling).  Values, right-hand sides and solutions
     stay in terms of A; order / q, tol, factors() and ordering() refer to B.  The matching is kept across refactorisations.
+    set_perturbation (LU only): pivots smaller than delta are replaced by +delta instead of stopping the factorisation;
+    perturbed() counts them and refine() removes the error from a solution.
     """
 
     def __init__(self, m, n, Ap, Ai, kind=CS3_LU, order=ORDER_AMD, q=None, batch=1, match_values=None):
@@ -329,6 +334,7 @@ class Factorization:
             qa = _i32(q)
             order = ORDER_GIVEN
         self.matched = match_values is not None
+        self.perturbation = 0.0
         if self.matched:
             assert kind == CS3_LU, "matching is for LU handles"
             mv = _f64(match_values).reshape(-1)
@@ -389,6 +395,21 @@ class Factorization:
         _check(lib().cs3_get_supernodes(self._h, _pi(sn_ptr), _pi(sn_parent), _pi(sn_level)))
         return sn_ptr, sn_parent, sn_level
 
+    # -- static pivot perturbation
+    def set_perturbation(self, delta):
+        """LU pivots with |p| < delta become +delta from the next factorisation on (0: off, the default).  On a matched
+        handle delta refers to B, where |B| <= 1.  The factors are then those of A(q, q) + diag(E): solutions need
+        refine(), and slogdet / condest describe the perturbed matrix."""
+        _check(lib().cs3_set_pivot_perturbation(self._h, float(delta)))
+        self.perturbation = float(delta)
+        return self
+
+    def perturbed(self, stream=0):
+        """-> int64[batch]: the pivots the last factorisation replaced, per matrix (synchronises `stream`)."""
+        count = np.zeros(self.batch, dtype=np.int64)
+        _check(lib().cs3_get_perturbed(self._h, count.ctypes.data_as(C.POINTER(I64)), C.c_void_p(stream)))
+        return count
+
     # -- numeric, host arrays
     def factor(self, Ax, tol=0.0):
         Ax = _f64(Ax)
@@ -402,6 +423,35 @@ class Factorization:
         per = self.batch * self.n
         assert x.size % per == 0, "right-hand side does not match [batch,] n [, k]"
         _check((lib().cs3_solve_t if trans else lib().cs3_solve)(self._h, _pf(x), x.size // per))
+        return x
+
+    def refine(self, Ax, b, x, steps=1):
+        """`steps` rounds of x += A \\ (b - A x) with the held factors and the values Ax (host arrays; the bits of
+        refine_dev).  -> (the refined x, a new array; max |dx| of the last round)."""
+        Ax, b = _f64(Ax), _f64(b)
+        x = np.array(x, dtype=np.float64, order="C", copy=True)
+        per = self.batch * self.n
+        assert Ax.size >= self.batch * self.nnz and x.size % per == 0 and b.size == x.size
+        out = C.c_double(0.0)
+        _check(lib().cs3_refine(self._h, _pf(Ax), _pf(b), _pf(x), x.size // per, steps, C.byref(out)))
+        return x, float(out.value)
+
+    def solve_refined(self, Ax, b, max_refine=10):
+        """solve(b), then -- when the factorisation replaced pivots -- refinement one round at a time until the correction
+        no longer falls below half of the one before, at most max_refine rounds (a round whose correction GREW is dropped).
+        Without replaced pivots this is solve(b), bit for bit."""
+        x = self.solve(b)
+        if not self.perturbed().any():
+            return x
+        prev = np.inf
+        for _ in range(max_refine):
+            x_new, corr = self.refine(Ax, b, x, 1)
+            if not corr <= prev:
+                break
+            x = x_new
+            if not corr < 0.5 * prev:
+                break
+            prev = corr
         return x
 
     def _sweep(self, fn, x):
@@ -616,11 +666,24 @@ def csc_utsolve_f(n, Up, Ui, Ux, x):
     _tri(lib().cs3_csc_utsolve, n, Up, Ui, Ux, x)
 
 
-def csc_lusol_f(order, m, n, Ap, Ai, Ax, b, tol=0.0, match=False):
+def perturbation_delta(perturb, Ax, match):
+    """The delta behind a `perturb` argument: True means sqrt(eps), times max |Ax| unless the handle is matched (B is
+    scaled to |B| <= 1); a number is taken as it is; False / 0: off."""
+    if perturb is True:
+        scale = 1.0 if match else float(np.abs(_f64(Ax)).max(initial=0.0))
+        return float(np.sqrt(np.finfo(np.float64).eps)) * scale
+    return float(perturb or 0.0)
+
+
+def csc_lusol_f(order, m, n, Ap, Ai, Ax, b, tol=0.0, match=False, perturb=0.0, max_refine=10):
     """x = A \\ b by LU (cs_lusol).  match: rows permuted and scaled by the maximum-product transversal first (matrices
-    without a strong diagonal)."""
+    without a strong diagonal).  perturb: pivots below delta are replaced instead of rejected (perturbation_delta), and
+    the solution is refined (Factorization.solve_refined, at most max_refine rounds)."""
     with Factorization(m, n, Ap, Ai, CS3_LU, order, match_values=Ax if match else None) as F:
-        return F.factor(Ax, tol).solve(b)
+        delta = perturbation_delta(perturb, Ax, match)
+        if delta == 0.0:
+            return F.factor(Ax, tol).solve(b)
+        return F.set_perturbation(delta).factor(Ax, tol).solve_refined(Ax, b, max_refine)
 
 
 def csc_cholsol_f(order, m, n, Ap, Ai, Ax, b):

@@ -28,12 +28,12 @@ void set_error(const std::string &msg) { g_error = msg; }
 
 // Captured graphs, one cache per handle, keyed by what a capture bakes in: (operation, trans, nrhs, the caller's X when
 // its address is inside the graph, else null).
-//   - GRAPH_FACTOR: one graph (trans false, nrhs 0), dropped when inv_tol changes.
+//   - GRAPH_FACTOR: one graph (trans false, nrhs 0), dropped when inv_tol or the perturbation delta changes.
 //   - GRAPH_SOLVE per (trans, nrhs): unbounded.  With fused permutations (X baked in) per (trans, nrhs, X): at most 8 per
 //     trans -- the 9th clears that class (callers that rotate buffers).
 //   - GRAPH_FUSED (factor + overlapped forward + backward) per nrhs: unbounded.  The same with the closing permutation
 //     inside the graph (no eager launch behind it: 5 us) per (nrhs, X): at most 4, and only from the third call in a row
-//     with the same X (fused_last_x / fused_same_x).  A change of inv_tol drops every fused-step graph.
+//     with the same X (fused_last_x / fused_same_x).  A change of inv_tol or delta drops every fused-step graph.
 //   - ensure_rhs_capacity drops every solve and fused-step graph (the buffers they read move).
 // A graph that may still be running on another stream is destroyed only after a hipDeviceSynchronize.
 enum GraphOp { GRAPH_FACTOR, GRAPH_SOLVE, GRAPH_FUSED };
@@ -44,11 +44,13 @@ struct cs3_handle_s {
     DeviceFactor D;
     long long batch = 1;
     bool on_device = false, factored = false;
+    bool factor_ran = false;          // a numeric factorisation was enqueued on this handle (its counters mean something)
     bool use_graph = true;
     hipStream_t cap_stream = nullptr;
     ForkJoin fj;
     std::map<GraphKey, hipGraphExec_t> graphs;
-    double factor_inv_tol = 0.0, fused_inv_tol = 0.0;     // what the factor / fused-step graphs were captured with
+    PivotCtl factor_ctl{0.0, 0.0, nullptr}, fused_ctl{0.0, 0.0, nullptr};     // what the factor / fused-step graphs were captured with
+    double perturb_delta = 0.0;       // cs3_set_pivot_perturbation: LU pivots with |p| < delta become +delta (0: off)
     const void *fused_last_x = nullptr;
     int fused_same_x = 0;
     long long fail_col = -1;
@@ -291,8 +293,9 @@ int ensure_device_impl(cs3_handle h)
     D.pool_pm = D.pool + il_doubles - D.il_len;            // virtual offsets >= il_len index this pointer directly
     if ((rc = factor_alloc(h, &D.dbuf, (size_t) (D.batch * D.dbuf_size)))) return rc;
     if ((rc = factor_alloc(h, &D.ax, (size_t) (D.batch * D.nnz_a)))) return rc;
-    if ((rc = factor_alloc(h, &D.status, 4))) return rc;    // [0] the status word, [1], [2] unused, [3] a hand-over between waves timed out
-    CS3_HIP(hipMemset(D.status, 0, 4 * sizeof(int)));
+    // [0] the status word, [1], [2] unused, [3] a hand-over between waves timed out, [4 + b] perturbed pivots of matrix b
+    if ((rc = factor_alloc(h, &D.status, 4 + (size_t) D.batch))) return rc;
+    CS3_HIP(hipMemset(D.status, 0, (4 + (size_t) D.batch) * sizeof(int)));
     CS3_HIP(hipMemset(D.status, 0x7f, sizeof(int)));      // "clean": a handle that only imports factors never runs a prologue
     if (const char *pf = std::getenv("CS3_PROFILE")) {
         if (pf[0] == '1') {
@@ -417,25 +420,32 @@ SweepCall select_sweep_schedule(cs3_handle h, int nrhs, bool trans = false)
     return c;
 }
 
+// The pivot rule of one factorisation: the caller's tol and the handle's perturbation.
+PivotCtl pivot_ctl(cs3_handle h, double tol)
+{
+    return PivotCtl{(tol > 0.0) ? 1.0 / tol : HUGE_VAL, h->perturb_delta, h->D.status + 4};
+}
+
 int run_factor(cs3_handle h, const double *ax_dev, double tol, hipStream_t st)
 {
     const DeviceFactor &D = h->D;
-    const double inv_tol = (tol > 0.0) ? 1.0 / tol : HUGE_VAL;
+    const PivotCtl pc = pivot_ctl(h, tol);
     if (h->match.on) {                                          // the values of B straight into the library's copy
         CS3_HIP(launch_match_values(match_view(h), ax_dev, D.ax, D.nnz_a, D.batch, st));
         ax_dev = D.ax;
     }
     CS3_HIP(launch_prologue(D, ax_dev, nullptr, 0, st));        // status 0x7f7f7f7f = clean, zeros, values
-    if (h->factor_inv_tol != inv_tol) {
+    if (h->factor_ctl != pc) {
         if (int rc = drop_graphs(h, [](const GraphKey &k) { return graph_op_is(k, GRAPH_FACTOR); })) return rc;
-        h->factor_inv_tol = inv_tol;
+        h->factor_ctl = pc;
     }
     const SweepCall call;
     int rc = replay_or_run(h, GraphKey(GRAPH_FACTOR, false, 0, nullptr), st, [&](hipStream_t s) {
-        return launch_factor_levels(D, call, h->S.groups, inv_tol, s, h->fj);
+        return launch_factor_levels(D, call, h->S.groups, pc, s, h->fj);
     });
     if (rc) return rc;
     h->factored = true;
+    h->factor_ran = true;
     h->inverses_valid = false;
     return CS3_OK;
 }
@@ -513,7 +523,7 @@ int run_factor_solve(cs3_handle h, const double *ax_dev, const double *b_dev, do
     if (rc) return rc;
     const DeviceFactor &D = h->D;
     const int nrhs = (int) k;
-    const double inv_tol = (tol > 0.0) ? 1.0 / tol : HUGE_VAL;
+    const PivotCtl pc = pivot_ctl(h, tol);
     SweepCall call = select_sweep_schedule(h, nrhs);
     call.fwd_in_factor = nrhs == 1 && !h->S.sub_forest.empty();   // the forest's factor launch carries its forward sweep
     call.inverses_in_sweep = true;                                 // the forward sweep inverts group by group
@@ -525,15 +535,15 @@ int run_factor_solve(cs3_handle h, const double *ax_dev, const double *b_dev, do
     } else {
         CS3_HIP(launch_prologue(D, ax_dev, b_dev, nrhs, st));      // right-hand sides are read from b_dev, the solution goes to x_dev
     }
-    if (h->fused_inv_tol != inv_tol) {
+    if (h->fused_ctl != pc) {
         if ((rc = drop_graphs(h, [](const GraphKey &g) { return graph_op_is(g, GRAPH_FUSED); }))) return rc;
-        h->fused_inv_tol = inv_tol;
+        h->fused_ctl = pc;
     }
     h->fused_same_x = (x_dev == h->fused_last_x) ? h->fused_same_x + 1 : 0;
     h->fused_last_x = x_dev;
     const bool per_x = h->fused_same_x >= 2;                       // third call in a row with this X: its own graph, permutation included
     rc = replay_or_run(h, GraphKey(GRAPH_FUSED, false, nrhs, per_x ? x_dev : nullptr), st, [&](hipStream_t s) {
-        hipError_t e = launch_factor_with_forward(D, call, h->S.groups, inv_tol, D.xp, nrhs, s, h->fj);
+        hipError_t e = launch_factor_with_forward(D, call, h->S.groups, pc, D.xp, nrhs, s, h->fj);
         if (e == hipSuccess) e = launch_solve_levels(D, call, D.xp, nrhs, false, s, h->fj);
         if (e == hipSuccess && per_x)
             e = matched ? launch_match_permute(h, D.xp, x_dev, nrhs, false, false, s) : launch_permute(D, D.xp, x_dev, nrhs, true, s);
@@ -542,6 +552,7 @@ int run_factor_solve(cs3_handle h, const double *ax_dev, const double *b_dev, do
     if (rc) return rc;
     if (!per_x) CS3_HIP(matched ? launch_match_permute(h, D.xp, x_dev, nrhs, false, false, st) : launch_permute(D, D.xp, x_dev, nrhs, true, st));
     h->factored = true;
+    h->factor_ran = true;
     h->inverses_valid = nrhs >= 16;                                // a many-RHS fused call leaves them current
     return CS3_OK;
 }
@@ -838,6 +849,28 @@ int cs3_factor(cs3_handle h, const double *Ax, double tol)
     if (count) CS3_HIP(hipMemcpy(h->D.ax, Ax, count * sizeof(double), hipMemcpyHostToDevice));
     if ((rc = run_factor(h, h->D.ax, tol, nullptr))) return rc;
     return read_status(h, nullptr);
+}
+
+int cs3_set_pivot_perturbation(cs3_handle h, double delta)
+{
+    int rc = guard(h); if (rc) return rc;
+    if (!(delta >= 0.0) || !std::isfinite(delta)) { set_error("cs3_set_pivot_perturbation: delta must be finite and >= 0"); return CS3_ERR_ARG; }
+    if (h->S.kind != CS3_LU) { set_error("cs3_set_pivot_perturbation: LU handles only"); return CS3_ERR_ARG; }
+    h->perturb_delta = delta;         // (the next factorisation sees the change and drops the graphs captured with the old one)
+    return CS3_OK;
+}
+
+int cs3_get_perturbed(cs3_handle h, int64_t *count, void *stream)
+{
+    int rc = guard(h); if (rc) return rc;
+    if (!count) { set_error("cs3_get_perturbed: null argument"); return CS3_ERR_ARG; }
+    if (!h->on_device || !h->factor_ran) { set_error("cs3_get_perturbed: nothing factorised yet"); return CS3_ERR_STATE; }
+    std::vector<int> word((size_t) h->batch);
+    hipStream_t st = (hipStream_t) stream;
+    CS3_HIP(hipMemcpyAsync(word.data(), h->D.status + 4, word.size() * sizeof(int), hipMemcpyDeviceToHost, st));
+    CS3_HIP(hipStreamSynchronize(st));
+    for (size_t b = 0; b < word.size(); ++b) count[b] = word[b];
+    return CS3_OK;
 }
 
 int cs3_solve_dev(cs3_handle h, double *X_dev, int64_t k, void *stream)
@@ -1219,9 +1252,9 @@ int cs3_matvec_t_dev(cs3_handle h, const double *Ax_dev, const double *X_dev, do
 }
 
 static int refine(cs3_handle h, const double *Ax_dev, const double *B_dev, double *X_dev, int64_t k, int64_t steps,
-                  double *last_correction, void *stream, bool trans)
+                  double *last_correction, void *stream, bool trans, const char *who = nullptr)
 {
-    const char *who = trans ? "cs3_refine_t_dev" : "cs3_refine_dev";
+    if (!who) who = trans ? "cs3_refine_t_dev" : "cs3_refine_dev";
     int rc = guard(h); if (rc) return rc;
     if (!Ax_dev || !B_dev || !X_dev || k < 1 || k > INT_MAX || steps < 0) { set_error(std::string(who) + ": bad argument"); return CS3_ERR_ARG; }
     if (!h->factored) { set_error(std::string(who) + ": refinement needs a factorisation"); return CS3_ERR_STATE; }
@@ -1257,6 +1290,29 @@ int cs3_refine_t_dev(cs3_handle h, const double *Ax_dev, const double *B_dev, do
                      double *last_correction, void *stream)
 {
     return refine(h, Ax_dev, B_dev, X_dev, k, steps, last_correction, stream, true);
+}
+
+// The host-array form: values, right-hand sides and the iterate are staged in HBM (the values through the buffer the
+// other host forms use), the steps are cs3_refine_dev's on the null stream -- the same kernels, the same bits.
+int cs3_refine(cs3_handle h, const double *Ax, const double *B, double *X, int64_t k, int64_t steps, double *last_correction)
+{
+    int rc = guard(h); if (rc) return rc;
+    if (!Ax || !B || !X || k < 1 || k > INT_MAX || steps < 0) { set_error("cs3_refine: bad argument"); return CS3_ERR_ARG; }
+    if (!h->factored) { set_error("cs3_refine: refinement needs a factorisation"); return CS3_ERR_STATE; }
+    auto &H = h->mem.host;
+    const size_t ax_count = (size_t) (h->batch * h->S.nnzA), x_count = (size_t) (h->batch * h->S.n * k);
+    CS3_HIP(H.ax.reserve(ax_count));
+    if (ax_count) CS3_HIP(hipMemcpy(H.ax.get(), Ax, ax_count * sizeof(double), hipMemcpyHostToDevice));
+    DevBuf<double> b, x;
+    CS3_HIP(b.alloc(x_count));
+    CS3_HIP(x.alloc(x_count));
+    if (x_count) {
+        CS3_HIP(hipMemcpy(b.get(), B, x_count * sizeof(double), hipMemcpyHostToDevice));
+        CS3_HIP(hipMemcpy(x.get(), X, x_count * sizeof(double), hipMemcpyHostToDevice));
+    }
+    if ((rc = refine(h, H.ax.get(), b.get(), x.get(), k, steps, last_correction, nullptr, false, "cs3_refine"))) return rc;
+    if (x_count) CS3_HIP(hipMemcpy(X, x.get(), x_count * sizeof(double), hipMemcpyDeviceToHost));
+    return CS3_OK;
 }
 
 // ---- condition estimates and log-determinants from the held factors --------------------------------------------------

@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "cs3_device.hpp"
+
 namespace cs3 {
 
 // Load-then-select: a predicated `cond ? p[i] : 0` makes hipcc branch around the
@@ -47,6 +49,33 @@ __device__ __forceinline__ void pivot_scale(double piv, double &dg, double &rp)
 {
     if (KIND == CS3_CHOLESKY) sqrt_and_rsqrt(piv, dg, rp);
     else { dg = piv; rp = fast_rcp(piv); }
+}
+
+// Static pivot perturbation (LU, PivotRule<true>): a pivot with |p| < delta becomes +delta -- always PLUS delta: several
+// kernels derive one pivot in more than one wave, with roundings of their own, and a rule that kept the sign would split
+// a noise-level pivot that straddles zero between them.  NaN and +-inf fail the comparison and go on to the pivot checks
+// as they are.  Returns whether the pivot was replaced.  The caller stores the replaced value where U_kk lives (the
+// sweeps, the inverted diagonal blocks, slogdet and the export read it there) and -- in the one wave or thread whose
+// copy of the pivot is the stored one -- counts it.  PivotRule<false>: nothing happens, and nothing is compiled.
+template <class Rule>
+__device__ __forceinline__ bool perturb_pivot(const Rule &rule, double &piv)
+{
+    if constexpr (Rule::on) {
+        const bool small = fabs(piv) < rule.delta;
+        piv = small ? rule.delta : piv;
+        return small;
+    } else {
+        return false;
+    }
+}
+
+// `hits` replaced pivots of matrix m: one atomic per front (or block) that had any, from one lane.
+template <class Rule>
+__device__ __forceinline__ void count_perturbed(const Rule &rule, long long m, int hits)
+{
+    if constexpr (Rule::on) {
+        if (hits > 0) atomicAdd(rule.count + m, hits);
+    }
 }
 
 // 1 / diagonal entry `i` of an r-row panel: the sweeps multiply by it (one division per lane instead
@@ -120,13 +149,17 @@ __device__ __forceinline__ void keep_here(double &x) { asm volatile("" : "+v"(x)
 // touched) and, in `ut`, the pivot ROWS transposed -- lane = a column to the right of the block, ut[i] = F(i, that
 // column).  Step k then also applies its multipliers to them, ut[i] -= L(i, k) ut[k] (L(i, k) sits in lane i of the
 // multiplier register), which leaves U12 in `ut`; the trailing matrix is left to schur_tiles (MFMA).
-template <int KIND, bool RHS, bool UT = false>
-__device__ __forceinline__ void sub_eliminate(double (&row)[32], double &rhs, int r, int w, double inv_tol, bool &suspect,
-                                              double (&ut)[32])
+// `hits` takes the number of pivots the rule replaced (this wave's copy of a pivot is the stored one).
+template <int KIND, bool RHS, bool UT = false, class Rule>
+__device__ __forceinline__ void sub_eliminate(double (&row)[32], double &rhs, int r, int w, const Rule &rule, bool &suspect,
+                                              double (&ut)[32], int &hits)
 {
     constexpr int NC = 32;
     const int lane = threadIdx.x & 63;
+    const double inv_tol = rule.inv_tol;
     double piv = bcast_lane(row[0], 0);
+    bool hit = false;
+    if constexpr (Rule::on) hit = perturb_pivot(rule, piv);
     double dg, rp;
     pivot_scale<KIND>(piv, dg, rp);
 #pragma unroll
@@ -139,6 +172,7 @@ __device__ __forceinline__ void sub_eliminate(double (&row)[32], double &rhs, in
             const double l = below ? row[k] * rp : 0.0;         // multiplier, zero on and above the pivot row
             if (below) row[k] = l;
             if (KIND == CS3_CHOLESKY && lane == k) row[k] = (piv > 0.0) ? dg : -1.0;
+            if constexpr (Rule::on) { if (lane == k) row[k] = piv; hits += (int) hit; }      // U_kk as it is stored
             if (KIND == CS3_LU) suspect = (int) suspect | (int) !(fabs(l) <= inv_tol) | (int) !(fabs(piv) > 0.0) | (int) !(fabs(piv) < 1.0e300);
             else suspect = (int) suspect | (int) !(piv > 0.0);
             // (the vector is scaled by what the separate forward sweep multiplies by, bit for bit: fast_rcp of the stored root)
@@ -147,6 +181,7 @@ __device__ __forceinline__ void sub_eliminate(double (&row)[32], double &rhs, in
                 if (KIND == CS3_LU) row[k + 1] -= l * bcast_lane(row[k + 1], k);
                 else { const double lj = bcast_lane(row[k], k + 1); row[k + 1] -= l * lj; }
                 piv = bcast_lane(row[k + 1], k + 1);
+                if constexpr (Rule::on) hit = perturb_pivot(rule, piv);
                 pivot_scale<KIND>(piv, dg, rp);
             }
             if (RHS) {                                          // forward substitution: y_k final, rows below take it
@@ -181,11 +216,11 @@ __device__ __forceinline__ void sub_eliminate(double (&row)[32], double &rhs, in
       }
     }
 }
-template <int KIND, bool RHS>
-__device__ __forceinline__ void sub_eliminate(double (&row)[32], double &rhs, int r, int w, double inv_tol, bool &suspect)
+template <int KIND, bool RHS, class Rule>
+__device__ __forceinline__ void sub_eliminate(double (&row)[32], double &rhs, int r, int w, const Rule &rule, bool &suspect, int &hits)
 {
     double none[32];
-    sub_eliminate<KIND, RHS, false>(row, rhs, r, w, inv_tol, suspect, none);
+    sub_eliminate<KIND, RHS, false>(row, rhs, r, w, rule, suspect, none, hits);
 }
 
 // The pivot ROWS of an LU front by themselves, transposed: lane = a column of the front (all r of them, the pivot columns
@@ -193,11 +228,14 @@ __device__ __forceinline__ void sub_eliminate(double (&row)[32], double &rhs, in
 // ut[i] -= (F(i, k) / pivot) ut[k] with the multiplier formed from lane k of ut[i] -- a wave-uniform value, so this wave needs
 // nothing from the wave that factors the pivot COLUMNS (sub_eliminate), and the two run side by side.  Every entry sees
 // the same operations in the same order as in the one-wave panel form: U11 comes out identical in both waves (only the
-// columns to the right of the block, U12, are taken from here).
-__device__ __forceinline__ void rows_eliminate_lu(double (&ut)[32], int w)
+// columns to the right of the block, U12, are taken from here) -- the perturbed pivots included: the same value meets
+// the same comparison in both waves.  A replaced pivot goes back into lane k of ut[k]: the rows below read it there.
+template <class Rule>
+__device__ __forceinline__ void rows_eliminate_lu(double (&ut)[32], int w, const Rule &rule)
 {
     constexpr int NC = 32;
     double piv = bcast_lane(ut[0], 0);
+    if constexpr (Rule::on) perturb_pivot(rule, piv);
     double rp = fast_rcp(piv);
 #pragma unroll
     for (int k0 = 0; k0 < NC; k0 += 8) {
@@ -206,10 +244,12 @@ __device__ __forceinline__ void rows_eliminate_lu(double (&ut)[32], int w)
        for (int k = k0; k < k0 + 8; ++k) {
         if (k < w) {
             const double rpk = rp;
+            if constexpr (Rule::on) { if ((int) (threadIdx.x & 63) == k) ut[k] = piv; }
             if (k + 1 < NC) {
                 const double l1 = bcast_lane(ut[k + 1], k) * rpk;
                 ut[k + 1] -= l1 * ut[k];
                 piv = bcast_lane(ut[k + 1], k + 1);
+                if constexpr (Rule::on) perturb_pivot(rule, piv);
                 rp = fast_rcp(piv);
             }
 #pragma unroll

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime_api.h>
 
+#include <cmath>
 #include <type_traits>
 #include <vector>
 
@@ -93,7 +94,8 @@ struct DeviceFactor {
     int n_inv_tasks = 0;
     std::vector<int> inv_tasks_host;
     long long nrhs_cap = 0;
-    int *status = nullptr;        // [0] first failing pivot column, 0x7f7f7f7f when clean; [3]: a hand-over between waves timed out
+    int *status = nullptr;        // [0] first failing pivot column, 0x7f7f7f7f when clean; [3]: a hand-over between waves timed out;
+                                  // [4 + b]: pivots of matrix b that the perturbation replaced (PivotCtl::count)
     long long *tbuf = nullptr;    // diagnostics (CS3_PROFILE=1): 8 shader-clock stamps per front, schedule order
 };
 
@@ -113,6 +115,38 @@ template <class F>
 auto with_kind(int kind, F &&f)
 {
     return (kind == CS3_LU) ? f(std::integral_constant<int, CS3_LU>{}) : f(std::integral_constant<int, CS3_CHOLESKY>{});
+}
+
+// How an LU pivot is accepted, as the factor launchers take it: a multiplier larger than inv_tol = 1 / tol rejects its
+// column, and (static pivot perturbation, delta > 0) a pivot with |p| < delta is replaced by +delta before its reciprocal
+// is formed; count [batch] takes the number of replaced pivots of every matrix.
+struct PivotCtl {
+    double inv_tol = HUGE_VAL, delta = 0.0;
+    int *count = nullptr;
+    bool operator==(const PivotCtl &o) const { return inv_tol == o.inv_tol && delta == o.delta; }
+    bool operator!=(const PivotCtl &o) const { return !(*this == o); }
+};
+// The same as a kernel argument (by value), and as a template argument of every factor kernel: PivotRule<false> is the
+// kernels' old `double inv_tol` and compiles to the instructions they had before the perturbation existed -- a handle
+// with delta = 0 (and every Cholesky handle) runs those instances; PivotRule<true> exists for LU only.
+template <bool ON> struct PivotRule;
+template <> struct PivotRule<false> {
+    static constexpr bool on = false;
+    double inv_tol;
+};
+template <> struct PivotRule<true> {
+    static constexpr bool on = true;
+    double inv_tol, delta;
+    int *count;
+};
+// f(rule) with the rule's type picked by delta.
+template <int KIND, class F>
+auto with_rule(const PivotCtl &pc, F &&f)
+{
+    if constexpr (KIND == CS3_LU) {
+        if (pc.delta > 0.0) return f(PivotRule<true>{pc.inv_tol, pc.delta, pc.count});
+    }
+    return f(PivotRule<false>{pc.inv_tol});
 }
 
 // What the assembly of a front reads, as a kernel argument (by value).
@@ -148,21 +182,21 @@ hipError_t launch_diag_inverses(const DeviceFactor &D, hipStream_t st);
 bool permutation_can_fuse(const DeviceFactor &D, int nrhs);   // once after a factorisation, before a many-RHS sweep
 bool big_group_in_one_workgroup(int kind, long long batch, const LaunchGroup &g);
 hipError_t launch_factor_levels(const DeviceFactor &D, const SweepCall &call, const std::vector<LaunchGroup> &groups,
-                                double inv_tol, hipStream_t st, ForkJoin &fj);
+                                const PivotCtl &pc, hipStream_t st, ForkJoin &fj);
 // sweeps over call.groups
 hipError_t launch_solve_levels(const DeviceFactor &D, const SweepCall &call, double *X, int nrhs, bool forward, hipStream_t st,
                                ForkJoin &fj);
 // Factorisation with the forward sweep partly hidden behind it: the sweep of the finished levels
 // runs on fj.aux beside the factorisation of the tail of the tree (one fork, one join).
 hipError_t launch_factor_with_forward(const DeviceFactor &D, const SweepCall &call, const std::vector<LaunchGroup> &fgroups,
-                                      double inv_tol, double *X, int nrhs, hipStream_t st, ForkJoin &fj);
+                                      const PivotCtl &pc, double *X, int nrhs, hipStream_t st, ForkJoin &fj);
 // status word, big-front zeros, copy of the caller's values and (x_src != null) the permuted right-hand sides, one launch
 hipError_t launch_prologue(const DeviceFactor &D, const double *ax_src, const double *x_src, int nrhs, hipStream_t st);
 // forest.hip: the bottom forest = one launch, one workgroup per task
 hipError_t prepare_forest_kernels();
 hipError_t set_withhold_handover(int on);          // diagnostics: producers of the LDS hand-overs keep their counters back
 hipError_t set_withhold_handover_forest(int on);   //   (the copy of the flag in forest.hip)
-hipError_t launch_sub_factor(const DeviceFactor &D, const SweepCall &call, double inv_tol, hipStream_t st);
+hipError_t launch_sub_factor(const DeviceFactor &D, const SweepCall &call, const PivotCtl &pc, hipStream_t st);
 hipError_t launch_sub_sweep(const DeviceFactor &D, double *X, bool forward, hipStream_t st);
 hipError_t launch_permute(const DeviceFactor &D, const double *src, double *dst, int nrhs, bool scatter,
                           hipStream_t st);

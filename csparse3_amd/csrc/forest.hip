@@ -185,17 +185,25 @@ __device__ __forceinline__ void coop_extend_add(double *S, int ld, int sdummy, i
 // The pivots of one part of a shared front, LU: one lane-masked region per pivot (the rows below it): scale, hand over,
 // update -- no selects, and the reciprocal of the next pivot is computed inside the region too (only rows below it will use
 // it).  Pivots and multipliers are checked afterwards, off this chain.
-template <bool RHS, int PART>
+// A part derives only its own pivots (the others receive its multipliers): one copy of every pivot, the stored one.  A
+// replaced pivot goes into its lane (outside the masked region: one more region per pivot, in the perturbing instance
+// only) and into `hits`.
+template <bool RHS, int PART, class Rule>
 __device__ __forceinline__ void coop_own_pivots_lu(double (&d)[COOP_NC], double &rhs, int w, bool last,
-                                                   lds_vdouble_ptr lm, lds_int_ptr ready, int gbase, bool withhold)
+                                                   lds_vdouble_ptr lm, lds_int_ptr ready, int gbase, bool withhold,
+                                                   const Rule &rule, int &hits)
 {
     constexpr int NC = COOP_NC, pc0 = NC * PART;
     const int lane = threadIdx.x & 63;
-    double rp = fast_rcp(bcast_lane(d[0], pc0));
+    double piv = bcast_lane(d[0], pc0);
+    bool hit = false;
+    if constexpr (Rule::on) hit = perturb_pivot(rule, piv);
+    double rp = fast_rcp(piv);
 #pragma unroll
     for (int k = 0; k < NC; ++k) {
         const int pl = pc0 + k;                                 // the pivot's lane
         if (pl >= w) continue;                                  // wave-uniform
+        if constexpr (Rule::on) { if (lane == pl && hit) d[k] = piv; hits += (int) hit; }
         if (lane > pl) {
             d[k] *= rp;                                         // the multipliers
             if (!last) {
@@ -204,7 +212,9 @@ __device__ __forceinline__ void coop_own_pivots_lu(double (&d)[COOP_NC], double 
             }
             if (k + 1 < NC) {
                 d[k + 1] -= d[k] * bcast_lane(d[k + 1], pl);
-                rp = fast_rcp(bcast_lane(d[k + 1], pl + 1));
+                piv = bcast_lane(d[k + 1], pl + 1);
+                if constexpr (Rule::on) hit = perturb_pivot(rule, piv);
+                rp = fast_rcp(piv);
             }
             if (RHS && last) rhs -= d[k] * bcast_lane(rhs, pl);
             double bc[NC];
@@ -216,14 +226,15 @@ __device__ __forceinline__ void coop_own_pivots_lu(double (&d)[COOP_NC], double 
     }
 }
 
-template <int KIND, bool RHS>
+template <int KIND, bool RHS, class Rule>
 __device__ __forceinline__ void
 sub_coop_front(const SubScalars &ds, int part, double *gimg, int img_stride, int *ready_generic, int gbase, const SubTask &t,
                const int4 *childs, const int *rels, double *arena, const int *__restrict__ a_tgt,
                const double *__restrict__ axf, double *__restrict__ pool, double *__restrict__ xp, double *__restrict__ cvg,
-               double inv_tol, int *status, long long *stamps, long long t_start)
+               const Rule &rule, int *status, long long *stamps, long long t_start)
 {
     constexpr int NC = COOP_NC;
+    const double inv_tol = rule.inv_tol;
     // diagnostics (CS3_PROFILE=1): slot 2 part = my columns assembled, 2 part + 1 = my pivots eliminated (part 0: 0 = begun,
     // 1 = stored), shader clock since the kernel began
 #define CS3_CSTAMP(p) do { if (stamps && blockIdx.y == 0 && (threadIdx.x & 63) == 0) stamps[p] = (long long) __builtin_amdgcn_s_memtime() - t_start; } while (0)
@@ -362,12 +373,15 @@ sub_coop_front(const SubScalars &ds, int part, double *gimg, int img_stride, int
         auto lm = (lds_vdouble_ptr) (S + COOP_SLICE);
         if (KIND == CS3_LU) {
             // (the part number as a compile-time constant: the pivot's lane is then an immediate of the lane-to-scalar reads)
+            int hits = 0;
             switch (part) {
-            case 0: coop_own_pivots_lu<RHS, 0>(d, rhs, w, last, lm, ready, gbase, withhold); break;
-            case 1: coop_own_pivots_lu<RHS, 1>(d, rhs, w, last, lm, ready, gbase, withhold); break;
-            case 2: coop_own_pivots_lu<RHS, 2>(d, rhs, w, last, lm, ready, gbase, withhold); break;
-            default: coop_own_pivots_lu<RHS, 3>(d, rhs, w, last, lm, ready, gbase, withhold); break;
+            case 0: coop_own_pivots_lu<RHS, 0>(d, rhs, w, last, lm, ready, gbase, withhold, rule, hits); break;
+            case 1: coop_own_pivots_lu<RHS, 1>(d, rhs, w, last, lm, ready, gbase, withhold, rule, hits); break;
+            case 2: coop_own_pivots_lu<RHS, 2>(d, rhs, w, last, lm, ready, gbase, withhold, rule, hits); break;
+            default: coop_own_pivots_lu<RHS, 3>(d, rhs, w, last, lm, ready, gbase, withhold, rule, hits); break;
             }
+            // (lane 63 lies below every pivot row: it ran every masked region, so its count is complete)
+            if (lane == 63) count_perturbed(rule, blockIdx.y, hits);
 #pragma unroll
             for (int j = 0; j < NC; ++j) {
                 const int col = pc0 + j;
@@ -486,16 +500,17 @@ sub_coop_front(const SubScalars &ds, int part, double *gimg, int img_stride, int
 #undef CS3_CSTAMP
 }
 
-template <int KIND, bool RHS>
+template <int KIND, bool RHS, class Rule>
 __global__ void __launch_bounds__(SUB_NT)
 k_sub_factor(const SubTask *__restrict__ tasks, const SubFront *__restrict__ fronts, const int *__restrict__ lvl_g,
              const int *__restrict__ rel_g, const int *__restrict__ child_g, const int *__restrict__ a_tgt,
              const double *__restrict__ axf_all, long long na, double *__restrict__ pool_all, long long pool_stride,
              double *__restrict__ xp_all, double *__restrict__ cv_all, long long n, long long cv_stride,
-             double inv_tol, int *status, SubLds lay, long long *tbuf)
+             Rule rule, int *status, SubLds lay, long long *tbuf)
 {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     int *smi = (int *) sm;
+    const double inv_tol = rule.inv_tol;
     // diagnostics (CS3_PROFILE=1): shader-clock stamps per front, slot = position of its SubFront: 0 begun, 1 entries of A in
     // the image, 2 children added, 3 row in registers, 4 eliminated, 5 stored, 6 the level's barrier passed (first front of a wave)
     const long long t_start = tbuf ? (long long) __builtin_amdgcn_s_memtime() : 0;
@@ -573,7 +588,9 @@ k_sub_factor(const SubTask *__restrict__ tasks, const SubFront *__restrict__ fro
         }
         CS3_SSTAMP(f, 3);
         bool suspect = false;
-        sub_eliminate<KIND, RHS>(row, rhs, r, w, inv_tol, suspect);
+        int hits = 0;
+        sub_eliminate<KIND, RHS>(row, rhs, r, w, rule, suspect, hits);
+        if (lane == 0) count_perturbed(rule, blockIdx.y, hits);
         CS3_SSTAMP(f, 4);
         // ---- checks and stores, one pass: column j of my row goes to the L panel (j < w), else to the U panel (my
         // row is a pivot row) or to the contribution block -- in the arena when my parent is in this task
@@ -686,7 +703,7 @@ k_sub_factor(const SubTask *__restrict__ tasks, const SubFront *__restrict__ fro
             if (f < f0 + nco) {
                 const SubScalars ds = sub_load_desc(fd, f);
                 sub_coop_front<KIND, RHS>(ds, part, sm + lay.img + 4 * grp * lay.img_stride, lay.img_stride, smi + lay.ready + grp, gbase,
-                                          t, childs, rels, arena, a_tgt, axf, pool, xp, cvg, inv_tol, status,
+                                          t, childs, rels, arena, a_tgt, axf, pool, xp, cvg, rule, status,
                                           tbuf ? tbuf + (long long) (t.front0 + f) * 8 : nullptr, t_start);
             } else {
                 if (fs + part < f1) single_front(fs + part);
@@ -866,8 +883,11 @@ hipError_t set_withhold_handover_forest(int on)
 hipError_t prepare_forest_kernels()
 {
     const int big = 160 * 1024;
-    const void *fns[] = {(const void *) k_sub_factor<CS3_LU, false>, (const void *) k_sub_factor<CS3_LU, true>,
-                         (const void *) k_sub_factor<CS3_CHOLESKY, false>, (const void *) k_sub_factor<CS3_CHOLESKY, true>,
+    using Plain = PivotRule<false>;
+    using Perturbed = PivotRule<true>;
+    const void *fns[] = {(const void *) k_sub_factor<CS3_LU, false, Plain>, (const void *) k_sub_factor<CS3_LU, true, Plain>,
+                         (const void *) k_sub_factor<CS3_LU, false, Perturbed>, (const void *) k_sub_factor<CS3_LU, true, Perturbed>,
+                         (const void *) k_sub_factor<CS3_CHOLESKY, false, Plain>, (const void *) k_sub_factor<CS3_CHOLESKY, true, Plain>,
                          (const void *) k_sub_fwd<CS3_LU>, (const void *) k_sub_fwd<CS3_CHOLESKY>,
                          (const void *) k_sub_bwd<CS3_LU>, (const void *) k_sub_bwd<CS3_CHOLESKY>};
     for (const void *f : fns) {
@@ -877,7 +897,7 @@ hipError_t prepare_forest_kernels()
     return hipSuccess;
 }
 
-hipError_t launch_sub_factor(const DeviceFactor &D, const SweepCall &call, double inv_tol, hipStream_t st)
+hipError_t launch_sub_factor(const DeviceFactor &D, const SweepCall &call, const PivotCtl &pc, hipStream_t st)
 {
     const SubForest &T = D.sub_forest;
     size_t bytes = 0;
@@ -885,11 +905,14 @@ hipError_t launch_sub_factor(const DeviceFactor &D, const SweepCall &call, doubl
     if (bytes > 160 * 1024) return hipErrorInvalidValue;           // (the analysis caps keep a task far below this)
     const dim3 grid((unsigned) T.ntasks, (unsigned) D.batch), block(SUB_NT);
     with_kind(D.kind, [&](auto K) {
+        with_rule<K>(pc, [&](auto rule) {
+            using Rule = decltype(rule);
 #define CS3_SUB_ARGS D.sub_tasks, D.sub_fronts, D.sub_lvl, D.sub_rel, D.sub_child, D.sub_a_tgt, D.axf, D.n_sub_a, D.pool_pm, \
-                     D.pm_stride, D.xp, D.cv, D.n, D.cv_size, inv_tol, D.status, lay, D.tbuf
-        if (call.fwd_in_factor) hipLaunchKernelGGL((k_sub_factor<K, true>), grid, block, bytes, st, CS3_SUB_ARGS);
-        else hipLaunchKernelGGL((k_sub_factor<K, false>), grid, block, bytes, st, CS3_SUB_ARGS);
+                     D.pm_stride, D.xp, D.cv, D.n, D.cv_size, rule, D.status, lay, D.tbuf
+            if (call.fwd_in_factor) hipLaunchKernelGGL((k_sub_factor<K, true, Rule>), grid, block, bytes, st, CS3_SUB_ARGS);
+            else hipLaunchKernelGGL((k_sub_factor<K, false, Rule>), grid, block, bytes, st, CS3_SUB_ARGS);
 #undef CS3_SUB_ARGS
+        });
     });
     CS3_LAUNCH_CHECK();
     return hipSuccess;

@@ -272,14 +272,15 @@ __device__ __forceinline__ void gather_front_vec(long long asm_begin, int nchunk
 // so per pivot only r + r doubles cross the LDS instead of the whole trailing
 // block being read and written there.  Results go back through the LDS image
 // so that the stores to the panels are row-contiguous.
-template <int KIND, int THREADS, int TX, int RI, int RJ>
+template <int KIND, int THREADS, int TX, int RI, int RJ, class Rule>
 __device__ __forceinline__ void
 front_lds_body(const FrontDesc &d, int first, double *F,
                AsmLists al,
                const double *__restrict__ ax_all, double *__restrict__ pool_all,
-               long long nnz_a, long long pool_stride, IlView il, double inv_tol, int *status, long long *tbuf, long long t_start)
+               long long nnz_a, long long pool_stride, IlView il, const Rule &rule, int *status, long long *tbuf, long long t_start)
 {
     constexpr int TY = THREADS / TX;
+    const double inv_tol = rule.inv_tol;
     const double *pil = il_lane_base(il, blockIdx.y);
 #define CS3_STAMP(p) do { if (tbuf && threadIdx.x == 0) tbuf[(long long) (first + blockIdx.x) * 8 + (p)] = (long long) __builtin_amdgcn_s_memtime() - t_start; } while (0)
     const double *ax = ax_all + (long long) blockIdx.y * nnz_a;
@@ -326,7 +327,9 @@ front_lds_body(const FrontDesc &d, int first, double *F,
                 }
         }
         __syncthreads();
-        const double piv = urow[k];
+        double piv = urow[k];                      // (every thread reads the same word: one value, one decision)
+        bool hit = false;
+        if constexpr (Rule::on) hit = perturb_pivot(rule, piv);
         double dg, rdg;                            // one reciprocal per pivot: multipliers are x * (1 / pivot)
         pivot_scale<KIND>(piv, dg, rdg);
         if (ty == tyk) {                           // 2. column k / pivot -> lcol
@@ -343,6 +346,7 @@ front_lds_body(const FrontDesc &d, int first, double *F,
                         }
                         if (i == k) {
                             if (KIND == CS3_LU) {
+                                if constexpr (Rule::on) { if (hit) { R[a][b] = piv; count_perturbed(rule, blockIdx.y, 1); } }      // the owner of U_kk
                                 if (!(fabs(piv) > 0.0) || !(fabs(piv) < 1.0e300)) flag_column(status, d.c0 + k);
                             } else {
                                 R[a][b] = dg;
@@ -406,13 +410,17 @@ constexpr int PAIR_NC = 16;                   // columns per wave of a two-wave 
 // (Cholesky: a column update runs in EVERY lane below the pivot row, also where the entry lies above the diagonal of the
 //  block -- those entries are never read, stored or checked, and leaving them alone cost a select or a lane mask per
 //  column update, a quarter of the instructions of a step.)
-template <int KIND, int NC, bool SKIP = false, class Publish>
-__device__ __forceinline__ void eliminate_slice(double (&d)[NC], int c0, bool keep_unscaled, Publish publish, int npiv = 1 << 30)
+// Perturbation: the pivots of the real steps (pl < npiv) are replaced, stored in their lane and added to `hits`; the
+// identity pivots of the padding are left alone whatever delta is.
+template <int KIND, int NC, bool SKIP = false, class Publish, class Rule>
+__device__ __forceinline__ void eliminate_slice(double (&d)[NC], int c0, bool keep_unscaled, Publish publish, int npiv, const Rule &rule, int &hits)
 {
     constexpr int EB = 8;
     const int lane = threadIdx.x & 63;
     const bool stacked = lane >= 32;
     double piv = bcast_lane(d[0], c0);
+    bool hit = false;
+    if constexpr (Rule::on) hit = (c0 < npiv) && perturb_pivot(rule, piv);
     double dg, rp;
     pivot_scale<KIND>(piv, dg, rp);
 #pragma unroll
@@ -423,10 +431,12 @@ __device__ __forceinline__ void eliminate_slice(double (&d)[NC], int c0, bool ke
         const double l = below ? d[k] * rp : 0.0;
         if (below && !(keep_unscaled && stacked)) d[k] = l;
         if (KIND == CS3_CHOLESKY && lane == pl && pl < npiv) d[k] = (piv > 0.0) ? dg : -1.0;
+        if constexpr (Rule::on) { if (lane == pl && hit) d[k] = piv; hits += (int) hit; }
         if (k + 1 < NC) {
             if (KIND == CS3_LU) d[k + 1] -= l * bcast_lane(d[k + 1], pl);
             else { const double lj = bcast_lane(d[k], pl + 1); d[k + 1] -= l * lj; }
             piv = bcast_lane(d[k + 1], pl + 1);
+            if constexpr (Rule::on) hit = (pl + 1 < npiv) && perturb_pivot(rule, piv);
             pivot_scale<KIND>(piv, dg, rp);
         }
         publish(k, l);
@@ -456,9 +466,9 @@ __device__ __forceinline__ void eliminate_slice(double (&d)[NC], int c0, bool ke
 // *ready = k + 1: LDS operations of a wave complete in order); wave 1 applies them to its columns one pivot behind,
 // then eliminates pivots 16..31 alone.  Wave 0 never waits for wave 1, so the wait below cannot deadlock; it is bounded
 // anyway, and a wave that gives up raises status[3]: cs3_factor_status reports the step as failed (handover_wait).
-template <int KIND>
+template <int KIND, class Rule>
 __device__ __forceinline__ void eliminate_pair(double (&d)[PAIR_NC], int part, bool keep_unscaled, double *lm_generic, int *ready_generic,
-                                               int *status, int npiv = 1 << 30)
+                                               int *status, int npiv, const Rule &rule, int &hits)
 {
     constexpr int NC = PAIR_NC;
     const int lane = threadIdx.x & 63;
@@ -472,7 +482,7 @@ __device__ __forceinline__ void eliminate_pair(double (&d)[PAIR_NC], int part, b
         eliminate_slice<KIND, NC>(d, 0, keep_unscaled, [&](int k, double l) {
             lm[k * 64 + lane] = l;
             if (lane == 0) handover_publish(ready, k + 1, withhold);
-        }, npiv);
+        }, npiv, rule, hits);
         return;
     }
     bool alive = true;                                          // (a consumer that gave up once does not wait again)
@@ -492,7 +502,7 @@ __device__ __forceinline__ void eliminate_pair(double (&d)[PAIR_NC], int part, b
             }
         }
     }
-    eliminate_slice<KIND, NC, true>(d, NC, keep_unscaled, [](int, double) {}, npiv);
+    eliminate_slice<KIND, NC, true>(d, NC, keep_unscaled, [](int, double) {}, npiv, rule, hits);
 }
 
 // ---------------------------------------------- front owned by ONE wave ----
@@ -501,13 +511,14 @@ __device__ __forceinline__ void eliminate_pair(double (&d)[PAIR_NC], int part, b
 // updates its own row.  Register indices must be static, so pivots are taken 8 at a time from
 // registers 0..7 (unrolled); the 8 finished columns are stored and the row is shifted down by 8,
 // which keeps "register j = column kb + j".  LDS is only the target of the assembly gather.
-template <int KIND, int NC>
+template <int KIND, int NC, class Rule>
 __device__ __forceinline__ void
 front_wave_body(const FrontDesc &d, int first, double *F,
                 AsmLists al,
                 const double *__restrict__ ax_all, double *__restrict__ pool_all,
-                long long nnz_a, long long pool_stride, IlView il, double inv_tol, int *status, long long *tbuf, long long t_start)
+                long long nnz_a, long long pool_stride, IlView il, const Rule &rule, int *status, long long *tbuf, long long t_start)
 {
+    const double inv_tol = rule.inv_tol;
 #define CS3_STAMP(p) do { if (tbuf && threadIdx.x == 0) tbuf[(long long) (first + blockIdx.x) * 8 + (p)] = (long long) __builtin_amdgcn_s_memtime() - t_start; } while (0)
     double *pil = il_lane_base(il, blockIdx.y);
     const double *ax = ax_all + (long long) blockIdx.y * nnz_a;
@@ -582,8 +593,10 @@ front_wave_body(const FrontDesc &d, int first, double *F,
                     for (int j = j0; j < j0 + 8; ++j) row[j] = F[at(li, min(j, w - 1))];
                 }
             CS3_STAMP(3);
-            if (split) sub_eliminate<KIND, false, false>(row, unused, w, w, inv_tol, suspect, ut);
-            else sub_eliminate<KIND, false, KIND == CS3_LU>(row, unused, w, w, inv_tol, suspect, ut);
+            int hits = 0;
+            if (split) sub_eliminate<KIND, false, false>(row, unused, w, w, rule, suspect, ut, hits);
+            else sub_eliminate<KIND, false, KIND == CS3_LU>(row, unused, w, w, rule, suspect, ut, hits);
+            if (lane == 0) count_perturbed(rule, blockIdx.y, hits);
             // what the tiles read goes back into the image: L21 ...
             if (has_parent && live && lane >= w) {
 #pragma unroll
@@ -595,7 +608,7 @@ front_wave_body(const FrontDesc &d, int first, double *F,
                     }
             }
         } else if (split && wave == 1) {
-            rows_eliminate_lu(ut, w);
+            rows_eliminate_lu(ut, w, rule);
         }
         if (KIND == CS3_LU && wave == uwave && has_parent && is_ucol) {         // ... and U12
 #pragma unroll
@@ -676,38 +689,38 @@ front_wave_body(const FrontDesc &d, int first, double *F,
 
 // The one-wave path as its own launch, one wave per front: used when a batch of matrices keeps
 // the chip busy anyway, so the three helper waves of k_front_mix would only cost occupancy.
-template <int KIND>
+template <int KIND, class Rule>
 __global__ void __launch_bounds__(64)
 k_front_wave(const FrontDesc *__restrict__ fdesc, int first,
              AsmLists al,
              const double *__restrict__ ax_all, double *__restrict__ pool_all,
-             long long nnz_a, long long pool_stride, IlView il, double inv_tol, int *status, long long *tbuf)
+             long long nnz_a, long long pool_stride, IlView il, Rule rule, int *status, long long *tbuf)
 {
     extern __shared__ __attribute__((aligned(16))) double F[];
     const long long t_start = tbuf ? (long long) __builtin_amdgcn_s_memtime() : 0;
     const FrontDesc d = fdesc[first + blockIdx.x];
     front_wave_body<KIND, 32>(d, first, F, al, ax_all, pool_all, nnz_a, pool_stride, il,
-                              inv_tol, status, tbuf, t_start);
+                              rule, status, tbuf, t_start);
 }
 
 // Every front of order <= 64 in one launch: one wave eliminates the small ones (r <= 32), the
 // 16 x 16 thread grid the others.  One launch instead of two per tree level.
-template <int KIND>
+template <int KIND, class Rule>
 __global__ void __launch_bounds__(256)
 k_front_mix(const FrontDesc *__restrict__ fdesc, int first,
             AsmLists al,
             const double *__restrict__ ax_all, double *__restrict__ pool_all,
-            long long nnz_a, long long pool_stride, IlView il, double inv_tol, int *status, long long *tbuf)
+            long long nnz_a, long long pool_stride, IlView il, Rule rule, int *status, long long *tbuf)
 {
     extern __shared__ __attribute__((aligned(16))) double F[];
     const long long t_start = tbuf ? (long long) __builtin_amdgcn_s_memtime() : 0;
     const FrontDesc d = fdesc[first + blockIdx.x];
     if (d.w <= 32)                      // (four waves assemble, one factors the panel, four form the Schur complement)
         front_wave_body<KIND, 32>(d, first, F, al, ax_all, pool_all, nnz_a, pool_stride, il,
-                                  inv_tol, status, tbuf, t_start);
+                                  rule, status, tbuf, t_start);
     else
         front_lds_body<KIND, 256, 16, 4, 4>(d, first, F, al, ax_all, pool_all, nnz_a,
-                                            pool_stride, il, inv_tol, status, tbuf, t_start);
+                                            pool_stride, il, rule, status, tbuf, t_start);
 }
 
 // ------------------------------------------- front too large for the LDS --
@@ -796,13 +809,17 @@ k_big_gather(const FrontDesc *__restrict__ fdesc, int first, int kind,
 //   * keep_unscaled (block-ROW tiles of LU): the block lanes hold D' and the stacked lanes columns of
 //     the tile; the multiplier t_k / u_kk drives the updates but the entry that is kept is t_k
 //     itself, which is U(k, column) for the unit-lower solve  L_D u = t.
-template <int KIND, int NBK>
-__device__ __forceinline__ void eliminate_block(double (&d)[NBK], bool keep_unscaled, int nsteps = NBK)
+// Perturbation: the first nreal pivots are the block's own (replaced where small, stored in their lane, added to `hits`);
+// the identity pivots of the padding behind them are left alone whatever delta is.
+template <int KIND, int NBK, class Rule>
+__device__ __forceinline__ void eliminate_block(double (&d)[NBK], bool keep_unscaled, int nsteps, int nreal, const Rule &rule, int &hits)
 {
     constexpr int EB = 8;                       // columns whose broadcasts are issued together
     const int lane = threadIdx.x & 63;
     const bool stacked = lane >= 32;
     double piv = bcast_lane(d[0], 0);
+    bool hit = false;
+    if constexpr (Rule::on) hit = perturb_pivot(rule, piv);     // (a block has at least one pivot of its own)
     double dg, rp;
     pivot_scale<KIND>(piv, dg, rp);
 #pragma unroll
@@ -812,10 +829,12 @@ __device__ __forceinline__ void eliminate_block(double (&d)[NBK], bool keep_unsc
         const double l = below ? d[k] * rp : 0.0;
         if (below && !(keep_unscaled && stacked)) d[k] = l;
         if (KIND == CS3_CHOLESKY && lane == k) d[k] = (piv > 0.0) ? dg : -1.0;
+        if constexpr (Rule::on) { if (lane == k && hit) d[k] = piv; hits += (int) hit; }
         if (k + 1 < NBK) {
             if (KIND == CS3_LU) d[k + 1] -= l * bcast_lane(d[k + 1], k);
             else { const double lj = bcast_lane(d[k], k + 1); d[k + 1] -= l * lj; }
             piv = bcast_lane(d[k + 1], k + 1);
+            if constexpr (Rule::on) hit = (k + 1 < nreal) && perturb_pivot(rule, piv);
             pivot_scale<KIND>(piv, dg, rp);
         }
         // the broadcasts of EB columns go out before their FMAs: a lane-to-scalar read needs wait states before the
@@ -841,8 +860,6 @@ __device__ __forceinline__ void eliminate_block(double (&d)[NBK], bool keep_unsc
     }
 }
 
-template <int KIND>
-__device__ __forceinline__ void eliminate32(double (&d)[BIG_NB], bool keep_unscaled) { eliminate_block<KIND, BIG_NB>(d, keep_unscaled); }
 
 
 // Fronts of order 65 .. 136: the front image lives in LDS (one workgroup of 8 waves per front) and is
@@ -854,13 +871,14 @@ __device__ __forceinline__ void eliminate32(double (&d)[BIG_NB], bool keep_unsca
 // NBK = pivots per block: 32, or 16 for a launch whose fronts have at most 16 pivots (the elimination runs all NBK
 // identity-padded steps).  The previous kernel for this class kept 5 x 9 register tiles and crossed the LDS and two block barriers for
 // every pivot (about 3 k cycles per pivot; this one: about 0.6 k).
-template <int KIND, int NBK, int NW = 8>
+template <int KIND, class Rule, int NBK, int NW = 8>
 __global__ void __launch_bounds__(NW * 64)
 k_front_block(const FrontDesc *__restrict__ fdesc, int first,
               AsmLists al,
               const double *__restrict__ ax_all, double *__restrict__ pool_all,
-              long long nnz_a, long long pool_stride, IlView il, double inv_tol, int *status, long long *tbuf)
+              long long nnz_a, long long pool_stride, IlView il, Rule rule, int *status, long long *tbuf)
 {
+    const double inv_tol = rule.inv_tol;
     extern __shared__ __attribute__((aligned(16))) double F[];
     const double *pil = il_lane_base(il, blockIdx.y);
     const long long t_start = tbuf ? (long long) __builtin_amdgcn_s_memtime() : 0;
@@ -932,7 +950,9 @@ k_front_block(const FrontDesc *__restrict__ fdesc, int first,
         __syncthreads();                                    // everybody has read D before wave 0 writes its factors back
         CS3_PHASE(0);
         if (active) {
-            eliminate_block<KIND, NBK>(e, row_wave, bw);
+            int hits = 0;
+            eliminate_block<KIND, NBK>(e, row_wave, bw, bw, rule, hits);
+            if (owner && lane == 0) count_perturbed(rule, blockIdx.y, hits);    // (the owner's copy is the stored one)
             // pivots and multipliers, then home into the image
 #pragma unroll
             for (int j = 0; j < NBK; ++j) {
@@ -1078,13 +1098,14 @@ k_front_block(const FrontDesc *__restrict__ fdesc, int first,
 // Two block barriers per 32 pivots, no grid-wide dependency.  Used when the batch alone fills the chip and the
 // panels fit the LDS (launch_front_group decides); results equal k_big_step's to rounding, not bit for bit
 // (the MFMA sums 32 products per step either way, but the diagonal block is updated tile-wise here).
-template <int KIND, int NB>
+template <int KIND, class Rule, int NB>
 __global__ void __launch_bounds__(512, (NB <= 16) ? 4 : 2)
 k_front_wg(const FrontDesc *__restrict__ fdesc, int first,
            AsmLists al,
            const double *__restrict__ ax_all, double *__restrict__ pool_all,
-           long long nnz_a, long long pool_stride, IlView il, double inv_tol, int *status, int pld, long long *tbuf)
+           long long nnz_a, long long pool_stride, IlView il, Rule rule, int *status, int pld, long long *tbuf)
 {
+    const double inv_tol = rule.inv_tol;
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const double *pil = il_lane_base(il, blockIdx.y);
     // diagnostics (CS3_PROFILE=1), matrix 0 of the batch: slot 0 zeroed, 1 gathered, 2 sum of the panel phases,
@@ -1208,7 +1229,8 @@ k_front_wg(const FrontDesc *__restrict__ fdesc, int first,
                         e[j] = (mine && j < bw) ? v : 0.0;
                     }
                 }
-                eliminate_block<KIND, NB>(e, false, bw);
+                int hits = 0;                       // (Cholesky: the rule is off)
+                eliminate_block<KIND, NB>(e, false, bw, bw, rule, hits);
 #pragma unroll
                 for (int j = 0; j < NB; ++j) {
                     if (j < bw) {
@@ -1258,7 +1280,9 @@ k_front_wg(const FrontDesc *__restrict__ fdesc, int first,
 #pragma unroll
                 for (int j = 0; j < NB; ++j) e[j] = load_if(F, base + j * stride, mine && j < bw);
             }
-            eliminate_block<KIND, NB>(e, row_wave);
+            int hits = 0;
+            eliminate_block<KIND, NB>(e, row_wave, NB, bw, rule, hits);
+            if (owner && lane == 0) count_perturbed(rule, blockIdx.y, hits);    // (the owner's copy is the stored one)
 #pragma unroll
             for (int j = 0; j < NB; ++j) {
                 if (j < bw) {
@@ -1378,12 +1402,13 @@ k_front_wg(const FrontDesc *__restrict__ fdesc, int first,
 // column of the factor up to block b is final in F, which is what lets the forward sweep of a
 // chunk start while later blocks are still being factorised.
 // Tile index 0 = the panel block [kb, ke); index t >= 1 = 64 rows/columns from ke + 64 (t-1).
-template <int KIND>
+template <int KIND, class Rule>
 __global__ void __launch_bounds__(256)
 k_big_step(const FrontDesc *__restrict__ fdesc, int first, int kb, double *__restrict__ pool_all,
            long long pool_stride, double *__restrict__ dbuf_all, long long dbuf_stride,
-           double inv_tol, int *status, int batch, long long *tbuf)
+           Rule rule, int *status, int batch, long long *tbuf)
 {
+    const double inv_tol = rule.inv_tol;
     // diagnostics (CS3_PROFILE=1): block-column tile (1, 0) of the step kb == 64 stamps its phases into the front's slot
     const long long t_start = tbuf ? (long long) __builtin_amdgcn_s_memtime() : 0;
 #define CS3_BSTAMP(p) do { if (tbuf && kb == 64 && blockIdx.x == 1 && blockIdx.y == 0 && threadIdx.x == 0) \
@@ -1564,11 +1589,16 @@ k_big_step(const FrontDesc *__restrict__ fdesc, int first, int kb, double *__res
         const double tv = T[32 * half + li][cbase + j];
         e[j] = stacked ? (diag_tile ? 0.0 : tv) : dv;
     }
-    eliminate_pair<KIND>(e, part, row_tile, (half == 0) ? &As[0][0] : &Bs[0][0], &pair_ready[half], status);
+    // (perturbation: the steps past bw run with zero multipliers instead of the padding's identity pivots, which a delta
+    //  above 1 would replace -- the same factors either way)
+    int hits = 0;
+    eliminate_pair<KIND>(e, part, row_tile, (half == 0) ? &As[0][0] : &Bs[0][0], &pair_ready[half], status,
+                         Rule::on ? bw : (1 << 30), rule, hits);
     CS3_BSTAMP(4);
     CS3_BSTAMP_ROW(6);
     if (diag_tile) {                                // park the factored block, check its pivots
         double *db = dbuf + (long long) (kb / BIG_NB) * (BIG_NB * BIG_NB);
+        if (lane == 0) count_perturbed(rule, bz, hits);         // (the parked copy is the stored one: each wave its own 16 pivots)
         if (lane < bw) {
 #pragma unroll
             for (int jj = 0; jj < HC; ++jj) {
@@ -2634,12 +2664,13 @@ constexpr int IL_TJ = 4;       // columns per tile of the trailing update
 constexpr int IL_NONE = INT32_MIN;             // pair source: no source (cs3::IL_ZERO)
 constexpr int IL_AV = 32;                      // assembly: sources in flight per round trip
 
-template <int KIND>
+template <int KIND, class Rule>
 __global__ void __launch_bounds__(64)
 k_front_il(const FrontDesc *__restrict__ fdesc, int first, const int *__restrict__ pairs,
            const double *__restrict__ ax_all, long long nnz_a, IlView il,
-           const double *__restrict__ pool_pm_all, long long pm_stride, int batch, double inv_tol, int *status)
+           const double *__restrict__ pool_pm_all, long long pm_stride, int batch, Rule rule, int *status)
 {
+    const double inv_tol = rule.inv_tol;
     const FrontDesc d = fdesc[first + blockIdx.x];
     const int lane = threadIdx.x;
     const long long m = (long long) blockIdx.y * 64 + lane;
@@ -2695,7 +2726,7 @@ k_front_il(const FrontDesc *__restrict__ fdesc, int first, const int *__restrict
 
     // ---- factorisation in place
     bool bad = false;
-    int bad_col = 0;
+    int bad_col = 0, hits = 0;                     // (lane = matrix: every lane counts the pivots of its own)
     for (int k0 = 0; k0 < w; k0 += IL_KB) {
         const int kb = min(IL_KB, w - k0), ke = k0 + kb;
         // 1. diagonal block, identity-padded past kb: dd[jj][ii] = element (k0 + ii, k0 + jj)
@@ -2710,7 +2741,14 @@ k_front_il(const FrontDesc *__restrict__ fdesc, int first, const int *__restrict
             }
 #pragma unroll
         for (int kk = 0; kk < IL_KB; ++kk) {
-            const double piv = dd[kk][kk];
+            double piv = dd[kk][kk];
+            if constexpr (Rule::on) {
+                if (kk < kb) {                                                // (not the identity pivots of the padding)
+                    const bool hit = perturb_pivot(rule, piv);
+                    dd[kk][kk] = piv;
+                    hits += (int) hit;
+                }
+            }
             double dg;
             pivot_scale<KIND>(piv, dg, rd[kk]);
             bool rej = (KIND == CS3_LU) ? (!(fabs(piv) > 0.0) || !(fabs(piv) < 1.0e300)) : !(piv > 0.0);
@@ -2834,6 +2872,7 @@ k_front_il(const FrontDesc *__restrict__ fdesc, int first, const int *__restrict
         }
     }
 #undef EL
+    if (live) count_perturbed(rule, m, hits);
     if (bad && live) flag_column(status, d.c0 + bad_col);
 }
 
@@ -3419,6 +3458,7 @@ k_prologue(int *status, double *__restrict__ pool, long long big_begin, long lon
 {
     const long long t0 = (long long) blockIdx.x * blockDim.x + threadIdx.x, stride = (long long) gridDim.x * blockDim.x;
     if (t0 == 0) { status[0] = 0x7f7f7f7f; status[1] = 0; status[2] = 0; }      // ... and the two hand-over words of the fused step
+    for (long long t = t0; t < batch; t += stride) status[4 + t] = 0;           // perturbed pivots per matrix
     const long long z_all = nzero * batch, x_all = x_src ? n * nrhs * batch : 0;
     // the values of the bottom forest's fronts in THEIR order (forest.hip reads them without an index indirection)
     for (long long t = t0; t < nf * batch; t += stride) axf[t] = ax_src[(t / nf) * nnz_a + f_src[t % nf]];
@@ -3650,7 +3690,7 @@ static hipError_t launch_big_gather(const DeviceFactor &D, const LaunchGroup &g,
 }
 
 template <int KIND>
-static hipError_t launch_big_block(const DeviceFactor &D, const LaunchGroup &g, int blk, double inv_tol, hipStream_t st)
+static hipError_t launch_big_block(const DeviceFactor &D, const LaunchGroup &g, int blk, const PivotCtl &pc, hipStream_t st)
 {
     const unsigned batch = (unsigned) D.batch;
     const int kb = blk * BIG_NB;
@@ -3659,8 +3699,10 @@ static hipError_t launch_big_block(const DeviceFactor &D, const LaunchGroup &g, 
     const int start = std::max(1, kb - BIG_NB + 1);
     const int rem = g.max_r - std::min(start, g.max_r);        // largest trailing order over the group
     const int tiles = 1 + (rem + 63) / 64;
-    hipLaunchKernelGGL((k_big_step<KIND>), dim3(tiles, tiles, g.count * batch), dim3(256), 0, st, D.fdesc,
-                       g.first, kb, D.pool_pm, D.pm_stride, D.dbuf, D.dbuf_size, inv_tol, D.status, (int) batch, D.tbuf);
+    with_rule<KIND>(pc, [&](auto rule) {
+        hipLaunchKernelGGL((k_big_step<KIND, decltype(rule)>), dim3(tiles, tiles, g.count * batch), dim3(256), 0, st, D.fdesc,
+                           g.first, kb, D.pool_pm, D.pm_stride, D.dbuf, D.dbuf_size, rule, D.status, (int) batch, D.tbuf);
+    });
     CS3_LAUNCH_CHECK();
     return hipSuccess;
 }
@@ -3683,29 +3725,34 @@ bool big_group_in_one_workgroup(int kind, long long batch, const LaunchGroup &g)
     return g.cls == FC_BIG && batch >= min_batch && wg_lds_bytes(kind, g) <= 150 * 1024;
 }
 
+// (every kernel launch below picks its instance by the rule: with_rule)
 template <int KIND>
-static hipError_t launch_front_group(const DeviceFactor &D, const SweepCall &call, const LaunchGroup &g, double inv_tol, hipStream_t st)
+static hipError_t launch_front_group(const DeviceFactor &D, const SweepCall &call, const LaunchGroup &g, const PivotCtl &pc, hipStream_t st)
 {
     const unsigned batch = (unsigned) D.batch;
-    if (g.cls == FC_SUB) return launch_sub_factor(D, call, inv_tol, st);     // the bottom forest
+    if (g.cls == FC_SUB) return launch_sub_factor(D, call, pc, st);     // the bottom forest
     if (big_group_in_one_workgroup(KIND, D.batch, g)) {
-        hipLaunchKernelGGL((k_front_wg<KIND, WG_NB>), dim3((unsigned) g.count, batch), dim3(512), wg_lds_bytes(KIND, g), st, D.fdesc,
-                           g.first, AsmLists{D.fa_tgt, D.fa_src, D.ch_tab, D.rel_idx}, D.ax, D.pool_pm, D.nnz_a, D.pm_stride,
-                           IlView{D.pool_il, D.il_len}, inv_tol, D.status, wg_panel_ld(g), D.tbuf);
+        with_rule<KIND>(pc, [&](auto rule) {
+            hipLaunchKernelGGL((k_front_wg<KIND, decltype(rule), WG_NB>), dim3((unsigned) g.count, batch), dim3(512), wg_lds_bytes(KIND, g), st, D.fdesc,
+                               g.first, AsmLists{D.fa_tgt, D.fa_src, D.ch_tab, D.rel_idx}, D.ax, D.pool_pm, D.nnz_a, D.pm_stride,
+                               IlView{D.pool_il, D.il_len}, rule, D.status, wg_panel_ld(g), D.tbuf);
+        });
         CS3_LAUNCH_CHECK();
         return hipSuccess;
     }
     if (g.cls == FC_IL) {
-        hipLaunchKernelGGL((k_front_il<KIND>), dim3((unsigned) g.count, (unsigned) D.ngroups), dim3(64), 0, st, D.fdesc, g.first,
-                           D.ila_pairs, D.ax, D.nnz_a, IlView{D.pool_il, D.il_len}, D.pool_pm, D.pm_stride, (int) D.batch,
-                           inv_tol, D.status);
+        with_rule<KIND>(pc, [&](auto rule) {
+            hipLaunchKernelGGL((k_front_il<KIND, decltype(rule)>), dim3((unsigned) g.count, (unsigned) D.ngroups), dim3(64), 0, st, D.fdesc, g.first,
+                               D.ila_pairs, D.ax, D.nnz_a, IlView{D.pool_il, D.il_len}, D.pool_pm, D.pm_stride, (int) D.batch,
+                               rule, D.status);
+        });
         CS3_LAUNCH_CHECK();
         return hipSuccess;
     }
     if (g.cls == FC_BIG) {
         hipError_t e = launch_big_gather(D, g, st);
         // one launch per block of BIG_NB pivots, plus the closing launch (last update + last parked block)
-        for (int blk = 0; e == hipSuccess && blk <= big_group_blocks(g); ++blk) e = launch_big_block<KIND>(D, g, blk, inv_tol, st);
+        for (int blk = 0; e == hipSuccess && blk <= big_group_blocks(g); ++blk) e = launch_big_block<KIND>(D, g, blk, pc, st);
         return e;
     }
     dim3 grid((unsigned) g.count, batch);
@@ -3714,16 +3761,18 @@ static hipError_t launch_front_group(const DeviceFactor &D, const SweepCall &cal
     //  grid that takes the others keeps the full image)
     const bool packed = KIND == CS3_CHOLESKY && g.max_w <= 32;
     const size_t lds = ((packed ? (size_t) g.max_r * (size_t) (g.max_r + 1) / 2 : ld * (size_t) g.max_r) + 4 * (size_t) g.max_r + 6) * sizeof(double);
-#define CS3_FRONT_ARGS D.fdesc, g.first, AsmLists{D.fa_tgt, D.fa_src, D.ch_tab, D.rel_idx}, D.ax, D.pool_pm, D.nnz_a, D.pm_stride, IlView{D.pool_il, D.il_len}, inv_tol, D.status, D.tbuf
+#define CS3_FRONT_ARGS D.fdesc, g.first, AsmLists{D.fa_tgt, D.fa_src, D.ch_tab, D.rel_idx}, D.ax, D.pool_pm, D.nnz_a, D.pm_stride, IlView{D.pool_il, D.il_len}, rule, D.status, D.tbuf
+    with_rule<KIND>(pc, [&](auto rule) {
+    using Rule = decltype(rule);
     switch (g.cls) {
     case FC_R16:
     case FC_R32:      // only present when the analysis split the small fronts off (batched handles)
-        hipLaunchKernelGGL((k_front_wave<KIND>), grid, dim3(64), lds, st, CS3_FRONT_ARGS); break;
+        hipLaunchKernelGGL((k_front_wave<KIND, Rule>), grid, dim3(64), lds, st, CS3_FRONT_ARGS); break;
     case FC_R64: {    // at most 32 pivots: panel by one wave + Schur complement by MFMA; more: the 16 x 16 thread grid
         // a batch fills the chip with fronts, not with waves per front: two waves (panel columns / pivot rows, then the
         // tiles) instead of four double the fronts per CU -- the image, not the registers, then bounds the occupancy
         const unsigned threads = (D.batch >= 16 && g.max_w <= 32) ? 128 : 256;
-        hipLaunchKernelGGL((k_front_mix<KIND>), grid, dim3(threads), lds, st, CS3_FRONT_ARGS); break;
+        hipLaunchKernelGGL((k_front_mix<KIND, Rule>), grid, dim3(threads), lds, st, CS3_FRONT_ARGS); break;
     }
     default:
         // 16 pivots per block step: the one-wave elimination of a block costs NBK^2 column updates, the MFMA update that
@@ -3733,12 +3782,13 @@ static hipError_t launch_front_group(const DeviceFactor &D, const SweepCall &cal
         const size_t blds = ((KIND == CS3_LU) ? ld * (size_t) g.max_r : (size_t) g.max_r * (size_t) (g.max_r + 1) / 2) * sizeof(double) + 16;
         // Cholesky has no block-row waves: four waves do all the eliminations of a block step, and a batch prefers more
         // workgroups per CU to more waves per front
-        if (KIND == CS3_CHOLESKY && D.batch >= 16)
-            hipLaunchKernelGGL((k_front_block<CS3_CHOLESKY, 16, 4>), grid, dim3(256), blds, st, CS3_FRONT_ARGS);
-        else
-            hipLaunchKernelGGL((k_front_block<KIND, 16>), grid, dim3(512), blds, st, CS3_FRONT_ARGS);
+        if constexpr (KIND == CS3_CHOLESKY) {
+            if (D.batch >= 16) { hipLaunchKernelGGL((k_front_block<CS3_CHOLESKY, Rule, 16, 4>), grid, dim3(256), blds, st, CS3_FRONT_ARGS); break; }
+        }
+        hipLaunchKernelGGL((k_front_block<KIND, Rule, 16>), grid, dim3(512), blds, st, CS3_FRONT_ARGS);
         break;
     }
+    });
 #undef CS3_FRONT_ARGS
     CS3_LAUNCH_CHECK();
     return hipSuccess;
@@ -3769,9 +3819,13 @@ hipError_t prepare_kernels()
     // the largest LDS-resident class needs more than the default 64 KiB of dynamic LDS
     const int big = 160 * 1024;
     hipError_t e;
-    const void *block_fns[] = {(const void *) k_front_block<CS3_LU, 16>, (const void *) k_front_block<CS3_CHOLESKY, 16>,
-                               (const void *) k_front_block<CS3_CHOLESKY, 16, 4>,
-                               (const void *) k_front_wg<CS3_LU, WG_NB>, (const void *) k_front_wg<CS3_CHOLESKY, WG_NB>};
+    using Plain = PivotRule<false>;
+    using Perturbed = PivotRule<true>;
+    const void *block_fns[] = {(const void *) k_front_block<CS3_LU, Plain, 16>, (const void *) k_front_block<CS3_LU, Perturbed, 16>,
+                               (const void *) k_front_block<CS3_CHOLESKY, Plain, 16>,
+                               (const void *) k_front_block<CS3_CHOLESKY, Plain, 16, 4>,
+                               (const void *) k_front_wg<CS3_LU, Plain, WG_NB>, (const void *) k_front_wg<CS3_LU, Perturbed, WG_NB>,
+                               (const void *) k_front_wg<CS3_CHOLESKY, Plain, WG_NB>};
     for (const void *f : block_fns) {
         e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, big);
         if (e != hipSuccess) return e;
@@ -3877,14 +3931,14 @@ static hipError_t run_level(const std::vector<LaunchGroup> &groups, size_t g0, s
 static std::vector<LaunchGroup> factor_groups(const DeviceFactor &D, const std::vector<LaunchGroup> &groups);
 
 hipError_t launch_factor_levels(const DeviceFactor &D, const SweepCall &call, const std::vector<LaunchGroup> &all_groups,
-                                double inv_tol, hipStream_t st, ForkJoin &fj)
+                                const PivotCtl &pc, hipStream_t st, ForkJoin &fj)
 {
     const std::vector<LaunchGroup> groups = factor_groups(D, all_groups);
     fj.rewind();                         // (the big-front buffers were zeroed by launch_prologue)
     for (size_t g0 = 0; g0 < groups.size(); ) {
         const size_t g1 = level_edge(groups, g0, true);
         hipError_t e = run_level(groups, g0, g1, st, fj, true, [&](const LaunchGroup &g, hipStream_t s) {
-            return with_kind(D.kind, [&](auto K) { return launch_front_group<K>(D, call, g, inv_tol, s); });
+            return with_kind(D.kind, [&](auto K) { return launch_front_group<K>(D, call, g, pc, s); });
         });
         if (e != hipSuccess) return e;
         g0 = g1;
@@ -4243,13 +4297,13 @@ static int sweep_group_cost(const LaunchGroup &g)
 // K is the last level whose tail is still long enough to cover the sweep; one fork, one join -- a
 // fork per level costs more than it hides (measured).  Same kernels, same operands: same bits.
 hipError_t launch_factor_with_forward(const DeviceFactor &D, const SweepCall &call, const std::vector<LaunchGroup> &all_fgroups,
-                                      double inv_tol, double *X, int nrhs, hipStream_t st, ForkJoin &fj)
+                                      const PivotCtl &pc, double *X, int nrhs, hipStream_t st, ForkJoin &fj)
 {
     hipError_t e;
     if (!D.sub_forest.empty() && call.sd != D.sdesc1) {
         // a bottom forest under the factorisation, but sweeps on the level schedule of the whole tree (several right-hand
         // sides): the two number their levels differently, so nothing is overlapped
-        if ((e = launch_factor_levels(D, call, all_fgroups, inv_tol, st, fj)) != hipSuccess) return e;
+        if ((e = launch_factor_levels(D, call, all_fgroups, pc, st, fj)) != hipSuccess) return e;
         return launch_solve_levels(D, call, X, nrhs, true, st, fj);
     }
     const std::vector<LaunchGroup> fgroups = factor_groups(D, all_fgroups);
@@ -4297,7 +4351,7 @@ hipError_t launch_factor_with_forward(const DeviceFactor &D, const SweepCall &ca
             const int level = fgroups[f0].level;
             const size_t f1 = level_edge(fgroups, f0, true);
             e = run_level(fgroups, f0, f1, st, fj, true, [&](const LaunchGroup &g, hipStream_t s2) {
-                return with_kind(D.kind, [&](auto K) { return launch_front_group<K>(D, call, g, inv_tol, s2); });
+                return with_kind(D.kind, [&](auto K) { return launch_front_group<K>(D, call, g, pc, s2); });
             });
             if (e != hipSuccess) return e;
             if ((e = flush()) != hipSuccess) return e;
@@ -4368,7 +4422,7 @@ hipError_t launch_factor_with_forward(const DeviceFactor &D, const SweepCall &ca
                 return hipSuccess;
             };
             for (int blk = 0; blk <= nblk; ++blk) {
-                e = with_kind(D.kind, [&](auto K) { return launch_big_block<K>(D, *rootf, blk, inv_tol, st); });
+                e = with_kind(D.kind, [&](auto K) { return launch_big_block<K>(D, *rootf, blk, pc, st); });
                 if (e != hipSuccess) return e;
                 if (!side_started && (e = start_side()) != hipSuccess) return e;      // after the chain's first block is captured
                 if (home && (e = release()) != hipSuccess) return e;                  // after the block that follows the release point
@@ -4385,7 +4439,7 @@ hipError_t launch_factor_with_forward(const DeviceFactor &D, const SweepCall &ca
             continue;
         }
         e = run_level(fgroups, f0, f1, st, fj, true, [&](const LaunchGroup &g, hipStream_t s) {
-            return with_kind(D.kind, [&](auto K) { return launch_front_group<K>(D, call, g, inv_tol, s); });
+            return with_kind(D.kind, [&](auto K) { return launch_front_group<K>(D, call, g, pc, s); });
         });
         if (e != hipSuccess) return e;
         if (ready_deferred && !rootf) {            // the level above the fork has been captured: now the side branch

@@ -167,6 +167,36 @@ int cs3_factor_solve_bx_dev(cs3_handle h, const double *Ax_dev, double tol, cons
 /* Deferred status of the last cs3_factor_dev / cs3_factor_solve_dev (synchronises the stream). */
 int cs3_factor_status(cs3_handle h, void *stream);
 
+/* ---- static pivot perturbation: LU that never stops on a tiny pivot ------
+ * Matching + scaling makes the diagonal of B equal to 1 BEFORE elimination; it says nothing about what elimination
+ * leaves there.  A Newton chain on a KKT system or an ill-scaled Jacobian meets a cancelling pivot sooner or later, and
+ * a static-pivot LU then either stops (CS3_ERR_PIVOT) or, with tol <= 0, returns 1e16 of growth.  The other half of what
+ * SuperLU_DIST, PARDISO and cuDSS do next to the matching: a pivot that is too small is REPLACED, and iterative
+ * refinement (cs3_refine_dev, cs3_refine) removes the error.
+ *
+ * The rule, for delta > 0: during the numeric LU of every matrix of the batch a pivot p with |p| < delta is replaced
+ * by +delta -- always plus delta, whatever the sign of p (a pivot that is rounding noise has no sign worth keeping, and
+ * one rule for both signs keeps every wave that derives the pivot in agreement).  NaN and +-inf are not smaller than
+ * delta: they stay as they are and are rejected as before.  The tol test is unchanged and sees the replaced pivot; with
+ * tol <= 0 and finite values an LU with delta > 0 cannot fail.
+ *
+ * The factors are then the exact factors (to rounding) of A(q, q) + diag(E), with E_kk != 0 only at the replaced
+ * pivots, E_kk = delta - p_k.  Everything that reads the factors sees delta as U_kk: the solves, cs3_get_factors, the
+ * export, cs3_slogdet and cs3_condest -- the last two describe the PERTURBED matrix.  A solution is x = (A + E')^-1 b and
+ * needs refinement against A: cs3_refine_dev / cs3_refine, whose corrections shrink by about |E| |A^-1| per round.
+ *
+ * cs3_set_pivot_perturbation: delta for this handle, kept across refactorisations; 0 (the default) switches it off, and
+ *   the handle then runs the kernels it ran before, instruction for instruction.  Null handle, delta < 0 or not finite,
+ *   or a Cholesky handle: CS3_ERR_ARG.  On a matched handle delta refers to B, where |B| <= 1: sqrt(DBL_EPSILON) is the
+ *   usual choice; on a plain handle sqrt(DBL_EPSILON) * max|Ax|.  A changed delta takes effect with the next
+ *   factorisation (captured graphs of the old value are dropped then).
+ * cs3_get_perturbed: count[batch], the number of pivots the last factorisation replaced in every matrix (synchronises
+ *   the stream, like cs3_factor_status).  CS3_ERR_STATE before any factorisation.  A perturbation is not a failure:
+ *   cs3_factor_status stays CS3_OK.
+ * Not offered: Cholesky, a relative delta read from device memory, a list of the perturbed columns. */
+int cs3_set_pivot_perturbation(cs3_handle h, double delta);
+int cs3_get_perturbed(cs3_handle h, int64_t *count, void *stream);
+
 /* ---- solves (cs_lsolve / cs_usolve / cs_ltsolve / cs_lusol / cs_cholsol) -
  * X is [n, k] row-major (the reference's multi-vector layout, csc.py:409-414),
  * overwritten in place.  With batch > 1, X is [batch, n, k].
@@ -208,6 +238,9 @@ int cs3_matvec_dev(cs3_handle h, const double *Ax_dev, const double *X_dev, doub
  * (reading it synchronises the stream). */
 int cs3_refine_dev(cs3_handle h, const double *Ax_dev, const double *B_dev, double *X_dev, int64_t k, int64_t steps,
                    double *last_correction, void *stream);
+/* The host-array form of cs3_refine_dev (Ax [batch][nnz], B and X [batch][n, k] in host memory, the null stream): the
+ * same kernels in the same order, so the same bits. */
+int cs3_refine(cs3_handle h, const double *Ax, const double *B, double *X, int64_t k, int64_t steps, double *last_correction);
 /* The transposed counterparts: R = B - A' X, Y = A' X, and x += A^-T (b - A' x).  Row j of A' X sums column j of A in
  * storage order with the same rounding discipline (bit-exact with csc_mat_vec_ff applied to A' when the columns of A are
  * sorted). */
