@@ -167,36 +167,46 @@ class CscMat:
         h.update(np.ascontiguousarray(self.indices[:nnz], dtype=np.int32).tobytes())
         return self.m, n, nnz, h.digest()
 
-    def _analysis(self, kind, order, q, match=False):
-        key = (kind, order, None if q is None else bytes(np.asarray(q, dtype=np.int32)), self._pattern_fingerprint(), bool(match))
+    def _analysis(self, kind, order, q, match=False, schur=None):
+        key = (kind, order, None if q is None else bytes(np.asarray(q, dtype=np.int32)), self._pattern_fingerprint(), bool(match),
+               None if schur is None else bytes(np.asarray(schur, dtype=np.int32)))
         f = self._factorization
         if f is None or f[0] != key:
             if f is not None:
                 f[1].close()
             fac = _k.Factorization(self.m, self.n, self.indptr, self.indices, kind=kind, order=order, q=q,
-                                   match_values=self.data if match else None)
+                                   match_values=self.data if match else None, schur=schur)
             self._factorization = f = (key, fac)
         return f[1]
 
-    def lu(self, tol=0.0, order=_k.ORDER_AMD, q=None, match=False, perturb=0.0):
+    def lu(self, tol=0.0, order=_k.ORDER_AMD, q=None, match=False, perturb=0.0, schur=None):
         """Numeric LU on the device; the symbolic analysis is cached on the object, so calling
         lu() again after changing .data is a refactorisation with the pattern reused.
         match: permute rows by the maximum-product transversal and scale before the analysis (matrices without a strong
         diagonal); the matching is computed from .data at the first analysis and kept across refactorisations.
         perturb: static pivot perturbation -- a pivot below delta becomes +delta instead of failing the factorisation
         (a number: delta itself; True: sqrt(eps), times max |data| when match is false).  The analysis is reused whatever
-        perturb is; F.perturbed() counts the replaced pivots and solutions then need F.refine / solve(perturb=...)."""
-        F = self._analysis(_k.CS3_LU, order, q, match)
+        perturb is; F.perturbed() counts the replaced pivots and solutions then need F.refine / solve(perturb=...).
+        schur: the variables that are not eliminated (Factorization(schur=...)): the interior is factorised and F.schur()
+        is the dense Schur complement on that set; order / q then refer to the interior."""
+        F = self._analysis(_k.CS3_LU, order, q, match, schur)
         delta = _k.perturbation_delta(perturb, self.data, match)
         if delta != F.perturbation:
             F.set_perturbation(delta)
         F.factor(self.data, tol)
         return F
 
-    def chol(self, order=_k.ORDER_AMD, q=None):
-        F = self._analysis(_k.CS3_CHOLESKY, order, q)
+    def chol(self, order=_k.ORDER_AMD, q=None, schur=None):
+        F = self._analysis(_k.CS3_CHOLESKY, order, q, schur=schur)
         F.factor(self.data)
         return F
+
+    def schur_complement(self, idx, kind="lu", tol=0.0):
+        """S = A22 - A21 A11^-1 A12 on the variables idx (in that order), dense [len(idx), len(idx)]: the interior is
+        factorised by LU (kind "lu") or Cholesky ("chol"), the Schur variables are never pivots."""
+        assert kind in ("lu", "chol")
+        F = self.lu(tol, schur=idx) if kind == "lu" else self.chol(schur=idx)
+        return F.schur()
 
     def solve(self, b, tol=0.0, trans=False, match=False, perturb=0.0, max_refine=10):
         """x = A \\ b by LU (factorises if needed); trans: A' x = b on the same factors; match, perturb: as in lu().

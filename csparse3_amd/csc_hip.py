@@ -98,6 +98,14 @@ def lib():
         L.cs3_match_scale.argtypes = [I64, _i32p, _i32p, _f64p, _i32p, _f64p, _f64p]
         L.cs3_analyze_matched.argtypes = [I64, I64, _i32p, _i32p, _f64p, _i32p, I64, C.POINTER(vp)]
         L.cs3_get_matching.argtypes = [vp, _i32p, _f64p, _f64p, C.POINTER(C.c_double)]
+        L.cs3_analyze_schur.argtypes = [I64, I64, I64, _i32p, _i32p, _i32p, I64, I64, _i32p, C.POINTER(vp)]
+        L.cs3_schur_info.argtypes = [vp, C.POINTER(I64), _i32p]
+        L.cs3_schur_get_dev.argtypes = [vp, vp, vp]
+        L.cs3_schur_get.argtypes = [vp, _f64p]
+        for f in (L.cs3_schur_fwd_dev, L.cs3_schur_bwd_dev):
+            f.argtypes = [vp, vp, I64, vp]
+        for f in (L.cs3_schur_fwd, L.cs3_schur_bwd):
+            f.argtypes = [vp, _f64p, I64]
         L.cs3_free.argtypes = [vp]
         L.cs3_get_info.argtypes = [vp, C.POINTER(Cs3Info)]
         L.cs3_get_ordering.argtypes = [vp] + [_i32p] * 6
@@ -319,9 +327,13 @@ class Factorization:
     stay in terms of A; order / q, tol, factors() and ordering() refer to B.  The matching is kept across refactorisations.
     set_perturbation (LU only): pivots smaller than delta are replaced by +delta instead of stopping the factorisation;
     perturbed() counts them and refine() removes the error from a solution.
+    schur: indices of the variables that are NOT eliminated (a Schur handle, cs3_analyze_schur).  factor() then factorises
+    the interior and holds the dense Schur complement S = A22 - A21 A11^-1 A12 on that set, in the order of the list:
+    schur(), schur_forward(), schur_backward().  order / q refer to the interior; slogdet() is that of A11; solve() and
+    everything else that would answer for the full matrix raise Cs3Error.  Not together with match_values.
     """
 
-    def __init__(self, m, n, Ap, Ai, kind=CS3_LU, order=ORDER_AMD, q=None, batch=1, match_values=None):
+    def __init__(self, m, n, Ap, Ai, kind=CS3_LU, order=ORDER_AMD, q=None, batch=1, match_values=None, schur=None):
         assert m == n, "square matrix required"
         self._h = C.c_void_p()
         self.kind = kind
@@ -335,7 +347,13 @@ class Factorization:
             order = ORDER_GIVEN
         self.matched = match_values is not None
         self.perturbation = 0.0
-        if self.matched:
+        self.ns = 0
+        if schur is not None:
+            assert not self.matched, "a Schur set and a matching exclude each other"
+            idx = _i32(schur).reshape(-1)
+            _check(lib().cs3_analyze_schur(kind, order, n, _pi(Ap), _pi(Ai), _pi(qa), batch, idx.size, _pi(idx), C.byref(self._h)))
+            self.ns = int(idx.size)
+        elif self.matched:
             assert kind == CS3_LU, "matching is for LU handles"
             mv = _f64(match_values).reshape(-1)
             assert mv.size >= self.nnz
@@ -394,6 +412,41 @@ class Factorization:
         sn_level = np.empty(ns, dtype=np.int32)
         _check(lib().cs3_get_supernodes(self._h, _pi(sn_ptr), _pi(sn_parent), _pi(sn_level)))
         return sn_ptr, sn_parent, sn_level
+
+    # -- Schur complements (a handle made with schur=...)
+    def schur_info(self):
+        """-> int32[ns]: the Schur set in the order of S's rows and columns (Cs3Error on a plain handle)."""
+        ns = I64()
+        _check(lib().cs3_schur_info(self._h, C.byref(ns), None))
+        idx = np.empty(int(ns.value), dtype=np.int32)
+        _check(lib().cs3_schur_info(self._h, None, _pi(idx)))
+        return idx
+
+    def schur(self):
+        """The Schur complement of the last factorisation: [ns, ns], or [batch, ns, ns]; S[i, j] belongs to
+        (schur_idx[i], schur_idx[j]).  Cholesky: the full symmetric matrix."""
+        S = np.empty((self.batch, self.ns, self.ns))
+        _check(lib().cs3_schur_get(self._h, _pf(S)))
+        return S[0] if self.batch == 1 else S
+
+    def schur_dev(self, s_ptr, stream=0):
+        """schur() into device memory [batch][ns, ns], asynchronous on `stream`."""
+        _check(lib().cs3_schur_get_dev(self._h, C.c_void_p(s_ptr), C.c_void_p(stream)))
+
+    def schur_forward(self, b):
+        """b: [n], [n, k] or [batch, n, k] in A's rows.  -> a new array whose Schur rows hold b2 - A21 A11^-1 b1 (the
+        right-hand side of S x2 = g); the interior rows are the half-solved interior, to be passed on to schur_backward."""
+        return self._sweep(lib().cs3_schur_fwd, b)
+
+    def schur_backward(self, y):
+        """y: what schur_forward returned, with the Schur rows replaced by x2.  -> the solution of A x = b."""
+        return self._sweep(lib().cs3_schur_bwd, y)
+
+    def schur_forward_dev(self, x_ptr, k=1, stream=0):
+        _check(lib().cs3_schur_fwd_dev(self._h, C.c_void_p(x_ptr), k, C.c_void_p(stream)))
+
+    def schur_backward_dev(self, x_ptr, k=1, stream=0):
+        _check(lib().cs3_schur_bwd_dev(self._h, C.c_void_p(x_ptr), k, C.c_void_p(stream)))
 
     # -- static pivot perturbation
     def set_perturbation(self, delta):

@@ -35,8 +35,9 @@ void set_error(const std::string &msg) { g_error = msg; }
 //     inside the graph (no eager launch behind it: 5 us) per (nrhs, X): at most 4, and only from the third call in a row
 //     with the same X (fused_last_x / fused_same_x).  A change of inv_tol or delta drops every fused-step graph.
 //   - ensure_rhs_capacity drops every solve and fused-step graph (the buffers they read move).
+//   - GRAPH_SCHUR_FWD / GRAPH_SCHUR_BWD (the half-solves of a Schur handle) per nrhs: unbounded, X never baked in.
 // A graph that may still be running on another stream is destroyed only after a hipDeviceSynchronize.
-enum GraphOp { GRAPH_FACTOR, GRAPH_SOLVE, GRAPH_FUSED };
+enum GraphOp { GRAPH_FACTOR, GRAPH_SOLVE, GRAPH_FUSED, GRAPH_SCHUR_FWD, GRAPH_SCHUR_BWD };
 using GraphKey = std::tuple<int, bool, int, const void *>;     // (GraphOp, trans, nrhs, X)
 
 struct cs3_handle_s {
@@ -88,6 +89,8 @@ struct cs3_handle_s {
         struct { DevBuf<double> z, x0; } upd;
         // ensure_match (matching.hip): the scalings, the row of A behind every pivot row, row and column of every entry
         struct { DevBuf<double> dr, dc; DevBuf<int> rq, erow, ecol; } match;
+        // ensure_device on a Schur handle (schur.hip): the held Schur complements S [batch][ns, ns]
+        DevBuf<double> schur;
     } mem;
     // diagnostics (cs3_debug_alloc_counters): device allocations / graph instantiations and host synchronisations made by the
     // solves and the paths on top of them
@@ -306,6 +309,16 @@ int ensure_device_impl(cs3_handle h)
     }
     if (h->match.on)
         if ((rc = ensure_match(h))) return rc;
+    if (S.schur_sn >= 0) {
+        // the Schur front's buffer is rewritten (with the identity) by every factorisation: the prologue zeroes it whatever
+        // the other big fronts do
+        const i64 ns = (i64) S.schur_idx.size();
+        D.zero_big = true;
+        D.schur_ns = (int) ns;
+        D.schur_lpan = S.lpan_off[S.schur_sn];
+        CS3_HIP(h->mem.schur.alloc((size_t) (D.batch * ns * ns)));
+        D.schur = h->mem.schur.get();
+    }
     CS3_HIP(hipStreamCreateWithFlags(&h->cap_stream, hipStreamNonBlocking));
     CS3_HIP(h->fj.init());
     const char *ng = std::getenv("CS3_NO_GRAPH");
@@ -410,6 +423,21 @@ hipError_t launch_match_permute(cs3_handle h, const double *src, double *dst, in
 // The sweeps of one call: launch groups and their descriptors.  One right-hand side on a handle with a bottom forest
 // follows the factor schedule (the forest, then the levels above it) with descriptors of its own.  (The forest's sweeps
 // have no transposed form: a transposed solve takes the level schedule whatever nrhs is.)
+// A Schur handle holds the factors of A with A22 replaced by A22 - S + I: whatever would silently answer for that matrix
+// is refused.
+int refuse_schur(cs3_handle h, const char *who)
+{
+    if (h->S.schur_sn < 0) return CS3_OK;
+    set_error(std::string(who) + ": not available on a Schur handle (cs3_analyze_schur) -- its factors are those of A with A22 replaced "
+              "by A22 - S + I, not of A; use cs3_schur_get / cs3_schur_fwd / cs3_schur_bwd");
+    return CS3_ERR_ARG;
+}
+
+// One half-solve of a Schur handle: the caller's X (rows of A) into D.xp, one direction of the unchanged sweeps, back.
+// Forward: the Schur rows end up as b2 - A21 A11^-1 b1, the interior rows half-solved.  Backward, entered with x2 in the
+// Schur rows: x1 = U11^-1 (y1 - U12 x2).  The sweeps are replayed from a graph per (direction, nrhs).
+int run_schur_sweep(cs3_handle h, const char *who, double *x_dev, long long k, bool forward, hipStream_t st);
+
 SweepCall select_sweep_schedule(cs3_handle h, int nrhs, bool trans = false)
 {
     const bool forest = nrhs == 1 && !trans && !h->S.sub_forest.empty();
@@ -482,6 +510,7 @@ int read_status(cs3_handle h, hipStream_t st)
 // On a Cholesky handle A' = A and trans changes nothing.
 int run_solve(cs3_handle h, double *x_dev, long long k, int mode, hipStream_t st, bool trans = false)
 {
+    if (int rc = refuse_schur(h, "solves and one-sided sweeps")) return rc;
     if (!h->factored) { set_error("solve before a successful factorisation"); return CS3_ERR_STATE; }
     if (k < 1 || k > INT_MAX) { set_error("solve: bad number of right-hand sides"); return CS3_ERR_ARG; }
     int rc = ensure_rhs_capacity(h, k);
@@ -515,12 +544,37 @@ int run_solve(cs3_handle h, double *x_dev, long long k, int mode, hipStream_t st
     return CS3_OK;
 }
 
+int run_schur_sweep(cs3_handle h, const char *who, double *x_dev, long long k, bool forward, hipStream_t st)
+{
+    if (h->S.schur_sn < 0) { set_error(std::string(who) + ": the handle has no Schur set (cs3_analyze_schur)"); return CS3_ERR_STATE; }
+    if (!x_dev) { set_error(std::string(who) + ": null right-hand side"); return CS3_ERR_ARG; }
+    if (!h->factored) { set_error(std::string(who) + ": called before a successful factorisation"); return CS3_ERR_STATE; }
+    if (k < 1 || k > INT_MAX) { set_error(std::string(who) + ": bad number of right-hand sides"); return CS3_ERR_ARG; }
+    int rc = ensure_rhs_capacity(h, k);
+    if (rc) return rc;
+    const DeviceFactor &D = h->D;
+    const int nrhs = (int) k;
+    const SweepCall call = select_sweep_schedule(h, nrhs);
+    if (nrhs >= 16 && D.n_inv_tasks > 0 && !h->inverses_valid) {
+        CS3_HIP(launch_diag_inverses(D, st));
+        h->inverses_valid = true;
+    }
+    CS3_HIP(launch_permute(D, x_dev, D.xp, nrhs, false, st));
+    rc = replay_or_run(h, GraphKey(forward ? GRAPH_SCHUR_FWD : GRAPH_SCHUR_BWD, false, nrhs, nullptr), st, [&](hipStream_t s) {
+        return launch_solve_levels(D, call, D.xp, nrhs, forward, s, h->fj);
+    });
+    if (rc) return rc;
+    CS3_HIP(launch_permute(D, D.xp, x_dev, nrhs, true, st));
+    return CS3_OK;
+}
+
 // numeric factorisation and full solve in one graph; the forward sweep runs beside the factorisation
 int run_factor_solve(cs3_handle h, const double *ax_dev, const double *b_dev, double *x_dev, long long k, double tol, hipStream_t st)
 {
     if (k < 1 || k > INT_MAX) { set_error("factor_solve: bad number of right-hand sides"); return CS3_ERR_ARG; }
-    int rc = ensure_rhs_capacity(h, k);
+    int rc = refuse_schur(h, "cs3_factor_solve(_bx)_dev");
     if (rc) return rc;
+    if ((rc = ensure_rhs_capacity(h, k))) return rc;
     const DeviceFactor &D = h->D;
     const int nrhs = (int) k;
     const PivotCtl pc = pivot_ctl(h, tol);
@@ -753,6 +807,90 @@ int cs3_get_matching(cs3_handle h, int32_t *rowperm, double *dr, double *dc, dou
     return CS3_OK;
 }
 
+int cs3_analyze_schur(int64_t kind, int64_t order, int64_t n, const int32_t *Ap, const int32_t *Ai,
+                      const int32_t *q_given, int64_t batch, int64_t ns, const int32_t *schur_idx, cs3_handle *out)
+{
+    if (!out) { set_error("cs3_analyze_schur: null output"); return CS3_ERR_ARG; }
+    *out = nullptr;
+    if (batch < 1) { set_error("cs3_analyze_schur: batch must be >= 1"); return CS3_ERR_ARG; }
+    cs3_handle h = nullptr;
+    try {
+        h = new cs3_handle_s();
+        h->batch = batch;
+        const SchurSet schur{schur_idx, ns};
+        analyze((int) kind, (int) order, n, Ap, Ai, q_given, h->S, batch, &schur);
+        h->Ap_host.assign(Ap, Ap + n + 1);
+        h->Ai_host.assign(Ai, Ai + (n > 0 ? Ap[n] : 0));
+    } catch (const std::bad_alloc &) {
+        delete h; set_error("cs3_analyze_schur: out of memory"); return CS3_ERR_ALLOC;
+    } catch (const std::exception &e) {
+        delete h; set_error(e.what()); return CS3_ERR_ARG;
+    }
+    *out = h;
+    return CS3_OK;
+}
+
+int cs3_schur_info(cs3_handle h, int64_t *ns, int32_t *schur_idx)
+{
+    int rc = guard(h); if (rc) return rc;
+    if (h->S.schur_sn < 0) { set_error("cs3_schur_info: the handle has no Schur set (cs3_analyze_schur)"); return CS3_ERR_STATE; }
+    if (ns) *ns = (int64_t) h->S.schur_idx.size();
+    if (schur_idx) std::memcpy(schur_idx, h->S.schur_idx.data(), h->S.schur_idx.size() * sizeof(int32_t));
+    return CS3_OK;
+}
+
+int cs3_schur_get_dev(cs3_handle h, double *S_dev, void *stream)
+{
+    int rc = guard(h); if (rc) return rc;
+    if (h->S.schur_sn < 0) { set_error("cs3_schur_get_dev: the handle has no Schur set (cs3_analyze_schur)"); return CS3_ERR_STATE; }
+    if (!S_dev) { set_error("cs3_schur_get_dev: null buffer"); return CS3_ERR_ARG; }
+    if (!h->factored) { set_error("cs3_schur_get_dev: called before a successful factorisation"); return CS3_ERR_STATE; }
+    CS3_HIP(hipMemcpyAsync(S_dev, h->D.schur, h->mem.schur.count() * sizeof(double), hipMemcpyDeviceToDevice, (hipStream_t) stream));
+    return CS3_OK;
+}
+
+int cs3_schur_get(cs3_handle h, double *S)
+{
+    int rc = guard(h); if (rc) return rc;
+    if (h->S.schur_sn < 0) { set_error("cs3_schur_get: the handle has no Schur set (cs3_analyze_schur)"); return CS3_ERR_STATE; }
+    if (!S) { set_error("cs3_schur_get: null buffer"); return CS3_ERR_ARG; }
+    if (!h->factored) { set_error("cs3_schur_get: called before a successful factorisation"); return CS3_ERR_STATE; }
+    CS3_HIP(hipMemcpy(S, h->D.schur, h->mem.schur.count() * sizeof(double), hipMemcpyDeviceToHost));
+    return CS3_OK;
+}
+
+int cs3_schur_fwd_dev(cs3_handle h, double *X_dev, int64_t k, void *stream)
+{
+    int rc = guard(h); if (rc) return rc;
+    return run_schur_sweep(h, "cs3_schur_fwd_dev", X_dev, k, true, (hipStream_t) stream);
+}
+
+int cs3_schur_bwd_dev(cs3_handle h, double *X_dev, int64_t k, void *stream)
+{
+    int rc = guard(h); if (rc) return rc;
+    return run_schur_sweep(h, "cs3_schur_bwd_dev", X_dev, k, false, (hipStream_t) stream);
+}
+
+// The host forms: X staged in HBM for the call, the same kernels on the null stream, the same bits.
+static int schur_sweep_host(cs3_handle h, const char *who, double *X, int64_t k, bool forward)
+{
+    int rc = guard(h); if (rc) return rc;
+    if (h->S.schur_sn < 0) { set_error(std::string(who) + ": the handle has no Schur set (cs3_analyze_schur)"); return CS3_ERR_STATE; }
+    if (!X) { set_error(std::string(who) + ": null right-hand side"); return CS3_ERR_ARG; }
+    if (!h->factored) { set_error(std::string(who) + ": called before a successful factorisation"); return CS3_ERR_STATE; }
+    if (k < 1 || k > INT_MAX) { set_error(std::string(who) + ": bad number of right-hand sides"); return CS3_ERR_ARG; }
+    const size_t count = (size_t) (h->batch * h->S.n * k);
+    DevBuf<double> x;
+    CS3_HIP(x.alloc(count));
+    CS3_HIP(hipMemcpy(x.get(), X, count * sizeof(double), hipMemcpyHostToDevice));
+    if ((rc = run_schur_sweep(h, who, x.get(), k, forward, nullptr))) return rc;
+    CS3_HIP(hipMemcpy(X, x.get(), count * sizeof(double), hipMemcpyDeviceToHost));
+    return CS3_OK;
+}
+
+int cs3_schur_fwd(cs3_handle h, double *X, int64_t k) { return schur_sweep_host(h, "cs3_schur_fwd", X, k, true); }
+int cs3_schur_bwd(cs3_handle h, double *X, int64_t k) { return schur_sweep_host(h, "cs3_schur_bwd", X, k, false); }
+
 int cs3_free(cs3_handle h)
 {
     if (!h) return CS3_OK;
@@ -820,6 +958,7 @@ int cs3_factor_dev(cs3_handle h, const double *Ax_dev, double tol, void *stream)
 int cs3_factor_solve_dev(cs3_handle h, const double *Ax_dev, double tol, double *X_dev, int64_t k, void *stream)
 {
     int rc = guard(h); if (rc) return rc;
+    if ((rc = refuse_schur(h, "cs3_factor_solve_dev"))) return rc;
     if ((!Ax_dev && h->S.nnzA > 0) || !X_dev) { set_error("cs3_factor_solve_dev: null argument"); return CS3_ERR_ARG; }
     if ((rc = ensure_device(h))) return rc;
     return run_factor_solve(h, Ax_dev, X_dev, X_dev, k, tol, (hipStream_t) stream);
@@ -828,6 +967,7 @@ int cs3_factor_solve_dev(cs3_handle h, const double *Ax_dev, double tol, double 
 int cs3_factor_solve_bx_dev(cs3_handle h, const double *Ax_dev, double tol, const double *B_dev, double *X_dev, int64_t k, void *stream)
 {
     int rc = guard(h); if (rc) return rc;
+    if ((rc = refuse_schur(h, "cs3_factor_solve_bx_dev"))) return rc;
     if ((!Ax_dev && h->S.nnzA > 0) || !B_dev || !X_dev) { set_error("cs3_factor_solve_bx_dev: null argument"); return CS3_ERR_ARG; }
     if ((rc = ensure_device(h))) return rc;
     return run_factor_solve(h, Ax_dev, B_dev, X_dev, k, tol, (hipStream_t) stream);
@@ -920,6 +1060,7 @@ int cs3_ltsolve_dev(cs3_handle h, double *X_dev, int64_t k, void *stream)
 static int solve_host(cs3_handle h, double *X, int64_t k, int mode, bool trans = false)
 {
     int rc = guard(h); if (rc) return rc;
+    if ((rc = refuse_schur(h, "solves and one-sided sweeps"))) return rc;
     if (!X) { set_error("solve: null right-hand side"); return CS3_ERR_ARG; }
     if (trans && mode == 1 && h->S.kind != CS3_LU) { set_error("utsolve: a Cholesky factorisation has no U"); return CS3_ERR_ARG; }
     if (!h->factored) { set_error("solve before a successful factorisation"); return CS3_ERR_STATE; }
@@ -942,6 +1083,7 @@ int cs3_ltsolve(cs3_handle h, double *X, int64_t k) { return solve_host(h, X, k,
 int cs3_export_factor_dev(cs3_handle h, double *dst_dev, void *stream)
 {
     int rc = guard(h); if (rc) return rc;
+    if ((rc = refuse_schur(h, "cs3_export_factor_dev"))) return rc;
     if (h->match.on) { set_error("cs3_export_factor_dev: not available for a matched handle"); return CS3_ERR_ARG; }
     if (!h->factored) { set_error("cs3_export_factor_dev: nothing factorised"); return CS3_ERR_STATE; }
     if (!dst_dev) { set_error("cs3_export_factor_dev: null buffer"); return CS3_ERR_ARG; }
@@ -957,6 +1099,7 @@ int cs3_export_factor_dev(cs3_handle h, double *dst_dev, void *stream)
 int cs3_import_factor_dev(cs3_handle h, const double *src_dev, void *stream)
 {
     int rc = guard(h); if (rc) return rc;
+    if ((rc = refuse_schur(h, "cs3_import_factor_dev"))) return rc;
     if (h->match.on) { set_error("cs3_import_factor_dev: not available for a matched handle"); return CS3_ERR_ARG; }
     if (!src_dev) { set_error("cs3_import_factor_dev: null buffer"); return CS3_ERR_ARG; }
     if ((rc = ensure_device(h))) return rc;
@@ -1030,6 +1173,7 @@ int cs3_get_factors(cs3_handle h, int64_t b, int32_t *Lp, int32_t *Li, double *L
 {
     int rc = guard(h); if (rc) return rc;
     const Symbolic &S = h->S;
+    if ((rc = refuse_schur(h, "cs3_get_factors"))) return rc;
     if (b < 0 || b >= h->batch) { set_error("cs3_get_factors: batch index out of range"); return CS3_ERR_ARG; }
     if (S.kind == CS3_CHOLESKY && (Up || Ui || Ux)) { set_error("cs3_get_factors: Cholesky has no U"); return CS3_ERR_ARG; }
     try { build_csc_factors(h->S); }                           // (first request: the CSC view of the factors is built now)
@@ -1256,6 +1400,7 @@ static int refine(cs3_handle h, const double *Ax_dev, const double *B_dev, doubl
 {
     if (!who) who = trans ? "cs3_refine_t_dev" : "cs3_refine_dev";
     int rc = guard(h); if (rc) return rc;
+    if ((rc = refuse_schur(h, who))) return rc;
     if (!Ax_dev || !B_dev || !X_dev || k < 1 || k > INT_MAX || steps < 0) { set_error(std::string(who) + ": bad argument"); return CS3_ERR_ARG; }
     if (!h->factored) { set_error(std::string(who) + ": refinement needs a factorisation"); return CS3_ERR_STATE; }
     if ((rc = trans ? ensure_col_view(h, k) : ensure_row_view(h, k))) return rc;
@@ -1297,6 +1442,7 @@ int cs3_refine_t_dev(cs3_handle h, const double *Ax_dev, const double *B_dev, do
 int cs3_refine(cs3_handle h, const double *Ax, const double *B, double *X, int64_t k, int64_t steps, double *last_correction)
 {
     int rc = guard(h); if (rc) return rc;
+    if ((rc = refuse_schur(h, "cs3_refine"))) return rc;
     if (!Ax || !B || !X || k < 1 || k > INT_MAX || steps < 0) { set_error("cs3_refine: bad argument"); return CS3_ERR_ARG; }
     if (!h->factored) { set_error("cs3_refine: refinement needs a factorisation"); return CS3_ERR_STATE; }
     auto &H = h->mem.host;
@@ -1374,6 +1520,7 @@ static int condest_run(cs3_handle h, const double *Ax_dev, double *cond_dev, dou
 static int condest_check(const char *who, cs3_handle h, const double *Ax, const double *cond)
 {
     int rc = guard(h); if (rc) return rc;
+    if ((rc = refuse_schur(h, who))) return rc;
     if (!Ax || !cond) { set_error(std::string(who) + ": null argument"); return CS3_ERR_ARG; }
     if (!h->factored) { set_error(std::string(who) + ": no successful factorisation"); return CS3_ERR_STATE; }
     return CS3_OK;
@@ -1543,6 +1690,7 @@ int cs3_updates_plan(cs3_handle h, int64_t ncases, const int32_t *cp, const int3
     int rc = guard(h); if (rc) return rc;
     if (!out) { set_error("cs3_updates_plan: null output"); return CS3_ERR_ARG; }
     *out = nullptr;
+    if ((rc = refuse_schur(h, "cs3_updates_plan"))) return rc;
     if (!cp) { set_error("cs3_updates_plan: null case pointers"); return CS3_ERR_ARG; }
     if (ncases < 1 || ncases > INT_MAX / 2) { set_error("cs3_updates_plan: ncases must be >= 1"); return CS3_ERR_ARG; }
     if (cp[0] != 0) { set_error("cs3_updates_plan: cp[0] != 0"); return CS3_ERR_ARG; }

@@ -97,6 +97,11 @@ struct DeviceFactor {
     int *status = nullptr;        // [0] first failing pivot column, 0x7f7f7f7f when clean; [3]: a hand-over between waves timed out;
                                   // [4 + b]: pivots of matrix b that the perturbation replaced (PivotCtl::count)
     long long *tbuf = nullptr;    // diagnostics (CS3_PROFILE=1): 8 shader-clock stamps per front, schedule order
+    // Schur handle (cs3_analyze_schur): the held Schur complements [batch][ns, ns] row-major, the order of the Schur
+    // front and the pool offset of its dense buffer (schur.hip); null / 0 on a plain handle
+    double *schur = nullptr;
+    int schur_ns = 0;
+    long long schur_lpan = 0;
 };
 
 // What one solve, factorisation or fused step needs beyond the handle's resident state: built per call by api.cpp and
@@ -215,6 +220,10 @@ hipError_t launch_residual(const int *Rp, const int *Rj, const int *Rmap, const 
 hipError_t launch_axpy_max(double *X, const double *D, long long total, unsigned long long *maxbits, hipStream_t st);
 hipError_t launch_matvec_rows(const int *Rp, const int *Rj, const double *Rx, const double *X, double *Y,
                               long long m, int nrhs, hipStream_t st);
+
+// schur.hip: the assembled Schur front of every matrix goes to D.schur (row-major; Cholesky: mirrored to the full
+// symmetric matrix), the identity takes its place in the pool
+hipError_t launch_schur_take(const DeviceFactor &D, hipStream_t st);
 
 // estimate.hip: condition estimates (LAPACK dlacn2, one state machine per matrix of a batch) and log-determinants.
 // The state of one matrix: step = what the next solve's result is for (1..5: dlacn2's J1..J5; J1, J3, J5 consume

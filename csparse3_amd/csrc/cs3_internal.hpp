@@ -37,7 +37,9 @@ void cholesky_counts(i64 n, const i32 *Ap, const i32 *Ai, const i32 *parent,
 // Size classes of fronts; each class is one kernel configuration.
 // FC_IL: small fronts of a large batch, stored matrix-interleaved and processed lane = matrix (k_front_il).
 // FC_SUB: fronts of the bottom forest -- whole subtrees of small fronts walked by ONE workgroup in one launch (k_sub_*).
-enum FrontClass : int { FC_R16 = 0, FC_R32 = 1, FC_R64 = 2, FC_LDS = 3, FC_BIG = 4, FC_IL = 5, FC_SUB = 6, FC_COUNT = 7 };
+// FC_SCHUR: the front of the Schur variables of a Schur handle (cs3_analyze_schur) -- assembled like a big front
+// (k_big_gather on its dense r x r buffer), never eliminated: k_schur_take moves it out and leaves the identity.
+enum FrontClass : int { FC_R16 = 0, FC_R32 = 1, FC_R64 = 2, FC_LDS = 3, FC_BIG = 4, FC_IL = 5, FC_SUB = 6, FC_SCHUR = 7, FC_COUNT = 8 };
 
 // Solve kernels by front shape.  SK_SMALL and SK_WAVE share the one-wave-per-front kernels for few
 // right-hand sides (adjacent in the schedule, launched as one group); with many right-hand sides
@@ -191,6 +193,10 @@ struct Symbolic {
     i64 max_front = 0, max_width = 0;
     double flops = 0.0;
     double t_order = 0.0, t_symbolic = 0.0;
+    // Schur handle (cs3_analyze_schur): the variables that are not eliminated, in the caller's order = positions
+    // n - ns .. n - 1 of q, and their supernode (the last one: columns [n - ns, n), r = w = ns); -1 / empty otherwise
+    std::vector<i32> schur_idx;
+    i32 schur_sn = -1;
 };
 
 constexpr i32 IL_ZERO = INT32_MIN;            // ila_pairs source: this entry has no source (starts at zero)
@@ -201,8 +207,10 @@ constexpr i32 ASM_DUMMY = 0x3fffffff;         // padding target: contributes now
 constexpr i32 ASM_LONG = 0x40000000;          // flag on a target: sources are long_src[src .. src+count)
 
 // Full analysis.  order: cs3_order.  Throws std::runtime_error on bad input.
+// schur (cs3_analyze_schur): the variables that stay uneliminated; `order` and q_given [n - ns] then refer to the others.
+struct SchurSet { const i32 *idx; i64 ns; };
 void analyze(int kind, int order, i64 n, const i32 *Ap, const i32 *Ai,
-             const i32 *q_given, Symbolic &S, i64 batch = 1);
+             const i32 *q_given, Symbolic &S, i64 batch = 1, const SchurSet *schur = nullptr);
 
 void build_csc_factors(Symbolic &S);
 

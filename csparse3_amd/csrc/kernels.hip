@@ -3749,6 +3749,10 @@ static hipError_t launch_front_group(const DeviceFactor &D, const SweepCall &cal
         CS3_LAUNCH_CHECK();
         return hipSuccess;
     }
+    if (g.cls == FC_SCHUR) {          // a Schur handle's last front: assembled, taken out, never eliminated (schur.hip)
+        hipError_t e = launch_big_gather(D, g, st);
+        return (e != hipSuccess) ? e : launch_schur_take(D, st);
+    }
     if (g.cls == FC_BIG) {
         hipError_t e = launch_big_gather(D, g, st);
         // one launch per block of BIG_NB pivots, plus the closing launch (last update + last parked block)

@@ -170,7 +170,7 @@ static void build_forest(Symbolic &S, const ForestLimits &lim)
     i32 tallest = 0;
     for (i32 s = 0; s < ns; ++s) {
         const i64 r = order_r(s), nb = r - width(s);
-        ok[s] = r <= SUB_RMAX; nf[s] = 1; ar[s] = nb * (nb + 1); hgt[s] = 0;
+        ok[s] = r <= SUB_RMAX && s != S.schur_sn; nf[s] = 1; ar[s] = nb * (nb + 1); hgt[s] = 0;
         for (i32 cp = S.child_ptr[s]; cp < S.child_ptr[s + 1]; ++cp) {
             const i32 c = S.child_idx[cp];
             ok[s] = ok[s] && ok[c];
@@ -314,7 +314,7 @@ static void fill_forest(Symbolic &S, const std::vector<i64> &fa_ptr, const std::
 }  // namespace
 
 void analyze(int kind, int order, i64 n, const i32 *Ap, const i32 *Ai,
-             const i32 *q_given, Symbolic &S, i64 batch)
+             const i32 *q_given, Symbolic &S, i64 batch, const SchurSet *schur)
 {
     if (n < 0 || !Ap || (n > 0 && !Ai && Ap[n] > 0)) throw std::runtime_error("analyze: null input");
     if (kind != CS3_LU && kind != CS3_CHOLESKY) throw std::runtime_error("analyze: unknown kind");
@@ -333,8 +333,27 @@ void analyze(int kind, int order, i64 n, const i32 *Ap, const i32 *Ai,
                 seen[Ai[p]] = j;
             }
     }
+    // a Schur set (cs3_analyze_schur): ns variables that are not eliminated; they are ordered last, in the caller's order
+    const i64 ns_schur = schur ? schur->ns : 0, n1 = n - ns_schur;
+    std::vector<char> is_border;
+    if (schur) {
+        if (!schur->idx) throw std::runtime_error("analyze: null Schur index list");
+        if (ns_schur < 1 || ns_schur >= n)
+            throw std::runtime_error("analyze: the Schur set must hold at least 1 and fewer than n variables, got ns = " + std::to_string(ns_schur));
+        is_border.assign(n, 0);
+        for (i64 i = 0; i < ns_schur; ++i) {
+            const i32 v = schur->idx[i];
+            if (v < 0 || v >= n) throw std::runtime_error("analyze: Schur index " + std::to_string(v) + " (entry " + std::to_string(i) + ") is outside [0, n)");
+        }
+        for (i64 i = 0; i < ns_schur; ++i) {
+            const i32 v = schur->idx[i];
+            if (is_border[v]) throw std::runtime_error("analyze: Schur index " + std::to_string(v) + " (entry " + std::to_string(i) + ") is repeated");
+            is_border[v] = 1;
+        }
+    }
     S = Symbolic();
     S.n = n; S.nnzA = nnzA; S.kind = kind; S.batch = batch;
+    if (schur) S.schur_idx.assign(schur->idx, schur->idx + ns_schur);
 
     // ---- 1. fill-reducing order on the pattern of A + A'
     auto t0 = std::chrono::steady_clock::now();
@@ -342,7 +361,54 @@ void analyze(int kind, int order, i64 n, const i32 *Ap, const i32 *Ai,
     std::vector<i32> Ci;
     symmetrized_pattern(n, Ap, Ai, Cp, Ci);
     S.q_amd.resize(n);
-    if (order == CS3_ORDER_NATURAL) {
+    if (schur) {
+        // the order applies to the interior: A11 alone, the Schur rows and columns removed (its entries in A's order, so
+        // that the result is amd_order's on that matrix, bit for bit); the Schur variables follow in the caller's order
+        std::vector<i32> interior, label(n, -1);
+        for (i64 j = 0; j < n; ++j) if (!is_border[j]) { label[j] = (i32) interior.size(); interior.push_back((i32) j); }
+        if (order == CS3_ORDER_NATURAL) {
+            std::copy(interior.begin(), interior.end(), S.q_amd.begin());
+        } else if (order == CS3_ORDER_AMD) {
+            std::vector<i32> Ap11(n1 + 1, 0), Ai11;
+            for (i64 k = 0; k < n1; ++k) {
+                const i64 j = interior[k];
+                for (i64 p = Ap[j]; p < Ap[j + 1]; ++p) if (!is_border[Ai[p]]) Ai11.push_back(label[Ai[p]]);
+                Ap11[k + 1] = (i32) Ai11.size();
+            }
+            std::vector<i64> Cp11;
+            std::vector<i32> Ci11, perm;
+            symmetrized_pattern(n1, Ap11.data(), Ai11.data(), Cp11, Ci11);
+            amd_order(n1, Cp11, Ci11, perm);
+            for (i64 k = 0; k < n1; ++k) S.q_amd[k] = interior[perm[k]];
+        } else if (order == CS3_ORDER_GIVEN) {
+            if (!q_given) throw std::runtime_error("analyze: CS3_ORDER_GIVEN without q");
+            std::vector<char> hit(n, 0);
+            for (i64 k = 0; k < n1; ++k) {
+                const i32 v = q_given[k];
+                if (v < 0 || v >= n || is_border[v] || hit[v]) throw std::runtime_error("analyze: q is not a permutation of the interior (the variables outside the Schur set)");
+                hit[v] = 1;
+                S.q_amd[k] = v;
+            }
+        } else {
+            throw std::runtime_error("analyze: unknown order");
+        }
+        for (i64 i = 0; i < ns_schur; ++i) S.q_amd[n1 + i] = schur->idx[i];
+        // the Schur block is analysed as structurally dense: a clique on the Schur variables joins the pattern
+        std::vector<i64> Dp(n + 1, 0);
+        std::vector<i32> Di;
+        Di.reserve(Ci.size() + (size_t) (ns_schur * ns_schur));
+        std::vector<i64> seen(n, -1);
+        for (i64 j = 0; j < n; ++j) {
+            for (i64 p = Cp[j]; p < Cp[j + 1]; ++p) { Di.push_back(Ci[p]); seen[Ci[p]] = j; }
+            if (is_border[j])
+                for (i64 i = 0; i < ns_schur; ++i) {
+                    const i32 v = schur->idx[i];
+                    if (v != j && seen[v] != j) Di.push_back(v);
+                }
+            Dp[j + 1] = (i64) Di.size();
+        }
+        Cp.swap(Dp); Ci.swap(Di);
+    } else if (order == CS3_ORDER_NATURAL) {
         std::iota(S.q_amd.begin(), S.q_amd.end(), 0);
     } else if (order == CS3_ORDER_AMD) {
         amd_order(n, Cp, Ci, S.q_amd);
@@ -412,6 +478,8 @@ void analyze(int kind, int order, i64 n, const i32 *Ap, const i32 *Ai,
             if (p < 0) continue;
             if (tallest[p] < 0 || height[j] >= height[tallest[p]]) tallest[p] = (i32) j;
         }
+        // (the Schur variables are a chain at the top of the tree and stay last and in order: the chain is never left)
+        for (i64 j = n1 + 1; j < n; ++j) tallest[j] = (i32) (j - 1);
         for (i64 j = n - 1; j >= 0; --j) {             // tallest child first in the list built backwards
             i32 p = S.parent_amd[j];
             if (p < 0 || tallest[p] != j) continue;
@@ -453,6 +521,7 @@ void analyze(int kind, int order, i64 n, const i32 *Ap, const i32 *Ai,
     fsn_ptr.clear();
     for (i64 j = 0; j < n; ++j) {
         bool join = j > 0 && S.parent[j - 1] == j && S.colcount[j] == S.colcount[j - 1] - 1;
+        if (schur && j == n1) join = false;            // the last interior column never joins the Schur supernode
         if (!join) fsn_ptr.push_back((i32) j);
         fcol2sn[j] = (i32) fsn_ptr.size() - 1;
     }
@@ -538,6 +607,7 @@ void analyze(int kind, int order, i64 n, const i32 *Ap, const i32 *Ai,
             if (!alive[s] || fparent[s] < 0) continue;
             const i32 p = alive_of(fparent[s]);
             if (fsn_ptr[s + 1] != mc0[p]) continue;                // not the last child of (merged) p
+            if (schur && fsn_ptr[p] >= n1) continue;               // nothing merges into the Schur supernode
             const i64 wn = mw[s] + mw[p], rn = mw[s] + mr[p], nbs = mr[s] - mw[s];
             const double zn = mz[s] + mz[p] + (double) mw[s] * (double) (mr[p] - nbs);
             const double tn = (double) wn * (double) rn - 0.5 * (double) wn * (double) (wn - 1);
@@ -565,6 +635,11 @@ void analyze(int kind, int order, i64 n, const i32 *Ap, const i32 *Ai,
     const i32 ns = S.nsuper;
     for (i32 s = 0; s < ns; ++s)
         for (i32 j = S.sn_ptr[s]; j < S.sn_ptr[s + 1]; ++j) S.col2sn[j] = s;
+    if (schur) {
+        S.schur_sn = ns - 1;
+        if (S.sn_ptr[ns - 1] != n1) throw std::runtime_error("analyze: the Schur variables did not form one supernode");
+    }
+    auto is_schur = [&](i32 s) { return s == S.schur_sn; };
     S.sn_parent.assign(ns, -1);
     for (i32 s = 0; s < ns; ++s) {
         i32 last = S.sn_ptr[s + 1] - 1;
@@ -608,7 +683,7 @@ void analyze(int kind, int order, i64 n, const i32 *Ap, const i32 *Ai,
         // (single matrices: batches of 16 .. 64 Cholesky matrices of 5000 columns measured 1.02 .. 2.1 ms through the forest
         //  against 0.77 .. 1.12 level by level)
         S.sn_in_forest.assign(ns, 0);
-        if (sub_on && S.batch == 1) build_forest(S, forest_limits());
+        if (sub_on && S.batch == 1) build_forest(S, forest_limits());     // (never the Schur supernode: build_forest)
     }
     const bool has_forest = !S.sub_forest.empty();
     auto in_forest = [&](i32 s) { return S.sn_in_forest[s] != 0; };
@@ -632,7 +707,7 @@ void analyze(int kind, int order, i64 n, const i32 *Ap, const i32 *Ai,
     const bool interleave = S.batch >= il_min_batch;
     for (i32 s = 0; s < ns; ++s) {                   // interleaved region first: dense r x r buffers of the FC_IL fronts
         const i64 w = width(s), r = order_r(s);
-        if (in_forest(s) || front_class(r, w, S.batch >= 8, interleave) != FC_IL) continue;
+        if (in_forest(s) || is_schur(s) || front_class(r, w, S.batch >= 8, interleave) != FC_IL) continue;
         S.lpan_off[s] = voff;
         S.upan_off[s] = voff + w * r; S.u_sk[s] = 1; S.u_sj[s] = (i32) r;
         S.cb_off[s] = voff + w + w * r; S.cb_ld[s] = (i32) r;
@@ -651,7 +726,7 @@ void analyze(int kind, int order, i64 n, const i32 *Ap, const i32 *Ai,
         for (i32 s = 0; s < ns; ++s) nl = std::max(nl, lvl[s] + 1);
         std::vector<i64> big_w(nl, 0), small_n(nl, 0), small_w(nl, 0);
         for (i32 s = 0; s < ns && S.batch == 1; ++s) {
-            if (in_forest(s)) continue;
+            if (in_forest(s) || is_schur(s)) continue;
             const int c = front_class(order_r(s), width(s), false, false);
             if (c == FC_BIG) big_w[lvl[s]] = std::max(big_w[lvl[s]], width(s));
             else { ++small_n[lvl[s]]; small_w[lvl[s]] = std::max(small_w[lvl[s]], width(s)); }
@@ -659,11 +734,13 @@ void analyze(int kind, int order, i64 n, const i32 *Ap, const i32 *Ai,
         for (i32 s = 0; s < ns && S.batch == 1; ++s) {
             const i32 l = lvl[s];
             // (no more block launches than the chain has: the riders' pivots fit the blocks it runs anyway)
-            ride[s] = !in_forest(s) && big_w[l] > 0 && small_n[l] <= ride_max && (small_w[l] + 31) / 32 <= (big_w[l] + 31) / 32;
+            ride[s] = !in_forest(s) && !is_schur(s) && big_w[l] > 0 && small_n[l] <= ride_max && (small_w[l] + 31) / 32 <= (big_w[l] + 31) / 32;
         }
     }
+    auto dense_front = [&](i32 s) { return S.sn_class[s] == FC_BIG || S.sn_class[s] == FC_SCHUR; };    // one r x r buffer
     auto class_of = [&](i32 s) -> int {
         if (in_forest(s)) return (int) FC_SUB;
+        if (is_schur(s)) return (int) FC_SCHUR;          // a launch group of its own, the dense layout of a big front
         return ride[s] ? (int) FC_BIG : front_class(order_r(s), width(s), S.batch >= 8, interleave);
     };
     // (interleaved PANELS for the lane = row fronts of order 17..32, so that their sweeps run lane = matrix too, were built and
@@ -676,18 +753,18 @@ void analyze(int kind, int order, i64 n, const i32 *Ap, const i32 *Ai,
         S.rel_ptr[s + 1] = S.rel_ptr[s] + nb;
         S.max_front = std::max(S.max_front, r);
         S.max_width = std::max(S.max_width, w);
-        for (i64 k = 0; k < w; ++k) {
+        for (i64 k = 0; k < w && !is_schur(s); ++k) {     // (eliminated columns only)
             double m = (double) (r - k - 1);
             S.flops += (kind == CS3_LU) ? (m + 2.0 * m * m) : (m + m * (m + 1.0) + 1.0);
         }
-        if (S.sn_class[s] == FC_BIG || S.sn_class[s] == FC_IL) continue;
+        if (dense_front(s) || S.sn_class[s] == FC_IL) continue;
         S.lpan_off[s] = voff; voff += r * w;
         // U panel w x nb, pivot rows contiguous: a wave whose lanes are rows stores and reads it coalesced
         if (kind == CS3_LU) { S.upan_off[s] = voff; voff += nb * w; S.u_sk[s] = 1; S.u_sj[s] = (i32) w; }
     }
     S.big_begin = voff;
     for (i32 s = 0; s < ns; ++s) {                   // dense buffers of the big fronts
-        if (S.sn_class[s] != FC_BIG) continue;
+        if (!dense_front(s)) continue;
         const i64 w = width(s), r = order_r(s);
         S.lpan_off[s] = voff;
         S.upan_off[s] = voff + w * r; S.u_sk[s] = 1; S.u_sj[s] = (i32) r;
@@ -697,7 +774,7 @@ void analyze(int kind, int order, i64 n, const i32 *Ap, const i32 *Ai,
     S.vals_size = voff;
     i64 cboff = voff;
     for (i32 s = 0; s < ns; ++s) {                   // compact contribution blocks
-        if (S.sn_class[s] == FC_BIG || S.sn_class[s] == FC_IL) continue;
+        if (dense_front(s) || S.sn_class[s] == FC_IL) continue;
         const i64 nb = order_r(s) - width(s);
         S.cb_ld[s] = (i32) nb;
         if (block_stays_in_lds(s)) { S.cb_off[s] = -1; continue; }
@@ -744,7 +821,7 @@ void analyze(int kind, int order, i64 n, const i32 *Ap, const i32 *Ai,
     // (leading dimension r | 1), absolute pool offset inside the r x r buffer for big ones
     auto target_of = [&](i32 s, i64 ti, i64 tj) -> i32 {
         const i64 r = order_r(s);
-        if (S.sn_class[s] == FC_BIG) return (i32) (S.lpan_off[s] + ti + tj * r);
+        if (dense_front(s)) return (i32) (S.lpan_off[s] + ti + tj * r);
         if (S.sn_class[s] == FC_IL) return (i32) (ti + tj * r);          // front-local; the kernel adds the buffer's offset
         return (i32) (ti + tj * (r | 1));
     };
@@ -1077,7 +1154,7 @@ void analyze(int kind, int order, i64 n, const i32 *Ap, const i32 *Ai,
     tick("10b. sweep lists and schedules");
     // ---- 11. the factors in CSC form are built when somebody asks for them (build_csc_factors): only their sizes here
     S.nnz_l = 0;
-    for (i64 j = 0; j < n; ++j) S.nnz_l += S.colcount[j];
+    for (i64 j = 0; j < n1; ++j) S.nnz_l += S.colcount[j];      // (a Schur handle: the eliminated columns, borders included)
     S.nnz_u = (kind == CS3_LU) ? S.nnz_l : 0;     // (the pattern is symmetric: row k of U mirrors column k of L)
     S.Lp.clear(); S.Li.clear(); S.Up.clear(); S.Ui.clear(); S.Lmap.clear(); S.Umap.clear();
     S.t_symbolic = seconds_since(t0);

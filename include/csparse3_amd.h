@@ -329,6 +329,63 @@ int cs3_updates_solve_dev(cs3_handle h, cs3_updates u, const double *cx_dev, con
 int cs3_updates_solve(cs3_handle h, cs3_updates u, const double *cx, const double *b,
                       double sing_tol, double *X, double *rpiv);
 
+/* ---- Schur complements: factor the interior, return the dense border -----
+ * A partial factorisation, as cuDSS, PARDISO, MUMPS and SuperLU_DIST offer it: the caller names ns variables that are NOT
+ * eliminated (boundary buses of a network equivalent, the constraint rows of a saddle-point system [[H, G'], [G, 0]], the
+ * interface of a subdomain).  With the matrix split as [[A11, A12], [A21, A22]], the Schur variables last, a
+ * factorisation returns the dense Schur complement  S = A22 - A21 A11^-1 A12,  and two half-solves carry right-hand sides
+ * onto the border and solutions back.  The Schur variables are never pivots, so a zero diagonal there is no obstacle.
+ *
+ * One design decision: where the factors of the Schur front would go, the handle stores the IDENTITY.  After a
+ * factorisation it holds the factors [L11 0; L21 I] [U11 U12; 0 I] (Cholesky: [L11 0; L21 I] and its transpose) of A
+ * with A22 replaced by A22 - S + I, and S sits in a buffer the handle owns.  The unchanged forward sweep then leaves
+ * b2 - A21 A11^-1 b1 in the Schur rows, the unchanged backward sweep entered with x2 there returns
+ * x1 = U11^-1 (y1 - U12 x2), and no sweep kernel knows about Schur sets.
+ *
+ * cs3_analyze_schur: cs3_analyze with a Schur set schur_idx[ns] (indices of A).  Checks, in this order: those of
+ *   cs3_analyze; then a null schur_idx, ns < 1 or ns >= n, an index outside [0, n), a repeated index (the message names
+ *   it): CS3_ERR_ARG.  `order` applies to the INTERIOR, the n1 = n - ns other variables: CS3_ORDER_AMD orders the
+ *   symmetrised pattern of A11 alone (Schur rows and columns removed, as MUMPS does; q_amd[0 .. n1) is
+ *   interior[cs3_amd(A11)] bit for bit), CS3_ORDER_NATURAL takes the interior ascending, CS3_ORDER_GIVEN takes
+ *   q_given[n1], a permutation of the interior in A's indices.  The Schur variables follow in the caller's order: the
+ *   last ns entries of q are schur_idx, they form the last supernode [n1, n), analysed as if A22 were dense, and no
+ *   interior column joins it.  cs3_info.nnz_l, nnz_u and flops_factor count the eliminated columns only (the borders L21
+ *   and U12 included, the Schur block not); max_front may be ns.  ns is bounded by the factor pool (ns^2 doubles inside
+ *   2^30 per matrix).
+ * cs3_schur_info: ns and the list.  Either pointer may be NULL.  On a handle without a Schur set: CS3_ERR_STATE.
+ * cs3_schur_get_dev: S_dev [batch][ns, ns] row-major, S[i, j] belongs to (schur_idx[i], schur_idx[j]); an asynchronous
+ *   copy of the S of the last factorisation on `stream`.  Cholesky: the full symmetric matrix, S == S' bit for bit.
+ * cs3_schur_get: the same into host memory (synchronises).
+ * cs3_schur_fwd_dev: X [batch][n, k] row-major in A's rows, as for cs3_solve.  On return row schur_idx[i] holds the
+ *   condensed right-hand side (b2 - A21 A11^-1 b1)_i; the interior rows hold the half-solved interior, opaque, to be
+ *   handed back unchanged.
+ * cs3_schur_bwd_dev: on entry the Schur rows hold x2, the caller's solution of S x2 = g, the interior rows are as fwd
+ *   left them; on return X solves A x = b.  After the first call with a given k, fwd and bwd neither allocate nor
+ *   synchronise.  cs3_schur_fwd / cs3_schur_bwd: the host forms, the same kernels and bits.
+ * All of them before a successful factorisation: CS3_ERR_STATE.
+ *
+ * On a Schur handle these work as on any other: cs3_factor(_dev), cs3_factor_status (fail_col can only be an interior
+ * column), cs3_get_info, cs3_get_ordering, cs3_get_supernodes, cs3_set_pivot_perturbation / cs3_get_perturbed (interior
+ * pivots), cs3_residual / matvec(_t)_dev, the cs3_debug_* calls, cs3_free -- and cs3_slogdet(_dev), which reads the pivots
+ * and therefore returns sign and log|det| of A11 (log|det A| = log|det A11| + log|det S|).
+ * These return CS3_ERR_ARG with a message that says why -- they would silently answer for A22 - S + I in place of A22:
+ * cs3_solve*, cs3_solve_t*, the one-sided sweeps (cs3_lsolve, cs3_usolve, cs3_ltsolve, cs3_utsolve and their _dev forms),
+ * cs3_factor_solve_dev, cs3_factor_solve_bx_dev, cs3_refine*, cs3_condest*, cs3_updates_plan, cs3_get_factors, cs3_export_factor_dev,
+ * cs3_import_factor_dev.
+ *
+ * Out of scope: matched handles (a row matching breaks the symmetric partition into interior and border); transposed
+ * half-solves; a dense solver for S (rocSOLVER or torch have one); a Schur set with ns = n; sharding one matrix over
+ * several GPUs on top of this; a sparse S. */
+int cs3_analyze_schur(int64_t kind, int64_t order, int64_t n, const int32_t *Ap, const int32_t *Ai,
+                      const int32_t *q_given, int64_t batch, int64_t ns, const int32_t *schur_idx, cs3_handle *out);
+int cs3_schur_info(cs3_handle h, int64_t *ns, int32_t *schur_idx);
+int cs3_schur_get_dev(cs3_handle h, double *S_dev, void *stream);
+int cs3_schur_get(cs3_handle h, double *S);
+int cs3_schur_fwd_dev(cs3_handle h, double *X_dev, int64_t k, void *stream);
+int cs3_schur_bwd_dev(cs3_handle h, double *X_dev, int64_t k, void *stream);
+int cs3_schur_fwd(cs3_handle h, double *X, int64_t k);
+int cs3_schur_bwd(cs3_handle h, double *X, int64_t k);
+
 /* ---- factors back to the host in CSparse's CSC form ---------------------
  * L: diagonal FIRST in each column (unit for LU); U: diagonal LAST; row
  * indices sorted otherwise.  Sizes from cs3_info.nnz_l / nnz_u.  NumPy-style
