@@ -2641,6 +2641,257 @@ k_bwd_big_step(const SolveDesc *__restrict__ sd, int first, int chunk_from_right
         v[row] -= ((part[0][tid] + part[1][tid]) + part[2][tid]) + part[3][tid];
 }
 
+// Four blocks of 64 per launch (BIG_CW4 = 256 columns) for the latency-bound sweeps of fronts wider than BIG_CW: a
+// dependent launch costs 10-13 us, a further block solve and coupling inside a launch about 1.5 us.  Eight waves.
+// Every workgroup still solves the whole chunk on its own; stage s = 0..3 is block s (forward) or block 3 - s (backward).
+//   waves 0-3  the triangle of stage 0..3 (BlockTriangle, as above)
+//   waves 4-6  the tile that couples stage s + 1 with stage s -- the only couplings on the dependent chain
+//   wave 7     stage 2 with stage 0, then (same registers) stage 3 with stage 1
+//   wave 0     after its solve: stage 3 with stage 0
+// Ten 64 x 64 operands and a slice of BIG_SR4 = 32 rows x 256 are 768 doubles per lane position; the CU's register file
+// holds 1024, and eight waves get 128 each before addresses and temporaries (with 64-row slices two instances spilled).
+// So the two tiles that are due last are loaded into registers that a finished stage has freed, each requested two
+// stages (a coupling and a block solve) before the phase that consumes it; everything else -- triangles, chain tiles,
+// right-hand sides, the slice, the slice rows' old values -- is requested before the first barrier.  No wave holds two
+// 64 x 64 operands at once.  Every wave passes the same seven barriers.
+//   phase:  solve 0 | cpl 1, far 2<-0 | solve 1 | cpl 2, far 3<-1, far 3<-0 | solve 2 | cpl 3 | solve 3
+// rhs(i, p): entry i of the front vector before this launch (0 where !p).  On return y[0 .. 256) holds the chunk's
+// solution, zeros past the chunk's width (0 x stale LDS is not 0).
+constexpr int BIG_CW4 = 4 * SOLVE_BW;
+constexpr int BIG_SR4 = 32;                     // rows of a workgroup's slice (16 threads per row, 16 columns each)
+
+// 64 loads in flight with a 64-bit address each are 128 registers of addresses beside the 128 of data: here a load is a
+// wave-uniform base (scalar registers) plus one 32-bit byte offset that all 64 loads of the lane share.
+__device__ __forceinline__ double load_at(const double *__restrict__ base, unsigned byte_off)
+{
+    return *reinterpret_cast<const double *>(reinterpret_cast<const char *>(base) + byte_off);
+}
+
+// T(row kb + 64 rb + lane, columns kb + 64 cb + [0, 64)) of the front at L, zero outside the chunk's bw columns.
+// TRI (rb == cb): strictly below the diagonal (FORWARD) or above it.
+template <int KIND, bool FORWARD, bool TRI = false>
+__device__ __forceinline__ void load_chunk_tile(double (&tm)[SOLVE_BW], const double *__restrict__ L, int r, int kb, int rb,
+                                                int cb, int bw)
+{
+    constexpr bool by_column = FORWARD ? (KIND != CS3_LU_T) : (KIND == CS3_LU);
+    const int lane = threadIdx.x & 63;
+    const int i = kb + SOLVE_BW * rb + lane, k0 = kb + SOLVE_BW * cb;
+    const bool row_in = SOLVE_BW * rb + lane < bw;
+    const int ncol = min(SOLVE_BW, max(0, bw - SOLVE_BW * cb));
+    if constexpr (by_column) {                              // entry (i, k) at i + k r: the column is the uniform part
+        const unsigned off = row_in ? 8u * (unsigned) i : 0u;
+#pragma unroll
+        for (int j = 0; j < SOLVE_BW; ++j) {
+            const double x = load_at(L + (j < ncol ? (long long) (k0 + j) * r : 0), off);
+            tm[j] = (row_in && j < ncol && (!TRI || (FORWARD ? lane > j : lane < j))) ? x : 0.0;
+        }
+    } else {                                                // entry (i, k) at k + i r: my row, 64 consecutive entries
+        const double *row = L + (row_in ? (long long) i * r + k0 : 0);
+#pragma unroll
+        for (int j = 0; j < SOLVE_BW; ++j) {
+            const double x = row[j < ncol ? j : 0];
+            tm[j] = (row_in && j < ncol && (!TRI || (FORWARD ? lane > j : lane < j))) ? x : 0.0;
+        }
+    }
+}
+
+// the triangle of block b of the chunk: what BlockTriangle::load leaves in t[] and rdg
+template <int KIND, bool FORWARD>
+__device__ __forceinline__ void load_chunk_triangle(BlockTriangle<KIND, FORWARD> &tri, const double *__restrict__ L, int r, int kb,
+                                                    int b, int bw)
+{
+    const int lane = threadIdx.x & 63;
+    tri.rdg = tri.DIAG ? recip_diag(L, kb + SOLVE_BW * b + lane, r, SOLVE_BW * b + lane < bw) : 1.0;
+    load_chunk_tile<KIND, FORWARD, true>(tri.t, L, r, kb, b, b, bw);
+    if (tri.DIAG) {
+#pragma unroll
+        for (int j = 0; j < SOLVE_BW; ++j) tri.t[j] *= tri.rdg;
+    }
+}
+
+__device__ __forceinline__ double chunk_tile_dot(const double (&tm)[SOLVE_BW], const double *__restrict__ yb, double acc)
+{
+#pragma unroll
+    for (int j = 0; j < SOLVE_BW; ++j) acc -= tm[j] * yb[j];
+    return acc;
+}
+
+template <int KIND, bool FORWARD, class Rhs>
+__device__ __forceinline__ void solve_chunk4(const double *__restrict__ L, int r, int kb, int bw, Rhs rhs, double *y,
+                                             double (*cpl)[SOLVE_BW], double (*far)[SOLVE_BW])
+{
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    auto blk = [](int s) { return FORWARD ? s : 3 - s; };
+    auto wid = [&](int b) { return min(SOLVE_BW, max(0, bw - SOLVE_BW * b)); };
+    auto row = [&](int b) { return kb + SOLVE_BW * b + lane; };
+    if (wv < 4) {
+        const int b = blk(wv), bwb = wid(b);
+        BlockTriangle<KIND, FORWARD> tri;
+        load_chunk_triangle(tri, L, r, kb, b, bw);
+        if (wv == 0) {
+            double vi = rhs(row(b), lane < bwb);
+            if (bwb > 0) vi = tri.solve(vi, bwb);
+            y[SOLVE_BW * b + lane] = (lane < bwb) ? vi : 0.0;
+            __syncthreads();
+            double tm[SOLVE_BW];                                            // stage 3 with stage 0, due in phase 3
+            load_chunk_tile<KIND, FORWARD>(tm, L, r, kb, blk(3), b, bw);
+            __syncthreads();
+            __syncthreads();
+            far[1][lane] = -chunk_tile_dot(tm, y + SOLVE_BW * b, 0.0);
+            __syncthreads();
+            __syncthreads();
+            __syncthreads();
+            __syncthreads();
+        } else {
+            for (int s = 0; s < 2 * wv; ++s) __syncthreads();
+            double vi = cpl[wv][lane];
+            if (bwb > 0) vi = tri.solve(vi, bwb);
+            y[SOLVE_BW * b + lane] = (lane < bwb) ? vi : 0.0;
+            for (int s = 2 * wv; s < 7; ++s) __syncthreads();
+        }
+    } else if (wv < 7) {                                                    // stage s with stage s - 1: phase 2 s - 1
+        const int s = wv - 3, b = blk(s), a = blk(s - 1);
+        double tm[SOLVE_BW];
+        load_chunk_tile<KIND, FORWARD>(tm, L, r, kb, b, a, bw);
+        double vi = rhs(row(b), lane < wid(b));
+        for (int t = 0; t < 2 * s - 1; ++t) __syncthreads();
+        if (s == 2) vi -= far[0][lane];
+        if (s == 3) vi = (vi - far[1][lane]) - far[2][lane];
+        cpl[s][lane] = chunk_tile_dot(tm, y + SOLVE_BW * a, vi);
+        for (int t = 2 * s - 1; t < 7; ++t) __syncthreads();
+    } else {
+        double tm[SOLVE_BW];
+        load_chunk_tile<KIND, FORWARD>(tm, L, r, kb, blk(2), blk(0), bw);
+        __syncthreads();
+        far[0][lane] = -chunk_tile_dot(tm, y + SOLVE_BW * blk(0), 0.0);
+        double tn[SOLVE_BW];                                                // stage 3 with stage 1, due in phase 3
+        load_chunk_tile<KIND, FORWARD>(tn, L, r, kb, blk(3), blk(1), bw);
+        __syncthreads();
+        __syncthreads();
+        far[2][lane] = -chunk_tile_dot(tn, y + SOLVE_BW * blk(1), 0.0);
+        __syncthreads();
+        __syncthreads();
+        __syncthreads();
+        __syncthreads();
+    }
+}
+
+template <int KIND>
+__global__ void __launch_bounds__(512)
+k_fwd_big_step4(const SolveDesc *__restrict__ sd, int first, int kb,
+                const double *__restrict__ pool_all, double *__restrict__ cv_all, double *__restrict__ X_all,
+                double *__restrict__ bigv_all, int nrhs, long long pool_stride, long long cv_stride,
+                long long x_stride, long long bv_size)
+{
+    constexpr int SC = BIG_CW4 / 16;                // chunk columns per thread in the slice update
+    __shared__ double y[BIG_CW4];
+    __shared__ double cpl[4][SOLVE_BW];             // stage s's right-hand side after its couplings (s = 1..3)
+    __shared__ double far[3][SOLVE_BW];             // T y of the couplings off the chain: 2<-0, 3<-0, 3<-1
+    __shared__ double part[16][BIG_SR4];
+    const SolveDesc d = sd[first + blockIdx.z];
+    const int r = d.r, w = d.w;
+    if (kb >= w) return;
+    const int bw = min(BIG_CW4, w - kb), ke = kb + bw;
+    const int nsl = (r - ke + BIG_SR4 - 1) / BIG_SR4;
+    if ((int) blockIdx.x > 0 && (int) blockIdx.x >= nsl) return;
+    const int b = blockIdx.y / nrhs, rhs = blockIdx.y % nrhs;
+    const double *L = pool_all + (long long) b * pool_stride + d.lpan;
+    double *v = bigv_all + ((long long) b * nrhs + rhs) * bv_size + d.bv;
+    const int tid = threadIdx.x;
+    // my slice of rows below the chunk: 16 threads per row, thread group cg takes columns [SC cg, SC cg + SC) of the chunk
+    const int cg = tid / BIG_SR4, row = ke + blockIdx.x * BIG_SR4 + tid % BIG_SR4;
+    double ls[SC];
+#pragma unroll
+    for (int j = 0; j < SC; ++j) {
+        const int jj = cg * SC + j;
+        if constexpr (KIND == CS3_LU_T) ls[j] = u_entry(L, pool_all + (long long) b * pool_stride + d.upan, d, kb + jj, row, row < r && jj < bw);
+        else ls[j] = (row < r && jj < bw) ? load_at(L + (jj < bw ? (long long) (kb + jj) * r : 0), row < r ? 8u * (unsigned) row : 0u) : 0.0;
+    }
+    const double old = load_if(v, row, cg == 0 && row < r);                 // (no other workgroup writes my slice's rows)
+    solve_chunk4<KIND, true>(L, r, kb, bw, [&](int i, bool p) { return load_if(v, i, p); }, y, cpl, far);
+    if (blockIdx.x == 0 && tid < bw)
+        X_all[(long long) b * x_stride + (long long) (d.c0 + kb + tid) * nrhs + rhs] = y[tid];
+    double acc = 0.0;
+#pragma unroll
+    for (int j = 0; j < SC; ++j) acc += ls[j] * y[cg * SC + j];             // ls[j] = 0 and y = 0 past the chunk
+    part[cg][tid % BIG_SR4] = acc;
+    __syncthreads();
+    if (cg == 0 && row < r) {
+        double sum = part[0][tid];
+#pragma unroll
+        for (int q = 1; q < 16; ++q) sum += part[q][tid];
+        const double nv = old - sum;
+        v[row] = nv;
+        if (ke >= w && row >= w && d.parent >= 0)           // last chunk: rows below the pivots are final
+            cv_all[(long long) b * cv_stride + (d.cv + row - w) * nrhs + rhs] = nv;
+    }
+}
+
+// A front without rows of ancestors (r == w) needs no k_bwd_big_init: its front vector is the pivot rows of X as they
+// stand (the init launch would copy them, X - 0.0).  xmode 1, the front's first launch: the front vector is read from
+// X, and the rows above the chunk are left in v for the launches that follow.  While other workgroups may still be
+// reading the chunk's rows of X, workgroup 0 must not overwrite them with the solution: it parks the solution in the
+// chunk's rows of v, which nobody reads in this launch, and the next launch (xmode 2) takes it home to X.
+template <int KIND>
+__global__ void __launch_bounds__(512)
+k_bwd_big_step4(const SolveDesc *__restrict__ sd, int first, int chunk_from_right, int xmode,
+                const double *__restrict__ pool_all, double *__restrict__ X_all, double *__restrict__ bigv_all,
+                int nrhs, long long pool_stride, long long x_stride, long long bv_size)
+{
+    constexpr int SC = BIG_CW4 / 16;
+    __shared__ double y[BIG_CW4];
+    __shared__ double cpl[4][SOLVE_BW];
+    __shared__ double far[3][SOLVE_BW];
+    __shared__ double part[16][BIG_SR4];
+    const SolveDesc d = sd[first + blockIdx.z];
+    const int r = d.r, w = d.w;
+    const int nchunk = (w + BIG_CW4 - 1) / BIG_CW4;
+    const int c = nchunk - 1 - chunk_from_right;
+    if (c < 0) return;
+    const int kb = c * BIG_CW4, bw = min(BIG_CW4, w - kb), ke = kb + bw;
+    const int nsl = (kb + BIG_SR4 - 1) / BIG_SR4;          // slices of rows above the chunk
+    if ((int) blockIdx.x > 0 && (int) blockIdx.x >= nsl) return;
+    const int b = blockIdx.y / nrhs, rhs = blockIdx.y % nrhs;
+    const double *L = pool_all + (long long) b * pool_stride + d.lpan;
+    double *v = bigv_all + ((long long) b * nrhs + rhs) * bv_size + d.bv;
+    double *X = X_all + (long long) b * x_stride;
+    const int tid = threadIdx.x;
+    const int cg = tid / BIG_SR4, row = blockIdx.x * BIG_SR4 + tid % BIG_SR4;
+    double us[SC];                                         // U(row, chunk columns [SC cg, SC cg + SC))
+#pragma unroll
+    for (int j = 0; j < SC; ++j) {
+        const int jj = cg * SC + j;
+        if constexpr (KIND == CS3_LU)
+            us[j] = (row < kb && jj < bw) ? load_at(L + (jj < bw ? (long long) (kb + jj) * r : 0), row < kb ? 8u * (unsigned) row : 0u) : 0.0;
+        else
+            us[j] = load_if(L, (long long) (kb + jj) + (long long) row * r, row < kb && jj < bw);
+    }
+    auto before = [&](int i, bool p) {                     // entry i of the front vector as this launch finds it
+        return (xmode == 1) ? load_if(X, (long long) (d.c0 + i) * nrhs + rhs, p) : load_if(v, i, p);
+    };
+    const double old = before(row, cg == 0 && row < kb);
+    // (xmode 2) the solution that the launch before parked: columns [kb + 256, w), at most 256 of them
+    const bool parked = xmode == 2 && blockIdx.x == 0 && tid < min(BIG_CW4, w - ke);
+    const double home = load_if(v, ke + tid, parked);
+    solve_chunk4<KIND, false>(L, r, kb, bw, before, y, cpl, far);
+    if (parked) X[(long long) (d.c0 + ke + tid) * nrhs + rhs] = home;
+    if (blockIdx.x == 0 && tid < bw) {
+        if (xmode == 1 && nsl > 0) v[kb + tid] = y[tid];
+        else X[(long long) (d.c0 + kb + tid) * nrhs + rhs] = y[tid];
+    }
+    double acc = 0.0;
+#pragma unroll
+    for (int j = 0; j < SC; ++j) acc += us[j] * y[cg * SC + j];
+    part[cg][tid % BIG_SR4] = acc;
+    __syncthreads();
+    if (cg == 0 && row < kb) {
+        double sum = part[0][tid];
+#pragma unroll
+        for (int q = 1; q < 16; ++q) sum += part[q][tid];
+        v[row] = old - sum;
+    }
+}
+
 // ============================================================ lane = matrix ==
 // Batches of 64 or more matrices that share a pattern: the fronts of order <= 32 (nine in ten of all
 // fronts, and most of the factor entries of a power-grid matrix) are stored MATRIX-INTERLEAVED -- entry e of the
@@ -3952,7 +4203,8 @@ hipError_t launch_factor_levels(const DeviceFactor &D, const SweepCall &call, co
 
 // Sweeps over a group of wide big fronts: a preparation launch, then one launch per chunk of columns.
 struct BigSweepPlan {
-    bool wide, multi;       // two 64-blocks per launch (latency-bound); BIG_KT right-hand sides per workgroup
+    bool wide, multi;       // several 64-blocks per launch (latency-bound); BIG_KT right-hand sides per workgroup
+    bool no_init;           // the backward sweep's first chunk launch reads X itself (k_bwd_big_step4, xmode)
     int cw, nchunk, slices;
     unsigned by, by_multi;
 };
@@ -3964,9 +4216,13 @@ static BigSweepPlan big_sweep_plan(const DeviceFactor &D, const LaunchGroup &g, 
     pl.wide = (long long) D.batch * nrhs < 8;
     pl.multi = nrhs >= BIG_KT;
     pl.by_multi = (unsigned) (D.batch * ((nrhs + BIG_KT - 1) / BIG_KT));
-    pl.cw = pl.wide ? BIG_CW : SOLVE_BW;
+    // latency-bound: two blocks per launch, four where that saves a launch
+    pl.cw = pl.wide ? (g.max_w > BIG_CW ? BIG_CW4 : BIG_CW) : SOLVE_BW;
+    // one front without rows of ancestors (the dense root): nothing for k_bwd_big_init to subtract
+    pl.no_init = pl.cw == BIG_CW4 && g.count == 1 && g.max_r == g.max_w;
     pl.nchunk = (g.max_w + pl.cw - 1) / pl.cw;
-    pl.slices = std::max(1, (g.max_r + 63) / 64);
+    const int sr = (pl.cw == BIG_CW4) ? BIG_SR4 : 64;       // rows of a workgroup's slice
+    pl.slices = std::max(1, (g.max_r + sr - 1) / sr);
     return pl;
 }
 
@@ -3985,7 +4241,10 @@ static hipError_t launch_fwd_big_chunk(const DeviceFactor &D, const SweepCall &c
 {
     const BigSweepPlan pl = big_sweep_plan(D, g, nrhs);
     const long long xs = D.n * (long long) nrhs, cvs = D.cv_size * (long long) nrhs;
-    if (pl.wide)
+    if (pl.cw == BIG_CW4)
+        hipLaunchKernelGGL((k_fwd_big_step4<KIND>), dim3(pl.slices, pl.by, g.count), dim3(512), 0, st, call.sd,
+                           g.first, c * pl.cw, D.pool_pm, D.cv, X, D.bigv, nrhs, D.pm_stride, cvs, xs, D.bv_size);
+    else if (pl.wide)
         hipLaunchKernelGGL((k_fwd_big_step<KIND, BIG_CW>), dim3(pl.slices, pl.by, g.count), dim3(256), 0, st, call.sd,
                            g.first, c * pl.cw, D.pool_pm, D.cv, X, D.bigv, nrhs, D.pm_stride, cvs, xs, D.bv_size);
     else if (pl.multi)
@@ -4015,7 +4274,10 @@ static hipError_t launch_bwd_big_chunk(const DeviceFactor &D, const SweepCall &c
 {
     const BigSweepPlan pl = big_sweep_plan(D, g, nrhs);
     const long long xs = D.n * (long long) nrhs;
-    if (pl.wide)
+    if (pl.cw == BIG_CW4)
+        hipLaunchKernelGGL((k_bwd_big_step4<KIND>), dim3(pl.slices, pl.by, g.count), dim3(512), 0, st, call.sd,
+                           g.first, c, (pl.no_init && c < 2) ? c + 1 : 0, D.pool_pm, X, D.bigv, nrhs, D.pm_stride, xs, D.bv_size);
+    else if (pl.wide)
         hipLaunchKernelGGL((k_bwd_big_step<KIND, BIG_CW>), dim3(pl.slices, pl.by, g.count), dim3(256), 0, st, call.sd,
                            g.first, c, D.pool_pm, X, D.bigv, nrhs, D.pm_stride, xs, D.bv_size);
     else if (pl.multi)
@@ -4185,7 +4447,8 @@ static hipError_t launch_solve_group(const DeviceFactor &D, const SweepCall &cal
         }
     } else if (g.cls == SK_BIG) {
         const BigSweepPlan pl = big_sweep_plan(D, g, nrhs);
-        hipError_t e = forward ? launch_fwd_big_pre(D, call, g, X, nrhs, st) : launch_bwd_big_pre<KIND>(D, call, g, X, nrhs, st);
+        hipError_t e = forward ? launch_fwd_big_pre(D, call, g, X, nrhs, st)
+                               : pl.no_init ? hipSuccess : launch_bwd_big_pre<KIND>(D, call, g, X, nrhs, st);
         for (int c = 0; e == hipSuccess && c < pl.nchunk; ++c)
             e = forward ? launch_fwd_big_chunk<KIND>(D, call, g, X, nrhs, c, st) : launch_bwd_big_chunk<KIND>(D, call, g, X, nrhs, c, st);
         return e;
