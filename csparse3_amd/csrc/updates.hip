@@ -73,7 +73,8 @@ k_upd_units(double *__restrict__ Z, long long n, int t, const int *__restrict__ 
 //   G (s x r): Z[col_a, zcol_k], gathered
 //   S = I + D G and the right-hand side D x0[C], sums over ascending a
 //   elimination with partial pivoting (largest |.|, ties to the lowest row), rpiv = min |pivot| / max(1, max |S|)
-// y_c is written zero-padded to 16; flag = an exactly zero pivot, or rpiv <= sing_tol when sing_tol > 0.
+// y_c is written zero-padded to 16; flag = an exactly zero pivot, or rpiv <= sing_tol when sing_tol > 0, or a NaN among
+// the pivot candidates (a NaN value of the case makes its whole row of S NaN, so step 0 meets it): rpiv = NaN then.
 __global__ void __launch_bounds__(64)
 k_upd_capacitance(const UpdCase *__restrict__ cases, const int *__restrict__ cp, const unsigned char *__restrict__ tpos,
                   const double *__restrict__ cx, const double *__restrict__ Z, int t, const double *__restrict__ x0,
@@ -126,13 +127,16 @@ k_upd_capacitance(const UpdCase *__restrict__ cases, const int *__restrict__ cp,
     double pmin = HUGE_VAL;
     bool zero = false;
     for (int k = 0; k < r; ++k) {
-        // pivot search over rows k .. r-1 of column k: every lane ends with the same (value, row)
+        // pivot search over rows k .. r-1 of column k: every lane ends with the same (value, row).  A NaN counts as larger
+        // than every number (plain comparisons would let a lane keep its own NaN and refuse its neighbour's, and the lanes
+        // would part ways); among numbers the order is the usual one
         double pv = (lane >= k && lane < r) ? fabs(Sm[lane * SLD + k]) : -1.0;
         int pi = lane;
         for (int off = 32; off > 0; off >>= 1) {
             const double ov = __shfl_xor(pv, off);
             const int oi = __shfl_xor(pi, off);
-            if (ov > pv || (ov == pv && oi < pi)) { pv = ov; pi = oi; }
+            const bool on = ov != ov, pn = pv != pv;
+            if (on ? (!pn || oi < pi) : (!pn && (ov > pv || (ov == pv && oi < pi)))) { pv = ov; pi = oi; }
         }
         if (!(pv > 0.0)) { pmin = pv; zero = true; break; }      // an exactly zero (or NaN) column: singular; uniform
         pmin = (pv < pmin) ? pv : pmin;

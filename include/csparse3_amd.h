@@ -292,7 +292,9 @@ int cs3_slogdet(cs3_handle h, double *sign, double *logabs);
  * an answer, not an error.  rpiv[c] = min_k |pivot_k| / max(1, max |S_c|) (1.0 for an empty case): the smallest pivot on
  * the scale of the identity that S_c perturbs -- normalising by max |S_c| alone would give 1.0 for EVERY case of rank 1,
  * singular or not.  A case with rpiv[c] <= sing_tol has its column of X filled with NaN (sing_tol <= 0 disables the test;
- * an exactly zero pivot always counts); the other cases of the call are unaffected.
+ * an exactly zero pivot always counts); the other cases of the call are unaffected.  A case with a NaN among its values
+ * has rpiv[c] = NaN and a NaN column whatever sing_tol is, and the other cases are unaffected too (infinite values:
+ * undefined).
  *
  * Two phases, as analysis and factorisation are: the case list of a screening run is fixed while values change.
  * cs3_updates_plan: host, pattern only, needs no GPU.  cp[ncases + 1] (cp[0] = 0), ci / cj[cp[ncases]] rows and columns
