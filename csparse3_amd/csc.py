@@ -121,7 +121,11 @@ class CscMat:
     __hash__ = None
 
     def __mul__(self, other):
-        """A * x for a vector or an [n, k] block, on the device (csc.py:372-415 semantics)."""
+        """A * B for a CscMat, on the device through the package's own kernel csc_multiply_ff (entries in its order, not
+        sorted; the reference's operator goes through SciPy's csc_matmat passes, csc.py:354-370 -- the dense results are
+        equal, which is what its test compares); A * x for a vector or an [n, k] block (csc.py:372-415 semantics)."""
+        if isinstance(other, CscMat):
+            return self.dot(other)
         if isinstance(other, np.ndarray):
             return _k.csc_mat_vec_ff(self.m, self.n, self.indptr, self.indices, self.data, other)
         if isinstance(other, (int, float)):
@@ -129,6 +133,19 @@ class CscMat:
             C.data *= other
             return C
         raise Exception("Type not supported")
+
+    def dot(self, o):
+        """A B on the device (csc.py:483-500 -> csc_multiply_ff), nzmax as that kernel returns it."""
+        C = CscMat()
+        C.m, C.n, C.indptr, C.indices, C.data, C.nzmax = _k.csc_multiply_ff(self.m, self.n, self.indptr, self.indices, self.data,
+                                                                            o.m, o.n, o.indptr, o.indices, o.data)
+        return C
+
+    def multiply_plan(self, o, transpose_self=False):
+        """The plan of A B (transpose_self: A' B) for these two patterns: SpgemmPlan.values / values_dev then refresh the
+        values of the product while the patterns stay (the matrix of a Gauss-Newton step, H' (W H))."""
+        return _k.SpgemmPlan(self.m, self.n, self.indptr, self.indices, o.m, o.n, o.indptr, o.indices,
+                             transpose_a=transpose_self)
 
     def to_csr(self):
         """CSR arrays (Bp, Bi, Bx) of this matrix, on the device (csc.py:466-478 -> csc_to_csr)."""

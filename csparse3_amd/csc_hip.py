@@ -38,6 +38,18 @@ class Cs3Info(C.Structure):
                 ("t_order_s", C.c_double), ("t_symbolic_s", C.c_double)]
 
 
+class SpgemmInfo(C.Structure):
+    """cs3_spgemm_info: sizes of a product plan and how much of it went through each path."""
+    _fields_ = [(name, C.c_int64) for name in ("m", "n", "nnz_a", "nnz_b", "nnz_c", "products", "cols_lds", "cols_global",
+                                               "entries_sliced", "entries_long", "padded_pairs", "long_list")]
+
+
+class SpgemmLimits(C.Structure):
+    """cs3_spgemm_limits_t: the constants that separate the paths of the product."""
+    _fields_ = [(name, C.c_int64) for name in ("lds_products", "lds_table_rows", "long_list", "slice_width",
+                                               "rank_chunk_lds", "rank_chunk_global")]
+
+
 class Cs3Error(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("cs3 error %d: %s" % (code, msg))
@@ -163,6 +175,14 @@ def lib():
         L.cs3_csc_add.argtypes = [I64, I64, _i32p, _i32p, _f64p, _i32p, _i32p, _f64p, C.c_double, C.c_double, _i32p, _i32p, _f64p]
         L.cs3_csc_sub_matrix.argtypes = [I64, _i32p, _i32p, _f64p, _i32p, I64, _i32p, I64, _i32p, _i32p, _f64p, I64]
         L.cs3_find_islands.argtypes = [I64, _i32p, _i32p, _i32p]
+        L.cs3_spgemm_limits.argtypes = [C.POINTER(SpgemmLimits)]
+        L.cs3_spgemm_plan_create.argtypes = [I64, I64, _i32p, _i32p, I64, I64, _i32p, _i32p, C.c_int, C.POINTER(vp)]
+        L.cs3_spgemm_plan_free.argtypes = [vp]
+        L.cs3_spgemm_plan_info.argtypes = [vp, C.POINTER(SpgemmInfo)]
+        L.cs3_spgemm_plan_pattern.argtypes = [vp, _i32p, _i32p]
+        L.cs3_spgemm_plan_pattern_dev.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+        L.cs3_spgemm_values_dev.argtypes = [vp, vp, vp, vp, vp]
+        L.cs3_spgemm_values.argtypes = [vp, _f64p, _f64p, _f64p]
         _lib = L
     return _lib
 
@@ -831,6 +851,98 @@ def csc_add_ff(Am, An, Ap, Ai, Ax, Bm, Bn, Bp, Bi, Bx, alpha, beta):
     _check(lib().cs3_csc_add(Am, An, _pi(Ap), _pi(Ai), _pf(Ax), _pi(Bp), _pi(Bi), _pf(Bx), alpha, beta, _pi(Cp), _pi(Ci), _pf(Cx)))
     nz = int(Cp[An])
     return Am, An, Cp, Ci[:nz].copy(), Cx[:nz].copy()
+
+
+def spgemm_limits():
+    """The constants that separate the paths of the sparse product (cs3_spgemm_limits); needs no GPU."""
+    out = SpgemmLimits()
+    _check(lib().cs3_spgemm_limits(C.byref(out)))
+    return out
+
+
+class SpgemmPlan:
+    """C = A B, or C = A' B with transpose_a, for fixed patterns: the pattern of C and the list of products behind every
+    entry are worked out once on the device, values() / values_dev() then refresh Cx as often as the values change
+    (cs3_spgemm_plan_create).  Pattern and values are those of the reference's csc_multiply_ff, bit for bit; with
+    transpose_a those of csc_transpose followed by csc_multiply_ff, read from A's own value array."""
+
+    def __init__(self, Am, An, Ap, Ai, Bm, Bn, Bp, Bi, transpose_a=False):
+        self._p = C.c_void_p()
+        Ap, Ai, Bp, Bi = _i32(Ap), _i32(Ai), _i32(Bp), _i32(Bi)
+        _check(lib().cs3_spgemm_plan_create(Am, An, _pi(Ap), _pi(Ai), Bm, Bn, _pi(Bp), _pi(Bi), 1 if transpose_a else 0,
+                                            C.byref(self._p)))
+        inf = self.info
+        self.m, self.n, self.nnz = int(inf.m), int(inf.n), int(inf.nnz_c)
+        self.nnz_a, self.nnz_b = int(inf.nnz_a), int(inf.nnz_b)
+
+    def close(self):
+        if self._p:
+            lib().cs3_spgemm_plan_free(self._p)
+            self._p = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    @property
+    def info(self):
+        out = SpgemmInfo()
+        _check(lib().cs3_spgemm_plan_info(self._p, C.byref(out)))
+        return out
+
+    def pattern(self):
+        """-> (Cp int32[n + 1], Ci int32[nnz]) on the host."""
+        Cp = np.empty(self.n + 1, dtype=np.int32)
+        Ci = np.empty(self.nnz, dtype=np.int32)
+        _check(lib().cs3_spgemm_plan_pattern(self._p, _pi(Cp), _pi(Ci)))
+        return Cp, Ci
+
+    def _pattern_dev(self):
+        cp, ci = C.c_void_p(), C.c_void_p()
+        _check(lib().cs3_spgemm_plan_pattern_dev(self._p, C.byref(cp), C.byref(ci)))
+        return cp.value or 0, ci.value or 0
+
+    @property
+    def cp_ptr(self):
+        """Device address of Cp (int32[n + 1]), valid until close()."""
+        return self._pattern_dev()[0]
+
+    @property
+    def ci_ptr(self):
+        """Device address of Ci (int32[nnz]), valid until close()."""
+        return self._pattern_dev()[1]
+
+    def values(self, Ax, Bx):
+        """-> Cx float64[nnz] from host value arrays in the patterns' entry order."""
+        Ax, Bx = _f64(Ax).reshape(-1), _f64(Bx).reshape(-1)
+        assert Ax.size >= self.nnz_a and Bx.size >= self.nnz_b
+        Cx = np.empty(self.nnz, dtype=np.float64)
+        _check(lib().cs3_spgemm_values(self._p, _pf(Ax), _pf(Bx), _pf(Cx)))
+        return Cx
+
+    def values_dev(self, ax_ptr, bx_ptr, cx_ptr, stream=0):
+        """Cx at cx_ptr from the values at ax_ptr, bx_ptr (device addresses), asynchronous on `stream`: at most two
+        launches, no allocation, no synchronisation.  The same bits as values()."""
+        _check(lib().cs3_spgemm_values_dev(self._p, C.c_void_p(ax_ptr), C.c_void_p(bx_ptr), C.c_void_p(cx_ptr),
+                                           C.c_void_p(stream)))
+
+
+def csc_multiply_ff(Am, An, Ap, Ai, Ax, Bm, Bn, Bp, Bi, Bx):
+    """C = A B -> (Cm, Cn, Cp, Ci, Cx, Cnzmax) as csc_multiply_ff (csc_numba.py:222-306): rows of a column in order of first
+    occurrence, sums in the reference's order, arrays trimmed to nnz.  One SpgemmPlan, used once."""
+    assert An == Bm                                      # csc_numba.py:240
+    with SpgemmPlan(Am, An, Ap, Ai, Bm, Bn, Bp, Bi) as plan:
+        Cp, Ci = plan.pattern()
+        Cx = plan.values(Ax, Bx)
+    return Am, Bn, Cp, Ci, Cx, int(Cp[Bn])
 
 
 def csc_sub_matrix(Am, Anz, Ap, Ai, Ax, rows, cols):

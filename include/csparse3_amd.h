@@ -515,6 +515,61 @@ int cs3_csc_sub_matrix(int64_t n, const int32_t *Ap, const int32_t *Ai, const do
  * islands by ascending start node and CscMat.islands (csc.py:515-521) sorts each -- both follow from the labels. */
 int cs3_find_islands(int64_t n, const int32_t *Ap, const int32_t *Ai, int32_t *label);
 
+/* ---- sparse products: C = A B and C = A' B with a reusable plan ----------
+ * csc_multiply_ff (csc_numba.py:222-306, Gustavson's product) on the device, bit for bit: for column j of C the products
+ * are enumerated as the reference's loops do (pb over B(:, j) in stored order, inside it pa over A(:, Bi[pb]) in stored
+ * order; position t); the rows of C(:, j) are the distinct rows in order of FIRST occurrence in t (not sorted), the value
+ * of a row is ((v1 + v2) + v3) + ... over its products v = Bx[pb] * Ax[pa] in ascending t, every product rounded on its
+ * own (no fused multiply-add) and the first one stored as it is ((-1) * 0 gives -0.0).  Explicit zeros, cancellations,
+ * unsorted rows and duplicate entries inside a column of A or B are kept and handled as those loops handle them.  The
+ * reference sizes its workspaces by the columns of C and so only runs when Am <= Bn; this one is defined for every shape
+ * by the same rule.
+ *
+ * Two phases, as analysis and factorisation are: a matrix product inside an iteration (the gain matrix H' W H of a
+ * Gauss-Newton step, Y = Cf' Yf Cf) has a fixed pattern and new values every step.
+ * cs3_spgemm_plan_create: host patterns.  C is Am x Bn; with transpose_a != 0 the plan computes C = T B, An x Bn, where
+ *   T = csc_transpose(A) as the reference's kernel defines it (columns of T = rows of A, entries in ascending column of A,
+ *   duplicates in stored order) -- the numeric phase reads A's OWN value array through recorded positions, no transposed
+ *   copy of the values is ever made.  Checked on the host, in this order, before anything is uploaded: null output,
+ *   negative dimensions, dimensions above INT_MAX, inner dimensions (An, or Am when transposing, against Bm), then for A and
+ *   for B: null indptr, indptr[0] != 0, a decreasing indptr, null indices with entries, an index outside [0, Am) resp.
+ *   [0, Bm); then a product that needs 2^31 - 1024 multiplications or more: CS3_ERR_ARG with a message.  After that the
+ *   device is required (CS3_ERR_HIP without one) and the symbolic product runs there; lists that would pad to 2^31 - 1024
+ *   pairs or more are CS3_ERR_ARG too.  CS3_SPGEMM_LONG in the environment, read by this call and by cs3_spgemm_limits,
+ *   moves the long-list threshold (2 ... 2^20; for measurements and tests).
+ * cs3_spgemm_plan_info: sizes, and how much went through each path (the tests use it to prove that every path ran).
+ * cs3_spgemm_limits: the constants that separate the paths.
+ * cs3_spgemm_plan_pattern: Cp[Bn + 1], Ci[nnz_c] to the host.  cs3_spgemm_plan_pattern_dev: borrowed device pointers,
+ *   valid until the plan is freed (either may be NULL).
+ * cs3_spgemm_values_dev: Cx_dev[nnz_c] from Ax_dev[nnz(A)], Bx_dev[nnz(B)], asynchronous on `stream`: at most two
+ *   launches, no allocation, no host synchronisation.  cs3_spgemm_values: the same from host arrays (synchronises). */
+typedef struct cs3_spgemm_s *cs3_spgemm;
+typedef struct cs3_spgemm_info {
+    int64_t m, n;                  /* shape of C */
+    int64_t nnz_a, nnz_b, nnz_c;
+    int64_t products;              /* multiplications = pairs over all lists */
+    int64_t cols_lds, cols_global; /* symbolic: columns of C through the LDS hash table / the global table (empty ones: neither) */
+    int64_t entries_sliced, entries_long;  /* numeric: entries of C added up by one lane of a slice / by a wave of their own */
+    int64_t padded_pairs;          /* pairs stored: slices padded to their longest list + the long lists */
+    int64_t long_list;             /* the threshold this plan was built with */
+} cs3_spgemm_info;
+typedef struct cs3_spgemm_limits_t {
+    int64_t lds_products;          /* most products of a column that takes the LDS path; one more goes to the global table */
+    int64_t lds_table_rows;        /* most distinct rows the LDS table holds (= lds_products: it is at most half full) */
+    int64_t long_list;             /* a list of this many pairs or more leaves its slice */
+    int64_t slice_width;           /* entries of C per slice */
+    int64_t rank_chunk_lds, rank_chunk_global;   /* products ranked together in the two symbolic paths */
+} cs3_spgemm_limits_t;
+int cs3_spgemm_limits(cs3_spgemm_limits_t *out);
+int cs3_spgemm_plan_create(int64_t Am, int64_t An, const int32_t *Ap, const int32_t *Ai,
+                           int64_t Bm, int64_t Bn, const int32_t *Bp, const int32_t *Bi, int transpose_a, cs3_spgemm *out);
+int cs3_spgemm_plan_free(cs3_spgemm plan);
+int cs3_spgemm_plan_info(cs3_spgemm plan, cs3_spgemm_info *info);
+int cs3_spgemm_plan_pattern(cs3_spgemm plan, int32_t *Cp, int32_t *Ci);
+int cs3_spgemm_plan_pattern_dev(cs3_spgemm plan, const int32_t **Cp_dev, const int32_t **Ci_dev);
+int cs3_spgemm_values_dev(cs3_spgemm plan, const double *Ax_dev, const double *Bx_dev, double *Cx_dev, void *stream);
+int cs3_spgemm_values(cs3_spgemm plan, const double *Ax, const double *Bx, double *Cx);
+
 #ifdef __cplusplus
 }
 #endif
