@@ -225,15 +225,15 @@ class CscMat:
         F = self.lu(tol, schur=idx) if kind == "lu" else self.chol(schur=idx)
         return F.schur()
 
-    def solve(self, b, tol=0.0, trans=False, match=False, perturb=0.0, max_refine=10):
+    def solve(self, b, tol=0.0, trans=False, match=False, perturb=0.0, max_refine=10, refine="stationary"):
         """x = A \\ b by LU (factorises if needed); trans: A' x = b on the same factors; match, perturb: as in lu().
         With perturb the solution is refined against A when pivots were replaced (Factorization.solve_refined; not
-        offered together with trans)."""
+        offered together with trans); refine="gmres": by GMRES on the held factors instead of the stationary rounds."""
         F = self.lu(tol, match=match, perturb=perturb)
         if F.perturbation == 0.0:
             return F.solve(b, trans=trans)
         assert not trans, "perturb refines A x = b only"
-        return F.solve_refined(self.data, b, max_refine)
+        return F.solve_refined(self.data, b, max_refine, refine)
 
     def solve_modified(self, b, deltas, tol=0.0, sing_tol=0.0):
         """x_c = (A + dA_c) \\ b for a list of sparse modifications, `deltas` = [(rows, cols, vals), ...] (triplets of dA_c;
@@ -275,11 +275,12 @@ def scipy_to_mat(scipy_mat):
     return CscMat(m, n, indptr=scipy_mat.indptr, indices=scipy_mat.indices, data=scipy_mat.data)
 
 
-def lusol(A, b, order=1, tol=0.0, match=False, perturb=0.0, max_refine=10):
+def lusol(A, b, order=1, tol=0.0, match=False, perturb=0.0, max_refine=10, refine="stationary"):
     """x = A \\ b (cs_lusol).  match: with the maximum-product matching and scaling in front (CscMat.lu).  perturb: small
-    pivots are replaced instead of rejected and the solution is refined, at most max_refine rounds (csc_lusol_f)."""
+    pivots are replaced instead of rejected and the solution is refined, at most max_refine rounds (csc_lusol_f);
+    refine="gmres": by GMRES on the held factors."""
     return _k.csc_lusol_f(order, A.m, A.n, A.indptr, A.indices, A.data, b, tol, match=match, perturb=perturb,
-                          max_refine=max_refine)
+                          max_refine=max_refine, refine=refine)
 
 
 def cholsol(A, b, order=1):

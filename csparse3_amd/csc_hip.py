@@ -50,6 +50,12 @@ class SpgemmLimits(C.Structure):
                                                "rank_chunk_lds", "rank_chunk_global")]
 
 
+class GmresLimits(C.Structure):
+    """cs3_gmres_limits_t: the largest restart, the rows per chunk of the fixed-order reductions, the right-hand sides
+    per tile of the kernels."""
+    _fields_ = [(name, C.c_int64) for name in ("max_restart", "chunk_rows", "rhs_tile")]
+
+
 class Cs3Error(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("cs3 error %d: %s" % (code, msg))
@@ -138,6 +144,11 @@ def lib():
         for f in (L.cs3_refine_dev, L.cs3_refine_t_dev):
             f.argtypes = [vp, vp, vp, vp, I64, I64, C.POINTER(C.c_double), vp]
         L.cs3_refine.argtypes = [vp, _f64p, _f64p, _f64p, I64, I64, C.POINTER(C.c_double)]
+        L.cs3_gmres_limits.argtypes = [C.POINTER(GmresLimits)]
+        L.cs3_gmres_dev.argtypes = [vp, vp, vp, vp, I64, I64, I64, C.c_double, I64, _i32p, _f64p, vp]
+        L.cs3_gmres.argtypes = [vp, _f64p, _f64p, _f64p, I64, I64, I64, C.c_double, I64, _i32p, _f64p]
+        L.cs3_debug_gmres_estimates.argtypes = [vp, _f64p, I64]
+        L.cs3_debug_gmres_kernel.argtypes = [vp, I64, I64, vp]
         L.cs3_set_pivot_perturbation.argtypes = [vp, C.c_double]
         L.cs3_get_perturbed.argtypes = [vp, C.POINTER(I64), vp]
         L.cs3_condest_dev.argtypes = [vp, vp, vp, vp, vp]
@@ -216,6 +227,13 @@ def _pf(a):
 
 def device_count():
     return int(lib().cs3_device_count())
+
+
+def gmres_limits():
+    """The constants of the GMRES refinement (cs3_gmres_limits); needs no GPU."""
+    out = GmresLimits()
+    _check(lib().cs3_gmres_limits(C.byref(out)))
+    return out
 
 
 def debug_live_device_buffers():
@@ -509,13 +527,49 @@ class Factorization:
         _check(lib().cs3_refine(self._h, _pf(Ax), _pf(b), _pf(x), x.size // per, steps, C.byref(out)))
         return x, float(out.value)
 
-    def solve_refined(self, Ax, b, max_refine=10):
-        """solve(b), then -- when the factorisation replaced pivots -- refinement one round at a time until the correction
-        no longer falls below half of the one before, at most max_refine rounds (a round whose correction GREW is dropped).
+    def gmres(self, Ax, b, x0=None, rtol=1e-12, restart=30, max_iters=100, trans=False):
+        """Restarted GMRES(restart) on A x = b (trans: A' x = b) with the values Ax, right-preconditioned with the held
+        factors: converges where refine() diverges (factors of an earlier iterate, a large perturbation).  b: [n], [n, k]
+        or [batch, n, k]; every column is a system of its own.  x0=None starts from solve(b, trans).
+        -> (x, iters int32[batch * k], relres float64[batch * k]: the true final ||b - A x|| / ||b|| of every system)."""
+        Ax, b = _f64(Ax), _f64(b)
+        x = self.solve(b, trans) if x0 is None else np.array(x0, dtype=np.float64, order="C", copy=True)
+        per = self.batch * self.n
+        assert Ax.size >= self.batch * self.nnz and x.size % per == 0 and b.size == x.size
+        k = x.size // per
+        iters = np.zeros(self.batch * k, dtype=np.int32)
+        relres = np.zeros(self.batch * k)
+        _check(lib().cs3_gmres(self._h, _pf(Ax), _pf(b), _pf(x), k, restart, max_iters, rtol, 1 if trans else 0,
+                               _pi(iters), _pf(relres)))
+        return x, iters, relres
+
+    def gmres_dev(self, ax_ptr, b_ptr, x_ptr, k=1, rtol=1e-12, restart=30, max_iters=100, stream=0, trans=False):
+        """gmres on device pointers: X at x_ptr holds x0 on entry and the solution on exit.  Host-driven: synchronises
+        `stream` after every iteration (one 4-byte read).  The same bits as gmres().  -> (iters, relres)."""
+        iters = np.zeros(self.batch * k, dtype=np.int32)
+        relres = np.zeros(self.batch * k)
+        _check(lib().cs3_gmres_dev(self._h, C.c_void_p(ax_ptr), C.c_void_p(b_ptr), C.c_void_p(x_ptr), k, restart, max_iters,
+                                   rtol, 1 if trans else 0, _pi(iters), _pf(relres), C.c_void_p(stream)))
+        return iters, relres
+
+    def debug_gmres_estimates(self, count):
+        """The recurrence's residual estimate every system of the last gmres call ended its last cycle with (diagnostic)."""
+        est = np.zeros(count)
+        _check(lib().cs3_debug_gmres_estimates(self._h, _pf(est), count))
+        return est
+
+    def solve_refined(self, Ax, b, max_refine=10, refine="stationary"):
+        """solve(b), then -- when the factorisation replaced pivots -- refinement.  refine="stationary": one round at a
+        time until the correction no longer falls below half of the one before, at most max_refine rounds (a round whose
+        correction GREW is dropped).  refine="gmres": gmres() from solve(b) with max_iters = max_refine, which also
+        converges when the perturbation is too large for the stationary rounds.
         Without replaced pivots this is solve(b), bit for bit."""
+        assert refine in ("stationary", "gmres")
         x = self.solve(b)
         if not self.perturbed().any():
             return x
+        if refine == "gmres":
+            return self.gmres(Ax, b, x0=x, max_iters=max_refine)[0]
         prev = np.inf
         for _ in range(max_refine):
             x_new, corr = self.refine(Ax, b, x, 1)
@@ -748,15 +802,16 @@ def perturbation_delta(perturb, Ax, match):
     return float(perturb or 0.0)
 
 
-def csc_lusol_f(order, m, n, Ap, Ai, Ax, b, tol=0.0, match=False, perturb=0.0, max_refine=10):
+def csc_lusol_f(order, m, n, Ap, Ai, Ax, b, tol=0.0, match=False, perturb=0.0, max_refine=10, refine="stationary"):
     """x = A \\ b by LU (cs_lusol).  match: rows permuted and scaled by the maximum-product transversal first (matrices
     without a strong diagonal).  perturb: pivots below delta are replaced instead of rejected (perturbation_delta), and
-    the solution is refined (Factorization.solve_refined, at most max_refine rounds)."""
+    the solution is refined (Factorization.solve_refined, at most max_refine rounds; refine="gmres": GMRES on the held
+    factors instead of the stationary rounds)."""
     with Factorization(m, n, Ap, Ai, CS3_LU, order, match_values=Ax if match else None) as F:
         delta = perturbation_delta(perturb, Ax, match)
         if delta == 0.0:
             return F.factor(Ax, tol).solve(b)
-        return F.set_perturbation(delta).factor(Ax, tol).solve_refined(Ax, b, max_refine)
+        return F.set_perturbation(delta).factor(Ax, tol).solve_refined(Ax, b, max_refine, refine)
 
 
 def csc_cholsol_f(order, m, n, Ap, Ai, Ax, b):

@@ -66,6 +66,7 @@ struct cs3_handle_s {
         double parity = 1.0, log_shift = 0.0; // det A = parity det B exp(log_shift): sign of rowperm, -(sum log dr + sum log dc)
     } match;
     std::vector<cs3_updates_s *> plans;       // the plans made for this handle (cs3_updates_plan)
+    KryWork kry_work{};                       // the work arrays of the last cs3_gmres* call (views of mem.kry)
     // Every HBM block of the handle, one group per feature that builds it; release_device drops them all at once.  A
     // new feature declares its DevBuf in a group here and allocates it in its ensure_*: nothing else has to know.
     struct Memory {
@@ -76,6 +77,14 @@ struct cs3_handle_s {
         // ensure_row_view / ensure_col_view (residuals, refinement): the analysed pattern by rows, the same by columns
         // (transposed products), the residual R [batch][n][k] (grows), the bits of max |dx|
         struct { DevBuf<int> rp, rj, rmap, cp, ci, cmap; DevBuf<double> res; DevBuf<unsigned long long> maxbits; } view;
+        // ensure_krylov (krylov.hip, cs3_gmres*): (restart + 1) basis vectors, w and the vector that goes through the
+        // solves, all [batch][n, k]; per system its state, R, the rotations, g, y; the partial sums of the reductions and
+        // their sums; the counters of active systems.  All grow with k and restart.
+        struct {
+            DevBuf<double> v, w, z, small, parts;
+            DevBuf<KrySys> sys;
+            DevBuf<unsigned> cnt;
+        } kry;
         // ensure_estimator (estimate.hip): X [batch][n] (stable address: the solves on it replay the cached graphs), the
         // sign vectors [2][batch][n], one state per matrix, the chunks of the partial reductions, the two "wants" counters
         struct { DevBuf<double> x; DevBuf<signed char> s; DevBuf<EstState> state; DevBuf<EstPart> parts; DevBuf<unsigned> cnt; } est;
@@ -177,6 +186,7 @@ void release_device(cs3_handle h)
     if (h->cap_stream) { (void) hipStreamDestroy(h->cap_stream); h->cap_stream = nullptr; }
     h->fj.destroy();
     h->mem = cs3_handle_s::Memory();
+    h->kry_work = KryWork();
     h->D = DeviceFactor();                  // (no pointer of it outlives its block; nrhs_cap = 0)
     h->on_device = false;
 }
@@ -1458,6 +1468,176 @@ int cs3_refine(cs3_handle h, const double *Ax, const double *B, double *X, int64
     }
     if ((rc = refine(h, H.ax.get(), b.get(), x.get(), k, steps, last_correction, nullptr, false, "cs3_refine"))) return rc;
     if (x_count) CS3_HIP(hipMemcpy(X, x.get(), x_count * sizeof(double), hipMemcpyDeviceToHost));
+    return CS3_OK;
+}
+
+// ---- GMRES refinement on the held factors (krylov.hip) ----------------------------------------------------------------
+// Work memory of one call, sized by k and by the restart of THIS call (not by KRY_MAX_RESTART).
+static int ensure_krylov(cs3_handle h, long long k, int restart, KryWork &K)
+{
+    auto &M = h->mem.kry;
+    const long long n = h->S.n, batch = h->batch, nsys = batch * k, total = batch * n * k, chunks = kry_chunks(n);
+    const size_t need_v = (size_t) (total * (restart + 1)), need_w = (size_t) total;
+    // per system: R [restart][restart], cs, sn, y [restart], g [restart + 1], the summed dots [2][restart]
+    const size_t per_sys = (size_t) restart * restart + 5 * (size_t) restart + 1;
+    const size_t need_small = (size_t) nsys * per_sys, need_parts = (size_t) (nsys * chunks) * (2 * (size_t) restart + 2);
+    if (need_v > M.v.count() || need_w > M.w.count() || need_small > M.small.count() || need_parts > M.parts.count() ||
+        (size_t) nsys > M.sys.count() || !M.cnt.get()) {
+        CS3_HIP(hipDeviceSynchronize());              // (the old blocks may still be in use)
+        h->dbg_syncs += 1;
+        CS3_HIP(M.v.reserve(need_v));
+        CS3_HIP(M.w.reserve(need_w));
+        CS3_HIP(M.z.reserve(need_w));
+        CS3_HIP(M.small.reserve(need_small));
+        CS3_HIP(M.parts.reserve(need_parts));
+        CS3_HIP(M.sys.reserve((size_t) nsys));
+        CS3_HIP(M.cnt.reserve(KRY_MAX_RESTART + 2));
+    }
+    K.V = M.v.get(); K.W = M.w.get(); K.Z = M.z.get(); K.sys = M.sys.get(); K.cnt = M.cnt.get();
+    double *p = M.small.get();
+    K.R = p; p += (size_t) nsys * restart * restart;
+    K.cs = p; p += (size_t) nsys * restart;
+    K.sn = p; p += (size_t) nsys * restart;
+    K.y = p; p += (size_t) nsys * restart;
+    K.g = p; p += (size_t) nsys * (restart + 1);
+    K.hsum = p;
+    K.parts = M.parts.get();
+    K.nparts = K.parts + (size_t) (nsys * chunks) * 2 * restart;
+    K.n = n; K.k = k; K.batch = batch; K.chunks = chunks; K.restart = restart;
+    h->kry_work = K;
+    return CS3_OK;
+}
+
+static int gmres_check(const char *who, cs3_handle h, const double *Ax, const double *B, const double *X, int64_t k,
+                       int64_t restart, int64_t max_iters, double rtol)
+{
+    int rc = guard(h); if (rc) return rc;
+    if ((rc = refuse_schur(h, who))) return rc;
+    if (!Ax || !B || !X || k < 1 || k > INT_MAX || restart < 1 || restart > KRY_MAX_RESTART || max_iters < 0 || max_iters > INT_MAX ||
+        !(rtol >= 0.0) || !std::isfinite(rtol)) {
+        set_error(std::string(who) + ": bad argument");
+        return CS3_ERR_ARG;
+    }
+    if (!h->factored) { set_error(std::string(who) + ": GMRES needs a factorisation"); return CS3_ERR_STATE; }
+    return CS3_OK;
+}
+
+// One 4-byte "systems still active" word, read after every iteration: the one host synchronisation of the method.
+static int read_active(cs3_handle h, const unsigned *cnt_dev, unsigned *out, hipStream_t st)
+{
+    CS3_HIP(hipMemcpyAsync(out, cnt_dev, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    CS3_HIP(hipStreamSynchronize(st));
+    h->dbg_syncs += 1;
+    return CS3_OK;
+}
+
+static int gmres_run(const char *who, cs3_handle h, const double *Ax_dev, const double *B_dev, double *X_dev, int64_t k,
+                     int64_t restart, int64_t max_iters, double rtol, bool trans, int32_t *iters, double *relres, hipStream_t st)
+{
+    int rc = gmres_check(who, h, Ax_dev, B_dev, X_dev, k, restart, max_iters, rtol);
+    if (rc) return rc;
+    const long long nsys = h->batch * k;
+    if (h->S.n == 0 || nsys == 0) {
+        for (long long s = 0; s < nsys; ++s) { if (iters) iters[s] = 0; if (relres) relres[s] = 0.0; }
+        return CS3_OK;
+    }
+    if ((rc = trans ? ensure_col_view(h, 0) : ensure_row_view(h, 0))) return rc;
+    KryWork K{};
+    if ((rc = ensure_krylov(h, k, (int) restart, K))) return rc;
+    const auto &V = h->mem.view;
+    const int *vp = (trans ? V.cp : V.rp).get(), *vj = (trans ? V.ci : V.rj).get(), *vmap = (trans ? V.cmap : V.rmap).get();
+    const long long n = h->S.n, nnz = h->S.nnzA, batch = h->batch;
+    const int m = (int) restart, cap = (int) max_iters;
+    // every system does at least one iteration in a cycle it enters, so max_iters + 1 cycles see every system finish
+    for (long long cycle = 0; cycle <= (long long) cap; ++cycle) {
+        CS3_HIP(launch_residual(vp, vj, vmap, Ax_dev, X_dev, B_dev, K.W, n, (int) k, nnz, batch, st));     // r = b - A x
+        CS3_HIP(launch_kry_start(K, B_dev, X_dev, cycle == 0, rtol, cap, st));
+        unsigned active = 0;
+        if ((rc = read_active(h, K.cnt, &active, st))) return rc;
+        if (!active) break;
+        int cols = 0;
+        while (active && cols < m) {
+            if ((rc = run_solve(h, K.Z, k, 0, st, trans))) return rc;                                     // z = M^-1 v_j
+            CS3_HIP(launch_residual(vp, vj, vmap, Ax_dev, K.Z, nullptr, K.W, n, (int) k, nnz, batch, st));  // w = A z
+            CS3_HIP(launch_kry_step(K, cols, rtol, cap, st));
+            if ((rc = read_active(h, K.cnt + 1 + cols, &active, st))) return rc;
+            ++cols;
+        }
+        CS3_HIP(launch_kry_combine(K, cols, st));                                                         // u = V y
+        if ((rc = run_solve(h, K.Z, k, 0, st, trans))) return rc;                                         // x += M^-1 u
+        CS3_HIP(launch_kry_axpy(K, X_dev, st));
+    }
+    if (iters || relres) {
+        std::vector<KrySys> sys((size_t) nsys);
+        CS3_HIP(hipMemcpyAsync(sys.data(), K.sys, sys.size() * sizeof(KrySys), hipMemcpyDeviceToHost, st));
+        CS3_HIP(hipStreamSynchronize(st));
+        for (long long s = 0; s < nsys; ++s) {
+            if (iters) iters[s] = sys[(size_t) s].iters;
+            if (relres) relres[s] = sys[(size_t) s].relres;
+        }
+    }
+    return CS3_OK;
+}
+
+int cs3_gmres_limits(cs3_gmres_limits_t *out)
+{
+    if (!out) { set_error("cs3_gmres_limits: null argument"); return CS3_ERR_ARG; }
+    out->max_restart = KRY_MAX_RESTART;
+    out->chunk_rows = KRY_CHUNK;
+    out->rhs_tile = KRY_RHS_TILE;
+    return CS3_OK;
+}
+
+int cs3_gmres_dev(cs3_handle h, const double *Ax_dev, const double *B_dev, double *X_dev, int64_t k, int64_t restart,
+                  int64_t max_iters, double rtol, int64_t trans, int32_t *iters, double *relres, void *stream)
+{
+    return gmres_run("cs3_gmres_dev", h, Ax_dev, B_dev, X_dev, k, restart, max_iters, rtol, trans != 0, iters, relres,
+                     (hipStream_t) stream);
+}
+
+// The host-array form: staged as cs3_refine stages, then cs3_gmres_dev's steps on the null stream -- the same bits.
+int cs3_gmres(cs3_handle h, const double *Ax, const double *B, double *X, int64_t k, int64_t restart, int64_t max_iters,
+              double rtol, int64_t trans, int32_t *iters, double *relres)
+{
+    int rc = gmres_check("cs3_gmres", h, Ax, B, X, k, restart, max_iters, rtol);
+    if (rc) return rc;
+    auto &H = h->mem.host;
+    const size_t ax_count = (size_t) (h->batch * h->S.nnzA), x_count = (size_t) (h->batch * h->S.n * k);
+    CS3_HIP(H.ax.reserve(ax_count));
+    if (ax_count) CS3_HIP(hipMemcpy(H.ax.get(), Ax, ax_count * sizeof(double), hipMemcpyHostToDevice));
+    DevBuf<double> b, x;
+    CS3_HIP(b.alloc(x_count));
+    CS3_HIP(x.alloc(x_count));
+    if (x_count) {
+        CS3_HIP(hipMemcpy(b.get(), B, x_count * sizeof(double), hipMemcpyHostToDevice));
+        CS3_HIP(hipMemcpy(x.get(), X, x_count * sizeof(double), hipMemcpyHostToDevice));
+    }
+    if ((rc = gmres_run("cs3_gmres", h, H.ax.get(), b.get(), x.get(), k, restart, max_iters, rtol, trans != 0, iters, relres, nullptr)))
+        return rc;
+    if (x_count) CS3_HIP(hipMemcpy(X, x.get(), x_count * sizeof(double), hipMemcpyDeviceToHost));
+    return CS3_OK;
+}
+
+// diagnostics (tools/bench_gmres.py): one vector kernel of iteration j on the work memory of the last cs3_gmres* call, as
+// that call shaped it (which = 0: the multi-dot, 1: the first update, 2: the second update with the norm)
+int cs3_debug_gmres_kernel(cs3_handle h, int64_t which, int64_t j, void *stream)
+{
+    int rc = guard(h); if (rc) return rc;
+    if (!h->kry_work.V) { set_error("cs3_debug_gmres_kernel: no cs3_gmres call on this handle yet"); return CS3_ERR_STATE; }
+    if (which < 0 || which > 2 || j < 0 || j >= h->kry_work.restart) { set_error("cs3_debug_gmres_kernel: bad argument"); return CS3_ERR_ARG; }
+    CS3_HIP(launch_kry_probe(h->kry_work, (int) which, (int) j, (hipStream_t) stream));
+    return CS3_OK;
+}
+
+// diagnostics: the residual estimate of the recurrence, |g_{j+1}| / ||b||, that every system of the last cs3_gmres* call
+// on this handle ended its last cycle with (0 for a system that never iterated); est [count], count = batch * k of that call
+int cs3_debug_gmres_estimates(cs3_handle h, double *est, int64_t count)
+{
+    int rc = guard(h); if (rc) return rc;
+    if (!est || count < 0 || (size_t) count > h->mem.kry.sys.count()) { set_error("cs3_debug_gmres_estimates: bad argument"); return CS3_ERR_ARG; }
+    std::vector<KrySys> sys((size_t) count);
+    if (count) CS3_HIP(hipMemcpy(sys.data(), h->mem.kry.sys.get(), sys.size() * sizeof(KrySys), hipMemcpyDeviceToHost));
+    for (int64_t s = 0; s < count; ++s) est[s] = sys[(size_t) s].est;
     return CS3_OK;
 }
 

@@ -295,4 +295,44 @@ hipError_t launch_upd_capacitance(const UpdTables &T, const double *cx, const do
 hipError_t launch_upd_apply(const UpdTables &T, const double *Z, int t, const double *x0, long long n, int c0, int nc, int rmax,
                             long long ldx, double *X, hipStream_t st);
 
+// krylov.hip: the vector layer of restarted GMRES on the held factors (cs3_gmres*), for batch * k systems in lock-step.
+// Every vector is [batch][n, k] row-major; system s = b * k + t is column t of matrix b.  Reductions over the rows run on
+// a FIXED partition (chunks of KRY_CHUNK rows) and the chunks are summed in index order by whoever consumes them: the
+// same bits on every run, whatever the grid.
+constexpr int KRY_MAX_RESTART = 32;
+constexpr long long KRY_CHUNK = 1024;
+constexpr int KRY_RHS_TILE = 64;
+inline long long kry_chunks(long long n) { return n > 0 ? (n + KRY_CHUNK - 1) / KRY_CHUNK : 1; }
+enum KryStatus : int { KRY_RUN = 0, KRY_DONE = 1, KRY_BAD = 2 };      // still iterating / finished / non-finite: frozen for good
+struct KrySys {                   // one system
+    double bnorm, relres;         // ||b||, the last TRUE ||b - A x|| / ||b|| (NaN: bad)
+    double est;                   // |g_{j+1}| / ||b|| of the recurrence when the system last froze or its cycle ended
+    double inv;                   // 1 / h_{j+1,j} for the next basis vector, 0: frozen
+    int status, active, part;     // KryStatus; advancing in this cycle; took part in this cycle (gets the cycle's update)
+    int iters, ncols;             // Krylov iterations so far; columns of this cycle's Hessenberg matrix
+};
+struct KryWork {                  // device arrays of one call (owned by the handle)
+    double *V, *W, *Z;            // (restart + 1) basis vectors, w, and the vector that goes through the solves
+    KrySys *sys;                  // [nsys]
+    double *R, *cs, *sn, *g, *y;  // per system: R [restart][restart] (column j at j * restart), rotations, g [restart + 1], y
+    double *parts;                // [2][nsys][restart][chunks] partial dots of the two Gram-Schmidt passes
+    double *hsum;                 // [2][nsys][restart] ... summed over the chunks (by the update that consumes them)
+    double *nparts;               // [2][nsys][chunks] partial squared norms (second half: of B, at the start)
+    unsigned *cnt;                // [restart + 2] systems still active: after the start, after iteration j at [1 + j]
+    long long n, k, batch, chunks;
+    int restart;
+};
+// r = W on entry.  The norms, the state of every system for the coming cycle (first: ||b|| too, zero right-hand sides
+// zero their column of X), v0 = r / ||r|| into V[0] and Z, cnt[0] = active systems.
+hipError_t launch_kry_start(const KryWork &K, const double *B, double *X, bool first, double rtol, int max_iters, hipStream_t st);
+// Iteration j on w = W: both Gram-Schmidt passes against V[0 .. j], the Hessenberg column with its rotations, the
+// decision per system, v_{j+1} into V[j + 1] and Z, cnt[1 + j] = systems still active.
+hipError_t launch_kry_step(const KryWork &K, int j, double rtol, int max_iters, hipStream_t st);
+// y from R y = g, u = sum over the cycle's `cols` columns of y_i v_i into Z (zero for a system that took no part)
+hipError_t launch_kry_combine(const KryWork &K, int cols, hipStream_t st);
+// diagnostics: which = 0 the multi-dot, 1 the first update, 2 the second update with the norm, of iteration j alone
+hipError_t launch_kry_probe(const KryWork &K, int which, int j, hipStream_t st);
+// X += Z for the systems that took part in the cycle; every other column keeps its bits
+hipError_t launch_kry_axpy(const KryWork &K, double *X, hipStream_t st);
+
 }  // namespace cs3

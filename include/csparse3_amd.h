@@ -250,6 +250,59 @@ int cs3_matvec_t_dev(cs3_handle h, const double *Ax_dev, const double *X_dev, do
 int cs3_refine_t_dev(cs3_handle h, const double *Ax_dev, const double *B_dev, double *X_dev, int64_t k, int64_t steps,
                      double *last_correction, void *stream);
 
+/* ---- GMRES refinement on the held factors --------------------------------
+ * cs3_refine_dev is the stationary iteration x += M^-1 (b - A x), M = the held factors: it converges only while the
+ * spectral radius of I - M^-1 A is below 1, and diverges beyond -- factors of an earlier Newton iterate against values
+ * that moved far, or a pivot perturbation (cs3_set_pivot_perturbation) with a large delta.  The Krylov half of what
+ * SuperLU_DIST, PARDISO and cuDSS pair with static pivoting: restarted GMRES(restart), right-preconditioned with the held
+ * factors.  When A M^-1 - I has rank r it ends in r iterations, whatever the size of the change.
+ *
+ * Systems: column t of matrix b of the batch is one system, batch * k independent systems advancing in lock-step; one
+ * solve and one product per iteration serve them all.  X, B [batch][n, k] row-major; X holds x0 on entry and the
+ * solution on exit.  iters, relres: HOST arrays [batch * k], either may be NULL: the Krylov iterations the system used,
+ * and its true final ||b - A x||_2 / ||b||_2.
+ *
+ * Per cycle: r = b - A x, v0 = r / ||r||, then w = A M^-1 v_j orthogonalised by classical Gram-Schmidt applied twice,
+ * Givens rotations per system, and at the end x += M^-1 (V y) -- one more solve.  trans != 0: A' and the transposed
+ * solve.  A system whose recurrence residual is <= rtol ||b||, or with a lucky breakdown (h_{j+1,j} == 0), or that has
+ * used max_iters iterations, is FROZEN: its next basis vectors are zero and it contributes nothing further.  A cycle
+ * ends when no system is active or after `restart` iterations.  Convergence is decided on the TRUE residual at the end
+ * of the cycle; a system still above rtol enters the next one.  The call ends when every system has converged or used
+ * max_iters iterations.  Not converging is not an error: CS3_OK, and relres tells.
+ *   ||b||_2 == 0: x = 0, iters = 0, relres = 0.  An x0 that already satisfies rtol: iters = 0, X untouched bit for bit.
+ *   A non-finite norm or Hessenberg entry freezes that system alone: relres = NaN, its column of X as the last completed
+ *   cycle left it; the other systems are unaffected.
+ * The reductions run in a fixed order without float atomics: the same bits on every run.
+ *
+ * HOST INVOLVEMENT: the call is host-driven.  After every iteration (and at the start of every cycle) it reads one
+ * 4-byte "systems still active" word, which synchronises `stream`, and it reads the two result arrays at the end.  It
+ * cannot be captured into a graph.
+ *
+ * Checks, in this order: null handle, a Schur handle, null Ax / B / X, k < 1, restart outside 1 .. max_restart,
+ * max_iters < 0, rtol negative or not finite: CS3_ERR_ARG; no factorisation: CS3_ERR_STATE (none of these needs a
+ * device).  LU and Cholesky handles; products over the stored entries as in cs3_residual_dev.  On a matched handle
+ * products and solves are with A, as in refinement.  Work memory ((restart + 1) basis vectors and two work vectors
+ * [batch][n, k], per system the Hessenberg factor, rotations, g and y, the partial sums) belongs to the handle, grows on
+ * demand with k and `restart`, and goes with cs3_free.
+ * cs3_gmres_limits: max_restart (32), the rows per chunk of the fixed-order reductions, the right-hand sides per tile of
+ *   the kernels; needs no device.
+ * cs3_gmres: the host-array form (the null stream): the same kernels in the same order, the same bits.
+ * Not offered: a capture-safe fixed-length form, block or deflated variants, CG for Cholesky handles, left
+ * preconditioning. */
+typedef struct { int64_t max_restart, chunk_rows, rhs_tile; } cs3_gmres_limits_t;
+int cs3_gmres_limits(cs3_gmres_limits_t *out);
+int cs3_gmres_dev(cs3_handle h, const double *Ax_dev, const double *B_dev, double *X_dev, int64_t k,
+                  int64_t restart, int64_t max_iters, double rtol, int64_t trans,
+                  int32_t *iters, double *relres, void *stream);
+int cs3_gmres(cs3_handle h, const double *Ax, const double *B, double *X, int64_t k,
+              int64_t restart, int64_t max_iters, double rtol, int64_t trans, int32_t *iters, double *relres);
+/* diagnostics: est [count] = the residual estimate of the recurrence, |g_{j+1}| / ||b||, that every system of the last
+ * cs3_gmres* call on this handle ended its last cycle with (count = batch * k of that call; synchronises the device) */
+int cs3_debug_gmres_estimates(cs3_handle h, double *est, int64_t count);
+/* diagnostics: one vector kernel of iteration j alone on the work memory of the last cs3_gmres* call on this handle
+ * (which = 0: the multi-dot, 1: the first update, 2: the second update with the norm), for timing */
+int cs3_debug_gmres_kernel(cs3_handle h, int64_t which, int64_t j, void *stream);
+
 /* ---- condition estimates and log-determinants from the held factors -----
  * Static diagonal pivots say nothing about how far a solution can be trusted; these are the cheap reliability signal
  * next to the factors (klu_condest, LAPACK xGECON, MATLAB condest).  Results are per matrix of the batch, [batch] each.

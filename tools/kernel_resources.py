@@ -1,11 +1,12 @@
 #!/usr/bin/env python3
-"""Register / spill / LDS report of every kernel in csparse3_amd/csrc/kernels.hip (hipcc -Rpass-analysis=kernel-resource-usage).
-    python tools/kernel_resources.py [filter]"""
+"""Register / spill / LDS report of every kernel in csparse3_amd/csrc/kernels.hip, or in another source file of that
+directory (hipcc -Rpass-analysis=kernel-resource-usage).
+    python tools/kernel_resources.py [filter [file.hip]]"""
 import os, re, subprocess, sys
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 src = os.path.join(root, "csparse3_amd", "csrc")
 cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "-mllvm", "-pragma-unroll-threshold=262144", "--offload-arch=gfx950",
-       "-Rpass-analysis=kernel-resource-usage", "-c", "kernels.hip", "-o", "/tmp/cs3_kres.o"]
+       "-Rpass-analysis=kernel-resource-usage", "-c", sys.argv[2] if len(sys.argv) > 2 else "kernels.hip", "-o", "/tmp/cs3_kres.o"]
 txt = subprocess.run(cmd, cwd=src, capture_output=True, text=True).stderr
 flt = sys.argv[1] if len(sys.argv) > 1 else ""
 for b in re.split(r"Function Name: ", txt)[1:]:
