@@ -197,7 +197,7 @@ double orc_norm(i64 n, const i32 *Ap, const double *Ax)
     for (i64 j = 0; j < n; j++) {
         double s = 0.0;
         for (i32 p = Ap[j]; p < Ap[j + 1]; p++) s += fabs(Ax[p]);
-        norm = MAX2(norm, s);
+        if (s > norm) norm = s;     /* max(norm, s) keeps norm unless s > norm: a NaN sum is passed over (csc_numba.py:738) */
     }
     return norm;
 }
