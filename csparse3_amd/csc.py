@@ -147,6 +147,13 @@ class CscMat:
         return _k.SpgemmPlan(self.m, self.n, self.indptr, self.indices, o.m, o.n, o.indptr, o.indices,
                              transpose_a=transpose_self)
 
+    def union_plan(self, others):
+        """The UnionPlan of this matrix (member 0) and `others` (members 1, 2, ...), square and of one order: their
+        value arrays then go to one batched handle on the union pattern (csparse3_amd.streams.UnionBatch)."""
+        mats = [self] + list(others)
+        assert all(a.m == self.n and a.n == self.n for a in mats), "square matrices of one order required"
+        return _k.UnionPlan(self.n, [(a.indptr, a.indices[:int(a.indptr[a.n])]) for a in mats])
+
     def to_csr(self):
         """CSR arrays (Bp, Bi, Bx) of this matrix, on the device (csc.py:466-478 -> csc_to_csr)."""
         nnz = int(self.indptr[self.n])

@@ -50,6 +50,16 @@ class SpgemmLimits(C.Structure):
                                                "rank_chunk_lds", "rank_chunk_global")]
 
 
+class UnionInfo(C.Structure):
+    """cs3_union_info: sizes of a union plan."""
+    _fields_ = [(name, C.c_int64) for name in ("n", "nmat", "nnz_union", "nnz_total", "distinct_patterns", "padded", "dup_slots")]
+
+
+class UnionLimits(C.Structure):
+    """cs3_union_limits_t: the constants that shape the launch of the embedding kernel."""
+    _fields_ = [(name, C.c_int64) for name in ("block", "grid_cap", "entries_per_lane")]
+
+
 class GmresLimits(C.Structure):
     """cs3_gmres_limits_t: the largest restart, the rows per chunk of the fixed-order reductions, the right-hand sides
     per tile of the kernels."""
@@ -194,6 +204,17 @@ def lib():
         L.cs3_spgemm_plan_pattern_dev.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
         L.cs3_spgemm_values_dev.argtypes = [vp, vp, vp, vp, vp]
         L.cs3_spgemm_values.argtypes = [vp, _f64p, _f64p, _f64p]
+        pp = C.POINTER(_i32p)
+        L.cs3_union_limits.argtypes = [C.POINTER(UnionLimits)]
+        L.cs3_union_plan_create.argtypes = [I64, I64, pp, pp, C.POINTER(vp)]
+        L.cs3_union_plan_free.argtypes = [vp]
+        L.cs3_union_plan_info.argtypes = [vp, C.POINTER(UnionInfo)]
+        L.cs3_union_plan_pattern.argtypes = [vp, _i32p, _i32p]
+        L.cs3_union_plan_offsets.argtypes = [vp, C.POINTER(I64)]
+        L.cs3_union_plan_slots.argtypes = [vp, I64, _i32p]
+        L.cs3_union_upload.argtypes = [vp]
+        L.cs3_union_values_dev.argtypes = [vp, vp, vp, vp]
+        L.cs3_union_values.argtypes = [vp, _f64p, _f64p]
         _lib = L
     return _lib
 
@@ -998,6 +1019,97 @@ def csc_multiply_ff(Am, An, Ap, Ai, Ax, Bm, Bn, Bp, Bi, Bx):
         Cp, Ci = plan.pattern()
         Cx = plan.values(Ax, Bx)
     return Am, Bn, Cp, Ci, Cx, int(Cp[Bn])
+
+
+def union_limits():
+    """The constants that shape the launch of the embedding kernel (cs3_union_limits); needs no GPU."""
+    out = UnionLimits()
+    _check(lib().cs3_union_limits(C.byref(out)))
+    return out
+
+
+class UnionPlan:
+    """Matrices of one order n whose patterns differ, for ONE batched handle: the union of the patterns (rows ascending)
+    and the place of every member entry in it are worked out once on the host (cs3_union_plan_create, no GPU needed);
+    values() / values_dev() then move the members' value arrays into the [nmat, nnz_union] layout that
+    Factorization(n, n, Up, Ui, batch=nmat) reads, as often as the values change.  patterns: a sequence of (Ap, Ai);
+    rows need not be sorted and may repeat (repeated entries are added up in storage order).  An entry a member does not
+    have is +0.0; an entry with one source is copied bit for bit."""
+
+    def __init__(self, n, patterns):
+        self._p = C.c_void_p()
+        pats = [(_i32(p[0]), _i32(p[1])) for p in patterns]            # (kept alive over the call)
+        nmat = len(pats)
+        aps = (_i32p * max(nmat, 1))(*[_pi(p[0]) for p in pats])
+        ais = (_i32p * max(nmat, 1))(*[_pi(p[1]) for p in pats])
+        _check(lib().cs3_union_plan_create(n, nmat, aps, ais, C.byref(self._p)))
+        inf = self.info
+        self.n, self.nmat, self.nnz = int(inf.n), int(inf.nmat), int(inf.nnz_union)
+        self.nnz_total = int(inf.nnz_total)
+
+    def close(self):
+        if self._p:
+            lib().cs3_union_plan_free(self._p)
+            self._p = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    @property
+    def info(self):
+        out = UnionInfo()
+        _check(lib().cs3_union_plan_info(self._p, C.byref(out)))
+        return out
+
+    def pattern(self):
+        """-> (Up int32[n + 1], Ui int32[nnz_union]) on the host."""
+        Up = np.empty(self.n + 1, dtype=np.int32)
+        Ui = np.empty(self.nnz, dtype=np.int32)
+        _check(lib().cs3_union_plan_pattern(self._p, _pi(Up), _pi(Ui)))
+        return Up, Ui
+
+    def offsets(self):
+        """-> int64[nmat + 1]: member b's values start at offsets()[b] of the concatenated value buffer."""
+        off = np.empty(self.nmat + 1, dtype=np.int64)
+        _check(lib().cs3_union_plan_offsets(self._p, off.ctypes.data_as(C.POINTER(I64))))
+        return off
+
+    def slots(self, b):
+        """-> int32[nnz_b]: the union entry every entry of member b lands on."""
+        off = self.offsets()
+        assert 0 <= b < self.nmat
+        slot = np.empty(int(off[b + 1] - off[b]), dtype=np.int32)
+        _check(lib().cs3_union_plan_slots(self._p, b, _pi(slot)))
+        return slot
+
+    def upload(self):
+        """Puts the tables on the device now (the first values call does it otherwise; do it before a graph capture)."""
+        _check(lib().cs3_union_upload(self._p))
+        return self
+
+    def values(self, Ax):
+        """Ax: the members' host value arrays, as a list or already concatenated.  -> float64[nmat, nnz_union]."""
+        if isinstance(Ax, (list, tuple)):
+            Ax = np.concatenate([_f64(a).reshape(-1) for a in Ax]) if len(Ax) else np.empty(0)
+        Ax = _f64(Ax).reshape(-1)
+        assert Ax.size >= self.nnz_total
+        out = np.empty((self.nmat, self.nnz), dtype=np.float64)
+        _check(lib().cs3_union_values(self._p, _pf(Ax), _pf(out)))
+        return out
+
+    def values_dev(self, cat_ptr, union_ptr, stream=0):
+        """[nmat, nnz_union] at union_ptr from the concatenated values at cat_ptr (device addresses), asynchronous on
+        `stream`: one launch, no allocation, no synchronisation.  The same bits as values()."""
+        _check(lib().cs3_union_values_dev(self._p, C.c_void_p(cat_ptr), C.c_void_p(union_ptr), C.c_void_p(stream)))
 
 
 def csc_sub_matrix(Am, Anz, Ap, Ai, Ax, rows, cols):

@@ -221,6 +221,28 @@ def spd_grid_pattern(n=5000, seed=5000, width=None, chord_frac=0.01):
     return _unique_edges(n, ei, ej)
 
 
+def chord_edges(n, ei, ej):
+    """Indices of the edges outside a spanning forest of the graph (walking the edges in order, the first one that joins
+    two components is a tree edge): removing any set of them disconnects nothing -- the branches a contingency case
+    may lack."""
+    root = np.arange(n)
+
+    def find(v):
+        while root[v] != v:
+            root[v] = root[root[v]]
+            v = root[v]
+        return v
+
+    chords = []
+    for k in range(len(ei)):
+        a, b = find(int(ei[k])), find(int(ej[k]))
+        if a == b:
+            chords.append(k)
+        else:
+            root[a] = b
+    return np.array(chords, dtype=np.int64)
+
+
 def spd_grid_matrix(n, ei, ej, seed, shift=1e-2, lower_only=False):
     """Config 5 values: weighted graph Laplacian + shift * I on a given pattern
     (same pattern, different values per matrix: contingency-style).

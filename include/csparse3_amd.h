@@ -623,6 +623,59 @@ int cs3_spgemm_plan_pattern_dev(cs3_spgemm plan, const int32_t **Cp_dev, const i
 int cs3_spgemm_values_dev(cs3_spgemm plan, const double *Ax_dev, const double *Bx_dev, double *Cx_dev, void *stream);
 int cs3_spgemm_values(cs3_spgemm plan, const double *Ax, const double *Bx, double *Cx);
 
+/* ---- union plans: matrices whose patterns differ, on ONE batched handle ----
+ * A family of matrices of one order whose patterns are all contained in a small common pattern (the contingency cases,
+ * switching states or topology scans of one network: the base case minus a few branches) can run as one batched handle on
+ * the UNION of the patterns: a matrix padded with explicit zeros to the union has the factors of the unpadded matrix
+ * embedded in the union's structure.  The plan computes the union and the place of every entry once; one kernel then moves
+ * the ragged per-matrix value arrays into the [nmat][nnz_union] layout that cs3_factor_solve_dev and every other call of
+ * a handle with batch = nmat reads, as often as the values change, without a host copy.
+ *
+ * cs3_union_plan_create: nmat >= 1 host patterns (Ap[b][n + 1], Ai[b][nnz_b]) of order n, as arrays of pointers; rows
+ *   inside a column need not be sorted and may repeat.  Host work only, O(entries of the distinct patterns + n) and a sort
+ *   per union column; no device is needed.  Checked in this order, each failure CS3_ERR_ARG with a message: null output,
+ *   null pointer arrays, nmat < 1, n outside [0, 2^30) (the range cs3_analyze takes), a null Ap[b]; then per member
+ *   Ap[b][0] != 0, a decreasing Ap[b], null Ai[b] with entries, a row outside [0, n); then a member, and then a union, of
+ *   2^31 - 1024 entries or more.
+ *   Union column j = the rows that occur in column j of any member, ASCENDING: independent of the order of the members.
+ *   Members whose (Ap, Ai) are equal element for element share one gather map (distinct_patterns counts the maps).
+ * cs3_union_plan_pattern: Up[n + 1], Ui[nnz_union] (either may be NULL).  cs3_union_plan_offsets: off[nmat + 1], prefix
+ *   sums of nnz_b: the ragged value buffer Ax_cat is the members' value arrays one after the other, member b at off[b].
+ * cs3_union_plan_slots: slot[nnz_b], the union entry that every entry of member b lands on.
+ * cs3_union_values_dev: Ax_union_dev[nmat][nnz_union] from Ax_cat_dev[off[nmat]], asynchronous on `stream`: ONE launch,
+ *   no memset, no atomics, no allocation, no host synchronisation -- it can be captured into a graph once the tables are
+ *   on the device (they are uploaded by the first call or by cs3_union_upload).  Every output entry is written:
+ *     no source in member b           +0.0
+ *     one source s                    the bit pattern of Ax_cat[off[b] + s] (-0.0, infinities, NaN payloads survive)
+ *     several, s1, s2, ... as stored  ((v1 + v2) + v3) + ..., plain double additions from v1 as stored
+ *   Ax_union_dev must be 8-byte aligned.
+ * cs3_union_values: the same from and to host arrays (synchronises).  Both return CS3_ERR_HIP without a device.
+ * cs3_union_limits: the constants that shape the launch. */
+typedef struct cs3_union_s *cs3_union;
+typedef struct cs3_union_info {
+    int64_t n, nmat;
+    int64_t nnz_union;
+    int64_t nnz_total;             /* entries of all members = length of the ragged value buffer */
+    int64_t distinct_patterns;     /* gather maps held */
+    int64_t padded;                /* nmat * nnz_union - output entries that have a source */
+    int64_t dup_slots;             /* output entries with more than one source, over all members */
+} cs3_union_info;
+typedef struct cs3_union_limits_t {
+    int64_t block;                 /* threads of a workgroup */
+    int64_t grid_cap;              /* most workgroups of a launch: beyond grid_cap * block * entries_per_lane entries a lane loops */
+    int64_t entries_per_lane;
+} cs3_union_limits_t;
+int cs3_union_limits(cs3_union_limits_t *out);
+int cs3_union_plan_create(int64_t n, int64_t nmat, const int32_t *const *Ap, const int32_t *const *Ai, cs3_union *out);
+int cs3_union_plan_free(cs3_union p);
+int cs3_union_plan_info(cs3_union p, cs3_union_info *info);
+int cs3_union_plan_pattern(cs3_union p, int32_t *Up, int32_t *Ui);
+int cs3_union_plan_offsets(cs3_union p, int64_t *off);
+int cs3_union_plan_slots(cs3_union p, int64_t b, int32_t *slot);
+int cs3_union_upload(cs3_union p);
+int cs3_union_values_dev(cs3_union p, const double *Ax_cat_dev, double *Ax_union_dev, void *stream);
+int cs3_union_values(cs3_union p, const double *Ax_cat, double *Ax_union);
+
 #ifdef __cplusplus
 }
 #endif
