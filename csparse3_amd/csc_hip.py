@@ -159,6 +159,7 @@ def lib():
         L.cs3_gmres.argtypes = [vp, _f64p, _f64p, _f64p, I64, I64, I64, C.c_double, I64, _i32p, _f64p]
         L.cs3_debug_gmres_estimates.argtypes = [vp, _f64p, I64]
         L.cs3_debug_gmres_kernel.argtypes = [vp, I64, I64, vp]
+        L.cs3_debug_gmres_basis.argtypes = [vp, _f64p, I64]
         L.cs3_set_pivot_perturbation.argtypes = [vp, C.c_double]
         L.cs3_get_perturbed.argtypes = [vp, C.POINTER(I64), vp]
         L.cs3_condest_dev.argtypes = [vp, vp, vp, vp, vp]
@@ -578,6 +579,13 @@ class Factorization:
         est = np.zeros(count)
         _check(lib().cs3_debug_gmres_estimates(self._h, _pf(est), count))
         return est
+
+    def debug_gmres_basis(self, nvec, k):
+        """The first nvec <= restart + 1 basis vectors as the last gmres call (with k right-hand sides) left them
+        (diagnostic) -> [nvec, batch, n, k].  Vector 0 is what the call's closing residual check left."""
+        V = np.zeros((nvec, self.batch, self.n, k))
+        _check(lib().cs3_debug_gmres_basis(self._h, _pf(V), nvec))
+        return V
 
     def solve_refined(self, Ax, b, max_refine=10, refine="stationary"):
         """solve(b), then -- when the factorisation replaced pivots -- refinement.  refine="stationary": one round at a

@@ -1479,7 +1479,8 @@ static int ensure_krylov(cs3_handle h, long long k, int restart, KryWork &K)
     const long long n = h->S.n, batch = h->batch, nsys = batch * k, total = batch * n * k, chunks = kry_chunks(n);
     const size_t need_v = (size_t) (total * (restart + 1)), need_w = (size_t) total;
     // per system: R [restart][restart], cs, sn, y [restart], g [restart + 1], the summed dots [2][restart]
-    const size_t per_sys = (size_t) restart * restart + 5 * (size_t) restart + 1;
+    // = restart^2 + (1 + 1 + 1 + 2) restart + (restart + 1)
+    const size_t per_sys = (size_t) restart * restart + 6 * (size_t) restart + 1;
     const size_t need_small = (size_t) nsys * per_sys, need_parts = (size_t) (nsys * chunks) * (2 * (size_t) restart + 2);
     if (need_v > M.v.count() || need_w > M.w.count() || need_small > M.small.count() || need_parts > M.parts.count() ||
         (size_t) nsys > M.sys.count() || !M.cnt.get()) {
@@ -1638,6 +1639,21 @@ int cs3_debug_gmres_estimates(cs3_handle h, double *est, int64_t count)
     std::vector<KrySys> sys((size_t) count);
     if (count) CS3_HIP(hipMemcpy(sys.data(), h->mem.kry.sys.get(), sys.size() * sizeof(KrySys), hipMemcpyDeviceToHost));
     for (int64_t s = 0; s < count; ++s) est[s] = sys[(size_t) s].est;
+    return CS3_OK;
+}
+
+// diagnostics: the first nvec <= restart + 1 basis vectors as the last cs3_gmres* call on this handle left them, V [nvec]
+// [batch][n, k] as stored.  Vector 0 is what the call's closing residual check left (zeros once every system has
+// finished); vectors 1 .. belong to the last cycle that iterated, and whatever an earlier cycle left behind it.
+int cs3_debug_gmres_basis(cs3_handle h, double *V, int64_t nvec)
+{
+    int rc = guard(h); if (rc) return rc;
+    if (!V || nvec < 0 || nvec > KRY_MAX_RESTART + 1) { set_error("cs3_debug_gmres_basis: bad argument"); return CS3_ERR_ARG; }
+    const KryWork &K = h->kry_work;
+    if (!K.V) { set_error("cs3_debug_gmres_basis: no cs3_gmres call on this handle yet"); return CS3_ERR_STATE; }
+    if (nvec > K.restart + 1) { set_error("cs3_debug_gmres_basis: bad argument"); return CS3_ERR_ARG; }
+    const size_t count = (size_t) nvec * (size_t) (K.batch * K.n * K.k);
+    if (count) CS3_HIP(hipMemcpy(V, K.V, count * sizeof(double), hipMemcpyDeviceToHost));
     return CS3_OK;
 }
 

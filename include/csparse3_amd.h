@@ -302,6 +302,11 @@ int cs3_debug_gmres_estimates(cs3_handle h, double *est, int64_t count);
 /* diagnostics: one vector kernel of iteration j alone on the work memory of the last cs3_gmres* call on this handle
  * (which = 0: the multi-dot, 1: the first update, 2: the second update with the norm), for timing */
 int cs3_debug_gmres_kernel(cs3_handle h, int64_t which, int64_t j, void *stream);
+/* diagnostics: V [nvec][batch][n, k] = the first nvec <= restart + 1 basis vectors as the last cs3_gmres* call on this
+ * handle left them (read-only; synchronises the device).  Vector 0 is what the call's closing residual check left (zeros
+ * once every system has finished), vectors 1 .. are the last iterating cycle's, exact zeros behind a system's last
+ * column.  CS3_ERR_STATE before any cs3_gmres* call, CS3_ERR_ARG on a null V or a count outside 0 .. restart + 1. */
+int cs3_debug_gmres_basis(cs3_handle h, double *V, int64_t nvec);
 
 /* ---- condition estimates and log-determinants from the held factors -----
  * Static diagonal pivots say nothing about how far a solution can be trusted; these are the cheap reliability signal

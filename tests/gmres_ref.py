@@ -10,16 +10,17 @@ from collections import namedtuple
 
 import numpy as np
 
-Result = namedtuple("Result", "x iters relres history cycles")
+Result = namedtuple("Result", "x iters relres history cycles V ncols", defaults=(None, 0))
 # history: |g_{j+1}| / ||b|| after every iteration; cycles: (that estimate at the cycle's end, the true relative residual
-# after the cycle's update) per completed cycle
+# after the cycle's update) per completed cycle; V [n, number of basis vectors built], ncols: the basis and the number of
+# Hessenberg columns of the last cycle that ran (keep_basis only)
 
 
 def _norm(v):
     return float(np.sqrt(np.dot(v, v)))
 
 
-def gmres(A, solve, b, x0, rtol=1e-12, restart=30, max_iters=100):
+def gmres(A, solve, b, x0, rtol=1e-12, restart=30, max_iters=100, keep_basis=False):
     b = np.asarray(b, dtype=np.float64)
     x = np.array(x0, dtype=np.float64, copy=True)
     bnorm = _norm(b)
@@ -27,17 +28,22 @@ def gmres(A, solve, b, x0, rtol=1e-12, restart=30, max_iters=100):
         return Result(np.zeros_like(x), 0, 0.0, [], [])
     iters, history, cycles, pending = 0, [], [], None
     m = restart
+    last = (None, 0)
+
+    def result(relres):
+        return Result(x, iters, relres, history, cycles, *last)
+
     while True:
         r = b - A @ x
         rn = _norm(r)
         if not (np.isfinite(rn) and np.isfinite(bnorm)):
-            return Result(x, iters, float("nan"), history, cycles)
+            return result(float("nan"))
         relres = rn / bnorm
         if pending is not None:
             cycles.append((pending, relres))
             pending = None
         if relres <= rtol or iters >= max_iters:
-            return Result(x, iters, relres, history, cycles)
+            return result(relres)
         V = [r * (1.0 / rn)]
         R = np.zeros((m, m))
         cs, sn, g = np.zeros(m), np.zeros(m), np.zeros(m + 1)
@@ -53,7 +59,7 @@ def gmres(A, solve, b, x0, rtol=1e-12, restart=30, max_iters=100):
                 h += hp
             hn = _norm(w)
             if not (np.all(np.isfinite(h)) and np.isfinite(hn)):
-                return Result(x, iters, float("nan"), history, cycles)
+                return result(float("nan"))
             prev = h[0]
             for i in range(j):
                 nxt = h[i + 1]
@@ -61,7 +67,7 @@ def gmres(A, solve, b, x0, rtol=1e-12, restart=30, max_iters=100):
                 prev = cs[i] * nxt - sn[i] * prev
             denom = float(np.hypot(prev, hn))
             if denom == 0.0 or not np.isfinite(denom):
-                return Result(x, iters, float("nan"), history, cycles)
+                return result(float("nan"))
             cs[j], sn[j] = prev / denom, hn / denom
             h[j] = denom
             R[:j + 1, j] = h
@@ -81,4 +87,6 @@ def gmres(A, solve, b, x0, rtol=1e-12, restart=30, max_iters=100):
         for i in range(ncols):
             u += y[i] * V[i]
         x = x + solve(u)
+        if keep_basis:
+            last = (np.stack(V, axis=1), ncols)
         pending = history[-1]

@@ -100,6 +100,17 @@ def test_argument_checks_need_no_device():
         assert _call(h, Ax, b, x, restart=1, max_iters=0, rtol=0.0, trans=1) == STATE
         dev = csc_hip.lib().cs3_gmres_dev
         assert dev(h, None, None, None, 1, 30, 10, 1e-12, 0, None, None, None) == ARG
+        # the basis diagnostic: a bad pointer or count first, then "no gmres call yet"
+        basis = csc_hip.lib().cs3_debug_gmres_basis
+        buf = np.zeros(n)
+        pv = buf.ctypes.data_as(C.POINTER(C.c_double))
+        assert basis(None, pv, 1) == ARG
+        assert basis(h, None, 1) == ARG
+        assert basis(h, pv, -1) == ARG
+        assert basis(h, pv, csc_hip.gmres_limits().max_restart + 2) == ARG
+        assert basis(h, pv, 0) == STATE and basis(h, pv, 1) == STATE
+        assert basis(h, pv, csc_hip.gmres_limits().max_restart + 1) == STATE
+        assert "no cs3_gmres call" in csc_hip.lib().cs3_last_error().decode()
     with csc_hip.Factorization(m, n, Ap, Ai, schur=[0, 1]) as S:
         assert _call(S._h, Ax, b, x) == ARG
         assert "Schur" in csc_hip.lib().cs3_last_error().decode()
