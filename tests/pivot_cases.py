@@ -129,9 +129,12 @@ def fronts(hip, F):
     """Everything the dispatch depends on, per supernode of the handle F, and the kernel class that follows from it:
     forest_wave / forest_shared (bottom forest, one wave / four waves per front), wave (k_front_wave), mix_wave / mix_grid
     (k_front_mix: one-wave panel for w <= 32, the 16 x 16 grid above), block (k_front_block), big_step (k_big_step),
-    wg (k_front_wg), il (k_front_il)."""
+    wg (k_front_wg), il (k_front_il).  On a Schur handle the last supernode is 'schur' (FC_SCHUR: assembled, never
+    eliminated, whatever its order; it neither rides nor counts on its level) and `rows` is None: such a handle refuses
+    factors()."""
     lib = hip.lib()
     ns = int(F.info.nsuper)
+    schur = ns - 1 if getattr(F, "ns", 0) else -1
     batch, kind, n = F.batch, F.kind, F.n
     i32p = C.POINTER(C.c_int32)
     p = lambda a: a.ctypes.data_as(i32p)                                   # noqa: E731
@@ -166,7 +169,7 @@ def fronts(hip, F):
     ride = np.zeros(ns, dtype=bool)
     if batch == 1:
         for lv in np.unique(height[~forest]):
-            on = [s for s in range(ns) if not forest[s] and height[s] == lv]
+            on = [s for s in range(ns) if not forest[s] and height[s] == lv and s != schur]
             big = [s for s in on if _front_class(r[s], w[s], False, False) == "big"]
             small = [s for s in on if s not in big]
             if big and len(small) <= 8 and (max([w[s] for s in small], default=0) + 31) // 32 <= (max(w[s] for s in big) + 31) // 32:
@@ -176,6 +179,9 @@ def fronts(hip, F):
         if forest[s]:
             cls.append("forest_shared" if shared[s] else "forest_wave")
             continue
+        if s == schur:
+            cls.append("schur")
+            continue
         fc = "big" if ride[s] else _front_class(r[s], w[s], batch >= 8, batch >= 128)
         if fc == "big":
             ld = (r[s] + 1) | 1                                            # kernels.hip: wg_lds_bytes, per front (<= per group)
@@ -183,11 +189,13 @@ def fronts(hip, F):
             cls.append("wg" if batch >= 48 and lds <= 150 * 1024 else "big_step")
         else:
             cls.append({"il": "il", "r32": "wave", "lds": "block", "r64": "mix_wave" if w[s] <= 32 else "mix_grid"}[fc])
-    Lp, Li = F.factors(values=False)[:2]
-    # (supernodes are relaxed: the front's rows are the union of its columns' patterns)
-    rows = [np.unique(Li[Lp[c0[s]]:Lp[c0[s] + w[s]]]).astype(np.int64) for s in range(ns)]
-    for s in range(ns):
-        assert len(rows[s]) == r[s] and np.array_equal(rows[s][:w[s]], np.arange(c0[s], c0[s] + w[s]))
+    rows = None
+    if schur < 0:
+        Lp, Li = F.factors(values=False)[:2]
+        # (supernodes are relaxed: the front's rows are the union of its columns' patterns)
+        rows = [np.unique(Li[Lp[c0[s]]:Lp[c0[s] + w[s]]]).astype(np.int64) for s in range(ns)]
+        for s in range(ns):
+            assert len(rows[s]) == r[s] and np.array_equal(rows[s][:w[s]], np.arange(c0[s], c0[s] + w[s]))
     return Fronts(c0, w, r, parent, forest, ftask, flevel, shared, cls, rows, F.ordering()["q"], n, batch, kind)
 
 

@@ -24,6 +24,7 @@ ORDER = {"w72": 358, "w100": 470, "w140": 590, "w200": 870}
 FRONTS = {"w72": ((142, 72), (142, 72), (214, 214)), "w100": ((170, 100), (170, 100), (270, 270)),
           "w140": ((170, 140), (170, 140), (310, 310)), "w200": ((270, 200), (270, 200), (470, 470))}
 BIG_BATCH_MAX = 15            # symbolic.cpp: a batch of 16 or more sweeps its wide big fronts with the block kernel
+SMALL_RMAX, WAVE_RMAX, WAVE_WMAX, BIG_RMIN = 32, 128, 64, 137      # symbolic.cpp: solve_kind (small_rmax; r <= 128, w <= 64; r > 136)
 
 
 # ------------------------------------------------------------------ construction --
@@ -111,20 +112,19 @@ def solve_kinds(hip, F):
     """r, w, parent and solve kind ('il', 'small', 'wave', 'big', 'block') of every supernode of the handle F, and its
     factor class (pivot_cases.fronts).  The kind restates symbolic.cpp's solve_kind."""
     FR = pc.fronts(hip, F)
-    kind = []
-    for s in range(len(FR.w)):
-        r, w = int(FR.r[s]), int(FR.w[s])
-        if FR.cls[s] == "il":
-            kind.append("il")
-        elif r <= 32:
-            kind.append("small")
-        elif r <= 128 and w <= 64:
-            kind.append("wave")
-        elif w > 64 and r > 136 and F.batch <= BIG_BATCH_MAX:
-            kind.append("big")
-        else:
-            kind.append("block")
+    kind = ["il" if FR.cls[s] == "il" else kind_of(int(FR.r[s]), int(FR.w[s]), F.batch) for s in range(len(FR.w))]
     return Kinds(FR.r, FR.w, np.asarray(FR.parent), kind, FR.cls)
+
+
+def kind_of(r, w, batch):
+    """symbolic.cpp's solve_kind for a front (r, w) that is not matrix-interleaved."""
+    if r <= SMALL_RMAX:
+        return "small"
+    if r <= WAVE_RMAX and w <= WAVE_WMAX:
+        return "wave"
+    if w > WAVE_WMAX and r >= BIG_RMIN and batch <= BIG_BATCH_MAX:
+        return "big"
+    return "block"
 
 
 def wide_fronts(K):
