@@ -252,6 +252,21 @@ class CscMat:
             cx = np.concatenate(vals) if vals else np.zeros(0)
             return F.solve_updates(plan, cx, b, sing_tol)
 
+    def sensitivities(self, B, C=None, tol=0.0, trans=False, side="auto"):
+        """Y = C op(A)^-1 B for a sparse B (CscMat, n x k) and a sparse C (CscMat, p x n; None: the identity, Y = the
+        solution itself), op(A) = A' with `trans`, from ONE LU factorisation of A (factorises as solve does).  Only the
+        dense Y [p, k] comes back; side "auto" solves for the fewer of k and p columns.  C is turned into the CSC form
+        of C' (its rows) with csc_transpose, values included."""
+        assert B.m == self.n and (C is None or C.n == self.n)
+        F = self.lu(tol)
+        Ct, Ctx = None, None
+        if C is not None:
+            _, p, Ctp, Cti, Ctx = _k.csc_transpose(C.m, C.n, C.indptr, C.indices, C.data)
+            Ct = (p, Ctp, Cti)
+        nb = int(B.indptr[B.n])
+        with F.sens_plan((B.n, B.indptr, B.indices[:nb]), Ct, side=side, trans=trans) as plan:
+            return F.sens_solve(plan, B.data[:nb], Ctx)
+
     def condest(self, tol=0.0):
         """1-norm condition estimate ||A||_1 * est(||A^-1||_1) from the LU factors (factorises as solve does)."""
         cond, _ = self.lu(tol).condest(self.data)

@@ -66,6 +66,20 @@ class GmresLimits(C.Structure):
     _fields_ = [(name, C.c_int64) for name in ("max_restart", "chunk_rows", "rhs_tile")]
 
 
+class SensInfo(C.Structure):
+    """cs3_sens_info_t: sizes of a plan for Y = C op(A)^-1 B, the side it is evaluated from (1 right, 2 left), its tiles."""
+    _fields_ = [(name, C.c_int64) for name in ("k", "p", "side", "trans", "ntiles", "max_width", "nnz_b", "nnz_c")]
+
+    def __repr__(self):
+        return "SensInfo(%s)" % ", ".join("%s=%d" % (f, getattr(self, f)) for f, _ in self._fields_)
+
+
+class SensLimits(C.Structure):
+    """cs3_sens_limits_t: the constants that shape the tiles and launches of the sparse right-hand-side path."""
+    _fields_ = [(name, C.c_int64) for name in ("max_tile", "pad_width", "scatter_rows", "scatter_threads", "combine_cols",
+                                               "combine_lanes", "tblock")]
+
+
 class Cs3Error(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("cs3 error %d: %s" % (code, msg))
@@ -174,6 +188,13 @@ def lib():
         L.cs3_debug_updates_tiles.argtypes = [vp] + [_i32p] * 4
         L.cs3_debug_updates_tiles.restype = I64
         L.cs3_debug_alloc_counters.argtypes = [vp, C.POINTER(I64), C.POINTER(I64)]
+        L.cs3_sens_limits.argtypes = [C.POINTER(SensLimits)]
+        L.cs3_sens_plan.argtypes = [vp, I64, _i32p, _i32p, I64, _i32p, _i32p, I64, I64, C.POINTER(vp)]
+        L.cs3_sens_free.argtypes = [vp]
+        L.cs3_sens_info.argtypes = [vp, C.POINTER(SensInfo)]
+        L.cs3_sens_solve_dev.argtypes = [vp, vp, vp, vp, vp, vp]
+        L.cs3_sens_solve.argtypes = [vp, vp, _f64p, _f64p, _f64p]
+        L.cs3_debug_sens_parts.argtypes = [vp, vp, I64, vp, vp, vp, vp]
         L.cs3_debug_live_device_buffers.argtypes = []
         L.cs3_debug_live_device_buffers.restype = I64
         L.cs3_export_factor_dev.argtypes = [vp, vp, vp]
@@ -374,6 +395,54 @@ class UpdatesPlan:
         arrs = [np.empty(nt, dtype=np.int32) for _ in range(4)]
         assert lib().cs3_debug_updates_tiles(self._u, *[_pi(a) for a in arrs]) == nt
         return np.stack(arrs, axis=1)
+
+
+SENS_SIDES = {"auto": 0, "right": 1, "left": 2}
+
+
+def sens_limits():
+    """The constants of the sparse right-hand-side path (cs3_sens_limits); needs no GPU."""
+    out = SensLimits()
+    _check(lib().cs3_sens_limits(C.byref(out)))
+    return out
+
+
+class SensPlan:
+    """The patterns of B and C' of Y = C op(A)^-1 B on a handle (Factorization.sens_plan): made once on the host, used by
+    every sens_solve of that handle, across refactorisations."""
+
+    def __init__(self, factorization, B, Ct=None, side="auto", trans=False):
+        self._u = C.c_void_p()
+        n = factorization.n
+        self.k, self.bp, self.bi = (n, None, None) if B is None else (int(B[0]), _i32(B[1]), _i32(B[2]))
+        self.p, self.ctp, self.cti = (n, None, None) if Ct is None else (int(Ct[0]), _i32(Ct[1]), _i32(Ct[2]))
+        assert self.bp is None or self.bp.size == self.k + 1, "B is (ncols, indptr[ncols + 1], indices)"
+        assert self.ctp is None or self.ctp.size == self.p + 1, "Ct is (ncols, indptr[ncols + 1], indices)"
+        _check(lib().cs3_sens_plan(factorization._h, self.k, _pi(self.bp), _pi(self.bi), self.p, _pi(self.ctp), _pi(self.cti),
+                                   SENS_SIDES.get(side, side), int(bool(trans)), C.byref(self._u)))
+
+    def close(self):
+        if self._u:
+            lib().cs3_sens_free(self._u)
+            self._u = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    @property
+    def info(self):
+        out = SensInfo()
+        _check(lib().cs3_sens_info(self._u, C.byref(out)))
+        return out
 
 
 class Factorization:
@@ -738,6 +807,36 @@ class Factorization:
         with a plan nothing is allocated and nothing synchronises.  The same bits as solve_updates()."""
         _check(lib().cs3_updates_solve_dev(self._h, plan._u, C.c_void_p(cx_ptr), C.c_void_p(b_ptr), sing_tol,
                                            C.c_void_p(x_ptr), C.c_void_p(rpiv_ptr), C.c_void_p(stream)))
+
+    # -- sparse right-hand sides on the held factors
+    def sens_plan(self, B, Ct=None, side="auto", trans=False):
+        """Plan for Y = C op(A)^-1 B with sparse B (n x k) and C (p x n): `B` = (k, indptr, indices) by columns, `Ct` =
+        (p, indptr, indices) the CSC pattern of C' (C by rows); None is the identity (not both).  side "auto" solves
+        for the fewer of k and p columns, "right" for columns of B, "left" for rows of C.  Needs no GPU.
+        -> SensPlan (.info, .close(), context manager)."""
+        return SensPlan(self, B, Ct, side, trans)
+
+    def sens_solve(self, plan, Bx, Ctx):
+        """Y [p, k] = C op(A)^-1 B from the held factors: Bx / Ctx the values in the plan's entry order (None for an
+        identity operand)."""
+        Bx = None if plan.bp is None else _f64(Bx).reshape(-1)
+        Ctx = None if plan.ctp is None else _f64(Ctx).reshape(-1)
+        assert Bx is None or Bx.size == int(plan.bp[-1])
+        assert Ctx is None or Ctx.size == int(plan.ctp[-1])
+        Y = np.empty((plan.p, plan.k))
+        _check(lib().cs3_sens_solve(self._h, plan._u, _pf(Bx), _pf(Ctx), _pf(Y)))
+        return Y
+
+    def sens_solve_dev(self, plan, bx_ptr, ctx_ptr, y_ptr, stream=0):
+        """sens_solve on device pointers, asynchronous on `stream`; Y [p, k] row-major.  After the first call with a plan
+        nothing is allocated and nothing synchronises.  The same bits as sens_solve()."""
+        _check(lib().cs3_sens_solve_dev(self._h, plan._u, C.c_void_p(bx_ptr), C.c_void_p(ctx_ptr), C.c_void_p(y_ptr),
+                                        C.c_void_p(stream)))
+
+    def debug_sens_parts(self, plan, parts, bx_ptr, ctx_ptr, y_ptr, stream=0):
+        """Diagnostics, for timing: the steps of sens_solve_dev in the mask `parts` (1 scatter, 2 solves, 4 combine)."""
+        _check(lib().cs3_debug_sens_parts(self._h, plan._u, parts, C.c_void_p(bx_ptr), C.c_void_p(ctx_ptr), C.c_void_p(y_ptr),
+                                          C.c_void_p(stream)))
 
     def debug_alloc_counters(self):
         """(device allocations incl. graph instantiations, host synchronisations) the handle's solves have made so far."""

@@ -66,6 +66,7 @@ struct cs3_handle_s {
         double parity = 1.0, log_shift = 0.0; // det A = parity det B exp(log_shift): sign of rowperm, -(sum log dr + sum log dc)
     } match;
     std::vector<cs3_updates_s *> plans;       // the plans made for this handle (cs3_updates_plan)
+    std::vector<cs3_sens_s *> sens_plans;     // ... and by cs3_sens_plan
     KryWork kry_work{};                       // the work arrays of the last cs3_gmres* call (views of mem.kry)
     // Every HBM block of the handle, one group per feature that builds it; release_device drops them all at once.  A
     // new feature declares its DevBuf in a group here and allocates it in its ensure_*: nothing else has to know.
@@ -96,6 +97,9 @@ struct cs3_handle_s {
         // ensure_updates (updates.hip): the tile of A^-1 columns Z [n][widest tile so far] (grows) and x0 [n] (stable
         // addresses: the solves on them replay the cached graphs)
         struct { DevBuf<double> z, x0; } upd;
+        // ensure_sens (sens.hip): the tile of right-hand sides T [n][widest solve width so far] (grows; a stable address:
+        // the solves on it replay the cached graphs)
+        struct { DevBuf<double> t; } sens;
         // ensure_match (matching.hip): the scalings, the row of A behind every pivot row, row and column of every entry
         struct { DevBuf<double> dr, dc; DevBuf<int> rq, erow, ecol; } match;
         // ensure_device on a Schur handle (schur.hip): the held Schur complements S [batch][ns, ns]
@@ -131,6 +135,30 @@ struct cs3_updates_s {
         DevBuf<double> y, rpiv, cx;
     } mem;
     bool on_device = false;
+};
+
+// The patterns of B and C' of one Y = C op(A)^-1 B, the side it is evaluated from and its tiles (cs3_sens_plan).
+struct cs3_sens_s {
+    cs3_handle h = nullptr;                   // null once the handle has been freed: the plan can then only be freed
+    i64 n = 0, k = 0, p = 0;
+    int side = 1;                             // 1: solve for columns of B, 2: for rows of C
+    bool trans = false;
+    bool b_ident = false, c_ident = false;
+    int tile_cap = SENS_MAX_TILE, wmax = 1;
+    std::vector<i32> bp, bi, ctp, cti;        // empty for an identity operand
+    struct Tile {
+        i64 c0;                               // first solved-for column
+        int t, w;                             // its columns, and the width it is solved at (zero columns behind t)
+    };
+    std::vector<Tile> tiles;
+    // device copies (uploaded by the first solve); the host form's copies of the values and of Y
+    struct Memory {
+        DevBuf<int> bp, bi, ctp, cti;
+        DevBuf<double> bx, ctx, y;
+    } mem;
+    bool on_device = false;
+    i64 nnz_b() const { return b_ident ? n : (i64) bi.size(); }
+    i64 nnz_c() const { return c_ident ? n : (i64) cti.size(); }
 };
 
 namespace {
@@ -178,10 +206,17 @@ void release_plan_device(cs3_updates_s *u)
     u->on_device = false;
 }
 
+void release_plan_device(cs3_sens_s *u)
+{
+    u->mem = cs3_sens_s::Memory();
+    u->on_device = false;
+}
+
 // Frees every HBM allocation of the handle (ensure_device's error path and cs3_free).
 void release_device(cs3_handle h)
 {
     for (cs3_updates_s *u : h->plans) release_plan_device(u);
+    for (cs3_sens_s *u : h->sens_plans) release_plan_device(u);
     (void) drop_graphs(h, [](const GraphKey &) { return true; }, true);     // (cs3_free has synchronised)
     if (h->cap_stream) { (void) hipStreamDestroy(h->cap_stream); h->cap_stream = nullptr; }
     h->fj.destroy();
@@ -909,6 +944,7 @@ int cs3_free(cs3_handle h)
         release_device(h);
     }
     for (cs3_updates_s *u : h->plans) u->h = nullptr;      // (their device arrays went with release_device)
+    for (cs3_sens_s *u : h->sens_plans) u->h = nullptr;
     delete h;
     return CS3_OK;
 }
@@ -2054,6 +2090,196 @@ int cs3_updates_solve(cs3_handle h, cs3_updates u, const double *cx, const doubl
     if ((rc = updates_run(h, u, u->mem.cx.get(), d_b, sing_tol, d_x, nullptr, nullptr))) return rc;
     if (n) CS3_HIP(hipMemcpy(X, d_x, n * nc * sizeof(double), hipMemcpyDeviceToHost));
     if (rpiv) CS3_HIP(hipMemcpy(rpiv, u->mem.rpiv.get(), nc * sizeof(double), hipMemcpyDeviceToHost));
+    CS3_HIP(hipDeviceSynchronize());
+    return CS3_OK;
+}
+
+// ---- sparse right-hand sides: Y = C op(A)^-1 B on the held factors (sens.hip) ------------------------------------------
+int cs3_sens_limits(cs3_sens_limits_t *out)
+{
+    if (!out) { set_error("cs3_sens_limits: null output"); return CS3_ERR_ARG; }
+    *out = cs3_sens_limits_t{SENS_MAX_TILE, SENS_PAD_WIDTH, SENS_SCATTER_ROWS, SENS_SCATTER_THREADS, SENS_COMBINE_COLS,
+                             SENS_COMBINE_LANES, SENS_TBLOCK};
+    return CS3_OK;
+}
+
+// One operand's pattern: pointers monotone from 0 (check 5); the indices are looked at afterwards (check 6), so that a
+// bad pointer array of either operand wins over a bad index of either.
+static int sens_check_pointers(const char *name, int64_t ncols, const int32_t *P, const int32_t *I)
+{
+    if (P[0] != 0) { set_error(std::string("cs3_sens_plan: ") + name + "[0] != 0"); return CS3_ERR_ARG; }
+    for (int64_t c = 0; c < ncols; ++c)
+        if (P[c + 1] < P[c]) { set_error(std::string("cs3_sens_plan: ") + name + " not monotone at column " + std::to_string(c)); return CS3_ERR_ARG; }
+    if (P[ncols] > 0 && !I) { set_error(std::string("cs3_sens_plan: null index array behind ") + name); return CS3_ERR_ARG; }
+    return CS3_OK;
+}
+
+static int sens_check_indices(const char *name, int64_t n, int64_t ncols, const int32_t *P, const int32_t *I)
+{
+    for (int64_t c = 0; c < ncols; ++c)
+        for (int e = P[c]; e < P[c + 1]; ++e)
+            if (I[e] < 0 || I[e] >= n) {
+                set_error(std::string("cs3_sens_plan: index out of range in column ") + std::to_string(c) + " of " + name);
+                return CS3_ERR_ARG;
+            }
+    return CS3_OK;
+}
+
+int cs3_sens_plan(cs3_handle h, int64_t k, const int32_t *Bp, const int32_t *Bi, int64_t p, const int32_t *Ctp, const int32_t *Cti,
+                  int64_t side, int64_t trans, cs3_sens *out)
+{
+    int rc = guard(h); if (rc) return rc;
+    if (!out) { set_error("cs3_sens_plan: null output"); return CS3_ERR_ARG; }
+    *out = nullptr;
+    const int64_t n = h->S.n;
+    if (k < 1 || p < 1 || k > INT_MAX / 2 || p > INT_MAX / 2) { set_error("cs3_sens_plan: k and p must be >= 1"); return CS3_ERR_ARG; }
+    if (!Bp && !Ctp) { set_error("cs3_sens_plan: B and C are both the identity (the dense inverse is not offered)"); return CS3_ERR_ARG; }
+    if (!Bp && k != n) { set_error("cs3_sens_plan: B is the identity but k != n"); return CS3_ERR_ARG; }
+    if (!Ctp && p != n) { set_error("cs3_sens_plan: C is the identity but p != n"); return CS3_ERR_ARG; }
+    if (Bp && (rc = sens_check_pointers("Bp", k, Bp, Bi))) return rc;
+    if (Ctp && (rc = sens_check_pointers("Ctp", p, Ctp, Cti))) return rc;
+    if (Bp && (rc = sens_check_indices("B", n, k, Bp, Bi))) return rc;
+    if (Ctp && (rc = sens_check_indices("C'", n, p, Ctp, Cti))) return rc;
+    if (side < 0 || side > 2) { set_error("cs3_sens_plan: side must be 0 (auto), 1 (right) or 2 (left)"); return CS3_ERR_ARG; }
+    if (!Bp && side == 1) { set_error("cs3_sens_plan: B is the identity, side right would solve for all n columns: use side 0 or 2"); return CS3_ERR_ARG; }
+    if (!Ctp && side == 2) { set_error("cs3_sens_plan: C is the identity, side left would solve for all n rows: use side 0 or 1"); return CS3_ERR_ARG; }
+    if (h->batch > 1) { set_error("cs3_sens_plan: handles with batch > 1 are not supported"); return CS3_ERR_ARG; }
+    if ((rc = refuse_schur(h, "cs3_sens_plan"))) return rc;
+    cs3_sens_s *u = nullptr;
+    try {
+        u = new cs3_sens_s();
+        u->n = n; u->k = k; u->p = p;
+        u->trans = trans != 0;
+        u->b_ident = !Bp; u->c_ident = !Ctp;
+        u->side = !Bp ? 2 : !Ctp ? 1 : side ? (int) side : (p < k ? 2 : 1);
+        if (Bp) { u->bp.assign(Bp, Bp + k + 1); u->bi.assign(Bi, Bi + Bp[k]); }
+        if (Ctp) { u->ctp.assign(Ctp, Ctp + p + 1); u->cti.assign(Cti, Cti + Ctp[p]); }
+        long long cap = SENS_MAX_TILE;
+        if (const char *e = std::getenv("CS3_SENS_TILE")) cap = std::min<long long>(SENS_MAX_TILE, std::max<long long>(1, std::atoll(e)));
+        u->tile_cap = (int) cap;
+        // full tiles at the tile width; the last at its own, padded to SENS_PAD_WIDTH where the tile width allows it
+        const i64 ns = (u->side == 1) ? k : p;
+        for (i64 c0 = 0; c0 < ns; c0 += cap) {
+            const int t = (int) std::min<i64>(cap, ns - c0);
+            const int w = (t < SENS_PAD_WIDTH && cap >= SENS_PAD_WIDTH) ? SENS_PAD_WIDTH : t;
+            u->tiles.push_back(cs3_sens_s::Tile{c0, t, w});
+            u->wmax = std::max(u->wmax, w);
+        }
+        h->sens_plans.push_back(u);
+    } catch (const std::bad_alloc &) {
+        delete u; set_error("cs3_sens_plan: out of memory"); return CS3_ERR_ALLOC;
+    }
+    u->h = h;
+    *out = u;
+    return CS3_OK;
+}
+
+int cs3_sens_free(cs3_sens u)
+{
+    if (!u) return CS3_OK;
+    if (u->h) {
+        if (u->on_device) { (void) hipDeviceSynchronize(); release_plan_device(u); }
+        auto &pl = u->h->sens_plans;
+        pl.erase(std::remove(pl.begin(), pl.end(), u), pl.end());
+    }
+    delete u;
+    return CS3_OK;
+}
+
+int cs3_sens_info(cs3_sens u, cs3_sens_info_t *out)
+{
+    if (!u || !out) { set_error("cs3_sens_info: null argument"); return CS3_ERR_ARG; }
+    *out = cs3_sens_info_t{u->k, u->p, u->side, u->trans ? 1 : 0, (int64_t) u->tiles.size(), u->wmax, u->nnz_b(), u->nnz_c()};
+    return CS3_OK;
+}
+
+static int sens_check(const char *who, cs3_handle h, cs3_sens u, const double *bx, const double *ctx, const double *Y)
+{
+    int rc = guard(h); if (rc) return rc;
+    if (!u) { set_error(std::string(who) + ": null plan"); return CS3_ERR_ARG; }
+    if (!Y || (!u->b_ident && u->nnz_b() > 0 && !bx) || (!u->c_ident && u->nnz_c() > 0 && !ctx)) {
+        set_error(std::string(who) + ": null argument");
+        return CS3_ERR_ARG;
+    }
+    if (u->h != h) { set_error(std::string(who) + ": the plan was made for another handle"); return CS3_ERR_ARG; }
+    if (!h->factored) { set_error(std::string(who) + ": no successful factorisation"); return CS3_ERR_STATE; }
+    return CS3_OK;
+}
+
+// Tables of the plan in HBM, the handle's tile buffer, room for the widest tile in the sweep buffers: everything a call
+// needs, so that later calls neither allocate nor synchronise.
+static int ensure_sens(cs3_handle h, cs3_sens_s *u)
+{
+    if (!u->on_device) {
+        auto &P = u->mem;
+        if (!u->b_ident) { CS3_HIP(P.bp.upload(u->bp)); CS3_HIP(P.bi.upload(u->bi)); h->dbg_allocs += 2; }
+        if (!u->c_ident) { CS3_HIP(P.ctp.upload(u->ctp)); CS3_HIP(P.cti.upload(u->cti)); h->dbg_allocs += 2; }
+        u->on_device = true;
+    }
+    auto &T = h->mem.sens.t;
+    const size_t need = std::max<size_t>(1, (size_t) h->S.n) * (size_t) u->wmax;
+    if (T.count() < need) {
+        if (T.get()) {                                     // a wider plan than any before: the old tile may still be in use
+            CS3_HIP(hipDeviceSynchronize());
+            h->dbg_syncs += 1;
+        }
+        CS3_HIP(T.alloc(need));
+        h->dbg_allocs += 1;
+    }
+    return ensure_rhs_capacity(h, u->wmax);
+}
+
+// Per tile: scatter the solved-for columns, solve in place, combine with the other operand.  Side left solves with the
+// transpose of op(A) and writes the transposed block.  parts (diagnostics): 1 the scatter, 2 the solve, 4 the combine.
+static int sens_run(cs3_handle h, cs3_sens_s *u, const double *bx_dev, const double *ctx_dev, double *Y_dev, hipStream_t st,
+                    int parts = 7)
+{
+    int rc = ensure_sens(h, u);
+    if (rc) return rc;
+    const i64 n = h->S.n;
+    const auto &P = u->mem;
+    const SensOperand B{u->b_ident ? nullptr : P.bp.get(), P.bi.get(), bx_dev};
+    const SensOperand Ct{u->c_ident ? nullptr : P.ctp.get(), P.cti.get(), ctx_dev};
+    const bool right = u->side == 1;
+    const SensOperand &solved = right ? B : Ct, &other = right ? Ct : B;
+    const i64 ng = right ? u->p : u->k;
+    double *T = h->mem.sens.t.get();
+    for (const auto &t : u->tiles) {
+        if (parts & 1) CS3_HIP(launch_sens_scatter(T, n, t.w, solved, t.c0, t.t, st));
+        if ((parts & 2) && (rc = run_solve(h, T, t.w, 0, st, right ? u->trans : !u->trans))) return rc;
+        if (parts & 4) CS3_HIP(launch_sens_combine(T, t.w, t.t, other, ng, t.c0, u->k, !right, Y_dev, st));
+    }
+    return CS3_OK;
+}
+
+int cs3_sens_solve_dev(cs3_handle h, cs3_sens u, const double *Bx_dev, const double *Ctx_dev, double *Y_dev, void *stream)
+{
+    int rc = sens_check("cs3_sens_solve_dev", h, u, Bx_dev, Ctx_dev, Y_dev);
+    if (rc) return rc;
+    return sens_run(h, u, Bx_dev, Ctx_dev, Y_dev, (hipStream_t) stream);
+}
+
+int cs3_debug_sens_parts(cs3_handle h, cs3_sens u, int64_t parts, const double *Bx_dev, const double *Ctx_dev, double *Y_dev,
+                         void *stream)
+{
+    int rc = sens_check("cs3_debug_sens_parts", h, u, Bx_dev, Ctx_dev, Y_dev);
+    if (rc) return rc;
+    if (parts < 1 || parts > 7) { set_error("cs3_debug_sens_parts: parts must be a mask of 1, 2 and 4"); return CS3_ERR_ARG; }
+    return sens_run(h, u, Bx_dev, Ctx_dev, Y_dev, (hipStream_t) stream, (int) parts);
+}
+
+int cs3_sens_solve(cs3_handle h, cs3_sens u, const double *Bx, const double *Ctx, double *Y)
+{
+    int rc = sens_check("cs3_sens_solve", h, u, Bx, Ctx, Y);
+    if (rc) return rc;
+    const size_t nb = u->b_ident ? 0 : (size_t) u->nnz_b(), nc = u->c_ident ? 0 : (size_t) u->nnz_c();
+    const size_t ny = (size_t) u->p * (size_t) u->k;
+    auto &P = u->mem;
+    CS3_HIP(P.bx.reserve(nb)); CS3_HIP(P.ctx.reserve(nc)); CS3_HIP(P.y.reserve(ny));
+    if (nb) CS3_HIP(hipMemcpy(P.bx.get(), Bx, nb * sizeof(double), hipMemcpyHostToDevice));
+    if (nc) CS3_HIP(hipMemcpy(P.ctx.get(), Ctx, nc * sizeof(double), hipMemcpyHostToDevice));
+    if ((rc = sens_run(h, u, P.bx.get(), P.ctx.get(), P.y.get(), nullptr))) return rc;
+    CS3_HIP(hipMemcpy(Y, P.y.get(), ny * sizeof(double), hipMemcpyDeviceToHost));
     CS3_HIP(hipDeviceSynchronize());
     return CS3_OK;
 }

@@ -295,6 +295,25 @@ hipError_t launch_upd_capacitance(const UpdTables &T, const double *cx, const do
 hipError_t launch_upd_apply(const UpdTables &T, const double *Z, int t, const double *x0, long long n, int c0, int nc, int rmax,
                             long long ldx, double *X, hipStream_t st);
 
+// sens.hip: sparse right-hand sides, Y = C op(A)^-1 B on the held factors (cs3_sens_*).
+constexpr int SENS_MAX_TILE = 1024;            // solved-for columns per tile (the width ensure_rhs_capacity and updates.hip use)
+constexpr int SENS_PAD_WIDTH = 16;             // a narrower last tile is padded to this width (the GEMM sweeps start there)
+constexpr int SENS_SCATTER_ROWS = 32;          // rows of the tile per k_sens_scatter workgroup
+constexpr int SENS_SCATTER_THREADS = 256;      //   ... and its threads (a thread owns columns j, j + 256, ...)
+constexpr int SENS_COMBINE_COLS = 32;          // columns of the other operand per k_sens_combine workgroup
+constexpr int SENS_COMBINE_LANES = 64;         //   ... and its tile columns
+constexpr int SENS_TBLOCK = 32;                // block edge of the transposing store: contiguous doubles per row of Y
+struct SensOperand {              // a sparse operand by columns on the device; p == null: the identity (i, x unused)
+    const int *p, *i;
+    const double *x;
+};
+// T [n, w] = columns c0 .. c0 + t - 1 of `op`, zero columns behind them
+hipError_t launch_sens_scatter(double *T, long long n, int w, const SensOperand &op, long long c0, int t, hipStream_t st);
+// out[g, j] = sum over the entries (i, v) of column g < ng of `op` of v T[i, j], j < t; stored at Y[g * ldy + c0 + j], or
+// (transposed) at Y[(c0 + j) * ldy + g]
+hipError_t launch_sens_combine(const double *T, int w, int t, const SensOperand &op, long long ng, long long c0, long long ldy,
+                               bool transposed, double *Y, hipStream_t st);
+
 // krylov.hip: the vector layer of restarted GMRES on the held factors (cs3_gmres*), for batch * k systems in lock-step.
 // Every vector is [batch][n, k] row-major; system s = b * k + t is column t of matrix b.  Reductions over the rows run on
 // a FIXED partition (chunks of KRY_CHUNK rows) and the chunks are summed in index order by whoever consumes them: the

@@ -389,6 +389,72 @@ int cs3_updates_solve_dev(cs3_handle h, cs3_updates u, const double *cx_dev, con
 int cs3_updates_solve(cs3_handle h, cs3_updates u, const double *cx, const double *b,
                       double sing_tol, double *X, double *rpiv);
 
+/* ---- sparse right-hand sides: Y = C op(A)^-1 B on the held factors -------
+ * PTDF and LODF tables, rows and columns of Z-bus, sensitivities of a few monitored quantities to many injections,
+ * selected entries of A^-1: B (n x k) is sparse with a few entries per column, C (p x n) is sparse with a few entries per
+ * row, and only the small dense Y [p, k] is wanted.  Nothing dense crosses PCIe: the right-hand sides are written on the
+ * device, tile by tile, go through the handle's many-right-hand-side solves, and are combined with the other operand
+ * there.  op(A) is A, or A' with `trans` (a Cholesky handle: trans changes nothing).
+ *
+ * B is given by columns: Bp[k + 1], Bi, values Bx.  C is given by ROWS, as the CSC arrays of C': Ctp[p + 1], Cti, Ctx
+ * (column r of C' = row r of C).  Y is [p, k] row-major.  Rows inside a column may be unsorted; duplicates of one index
+ * inside a column ADD, in storage order; an empty column of B gives a zero column of Y, an empty row of C a zero row.
+ * Bp == NULL: B = I (k must be n).  Ctp == NULL: C = I (p must be n).  Both NULL (the dense inverse) is refused.
+ *
+ * side 1 ("right"): solves op(A) T = B for tiles of columns of B, then Y[:, tile] = C T.
+ * side 2 ("left"): solves op(A)' T = C' for tiles of rows of C, then Y[tile, :] = (B' T)'.
+ * side 0: the side with fewer columns to solve for, k against p; a tie goes right.  An identity operand forces the other
+ *   side (B = I: left, C = I: right).  With p = 100 monitored rows and k = 50 000 injections, left is 100 transposed
+ *   solves instead of 50 000 plain ones.
+ *
+ * cs3_sens_plan: host, pattern only, needs no GPU; copies the patterns.  Checks, in this order: a null handle or out
+ *   pointer; k < 1 or p < 1; both operands the identity; an identity operand with k (p) != n; pointer arrays not monotone
+ *   from 0 (or null index arrays behind them); an index outside [0, n); side not 0, 1 or 2; a side that an identity
+ *   operand rules out; a handle with batch > 1; a Schur handle: CS3_ERR_ARG, and the message names what failed.
+ *   The solved-for columns are grouped, in order, into TILES of at most 1024; every tile but the last is solved at the
+ *   full width, the last at its own (padded with zero columns to 16 when it is narrower than that): at most two solve
+ *   widths per plan, on one tile buffer, so a plan keeps two captured graphs per handle and never evicts a caller's.
+ *   CS3_SENS_TILE in the environment, read by this call, lowers the tile width (for tests that must cross tile boundaries
+ *   at small sizes); below 16 nothing is padded and the tiles run on the few-right-hand-side sweeps.
+ * cs3_sens_info: k, p, the side chosen (1 or 2), trans, the number of tiles, the widest solve width, nnz(B), nnz(C) (n for
+ *   an identity operand).
+ * cs3_sens_limits: the constants that shape tiles and launches; needs no device.
+ * cs3_sens_solve_dev: Bx_dev / Ctx_dev the values in the plan's entry order (the value pointer of an identity operand is
+ *   ignored), Y_dev [p, k].  Asynchronous on `stream`.  Checks, in this order: null arguments, a plan made for another
+ *   handle: CS3_ERR_ARG; no successful factorisation: CS3_ERR_STATE.
+ *   Workspace: one tile buffer of n x (widest width) doubles on the handle and the plan's tables, allocated by the first
+ *   call; later calls neither allocate nor synchronise.
+ * cs3_sens_solve: the same from host arrays (synchronises); the same bits.  Its device copies of the values and of Y
+ *   stay on the plan.
+ * Every sum runs in storage order, product rounded before the add, without atomics: the same bits on every run; a unit
+ * value hands the solution's bits over unchanged.  A NaN value in B reaches exactly its column of Y, one in C its row.
+ * A plan survives refactorisations of its handle.  Plans and handle may be freed in either order: freeing the handle
+ * releases the device memory of its plans, which can then only be freed (a solve with one is CS3_ERR_ARG).
+ * On a matched handle indices are in A's rows and columns, as everywhere.
+ *
+ * Out of scope: skipping the fronts off the elimination-tree paths of the nonzero rows inside the sweeps; batched and
+ * Schur handles; a sparse Y; the dense inverse; more than one op per plan. */
+typedef struct cs3_sens_s *cs3_sens;
+typedef struct cs3_sens_info_t {
+    int64_t k, p, side, trans, ntiles, max_width, nnz_b, nnz_c;
+} cs3_sens_info_t;
+typedef struct cs3_sens_limits_t {
+    int64_t max_tile;          /* solved-for columns per tile (CS3_SENS_TILE lowers it per plan) */
+    int64_t pad_width;         /* a narrower last tile is padded to this width; a lower CS3_SENS_TILE runs unpadded */
+    int64_t scatter_rows;      /* rows of the tile per k_sens_scatter workgroup */
+    int64_t scatter_threads;   /* its threads: thread j owns tile columns j, j + scatter_threads, ... */
+    int64_t combine_cols;      /* columns of the other operand per k_sens_combine workgroup */
+    int64_t combine_lanes;     /* tile columns per k_sens_combine workgroup */
+    int64_t tblock;            /* block edge of the transposing store (side left): contiguous doubles per row of Y */
+} cs3_sens_limits_t;
+int cs3_sens_limits(cs3_sens_limits_t *out);
+int cs3_sens_plan(cs3_handle h, int64_t k, const int32_t *Bp, const int32_t *Bi, int64_t p, const int32_t *Ctp,
+                  const int32_t *Cti, int64_t side, int64_t trans, cs3_sens *out);
+int cs3_sens_free(cs3_sens s);
+int cs3_sens_info(cs3_sens s, cs3_sens_info_t *out);
+int cs3_sens_solve_dev(cs3_handle h, cs3_sens s, const double *Bx_dev, const double *Ctx_dev, double *Y_dev, void *stream);
+int cs3_sens_solve(cs3_handle h, cs3_sens s, const double *Bx, const double *Ctx, double *Y);
+
 /* ---- Schur complements: factor the interior, return the dense border -----
  * A partial factorisation, as cuDSS, PARDISO, MUMPS and SuperLU_DIST offer it: the caller names ns variables that are NOT
  * eliminated (boundary buses of a network equivalent, the constraint rows of a saddle-point system [[H, G'], [G, 0]], the
@@ -430,7 +496,7 @@ int cs3_updates_solve(cs3_handle h, cs3_updates u, const double *cx, const doubl
  * and therefore returns sign and log|det| of A11 (log|det A| = log|det A11| + log|det S|).
  * These return CS3_ERR_ARG with a message that says why -- they would silently answer for A22 - S + I in place of A22:
  * cs3_solve*, cs3_solve_t*, the one-sided sweeps (cs3_lsolve, cs3_usolve, cs3_ltsolve, cs3_utsolve and their _dev forms),
- * cs3_factor_solve_dev, cs3_factor_solve_bx_dev, cs3_refine*, cs3_condest*, cs3_updates_plan, cs3_get_factors, cs3_export_factor_dev,
+ * cs3_factor_solve_dev, cs3_factor_solve_bx_dev, cs3_refine*, cs3_condest*, cs3_updates_plan, cs3_sens_plan, cs3_get_factors, cs3_export_factor_dev,
  * cs3_import_factor_dev.
  *
  * Out of scope: matched handles (a row matching breaks the symmetric partition into interior and border); transposed
@@ -490,6 +556,11 @@ int64_t cs3_debug_live_device_buffers(void);
  * first case, its number of cases, its touched rows and the number of right-hand sides it is solved with (the touched rows
  * rounded up to a multiple of 64, at most the tile width).  Diagnostics, tests and tools. */
 int64_t cs3_debug_updates_tiles(cs3_updates u, int32_t *first_case, int32_t *ncases, int32_t *nrows, int32_t *width);
+/* diagnostics, for timing: the steps of a cs3_sens_solve_dev call selected by the mask `parts` (1: k_sens_scatter, 2: the
+ * solves, 4: k_sens_combine), over all tiles of the plan, on whatever the tile buffer holds.  Arguments and checks as for
+ * cs3_sens_solve_dev; parts outside 1 .. 7: CS3_ERR_ARG. */
+int cs3_debug_sens_parts(cs3_handle h, cs3_sens s, int64_t parts, const double *Bx_dev, const double *Ctx_dev, double *Y_dev,
+                         void *stream);
 /* Factorisation schedule: supernode id, front order r and width w per schedule slot. */
 int cs3_debug_schedule(cs3_handle h, int32_t *sched, int32_t *front_r, int32_t *front_w);
 /* The bottom forest (subtrees of small fronts walked by one workgroup each, all in one launch): returns the
