@@ -1180,6 +1180,31 @@ int cs3_debug_schedule(cs3_handle h, int32_t *sched, int32_t *front_r, int32_t *
     return CS3_OK;
 }
 
+int64_t cs3_debug_launch_plan(cs3_handle h, int32_t op, int64_t nrhs, int32_t trans, int32_t *rows, int64_t cap)
+{
+    if (guard(h)) return -1;
+    if (op < 0 || op > 5 || (op != 0 && (nrhs < 1 || nrhs > INT_MAX))) { set_error("cs3_debug_launch_plan: bad operation or number of right-hand sides"); return -1; }
+    const Symbolic &S = h->S;
+    const SweepCall call = select_sweep_schedule(h, (int) nrhs, (op == 1 || op == 2) && trans && S.kind == CS3_LU);
+    ScheduleInput in;
+    in.fgroups = &S.groups; in.sgroups = call.groups;
+    in.kind = S.kind; in.nrhs = (op == 0) ? 0 : (int) nrhs; in.batch = h->batch;
+    in.forest = !S.sub_forest.empty();
+    in.forest_sweeps = call.groups == &S.sgroups1;
+    in.fwd_in_factor = op == 3 && nrhs == 1 && in.forest;       // (run_factor_solve)
+    LaunchPlan plan = (op == 0) ? plan_factor_levels(in) : (op == 3) ? plan_factor_with_forward(in) : plan_solve_levels(in, op == 1 || op == 4);
+    if (op == 3) {
+        const LaunchPlan back = plan_solve_levels(in, false);
+        plan.insert(plan.end(), back.begin(), back.end());
+    }
+    for (size_t i = 0; rows && i < plan.size() && (int64_t) i < cap; ++i) {
+        const PlanStep &s = plan[i];
+        const int32_t row[10] = {s.kind, s.slot, s.g.first, s.g.count, s.g.cls, s.g.level, s.g.max_r, s.g.max_w, s.arg, s.event};
+        std::copy(row, row + 10, rows + 10 * i);
+    }
+    return (int64_t) plan.size();
+}
+
 int64_t cs3_debug_forest(cs3_handle h, int32_t *supernode, int32_t *task, int32_t *level, int32_t *tier)
 {
     if (guard(h)) return -1;

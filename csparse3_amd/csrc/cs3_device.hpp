@@ -181,6 +181,65 @@ struct ForkJoin {
     void rewind() { next = 0; }
 };
 
+// ---- the launch schedule (schedule.cpp plans it, kernels.hip issues it) ---------------------------------------------
+// Sizes of the kernels in kernels.hip that the schedule depends on.
+constexpr int BIG_NB = 32;                 // big fronts: pivots per block-step launch
+constexpr int SOLVE_BW = 64;               // the triangles of the block sweeps
+constexpr int BIG_CW = 2 * SOLVE_BW;       // big-front sweeps, few right-hand sides: columns per chunk launch ...
+constexpr int BIG_CW4 = 4 * SOLVE_BW;      //   ... of a front with more than BIG_CW pivots
+constexpr int BIG_SR4 = 32;                // rows of a workgroup's slice (16 threads per row, 16 columns each)
+constexpr int BIG_KT = 8;                  // right-hand sides per workgroup of the multi-vector chunk step
+constexpr int GC = 64;                     // GEMM sweeps: pivots per chunk
+constexpr int RHS_LANES_MIN = 16;          // from this many right-hand sides on, SK_SMALL fronts run lane = right-hand side
+                                           //   and the fronts of order > 64 sweep as GEMMs
+// pivots per block step: 16 keeps the kernel within 128 registers, i.e. two workgroups per CU (its phases are serial and
+// latency-bound: 512 matrices took 809 us with one workgroup per CU, in two rounds; the 32-pivot form of round 2a is gone)
+constexpr int WG_NB = 16;
+constexpr int PROMOTE_MAX = 16;            // (8 .. 200 measured identical on config 3: only the top three levels hold such a group)
+
+// A plan = the launches, event records and stream waits of one factorisation, sweep or factorisation with forward sweep,
+// in the order they are issued.  Stream slot 0 is the caller's stream, 1 .. NSIDE are ForkJoin::side, SLOT_AUX is
+// ForkJoin::aux; events are numbered from 0 in the order of their first record.
+enum StepKind : int {
+    STEP_FRONT_GROUP = 0,         // one call of launch_front_group (every class that is a single launch)
+    STEP_BIG_GATHER, STEP_BIG_BLOCK /* arg: block */, STEP_SCHUR_TAKE,
+    STEP_SWEEP_FWD, STEP_SWEEP_BWD,                   // one call of launch_solve_group
+    STEP_FWD_BIG_PRE, STEP_FWD_BIG_CHUNK /* arg: chunk */, STEP_BWD_BIG_PRE, STEP_BWD_BIG_CHUNK /* arg: chunk */,
+    STEP_RECORD, STEP_WAIT                            // event on / stream behind: slot, event
+};
+constexpr int SLOT_AUX = 4;
+struct PlanStep {
+    int kind, slot;
+    LaunchGroup g;                // launches: the group (after factor_groups / sweep_groups)
+    int arg, event;               // -1 where there is none
+};
+using LaunchPlan = std::vector<PlanStep>;
+
+// What the schedule depends on, and nothing else.
+struct ScheduleInput {
+    const std::vector<LaunchGroup> *fgroups = nullptr;   // Symbolic::groups
+    const std::vector<LaunchGroup> *sgroups = nullptr;   // Symbolic::sgroups, or sgroups1 when the sweeps follow the forest schedule
+    int kind = CS3_LU, nrhs = 0;
+    long long batch = 1;
+    bool forest = false, forest_sweeps = false;          // a bottom forest exists; the sweeps follow its schedule (sgroups1)
+    bool fwd_in_factor = false;                          // SweepCall::fwd_in_factor
+};
+LaunchPlan plan_factor_levels(const ScheduleInput &in);
+LaunchPlan plan_solve_levels(const ScheduleInput &in, bool forward);
+LaunchPlan plan_factor_with_forward(const ScheduleInput &in);
+
+// Sweeps over a group of wide big fronts: a preparation launch, then one launch per chunk of columns.
+struct BigSweepPlan {
+    bool wide, multi;       // several 64-blocks per launch (latency-bound); BIG_KT right-hand sides per workgroup
+    bool no_init;           // the backward sweep's first chunk launch reads X itself (k_bwd_big_step4, xmode)
+    int cw, nchunk, slices;
+    unsigned by, by_multi;
+};
+BigSweepPlan big_sweep_plan(long long batch, const LaunchGroup &g, int nrhs);
+int wg_panel_ld(const LaunchGroup &g);
+size_t wg_lds_bytes(int kind, const LaunchGroup &g);
+bool gemm_sweeps_on();            // CS3_NO_GEMM_SWEEPS=1: many right-hand sides sweep the fronts of order > 64 by substitution
+
 hipError_t prepare_kernels();
 hipError_t launch_poison_lds(hipStream_t st);     // diagnostics: NaN patterns into every CU's LDS
 hipError_t launch_diag_inverses(const DeviceFactor &D, hipStream_t st);

@@ -728,7 +728,7 @@ k_front_mix(const FrontDesc *__restrict__ fdesc, int first,
 // start of the factorisation).  Per front: one gather launch, then per block
 // of BIG_NB pivots a panel launch and a trailing-update launch -- a blocked
 // right-looking LU / Cholesky without pivoting, many workgroups per launch.
-constexpr int BIG_NB = 32;
+// (BIG_NB = 32 pivots per block-step launch: cs3_device.hpp)
 static_assert(BIG_NB == 2 * PAIR_NC, "eliminate_pair splits a block of BIG_NB pivots in two");
 
 __global__ void __launch_bounds__(256)
@@ -2049,7 +2049,7 @@ k_bwd_rhs(const SolveDesc *__restrict__ sd, int first, const int *__restrict__ s
 // with every lane owning one row (whole row prefetched, shuffles for y_k), then
 // all threads apply the chunk to the rows below (one row per thread, 64 loads
 // in flight).
-constexpr int SOLVE_BW = 64;
+// (SOLVE_BW = 64: cs3_device.hpp)
 
 // Triangle of a block [kb, kb + bw), bw <= 64, by one wave: lane = row kb + lane keeps its row of the
 // triangle in registers.  FORWARD: unit lower L (Cholesky: L with its diagonal), else upper U with its
@@ -2304,7 +2304,7 @@ k_fwd_big_gather(const SolveDesc *__restrict__ sd, int first,
 // triangles; partial sums combined in a fixed order).
 // CW = 128 when the sweep is latency-bound (few right-hand sides: half the dependent launches),
 // CW = 64 when there are enough right-hand sides to fill the chip (no idle second block).
-constexpr int BIG_CW = 2 * SOLVE_BW;
+// (BIG_CW = 2 * SOLVE_BW: cs3_device.hpp)
 
 template <int KIND, int CW>
 __global__ void __launch_bounds__(256)
@@ -2391,7 +2391,7 @@ k_fwd_big_step(const SolveDesc *__restrict__ sd, int first, int kb,
 // one right-hand side per workgroup every one of them re-reads the chunk's triangle and its slice of the
 // panel from L2 (64 KB each, 64 MB per launch at 128 right-hand sides: that traffic, not latency, set the
 // launch time); here the operands are read once and applied to BIG_KT vectors.
-constexpr int BIG_KT = 8;
+// (BIG_KT = 8: cs3_device.hpp)
 
 template <int KIND>
 __global__ void __launch_bounds__(256)
@@ -2657,8 +2657,8 @@ k_bwd_big_step(const SolveDesc *__restrict__ sd, int first, int chunk_from_right
 //   phase:  solve 0 | cpl 1, far 2<-0 | solve 1 | cpl 2, far 3<-1, far 3<-0 | solve 2 | cpl 3 | solve 3
 // rhs(i, p): entry i of the front vector before this launch (0 where !p).  On return y[0 .. 256) holds the chunk's
 // solution, zeros past the chunk's width (0 x stale LDS is not 0).
-constexpr int BIG_CW4 = 4 * SOLVE_BW;
-constexpr int BIG_SR4 = 32;                     // rows of a workgroup's slice (16 threads per row, 16 columns each)
+// (BIG_CW4 = 4 * SOLVE_BW columns per launch, BIG_SR4 = 32 rows of a workgroup's slice -- 16 threads per row, 16 columns
+//  each: cs3_device.hpp)
 
 // 64 loads in flight with a 64-bit address each are 128 registers of addresses beside the 128 of data: here a load is a
 // wave-uniform base (scalar registers) plus one 32-bit byte offset that all 64 loads of the lane share.
@@ -3288,7 +3288,7 @@ k_bwd_il(const SolveDesc *__restrict__ sd, int first, const int *__restrict__ st
 // A chunk step is still one launch (chunk c + 1 needs what chunk c did to the rows below it), but takes a few
 // microseconds instead of the 15 to 35 of the substitution kernels, and fronts with up to 64 pivots need one.
 // Every workgroup recomputes Y for its tile (cheap) rather than wait for another one.
-constexpr int GC = 64;                         // pivots per chunk
+// (GC = 64 pivots per chunk: cs3_device.hpp)
 constexpr int GLD = 80;                        // LDS row stride of the 64 x 64 operand tiles: 80 = 16 mod 32 doubles, so the
                                                //   two 16-lane rows of a half-wave's ds_read_b64 fall on disjoint banks
 constexpr size_t GEMM_LDS = 2 * (size_t) GC * GLD * sizeof(double);     // 80 KB: two workgroups per CU
@@ -3916,8 +3916,8 @@ hipError_t launch_restack_values(long long nnz, const int *map, long long na, lo
 }
 
 // ================================================================ launchers ==
-constexpr int RHS_LANES_MIN = 16;          // from this many right-hand sides on, SK_SMALL fronts run lane = right-hand side
-                                           //   and the fronts of order > 64 sweep as GEMMs
+// What is launched where, in what order and behind which event is decided by the planners of schedule.cpp; the functions
+// below launch one step each, issue_plan walks a plan.
 #define CS3_LAUNCH_CHECK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return e_; } while (0)
 
 static int grid_for(long long work, int block, int cap = 4096)
@@ -3927,9 +3927,6 @@ static int grid_for(long long work, int block, int cap = 4096)
     if (g > cap) g = cap;
     return (int) g;
 }
-
-// A group of big fronts = one gather launch, then launches 0 .. nblk of the block step (nblk = closing).
-static int big_group_blocks(const LaunchGroup &g) { return (g.max_w + BIG_NB - 1) / BIG_NB; }
 
 static hipError_t launch_big_gather(const DeviceFactor &D, const LaunchGroup &g, hipStream_t st)
 {
@@ -3958,25 +3955,8 @@ static hipError_t launch_big_block(const DeviceFactor &D, const LaunchGroup &g, 
     return hipSuccess;
 }
 
-// One workgroup per (big front, matrix) when the batch fills the chip by itself and the panels fit the LDS.
-static int wg_panel_ld(const LaunchGroup &g) { return (g.max_r + 1) | 1; }
-// pivots per block step: 16 keeps the kernel within 128 registers, i.e. two workgroups per CU (its phases are serial and
-// latency-bound: 512 matrices took 809 us with one workgroup per CU, in two rounds; the 32-pivot form of round 2a is gone)
-constexpr int WG_NB = 16;
-static int wg_nb() { return WG_NB; }
-static size_t wg_lds_bytes(int kind, const LaunchGroup &g)
-{
-    // (Cholesky, left-looking: the block column + the block's own rows of the factor, 16 x max_w)
-    return ((size_t) wg_nb() * 33 + (size_t) (kind == CS3_LU ? 2 : 1) * wg_nb() * wg_panel_ld(g) +
-            (kind == CS3_LU ? 0 : (size_t) 16 * (size_t) g.max_w)) * sizeof(double);
-}
-bool big_group_in_one_workgroup(int kind, long long batch, const LaunchGroup &g)
-{
-    static const long long min_batch = getenv("CS3_WG_MIN_BATCH") ? atoll(getenv("CS3_WG_MIN_BATCH")) : 48;    // (32 matrices: 1.01 ms in one workgroup each, 0.95 block step by block step; 64: 1.21 / 1.22; 128: 1.56 / 1.70)
-    return g.cls == FC_BIG && batch >= min_batch && wg_lds_bytes(kind, g) <= 150 * 1024;
-}
-
 // (every kernel launch below picks its instance by the rule: with_rule)
+// The classes that are one launch; the planner expands a chain of big fronts and a Schur front into their steps.
 template <int KIND>
 static hipError_t launch_front_group(const DeviceFactor &D, const SweepCall &call, const LaunchGroup &g, const PivotCtl &pc, hipStream_t st)
 {
@@ -4000,16 +3980,7 @@ static hipError_t launch_front_group(const DeviceFactor &D, const SweepCall &cal
         CS3_LAUNCH_CHECK();
         return hipSuccess;
     }
-    if (g.cls == FC_SCHUR) {          // a Schur handle's last front: assembled, taken out, never eliminated (schur.hip)
-        hipError_t e = launch_big_gather(D, g, st);
-        return (e != hipSuccess) ? e : launch_schur_take(D, st);
-    }
-    if (g.cls == FC_BIG) {
-        hipError_t e = launch_big_gather(D, g, st);
-        // one launch per block of BIG_NB pivots, plus the closing launch (last update + last parked block)
-        for (int blk = 0; e == hipSuccess && blk <= big_group_blocks(g); ++blk) e = launch_big_block<KIND>(D, g, blk, pc, st);
-        return e;
-    }
+    if (g.cls == FC_SCHUR || g.cls == FC_BIG) return hipErrorInvalidValue;
     dim3 grid((unsigned) g.count, batch);
     const size_t ld = (size_t) (g.max_r | 1);
     // (front_wave_body, the path of every front with <= 32 pivots, packs the lower triangle for Cholesky; the 16 x 16 thread
@@ -4073,31 +4044,21 @@ hipError_t prepare_kernels()
 {
     // the largest LDS-resident class needs more than the default 64 KiB of dynamic LDS
     const int big = 160 * 1024;
-    hipError_t e;
     using Plain = PivotRule<false>;
     using Perturbed = PivotRule<true>;
-    const void *block_fns[] = {(const void *) k_front_block<CS3_LU, Plain, 16>, (const void *) k_front_block<CS3_LU, Perturbed, 16>,
-                               (const void *) k_front_block<CS3_CHOLESKY, Plain, 16>,
-                               (const void *) k_front_block<CS3_CHOLESKY, Plain, 16, 4>,
-                               (const void *) k_front_wg<CS3_LU, Plain, WG_NB>, (const void *) k_front_wg<CS3_LU, Perturbed, WG_NB>,
-                               (const void *) k_front_wg<CS3_CHOLESKY, Plain, WG_NB>};
-    for (const void *f : block_fns) {
-        e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, big);
-        if (e != hipSuccess) return e;
-    }
-    const void *gemm_fns[] = {(const void *) k_gemm_fwd<CS3_LU>, (const void *) k_gemm_fwd<CS3_CHOLESKY>,
-                              (const void *) k_gemm_bwd<CS3_LU>, (const void *) k_gemm_bwd<CS3_CHOLESKY>,
-                              (const void *) k_gemm_bwd_init<CS3_LU>, (const void *) k_gemm_bwd_init<CS3_CHOLESKY>};
-    for (const void *f : gemm_fns) {
-        e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, big);
-        if (e != hipSuccess) return e;
-    }
-    const void *solve_fns[] = {
-        (const void *) k_fwd_blk<CS3_LU>, (const void *) k_fwd_blk<CS3_CHOLESKY>,
-        (const void *) k_bwd_blk<CS3_LU>, (const void *) k_bwd_blk<CS3_CHOLESKY>,
-        (const void *) k_bwd_big_init<CS3_LU>, (const void *) k_bwd_big_init<CS3_CHOLESKY>};
-    for (const void *f : solve_fns) {
-        e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, big);
+    const void *fns[] = {(const void *) k_front_block<CS3_LU, Plain, 16>, (const void *) k_front_block<CS3_LU, Perturbed, 16>,
+                         (const void *) k_front_block<CS3_CHOLESKY, Plain, 16>,
+                         (const void *) k_front_block<CS3_CHOLESKY, Plain, 16, 4>,
+                         (const void *) k_front_wg<CS3_LU, Plain, WG_NB>, (const void *) k_front_wg<CS3_LU, Perturbed, WG_NB>,
+                         (const void *) k_front_wg<CS3_CHOLESKY, Plain, WG_NB>,
+                         (const void *) k_gemm_fwd<CS3_LU>, (const void *) k_gemm_fwd<CS3_CHOLESKY>,
+                         (const void *) k_gemm_bwd<CS3_LU>, (const void *) k_gemm_bwd<CS3_CHOLESKY>,
+                         (const void *) k_gemm_bwd_init<CS3_LU>, (const void *) k_gemm_bwd_init<CS3_CHOLESKY>,
+                         (const void *) k_fwd_blk<CS3_LU>, (const void *) k_fwd_blk<CS3_CHOLESKY>,
+                         (const void *) k_bwd_blk<CS3_LU>, (const void *) k_bwd_blk<CS3_CHOLESKY>,
+                         (const void *) k_bwd_big_init<CS3_LU>, (const void *) k_bwd_big_init<CS3_CHOLESKY>};
+    for (const void *f : fns) {
+        hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, big);
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
@@ -4133,15 +4094,6 @@ hipError_t ForkJoin::event(hipEvent_t *out)
     return hipSuccess;
 }
 
-// The groups of one level: forward, the end of the run that starts at g; backward, the start of the run that ends at g.
-static size_t level_edge(const std::vector<LaunchGroup> &groups, size_t g, bool forward)
-{
-    const int level = groups[forward ? g : g - 1].level;
-    if (forward) while (g < groups.size() && groups[g].level == level) ++g;
-    else while (g > 0 && groups[g - 1].level == level) --g;
-    return g;
-}
-
 // with_kind for the sweeps: a transposed solve on an LU handle takes the CS3_LU_T instances.
 template <class F>
 static auto with_sweep_kind(int kind, bool trans, F &&f)
@@ -4150,85 +4102,9 @@ static auto with_sweep_kind(int kind, bool trans, F &&f)
     return with_kind(kind, f);
 }
 
-// Run the launch groups of one tree level concurrently: the first on `st`, the others on side
-// streams that fork from `st` and join it again.  `launch(group, stream)` enqueues one group.
-template <class Launch>
-static hipError_t run_level(const std::vector<LaunchGroup> &groups, size_t g0, size_t g1, hipStream_t st,
-                            ForkJoin &fj, bool parallel, Launch launch)
-{
-    const size_t ng = g1 - g0;
-    if (ng <= 1) return ng ? launch(groups[g0], st) : hipSuccess;
-    if (!parallel) {
-        for (size_t i = g0; i < g1; ++i) { hipError_t e = launch(groups[i], st); if (e != hipSuccess) return e; }
-        return hipSuccess;
-    }
-    hipEvent_t fork;
-    hipError_t e = fj.event(&fork);
-    if (e != hipSuccess) return e;
-    if ((e = hipEventRecord(fork, st)) != hipSuccess) return e;
-    // the heaviest group (last: big fronts / block kernels sort last) stays on the main stream and is captured FIRST: the
-    // runtime keeps a node's first captured dependent in the node's own hardware queue (launch_factor_with_forward)
-    if ((e = launch(groups[g1 - 1], st)) != hipSuccess) return e;
-    for (size_t i = 0; i + 1 < ng; ++i) {
-        hipStream_t s = fj.side[i % ForkJoin::NSIDE];
-        if (i < (size_t) ForkJoin::NSIDE) { if ((e = hipStreamWaitEvent(s, fork, 0)) != hipSuccess) return e; }
-        if ((e = launch(groups[g0 + i], s)) != hipSuccess) return e;
-    }
-    for (size_t i = 0; i < std::min(ng - 1, (size_t) ForkJoin::NSIDE); ++i) {
-        hipEvent_t j;
-        if ((e = fj.event(&j)) != hipSuccess) return e;
-        if ((e = hipEventRecord(j, fj.side[i])) != hipSuccess) return e;
-        if ((e = hipStreamWaitEvent(st, j, 0)) != hipSuccess) return e;
-    }
-    return hipSuccess;
-}
-
-static std::vector<LaunchGroup> factor_groups(const DeviceFactor &D, const std::vector<LaunchGroup> &groups);
-
-hipError_t launch_factor_levels(const DeviceFactor &D, const SweepCall &call, const std::vector<LaunchGroup> &all_groups,
-                                const PivotCtl &pc, hipStream_t st, ForkJoin &fj)
-{
-    const std::vector<LaunchGroup> groups = factor_groups(D, all_groups);
-    fj.rewind();                         // (the big-front buffers were zeroed by launch_prologue)
-    for (size_t g0 = 0; g0 < groups.size(); ) {
-        const size_t g1 = level_edge(groups, g0, true);
-        hipError_t e = run_level(groups, g0, g1, st, fj, true, [&](const LaunchGroup &g, hipStream_t s) {
-            return with_kind(D.kind, [&](auto K) { return launch_front_group<K>(D, call, g, pc, s); });
-        });
-        if (e != hipSuccess) return e;
-        g0 = g1;
-    }
-    return hipSuccess;
-}
-
-// Sweeps over a group of wide big fronts: a preparation launch, then one launch per chunk of columns.
-struct BigSweepPlan {
-    bool wide, multi;       // several 64-blocks per launch (latency-bound); BIG_KT right-hand sides per workgroup
-    bool no_init;           // the backward sweep's first chunk launch reads X itself (k_bwd_big_step4, xmode)
-    int cw, nchunk, slices;
-    unsigned by, by_multi;
-};
-
-static BigSweepPlan big_sweep_plan(const DeviceFactor &D, const LaunchGroup &g, int nrhs)
-{
-    BigSweepPlan pl;
-    pl.by = (unsigned) (D.batch * nrhs);
-    pl.wide = (long long) D.batch * nrhs < 8;
-    pl.multi = nrhs >= BIG_KT;
-    pl.by_multi = (unsigned) (D.batch * ((nrhs + BIG_KT - 1) / BIG_KT));
-    // latency-bound: two blocks per launch, four where that saves a launch
-    pl.cw = pl.wide ? (g.max_w > BIG_CW ? BIG_CW4 : BIG_CW) : SOLVE_BW;
-    // one front without rows of ancestors (the dense root): nothing for k_bwd_big_init to subtract
-    pl.no_init = pl.cw == BIG_CW4 && g.count == 1 && g.max_r == g.max_w;
-    pl.nchunk = (g.max_w + pl.cw - 1) / pl.cw;
-    const int sr = (pl.cw == BIG_CW4) ? BIG_SR4 : 64;       // rows of a workgroup's slice
-    pl.slices = std::max(1, (g.max_r + sr - 1) / sr);
-    return pl;
-}
-
 static hipError_t launch_fwd_big_pre(const DeviceFactor &D, const SweepCall &call, const LaunchGroup &g, double *X, int nrhs, hipStream_t st)
 {
-    const BigSweepPlan pl = big_sweep_plan(D, g, nrhs);
+    const BigSweepPlan pl = big_sweep_plan(D.batch, g, nrhs);
     hipLaunchKernelGGL(k_fwd_big_gather, dim3(1, pl.by, g.count), dim3(256), 0, st, call.sd, g.first, D.fasm_src,
                        D.fasm_tgt, D.flong_src, D.cv, X, D.bigv, nrhs, D.cv_size * (long long) nrhs, D.n * (long long) nrhs, D.bv_size);
     CS3_LAUNCH_CHECK();
@@ -4239,7 +4115,7 @@ template <int KIND>
 static hipError_t launch_fwd_big_chunk(const DeviceFactor &D, const SweepCall &call, const LaunchGroup &g, double *X, int nrhs, int c,
                                        hipStream_t st)
 {
-    const BigSweepPlan pl = big_sweep_plan(D, g, nrhs);
+    const BigSweepPlan pl = big_sweep_plan(D.batch, g, nrhs);
     const long long xs = D.n * (long long) nrhs, cvs = D.cv_size * (long long) nrhs;
     if (pl.cw == BIG_CW4)
         hipLaunchKernelGGL((k_fwd_big_step4<KIND>), dim3(pl.slices, pl.by, g.count), dim3(512), 0, st, call.sd,
@@ -4260,7 +4136,7 @@ static hipError_t launch_fwd_big_chunk(const DeviceFactor &D, const SweepCall &c
 template <int KIND>
 static hipError_t launch_bwd_big_pre(const DeviceFactor &D, const SweepCall &call, const LaunchGroup &g, double *X, int nrhs, hipStream_t st)
 {
-    const BigSweepPlan pl = big_sweep_plan(D, g, nrhs);
+    const BigSweepPlan pl = big_sweep_plan(D.batch, g, nrhs);
     const size_t lds = (size_t) std::max(1, g.max_r) * sizeof(double);
     hipLaunchKernelGGL((k_bwd_big_init<KIND>), dim3(2, pl.by, g.count), dim3(256), lds, st, call.sd, g.first,
                        D.st_idx, D.pool_pm, X, D.bigv, nrhs, D.pm_stride, D.n * (long long) nrhs, D.bv_size);
@@ -4272,7 +4148,7 @@ template <int KIND>
 static hipError_t launch_bwd_big_chunk(const DeviceFactor &D, const SweepCall &call, const LaunchGroup &g, double *X, int nrhs, int c,
                                        hipStream_t st)
 {
-    const BigSweepPlan pl = big_sweep_plan(D, g, nrhs);
+    const BigSweepPlan pl = big_sweep_plan(D.batch, g, nrhs);
     const long long xs = D.n * (long long) nrhs;
     if (pl.cw == BIG_CW4)
         hipLaunchKernelGGL((k_bwd_big_step4<KIND>), dim3(pl.slices, pl.by, g.count), dim3(512), 0, st, call.sd,
@@ -4301,24 +4177,6 @@ static hipError_t launch_inv_tasks(const DeviceFactor &D, int t0, int t1, hipStr
                        D.pool_pm, D.pm_stride, D.dinv, D.dinv_size);
     CS3_LAUNCH_CHECK();
     return hipSuccess;
-}
-
-// CS3_NO_GEMM_SWEEPS=1: many right-hand sides sweep the fronts of order > 64 with the substitution kernels
-static bool gemm_sweeps_on()
-{
-    static const bool on = !(getenv("CS3_NO_GEMM_SWEEPS") && getenv("CS3_NO_GEMM_SWEEPS")[0] == '1');
-    return on;
-}
-
-// The permutations can ride on the sweeps when every pivot row of X is read (forward) and written (backward) by a kernel
-// that knows the row map: the lane = right-hand-side kernels and the GEMM sweeps, i.e. 16 or more right-hand sides, no
-// interleaved batch, GEMM sweeps on.
-bool permutation_can_fuse(const DeviceFactor &D, int nrhs)
-{
-    // (measured on config 4: the extra row-map round trip per front costs more than the two permutation kernels below a
-    // few hundred right-hand sides; at 1024 the fused form saves 0.14 ms of 2.3)
-    constexpr int min_rhs = 256;
-    return gemm_sweeps_on() && nrhs >= std::max(min_rhs, RHS_LANES_MIN) && D.il_len == 0;
 }
 
 hipError_t launch_diag_inverses(const DeviceFactor &D, hipStream_t st)
@@ -4445,13 +4303,8 @@ static hipError_t launch_solve_group(const DeviceFactor &D, const SweepCall &cal
                 hipLaunchKernelGGL((k_bwd_wave<KIND, KT>), grid, dim3(256), 0, st, call.sd, g.first, g.count, D.st_idx,
                                    D.pool_pm, X, nrhs, D.pm_stride, xs);
         }
-    } else if (g.cls == SK_BIG) {
-        const BigSweepPlan pl = big_sweep_plan(D, g, nrhs);
-        hipError_t e = forward ? launch_fwd_big_pre(D, call, g, X, nrhs, st)
-                               : pl.no_init ? hipSuccess : launch_bwd_big_pre<KIND>(D, call, g, X, nrhs, st);
-        for (int c = 0; e == hipSuccess && c < pl.nchunk; ++c)
-            e = forward ? launch_fwd_big_chunk<KIND>(D, call, g, X, nrhs, c, st) : launch_bwd_big_chunk<KIND>(D, call, g, X, nrhs, c, st);
-        return e;
+    } else if (g.cls == SK_BIG) {          // (the planner expands it: preparation launch, then a launch per chunk)
+        return hipErrorInvalidValue;
     } else {
         dim3 grid((unsigned) g.count, (unsigned) D.batch, (unsigned) nrhs);
         const size_t lds = (size_t) (g.max_r + 1 + SOLVE_BW) * sizeof(double);
@@ -4466,272 +4319,67 @@ static hipError_t launch_solve_group(const DeviceFactor &D, const SweepCall &cal
     return hipSuccess;
 }
 
-// With few right-hand sides SK_SMALL and SK_WAVE fronts share the one-wave-per-front kernels:
-// the two groups of a level are adjacent in the schedule and go out as one launch.
-// A handful of small fronts beside the level's workgroup-per-front group (the top of the tree) join that group: a second
-// launch for four fronts costs a dependent launch (sweeps, 11 us) or a fork and a join across hardware queues
-// (factorisation, 13 us), the workgroup kernels take fronts of any order.
-static int promote_max()
+// Issue a plan: stream slots to streams, events from the pool in plan order, one launcher per step.
+static hipError_t issue_plan(const DeviceFactor &D, const SweepCall &call, const LaunchPlan &plan, const PivotCtl &pc, double *X,
+                             int nrhs, hipStream_t st, ForkJoin &fj)
 {
-    return 16;                                   // (8 .. 200 measured identical on config 3: only the top three levels hold such a group)
-}
-
-static void absorb_small_group(std::vector<LaunchGroup> &out, const LaunchGroup &g, int small_cls, int wg_cls)
-{
-    if (!out.empty() && out.back().level == g.level && out.back().cls == small_cls && g.cls == wg_cls &&
-        out.back().count <= promote_max() && out.back().first + out.back().count == g.first) {
-        LaunchGroup &m = out.back();
-        m.cls = wg_cls; m.count += g.count;
-        m.max_r = std::max(m.max_r, g.max_r); m.max_w = std::max(m.max_w, g.max_w);
-        m.n16 = 0;
-    } else {
-        out.push_back(g);
-    }
-}
-
-static std::vector<LaunchGroup> sweep_groups(const std::vector<LaunchGroup> &groups, int nrhs, long long batch)
-{
-    if (nrhs >= RHS_LANES_MIN) return groups;
-    std::vector<LaunchGroup> merged, out;
-    for (const LaunchGroup &g : groups) {
-        if (!merged.empty() && merged.back().level == g.level && merged.back().cls == SK_SMALL && g.cls == SK_WAVE &&
-            merged.back().first + merged.back().count == g.first) {
-            LaunchGroup &m = merged.back();
-            m.cls = SK_WAVE; m.count += g.count;
-            m.max_r = std::max(m.max_r, g.max_r); m.max_w = std::max(m.max_w, g.max_w);
-        } else {
-            merged.push_back(g);
+    fj.rewind();                         // (the big-front buffers were zeroed by launch_prologue)
+    for (const PlanStep &s : plan) {
+        const LaunchGroup &g = s.g;
+        hipStream_t q = (s.slot == 0) ? st : (s.slot == SLOT_AUX) ? fj.aux : fj.side[s.slot - 1];
+        hipError_t e = hipSuccess;
+        switch (s.kind) {
+        case STEP_FRONT_GROUP: e = with_kind(D.kind, [&](auto K) { return launch_front_group<K>(D, call, g, pc, q); }); break;
+        case STEP_BIG_GATHER: e = launch_big_gather(D, g, q); break;
+        case STEP_BIG_BLOCK: e = with_kind(D.kind, [&](auto K) { return launch_big_block<K>(D, g, s.arg, pc, q); }); break;
+        case STEP_SCHUR_TAKE: e = launch_schur_take(D, q); break;
+        case STEP_SWEEP_FWD: case STEP_SWEEP_BWD:
+            e = with_sweep_kind(D.kind, call.trans, [&](auto K) { return launch_solve_group<K>(D, call, g, X, nrhs, s.kind == STEP_SWEEP_FWD, q); });
+            break;
+        case STEP_FWD_BIG_PRE: e = launch_fwd_big_pre(D, call, g, X, nrhs, q); break;
+        case STEP_FWD_BIG_CHUNK: e = with_sweep_kind(D.kind, call.trans, [&](auto K) { return launch_fwd_big_chunk<K>(D, call, g, X, nrhs, s.arg, q); }); break;
+        case STEP_BWD_BIG_PRE: e = with_sweep_kind(D.kind, call.trans, [&](auto K) { return launch_bwd_big_pre<K>(D, call, g, X, nrhs, q); }); break;
+        case STEP_BWD_BIG_CHUNK: e = with_sweep_kind(D.kind, call.trans, [&](auto K) { return launch_bwd_big_chunk<K>(D, call, g, X, nrhs, s.arg, q); }); break;
+        case STEP_RECORD: {
+            hipEvent_t fresh;            // an event's first record takes it from the pool
+            if ((size_t) s.event == fj.next) e = fj.event(&fresh);
+            if (e == hipSuccess) e = hipEventRecord(fj.events[s.event], q);
+            break;
         }
+        case STEP_WAIT: e = hipStreamWaitEvent(q, fj.events[s.event], 0); break;
+        default: e = hipErrorInvalidValue;
+        }
+        if (e != hipSuccess) return e;
     }
-    if (batch != 1) return merged;       // (a batch fills the chip with waves: one per front stays cheaper)
-    for (const LaunchGroup &g : merged) absorb_small_group(out, g, SK_WAVE, SK_BLOCK);
-    return out;
+    return hipSuccess;
 }
 
-// the same for the factorisation of a single matrix: few fronts of order <= 64 beside the level's LDS-image fronts
-static std::vector<LaunchGroup> factor_groups(const DeviceFactor &D, const std::vector<LaunchGroup> &groups)
+static ScheduleInput schedule_input(const DeviceFactor &D, const SweepCall &call, const std::vector<LaunchGroup> *fgroups, int nrhs)
 {
-    if (D.batch != 1) return groups;
-    std::vector<LaunchGroup> out;
-    for (const LaunchGroup &g : groups) absorb_small_group(out, g, FC_R64, FC_LDS);
-    return out;
+    ScheduleInput in;
+    in.fgroups = fgroups; in.sgroups = call.groups;
+    in.kind = D.kind; in.nrhs = nrhs; in.batch = D.batch;
+    in.forest = !D.sub_forest.empty();
+    in.forest_sweeps = in.forest && call.sd == D.sdesc1;
+    in.fwd_in_factor = call.fwd_in_factor;
+    return in;
+}
+
+hipError_t launch_factor_levels(const DeviceFactor &D, const SweepCall &call, const std::vector<LaunchGroup> &groups,
+                                const PivotCtl &pc, hipStream_t st, ForkJoin &fj)
+{
+    return issue_plan(D, call, plan_factor_levels(schedule_input(D, call, &groups, 0)), pc, nullptr, 0, st, fj);
 }
 
 hipError_t launch_solve_levels(const DeviceFactor &D, const SweepCall &call, double *X, int nrhs, bool forward, hipStream_t st, ForkJoin &fj)
 {
-    const std::vector<LaunchGroup> groups = sweep_groups(*call.groups, nrhs, D.batch);
-    fj.rewind();
-    // one right-hand side: the per-level launches are short, fork/join costs more than it hides (measured), so they stay
-    // in line.  Many right-hand sides: the lane = right-hand-side group and the GEMM group of a level take 10-40 us each
-    // and are independent -- side by side they save 60 us of 1.73 ms at 1024 right-hand sides, 24 us of 0.83 at 128.
-    // (re-measured with the fronts of order 33-64 on the GEMM sweeps: the fork now pays from 512 right-hand sides on only
-    //  -- 128: 0.82 ms forked, 0.77 in line; 256: equal; 1024: equal to 0.5 %)
-    const bool solve_parallel = nrhs >= 512;
-    auto launch = [&](const LaunchGroup &g, hipStream_t s) {
-        return with_sweep_kind(D.kind, call.trans, [&](auto K) { return launch_solve_group<K>(D, call, g, X, nrhs, forward, s); });
-    };
-    if (forward) {
-        for (size_t g0 = 0; g0 < groups.size(); ) {
-            const size_t g1 = level_edge(groups, g0, true);
-            hipError_t e = run_level(groups, g0, g1, st, fj, solve_parallel, launch);
-            if (e != hipSuccess) return e;
-            g0 = g1;
-        }
-    } else {
-        for (size_t g1 = groups.size(); g1 > 0; ) {
-            const size_t g0 = level_edge(groups, g1, false);
-            hipError_t e = run_level(groups, g0, g1, st, fj, solve_parallel, launch);
-            if (e != hipSuccess) return e;
-            g1 = g0;
-        }
-    }
-    return hipSuccess;
+    return issue_plan(D, call, plan_solve_levels(schedule_input(D, call, nullptr, nrhs), forward), PivotCtl{}, X, nrhs, st, fj);
 }
 
-// Rough cost of a launch group in dependent-launch units, to place the fork below.
-static int factor_group_cost(const LaunchGroup &g)
-{
-    return (g.cls == FC_BIG) ? 4 * ((g.max_w + BIG_NB - 1) / BIG_NB + 2) : 2;
-}
-static int sweep_group_cost(const LaunchGroup &g)
-{
-    return (g.cls == SK_BIG) ? 2 + (g.max_w + BIG_CW - 1) / BIG_CW : 1;
-}
-
-// Factorisation with the forward sweep partly hidden behind it.  The sweep of levels 0..K needs only
-// the panels of those levels, so once level K is factorised it runs on fj.aux beside the
-// factorisation of levels K+1.. (the tail of the tree: few, large fronts, many dependent launches).
-// K is the last level whose tail is still long enough to cover the sweep; one fork, one join -- a
-// fork per level costs more than it hides (measured).  Same kernels, same operands: same bits.
-hipError_t launch_factor_with_forward(const DeviceFactor &D, const SweepCall &call, const std::vector<LaunchGroup> &all_fgroups,
+hipError_t launch_factor_with_forward(const DeviceFactor &D, const SweepCall &call, const std::vector<LaunchGroup> &fgroups,
                                       const PivotCtl &pc, double *X, int nrhs, hipStream_t st, ForkJoin &fj)
 {
-    hipError_t e;
-    if (!D.sub_forest.empty() && call.sd != D.sdesc1) {
-        // a bottom forest under the factorisation, but sweeps on the level schedule of the whole tree (several right-hand
-        // sides): the two number their levels differently, so nothing is overlapped
-        if ((e = launch_factor_levels(D, call, all_fgroups, pc, st, fj)) != hipSuccess) return e;
-        return launch_solve_levels(D, call, X, nrhs, true, st, fj);
-    }
-    const std::vector<LaunchGroup> fgroups = factor_groups(D, all_fgroups);
-    const std::vector<LaunchGroup> sgroups = sweep_groups(*call.groups, nrhs, D.batch);
-    fj.rewind();
-    const int nlevels = fgroups.empty() ? 0 : fgroups.back().level + 1;
-    std::vector<long long> tail(nlevels + 1, 0), head(nlevels + 1, 0);   // factor cost of levels >= l; sweep cost of levels < l
-    for (const LaunchGroup &g : fgroups) tail[g.level] += factor_group_cost(g);
-    for (int l = nlevels - 1; l >= 0; --l) tail[l] += tail[l + 1];
-    // (the bottom forest, when its factor launch carries the forward sweep, has nothing left to sweep)
-    for (const LaunchGroup &g : sgroups) head[g.level + 1] += (g.cls == SK_SUB && call.fwd_in_factor) ? 0 : sweep_group_cost(g);
-    for (int l = 0; l < nlevels; ++l) head[l + 1] += head[l];
-    int fork_level = -1;
-    static const bool overlap = !(getenv("CS3_NO_OVERLAP") && getenv("CS3_NO_OVERLAP")[0] == '1');
-    for (int l = 0; overlap && l + 1 < nlevels; ++l)
-        if (tail[l + 1] >= head[l + 1]) fork_level = l;
-
-    auto sweep = [&](int lo, int hi, hipStream_t s) -> hipError_t {      // forward sweep of levels lo..hi
-        for (const LaunchGroup &g : sgroups) {
-            if (g.level < lo || g.level > hi) continue;
-            if (g.cls == SK_SUB && call.fwd_in_factor) continue;
-            hipError_t se = with_sweep_kind(D.kind, call.trans,
-                                            [&](auto K) { return launch_solve_group<K>(D, call, g, X, nrhs, true, s); });
-            if (se != hipSuccess) return se;
-        }
-        return hipSuccess;
-    };
-    // BATCHES: every level is a launch of 100 us or more, so a cross-queue edge (5-10 us) per level is cheap and the
-    // forward sweep follows the factorisation level by level on fj.aux -- sweep level l as soon as level l is factorised --
-    // instead of waiting for the fork level (round 3; kernel trace of 512 matrices: the sweep of levels 1..9, 400 us of
-    // small launches, ran after the root with nothing beside it).  Sweep level l is CAPTURED after factor level l + 1, so
-    // that the factor chain stays the first captured dependent of its own nodes (see below).
-    if (overlap && D.batch >= 16 && nlevels >= 2) {
-        hipEvent_t pending = nullptr;
-        int pending_level = -1;
-        auto flush = [&]() -> hipError_t {
-            if (!pending) return hipSuccess;
-            hipError_t fe;
-            if ((fe = hipStreamWaitEvent(fj.aux, pending, 0)) != hipSuccess) return fe;
-            fe = sweep(pending_level, pending_level, fj.aux);
-            pending = nullptr;
-            return fe;
-        };
-        for (size_t f0 = 0; f0 < fgroups.size(); ) {
-            const int level = fgroups[f0].level;
-            const size_t f1 = level_edge(fgroups, f0, true);
-            e = run_level(fgroups, f0, f1, st, fj, true, [&](const LaunchGroup &g, hipStream_t s2) {
-                return with_kind(D.kind, [&](auto K) { return launch_front_group<K>(D, call, g, pc, s2); });
-            });
-            if (e != hipSuccess) return e;
-            if ((e = flush()) != hipSuccess) return e;
-            if ((e = fj.event(&pending)) != hipSuccess) return e;
-            if ((e = hipEventRecord(pending, st)) != hipSuccess) return e;
-            pending_level = level;
-            f0 = f1;
-        }
-        if ((e = flush()) != hipSuccess) return e;
-        hipEvent_t done;
-        if ((e = fj.event(&done)) != hipSuccess) return e;
-        if ((e = hipEventRecord(done, fj.aux)) != hipSuccess) return e;
-        return hipStreamWaitEvent(st, done, 0);
-    }
-    // The last level, when it is one group of wide big fronts (the dense root): its forward sweep does not wait
-    // for the end of its factorisation either.  Column block b of the factor is final in F after block launch
-    // b + 1 (k_big_step), so chunk c of the sweep follows on fj.aux as soon as its blocks are home, while the
-    // later blocks are still being factorised.
-    const LaunchGroup *rootf = nullptr, *roots = nullptr;
-    // (with many right-hand sides the root sweeps as GEMMs through launch_solve_group like every other group)
-    if (nrhs < RHS_LANES_MIN && nlevels >= 2 && fork_level == nlevels - 2) {
-        int nf = 0, ns = 0;
-        for (const LaunchGroup &g : fgroups) if (g.level == nlevels - 1) { ++nf; rootf = &g; }
-        for (const LaunchGroup &g : sgroups) if (g.level == nlevels - 1) { ++ns; roots = &g; }
-        if (nf != 1 || ns != 1 || rootf->cls != FC_BIG || roots->cls != SK_BIG || rootf->count != roots->count)
-            rootf = roots = nullptr;
-    }
-    // The side branch is CAPTURED after the next launch of the chain it forks from: the runtime keeps a node's FIRST
-    // captured dependent in the node's own hardware queue and moves the others to another queue, whose first dispatch
-    // then waits 40-60 us (measured: profiles/r02_timeline_fused_step.json) -- the late start must land on the sweep,
-    // which has slack, not on the factorisation.  (Tried and removed, DESIGN.md: the sweep captured first; the block chain
-    // waiting for the side branch before the release; hand-overs through memory words with a waiting kernel.)
-    hipEvent_t swept = nullptr, ready_deferred = nullptr;
-    int root_rest = 0;                             // first chunk of the root's sweep that is still to do after the join
-    for (size_t f0 = 0; f0 < fgroups.size(); ) {
-        const int level = fgroups[f0].level;
-        const size_t f1 = level_edge(fgroups, f0, true);
-        if (rootf && level == nlevels - 1) {
-            const BigSweepPlan pl = big_sweep_plan(D, *roots, nrhs);
-            const int nblk = big_group_blocks(*rootf), cwb = pl.cw / BIG_NB;
-            if ((e = launch_big_gather(D, *rootf, st)) != hipSuccess) return e;
-            // ONE release (every cross-stream edge costs the block chain about 10 us): the first k chunks go to
-            // fj.aux after block launch k * cwb, k the largest count that the remaining launches still cover (one launch
-            // of slack: the side queue starts a chunk 10-15 us after its release); the other chunks follow on st after
-            // the join.
-            int k = 0;
-            while (k < pl.nchunk && (k + 1) * cwb <= nblk && nblk - (k + 1) * cwb >= k + 2) ++k;
-            hipEvent_t home = nullptr;
-            bool side_started = false;
-            auto start_side = [&]() -> hipError_t {                        // sweep of the lower levels + the root's gather
-                side_started = true;
-                if (ready_deferred) {
-                    hipError_t se;
-                    if ((se = hipStreamWaitEvent(fj.aux, ready_deferred, 0)) != hipSuccess) return se;
-                    if ((se = sweep(0, fork_level, fj.aux)) != hipSuccess) return se;
-                }
-                return launch_fwd_big_pre(D, call, *roots, X, nrhs, fj.aux);
-            };
-            auto release = [&]() -> hipError_t {                           // chunks 0 .. k - 1 hang off block launch k * cwb
-                hipError_t se;
-                if ((se = hipStreamWaitEvent(fj.aux, home, 0)) != hipSuccess) return se;
-                for (int c = 0; c < k; ++c) {
-                    se = with_sweep_kind(D.kind, call.trans,
-                                         [&](auto K) { return launch_fwd_big_chunk<K>(D, call, *roots, X, nrhs, c, fj.aux); });
-                    if (se != hipSuccess) return se;
-                }
-                home = nullptr;
-                return hipSuccess;
-            };
-            for (int blk = 0; blk <= nblk; ++blk) {
-                e = with_kind(D.kind, [&](auto K) { return launch_big_block<K>(D, *rootf, blk, pc, st); });
-                if (e != hipSuccess) return e;
-                if (!side_started && (e = start_side()) != hipSuccess) return e;      // after the chain's first block is captured
-                if (home && (e = release()) != hipSuccess) return e;                  // after the block that follows the release point
-                if (k > 0 && blk == k * cwb) {                         // blocks 0 .. blk - 1 are home
-                    if ((e = fj.event(&home)) != hipSuccess) return e;
-                    if ((e = hipEventRecord(home, st)) != hipSuccess) return e;
-                }
-            }
-            if (home && (e = release()) != hipSuccess) return e;
-            root_rest = k;
-            if ((e = fj.event(&swept)) != hipSuccess) return e;           // replaces the join recorded at the fork
-            if ((e = hipEventRecord(swept, fj.aux)) != hipSuccess) return e;
-            f0 = f1;
-            continue;
-        }
-        e = run_level(fgroups, f0, f1, st, fj, true, [&](const LaunchGroup &g, hipStream_t s) {
-            return with_kind(D.kind, [&](auto K) { return launch_front_group<K>(D, call, g, pc, s); });
-        });
-        if (e != hipSuccess) return e;
-        if (ready_deferred && !rootf) {            // the level above the fork has been captured: now the side branch
-            if ((e = hipStreamWaitEvent(fj.aux, ready_deferred, 0)) != hipSuccess) return e;
-            if ((e = sweep(0, fork_level, fj.aux)) != hipSuccess) return e;
-            if ((e = fj.event(&swept)) != hipSuccess) return e;
-            if ((e = hipEventRecord(swept, fj.aux)) != hipSuccess) return e;
-            ready_deferred = nullptr;
-        }
-        if (level == fork_level) {
-            hipEvent_t ready;                      // panels of levels 0..fork_level are final
-            if ((e = fj.event(&ready)) != hipSuccess) return e;
-            if ((e = hipEventRecord(ready, st)) != hipSuccess) return e;
-            ready_deferred = ready;                // captured after the chain above has begun (see the root's chain)
-        }
-        f0 = f1;
-    }
-    if (swept && (e = hipStreamWaitEvent(st, swept, 0)) != hipSuccess) return e;
-    if (!rootf) return sweep(fork_level + 1, nlevels, st);
-    const BigSweepPlan pl = big_sweep_plan(D, *roots, nrhs);
-    for (int c = root_rest; c < pl.nchunk; ++c) {
-        e = with_sweep_kind(D.kind, call.trans, [&](auto K) { return launch_fwd_big_chunk<K>(D, call, *roots, X, nrhs, c, st); });
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+    return issue_plan(D, call, plan_factor_with_forward(schedule_input(D, call, &fgroups, nrhs)), pc, X, nrhs, st, fj);
 }
 
 hipError_t launch_prologue(const DeviceFactor &D, const double *ax_src, const double *x_src, int nrhs, hipStream_t st)

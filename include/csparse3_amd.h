@@ -563,6 +563,15 @@ int cs3_debug_sens_parts(cs3_handle h, cs3_sens s, int64_t parts, const double *
                          void *stream);
 /* Factorisation schedule: supernode id, front order r and width w per schedule slot. */
 int cs3_debug_schedule(cs3_handle h, int32_t *sched, int32_t *front_r, int32_t *front_w);
+/* The launch plan of an operation on this handle (op 0: factorisation, 1 / 2: forward / backward sweep, 3: the fused step =
+ * factorisation with forward sweep, then the backward sweep's plan, 4 / 5: Schur forward / backward) with nrhs right-hand
+ * sides (op 0: ignored); trans: the transposed sweeps (op 1 / 2, LU).  Returns the number of steps and writes at most cap
+ * of them to rows (may be NULL), 10 int32 each: step kind (StepKind of csrc/cs3_device.hpp: 0 front group, 1 big gather,
+ * 2 big block, 3 Schur take, 4 / 5 sweep group forward / backward, 6 / 7 big-sweep forward pre / chunk, 8 / 9 backward
+ * pre / chunk, 10 event record, 11 stream wait), stream slot (0: the caller's stream, 1 .. 3: side streams, 4: aux), the
+ * group's first, count, cls, level, max_r, max_w (zeros for 10 / 11), argument (block or chunk, else -1), event number
+ * (10 / 11, else -1; counted from 0 per plan, so op 3 counts twice).  Needs no device.  -1: error. */
+int64_t cs3_debug_launch_plan(cs3_handle h, int32_t op, int64_t nrhs, int32_t trans, int32_t *rows, int64_t cap);
 /* The bottom forest (subtrees of small fronts walked by one workgroup each, all in one launch): returns the
  * number of forest fronts (0: no forest) and, for arrays that are not null, per forest front in task order its supernode,
  * its task and its local level inside the task.  tier[] is kept for existing callers and always receives 0 (the forest

@@ -14,7 +14,7 @@ has no such protection in the first pass; after it, it absorbs nothing that woul
 a front that is to have 64 pivots and more than 136 rows is written down with 63, and its tallest child is one column
 (`_sacrifice`, or a single-column leaf) that it absorbs.
 
-With fewer than 16 right-hand sides a front is swept (api.cpp: select_sweep_schedule; kernels.hip: sweep_groups,
+With fewer than 16 right-hand sides a front is swept (api.cpp: select_sweep_schedule; schedule.cpp: sweep_groups,
 absorb_small_group, launch_solve_group) by
   the bottom forest's own sweeps   one plain right-hand side of a lone matrix, the fronts of the forest ('sub'),
   k_fwd_il / k_bwd_il              order <= 16 in a batch of 128 or more ('il'),
@@ -37,8 +37,8 @@ import rhs_cases as rc
 import sweep_cases as sc
 from rhs_cases import _leaves, _node
 
-FEW_RHS_MAX = rc.RHS_LANES_MIN - 1     # kernels.hip: sweep_groups regroups below RHS_LANES_MIN
-PROMOTE_MAX = 16                       # kernels.hip: promote_max
+FEW_RHS_MAX = rc.RHS_LANES_MIN - 1     # schedule.cpp: sweep_groups regroups below RHS_LANES_MIN
+PROMOTE_MAX = 16                       # cs3_device.hpp: PROMOTE_MAX
 WAVES_PER_WG = 4                       # kernels.hip: k_fwd_wave / k_bwd_wave, fronts per workgroup
 KT = 8                                 # kernels.hip: launch_solve_group, right-hand sides per wave
 SOLVE_PF = 8                           # kernels.hip: panel columns prefetched at a time

@@ -184,7 +184,7 @@ def fronts(hip, F):
             continue
         fc = "big" if ride[s] else _front_class(r[s], w[s], batch >= 8, batch >= 128)
         if fc == "big":
-            ld = (r[s] + 1) | 1                                            # kernels.hip: wg_lds_bytes, per front (<= per group)
+            ld = (r[s] + 1) | 1                                            # schedule.cpp: wg_lds_bytes, per front (<= per group)
             lds = (16 * 33 + (2 if kind == hip.CS3_LU else 1) * 16 * ld + (0 if kind == hip.CS3_LU else 16 * w[s])) * 8
             cls.append("wg" if batch >= 48 and lds <= 150 * 1024 else "big_step")
         else:

@@ -122,7 +122,7 @@ PAIRS = {(1, 1): "wide", (1, 7): "wide", (1, 8): "multi", (1, 9): "multi", (1, 1
          (1, 16): "gemm", (1, 17): "gemm", (1, 65): "gemm", (1, 256): "gemm",            # (256: the permutation rides the sweeps)
          (2, 3): "wide", (2, 4): "narrow", (4, 1): "wide", (4, 2): "narrow", (4, 7): "narrow", (4, 9): "multi", (4, 17): "gemm",
          (15, 1): "narrow", (15, 7): "narrow", (16, 1): "block"}
-GEMM_MIN = 16                  # kernels.hip: RHS_LANES_MIN
+GEMM_MIN = 16                  # cs3_device.hpp: RHS_LANES_MIN
 
 
 def _path(batch, nrhs):

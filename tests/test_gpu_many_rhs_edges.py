@@ -77,9 +77,9 @@ def _factors(h, b):
 # -------------------------------------------------------------------------- paths --
 
 TILE = 64                      # kernels.hip: right-hand sides per wave (k_fwd_rhs) and per GEMM tile (GC)
-FUSED_PERM_MIN = 256           # kernels.hip: permutation_can_fuse (and no interleaved pool: il_len == 0)
-BRANCHES_MIN = 512             # kernels.hip: launch_solve_levels, solve_parallel
-WG_MIN_BATCH = 48              # kernels.hip: CS3_WG_MIN_BATCH (k_front_wg factors the big fronts)
+FUSED_PERM_MIN = 256           # schedule.cpp: permutation_can_fuse (and no interleaved pool: il_len == 0)
+BRANCHES_MIN = 512             # schedule.cpp: plan_solve_levels, parallel
+WG_MIN_BATCH = 48              # schedule.cpp: CS3_WG_MIN_BATCH (k_front_wg factors the big fronts)
 
 Path = collections.namedtuple("Path", "tiles last_tile perm branches batch")
 

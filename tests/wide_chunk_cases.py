@@ -3,7 +3,7 @@ picks the chunk width, for tests/test_wide_chunk_cases_cpu.py and tests/test_gpu
 
 The matrices are sweep_cases.blocks_on_separator((d,) * 4, s): two fronts (d + s, d) on one level below a parentless root
 (2 d + s, 2 d + s).  With few right-hand sides (batch * nrhs < 8) a launch group of big fronts whose widest front has
-more than 128 pivots takes k_fwd_big_step4 / k_bwd_big_step4 (kernels.hip: big_sweep_plan); the cases put a front's
+more than 128 pivots takes k_fwd_big_step4 / k_bwd_big_step4 (schedule.cpp: big_sweep_plan); the cases put a front's
 width w at every place where those kernels change what they do:
 
   case      non-root fronts   root        256-chunks of (non-root, root)    last chunk's columns (non-root, root)
@@ -31,8 +31,8 @@ ORDER = {name: sum(ds) + s for name, (ds, s) in CASES.items()}
 # (r, w) of the fronts with w > 64 in supernode order, the root last
 FRONTS = {name: ((ds[0] + s, ds[0]),) * 2 + ((2 * ds[0] + s,) * 2,) for name, (ds, s) in CASES.items()}
 
-SOLVE_BW, BIG_CW, BIG_CW4 = 64, 128, 256       # kernels.hip
-GEMM_MIN = 16                                  # kernels.hip: RHS_LANES_MIN
+SOLVE_BW, BIG_CW, BIG_CW4 = 64, 128, 256       # cs3_device.hpp
+GEMM_MIN = 16                                  # cs3_device.hpp: RHS_LANES_MIN
 
 # (batch, right-hand sides): the first five sweep the cases' fronts in 256-column chunks, the last two as before
 PAIRS_NEW = ((1, 1), (1, 2), (1, 7), (2, 3), (7, 1))
@@ -41,7 +41,7 @@ BATCHES = (1, 2, 7)
 
 
 def chunk_width(batch, nrhs, max_w):
-    """kernels.hip, big_sweep_plan: columns per chunk launch of a group of big fronts whose widest has max_w pivots
+    """schedule.cpp, big_sweep_plan: columns per chunk launch of a group of big fronts whose widest has max_w pivots
     (fewer than 16 right-hand sides: beyond, the GEMM sweeps take them)."""
     assert nrhs < GEMM_MIN and batch <= sc.BIG_BATCH_MAX
     if batch * nrhs < 8:
@@ -50,7 +50,7 @@ def chunk_width(batch, nrhs, max_w):
 
 
 def skips_init(batch, nrhs, fronts):
-    """kernels.hip, big_sweep_plan: no k_bwd_big_init for a group of one front without rows of ancestors, on the 256 path.
+    """schedule.cpp, big_sweep_plan: no k_bwd_big_init for a group of one front without rows of ancestors, on the 256 path.
     fronts: the (r, w) of the group."""
     return chunk_width(batch, nrhs, max(w for _, w in fronts)) == BIG_CW4 and len(fronts) == 1 and fronts[0][0] == fronts[0][1]
 

@@ -12,11 +12,11 @@ RT=$(find /opt/rocm/lib/llvm -name "libclang_rt.asan-x86_64.so" | head -1)
 mkdir -p $OUT
 make -C $SRC > /dev/null
 SAN="-O1 -g -fPIC -fsanitize=address,undefined -fno-omit-frame-pointer"
-for f in api ordering symbolic; do
+for f in api ordering symbolic schedule; do
   /opt/rocm/bin/hipcc -std=c++17 $SAN -fno-gpu-sanitize -c $SRC/$f.cpp -o $OUT/$f.o
 done
 /opt/rocm/bin/hipcc -shared $SAN -fno-gpu-sanitize --offload-arch=gfx950 -o $OUT/libcsparse3_hip_asan.so \
-    $OUT/api.o $OUT/ordering.o $OUT/symbolic.o $SRC/build/kernels.o $SRC/build/substrate.o
+    $OUT/api.o $OUT/ordering.o $OUT/symbolic.o $OUT/schedule.o $SRC/build/kernels.o $SRC/build/substrate.o
 $CLANG -std=c99 $SAN -shared -o $OUT/liboracle_asan.so $ROOT/oracle/cs_oracle.c -lm
 cd $ROOT
 LD_PRELOAD=$RT ASAN_OPTIONS=detect_leaks=0:abort_on_error=0 UBSAN_OPTIONS=print_stacktrace=1 \
