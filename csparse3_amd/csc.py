@@ -235,8 +235,12 @@ class CscMat:
     def solve(self, b, tol=0.0, trans=False, match=False, perturb=0.0, max_refine=10, refine="stationary"):
         """x = A \\ b by LU (factorises if needed); trans: A' x = b on the same factors; match, perturb: as in lu().
         With perturb the solution is refined against A when pivots were replaced (Factorization.solve_refined; not
-        offered together with trans); refine="gmres": by GMRES on the held factors instead of the stationary rounds."""
+        offered together with trans); refine="gmres": by GMRES on the held factors instead of the stationary rounds.
+        refine="extra": the solve is followed by the extra-precise refinement (Factorization.refine_xp, at most max_refine
+        corrections), with or without perturb, with or without trans."""
         F = self.lu(tol, match=match, perturb=perturb)
+        if refine == "extra":
+            return F.refine_xp(self.data, b, max_iters=max_refine, trans=trans)[0]
         if F.perturbation == 0.0:
             return F.solve(b, trans=trans)
         assert not trans, "perturb refines A x = b only"
@@ -300,7 +304,8 @@ def scipy_to_mat(scipy_mat):
 def lusol(A, b, order=1, tol=0.0, match=False, perturb=0.0, max_refine=10, refine="stationary"):
     """x = A \\ b (cs_lusol).  match: with the maximum-product matching and scaling in front (CscMat.lu).  perturb: small
     pivots are replaced instead of rejected and the solution is refined, at most max_refine rounds (csc_lusol_f);
-    refine="gmres": by GMRES on the held factors."""
+    refine="gmres": by GMRES on the held factors; refine="extra": extra-precise refinement (doubled-precision residuals)
+    after the solve, with or without perturb."""
     return _k.csc_lusol_f(order, A.m, A.n, A.indptr, A.indices, A.data, b, tol, match=match, perturb=perturb,
                           max_refine=max_refine, refine=refine)
 

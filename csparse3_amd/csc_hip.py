@@ -66,6 +66,13 @@ class GmresLimits(C.Structure):
     _fields_ = [(name, C.c_int64) for name in ("max_restart", "chunk_rows", "rhs_tile")]
 
 
+class RefineXpLimits(C.Structure):
+    """cs3_refine_xp_limits_t: threads per workgroup and the workgroup cap of the doubled-precision residual kernel, the
+    default max_iters, eps = 2^-52 and the stall ratio of the extra-precise refinement."""
+    _fields_ = [(name, C.c_int64) for name in ("block", "grid_cap", "max_iters_default")] + \
+               [(name, C.c_double) for name in ("eps", "stall_ratio")]
+
+
 class SensInfo(C.Structure):
     """cs3_sens_info_t: sizes of a plan for Y = C op(A)^-1 B, the side it is evaluated from (1 right, 2 left), its tiles."""
     _fields_ = [(name, C.c_int64) for name in ("k", "p", "side", "trans", "ntiles", "max_width", "nnz_b", "nnz_c")]
@@ -174,6 +181,11 @@ def lib():
         L.cs3_debug_gmres_estimates.argtypes = [vp, _f64p, I64]
         L.cs3_debug_gmres_kernel.argtypes = [vp, I64, I64, vp]
         L.cs3_debug_gmres_basis.argtypes = [vp, _f64p, I64]
+        L.cs3_refine_xp_limits.argtypes = [C.POINTER(RefineXpLimits)]
+        L.cs3_residual_xp_dev.argtypes = [vp, vp, vp, vp, vp, vp, vp, I64, I64, vp]
+        L.cs3_residual_xp.argtypes = [vp, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, I64, I64]
+        L.cs3_refine_xp_dev.argtypes = [vp, vp, vp, vp, vp, I64, I64, I64, _i32p, _i32p, _f64p, _f64p, _f64p, vp]
+        L.cs3_refine_xp.argtypes = [vp, _f64p, _f64p, _f64p, _f64p, I64, I64, I64, _i32p, _i32p, _f64p, _f64p, _f64p]
         L.cs3_set_pivot_perturbation.argtypes = [vp, C.c_double]
         L.cs3_get_perturbed.argtypes = [vp, C.POINTER(I64), vp]
         L.cs3_condest_dev.argtypes = [vp, vp, vp, vp, vp]
@@ -276,6 +288,13 @@ def gmres_limits():
     """The constants of the GMRES refinement (cs3_gmres_limits); needs no GPU."""
     out = GmresLimits()
     _check(lib().cs3_gmres_limits(C.byref(out)))
+    return out
+
+
+def refine_xp_limits():
+    """The constants of the extra-precise refinement (cs3_refine_xp_limits); needs no GPU."""
+    out = RefineXpLimits()
+    _check(lib().cs3_refine_xp_limits(C.byref(out)))
     return out
 
 
@@ -656,13 +675,71 @@ class Factorization:
         _check(lib().cs3_debug_gmres_basis(self._h, _pf(V), nvec))
         return V
 
+    def residual_xp(self, Ax, b, x, xt=None, trans=False):
+        """r = b - A (x + xt) (trans: with A') accumulated in doubled precision and rounded once, and
+        s = |b| + |A| |x|, on host arrays (cs3_residual_xp; needs the analysis only).  -> (r, s), shaped like b."""
+        Ax, b, x = _f64(Ax), _f64(b), _f64(x)
+        xt = None if xt is None else _f64(xt)
+        per = self.batch * self.n
+        assert Ax.size >= self.batch * self.nnz and b.size % per == 0 and x.size == b.size
+        assert xt is None or xt.size == b.size
+        r, s = np.empty_like(b), np.empty_like(b)
+        _check(lib().cs3_residual_xp(self._h, _pf(Ax), _pf(b), _pf(x), _pf(xt), _pf(r), _pf(s), b.size // per,
+                                     1 if trans else 0))
+        return r, s
+
+    def refine_xp(self, Ax, b, x=None, max_iters=10, trans=False, want_tail=False):
+        """Extra-precise refinement of A x = b (trans: A' x = b) with the values Ax on the held factors: residuals in
+        doubled precision, x carried as a head and a tail (LAPACK's xGERFSX).  b: [n], [n, k] or [batch, n, k]; every
+        column is a system of its own.  x=None starts from solve(b, trans).
+        -> (x, info): info["iters"], ["flag"] (0 still iterating after max_iters, 1 converged, 2 stalled, 3 non-finite),
+        ["ferr"] (bound on the normwise relative error, infinity norm), ["berr"] (componentwise backward error of x) and
+        ["rate"], [batch * k] each; with want_tail info["xt"], x + xt being the solution in doubled precision."""
+        Ax, b = _f64(Ax), _f64(b)
+        x = self.solve(b, trans) if x is None else np.array(x, dtype=np.float64, order="C", copy=True)
+        per = self.batch * self.n
+        assert Ax.size >= self.batch * self.nnz and x.size % per == 0 and b.size == x.size
+        k = x.size // per
+        info = self._xp_info(k)
+        xt = np.zeros_like(x) if want_tail else None
+        _check(lib().cs3_refine_xp(self._h, _pf(Ax), _pf(b), _pf(x), _pf(xt), k, max_iters, 1 if trans else 0,
+                                   _pi(info["iters"]), _pi(info["flag"]), _pf(info["ferr"]), _pf(info["berr"]), _pf(info["rate"])))
+        if want_tail:
+            info["xt"] = xt
+        return x, info
+
+    def refine_xp_dev(self, ax_ptr, b_ptr, x_ptr, k=1, max_iters=10, xt_ptr=0, stream=0, trans=False):
+        """refine_xp on device pointers: X at x_ptr holds x0 on entry and the refined head on exit, xt_ptr (optional)
+        receives the tail.  Host-driven: synchronises `stream` after every pass (one 4-byte read).  The same bits as
+        refine_xp().  -> info."""
+        info = self._xp_info(k)
+        _check(lib().cs3_refine_xp_dev(self._h, C.c_void_p(ax_ptr), C.c_void_p(b_ptr), C.c_void_p(x_ptr),
+                                       C.c_void_p(xt_ptr) if xt_ptr else None, k, max_iters, 1 if trans else 0,
+                                       _pi(info["iters"]), _pi(info["flag"]), _pf(info["ferr"]), _pf(info["berr"]),
+                                       _pf(info["rate"]), C.c_void_p(stream)))
+        return info
+
+    def residual_xp_dev(self, ax_ptr, b_ptr, x_ptr, r_ptr, s_ptr=0, xt_ptr=0, k=1, stream=0, trans=False):
+        """residual_xp on device pointers, asynchronous on `stream` (s_ptr, xt_ptr optional)."""
+        _check(lib().cs3_residual_xp_dev(self._h, C.c_void_p(ax_ptr), C.c_void_p(b_ptr), C.c_void_p(x_ptr),
+                                         C.c_void_p(xt_ptr) if xt_ptr else None, C.c_void_p(r_ptr),
+                                         C.c_void_p(s_ptr) if s_ptr else None, k, 1 if trans else 0, C.c_void_p(stream)))
+
+    def _xp_info(self, k):
+        nsys = self.batch * k
+        return {"iters": np.zeros(nsys, dtype=np.int32), "flag": np.zeros(nsys, dtype=np.int32), "ferr": np.zeros(nsys),
+                "berr": np.zeros(nsys), "rate": np.zeros(nsys)}
+
     def solve_refined(self, Ax, b, max_refine=10, refine="stationary"):
         """solve(b), then -- when the factorisation replaced pivots -- refinement.  refine="stationary": one round at a
         time until the correction no longer falls below half of the one before, at most max_refine rounds (a round whose
         correction GREW is dropped).  refine="gmres": gmres() from solve(b) with max_iters = max_refine, which also
         converges when the perturbation is too large for the stationary rounds.
-        Without replaced pivots this is solve(b), bit for bit."""
-        assert refine in ("stationary", "gmres")
+        Without replaced pivots these two are solve(b), bit for bit.
+        refine="extra": solve(b), then refine_xp() with max_iters = max_refine, with or without replaced pivots."""
+        assert refine in ("stationary", "gmres", "extra")
+        if refine == "extra":
+            return self.refine_xp(Ax, b, max_iters=max_refine)[0]
         x = self.solve(b)
         if not self.perturbed().any():
             return x
@@ -934,11 +1011,13 @@ def csc_lusol_f(order, m, n, Ap, Ai, Ax, b, tol=0.0, match=False, perturb=0.0, m
     """x = A \\ b by LU (cs_lusol).  match: rows permuted and scaled by the maximum-product transversal first (matrices
     without a strong diagonal).  perturb: pivots below delta are replaced instead of rejected (perturbation_delta), and
     the solution is refined (Factorization.solve_refined, at most max_refine rounds; refine="gmres": GMRES on the held
-    factors instead of the stationary rounds)."""
+    factors instead of the stationary rounds).  refine="extra": the solve is followed by the extra-precise refinement
+    (Factorization.refine_xp, at most max_refine corrections), with or without perturb."""
     with Factorization(m, n, Ap, Ai, CS3_LU, order, match_values=Ax if match else None) as F:
         delta = perturbation_delta(perturb, Ax, match)
         if delta == 0.0:
-            return F.factor(Ax, tol).solve(b)
+            F.factor(Ax, tol)
+            return F.solve_refined(Ax, b, max_refine, refine) if refine == "extra" else F.solve(b)
         return F.set_perturbation(delta).factor(Ax, tol).solve_refined(Ax, b, max_refine, refine)
 
 

@@ -86,6 +86,9 @@ struct cs3_handle_s {
             DevBuf<KrySys> sys;
             DevBuf<unsigned> cnt;
         } kry;
+        // ensure_refine_xp (refine_xp.hip, cs3_refine_xp*): the tail of the iterate [batch][n, k], one state per system,
+        // the counter of active systems.  Grow with k.  (The residual / correction vector is view.res.)
+        struct { DevBuf<double> tail; DevBuf<XpSys> sys; DevBuf<unsigned> cnt; } xpr;
         // ensure_estimator (estimate.hip): X [batch][n] (stable address: the solves on it replay the cached graphs), the
         // sign vectors [2][batch][n], one state per matrix, the chunks of the partial reductions, the two "wants" counters
         struct { DevBuf<double> x; DevBuf<signed char> s; DevBuf<EstState> state; DevBuf<EstPart> parts; DevBuf<unsigned> cnt; } est;
@@ -1715,6 +1718,203 @@ int cs3_debug_gmres_basis(cs3_handle h, double *V, int64_t nvec)
     if (nvec > K.restart + 1) { set_error("cs3_debug_gmres_basis: bad argument"); return CS3_ERR_ARG; }
     const size_t count = (size_t) nvec * (size_t) (K.batch * K.n * K.k);
     if (count) CS3_HIP(hipMemcpy(V, K.V, count * sizeof(double), hipMemcpyDeviceToHost));
+    return CS3_OK;
+}
+
+// ---- extra-precise refinement: doubled-precision residuals, berr and ferr (refine_xp.hip) ----------------------------
+int cs3_refine_xp_limits(cs3_refine_xp_limits_t *out)
+{
+    if (!out) { set_error("cs3_refine_xp_limits: null argument"); return CS3_ERR_ARG; }
+    out->block = XP_BLOCK;
+    out->grid_cap = XP_GRID_CAP;
+    out->max_iters_default = XP_MAX_ITERS_DEFAULT;
+    out->eps = XP_EPS;
+    out->stall_ratio = XP_STALL_RATIO;
+    return CS3_OK;
+}
+
+static int residual_xp_check(const char *who, cs3_handle h, const double *Ax, const double *B, const double *X, const double *R,
+                             int64_t k)
+{
+    int rc = guard(h); if (rc) return rc;
+    if ((rc = refuse_schur(h, who))) return rc;
+    if (!Ax || !B || !X || !R || k < 1 || k > INT_MAX) { set_error(std::string(who) + ": bad argument"); return CS3_ERR_ARG; }
+    return CS3_OK;
+}
+
+static int residual_xp_run(const char *who, cs3_handle h, const double *Ax_dev, const double *B_dev, const double *X_dev,
+                           const double *XT_dev, double *R_dev, double *S_dev, int64_t k, bool trans, hipStream_t st)
+{
+    int rc = residual_xp_check(who, h, Ax_dev, B_dev, X_dev, R_dev, k);
+    if (rc) return rc;
+    if ((rc = trans ? ensure_col_view(h, 0) : ensure_row_view(h, 0))) return rc;
+    const auto &V = h->mem.view;
+    const int *vp = (trans ? V.cp : V.rp).get(), *vj = (trans ? V.ci : V.rj).get(), *vmap = (trans ? V.cmap : V.rmap).get();
+    CS3_HIP(launch_residual_xp(vp, vj, vmap, Ax_dev, B_dev, X_dev, XT_dev, R_dev, S_dev, h->S.n, (int) k, h->S.nnzA, h->batch,
+                               false, st));
+    return CS3_OK;
+}
+
+int cs3_residual_xp_dev(cs3_handle h, const double *Ax_dev, const double *B_dev, const double *X_dev, const double *XT_dev,
+                        double *R_dev, double *S_dev, int64_t k, int64_t trans, void *stream)
+{
+    return residual_xp_run("cs3_residual_xp_dev", h, Ax_dev, B_dev, X_dev, XT_dev, R_dev, S_dev, k, trans != 0, (hipStream_t) stream);
+}
+
+// The host-array form: staged as cs3_refine stages, the same kernel on the null stream.
+int cs3_residual_xp(cs3_handle h, const double *Ax, const double *B, const double *X, const double *XT, double *R, double *S,
+                    int64_t k, int64_t trans)
+{
+    int rc = residual_xp_check("cs3_residual_xp", h, Ax, B, X, R, k);
+    if (rc) return rc;
+    if ((rc = ensure_device(h))) return rc;
+    auto &H = h->mem.host;
+    const size_t ax_count = (size_t) (h->batch * h->S.nnzA), x_count = (size_t) (h->batch * h->S.n * k);
+    CS3_HIP(H.ax.reserve(ax_count));
+    if (ax_count) CS3_HIP(hipMemcpy(H.ax.get(), Ax, ax_count * sizeof(double), hipMemcpyHostToDevice));
+    DevBuf<double> b, x, xt, r, s;
+    for (DevBuf<double> *buf : {&b, &x, &r}) CS3_HIP(buf->alloc(x_count));
+    if (XT) CS3_HIP(xt.alloc(x_count));
+    if (S) CS3_HIP(s.alloc(x_count));
+    if (x_count) {
+        CS3_HIP(hipMemcpy(b.get(), B, x_count * sizeof(double), hipMemcpyHostToDevice));
+        CS3_HIP(hipMemcpy(x.get(), X, x_count * sizeof(double), hipMemcpyHostToDevice));
+        if (XT) CS3_HIP(hipMemcpy(xt.get(), XT, x_count * sizeof(double), hipMemcpyHostToDevice));
+    }
+    if ((rc = residual_xp_run("cs3_residual_xp", h, H.ax.get(), b.get(), x.get(), XT ? xt.get() : nullptr, r.get(),
+                              S ? s.get() : nullptr, k, trans != 0, nullptr)))
+        return rc;
+    if (x_count) {
+        CS3_HIP(hipMemcpy(R, r.get(), x_count * sizeof(double), hipMemcpyDeviceToHost));
+        if (S) CS3_HIP(hipMemcpy(S, s.get(), x_count * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    return CS3_OK;
+}
+
+// Work memory of one call: the views with the residual vector at this k, the tail, the states, the counter.
+static int ensure_refine_xp(cs3_handle h, long long k, bool trans)
+{
+    const size_t res_before = h->mem.view.res.count();
+    int rc = trans ? ensure_col_view(h, k) : ensure_row_view(h, k);
+    if (rc) return rc;
+    if (h->mem.view.res.count() != res_before) h->dbg_allocs += 1;
+    auto &M = h->mem.xpr;
+    const size_t total = (size_t) (h->batch * h->S.n * k), nsys = (size_t) (h->batch * k);
+    if (total > M.tail.count() || nsys > M.sys.count() || !M.tail.get() || !M.sys.get() || !M.cnt.get()) {
+        CS3_HIP(hipDeviceSynchronize());              // (the old blocks may still be in use)
+        h->dbg_syncs += 1;
+        const double *t0 = M.tail.get(); const XpSys *s0 = M.sys.get(); const unsigned *c0 = M.cnt.get();
+        CS3_HIP(M.tail.reserve(total));
+        CS3_HIP(M.sys.reserve(nsys));
+        CS3_HIP(M.cnt.reserve(1));
+        h->dbg_allocs += (M.tail.get() != t0) + (M.sys.get() != s0) + (M.cnt.get() != c0);
+    }
+    return CS3_OK;
+}
+
+static int refine_xp_check(const char *who, cs3_handle h, const double *Ax, const double *B, const double *X, int64_t k,
+                           int64_t max_iters)
+{
+    int rc = guard(h); if (rc) return rc;
+    if ((rc = refuse_schur(h, who))) return rc;
+    if (!Ax || !B || !X || k < 1 || k > INT_MAX || max_iters < 0 || max_iters > INT_MAX) {
+        set_error(std::string(who) + ": bad argument");
+        return CS3_ERR_ARG;
+    }
+    if (!h->factored) { set_error(std::string(who) + ": refinement needs a factorisation"); return CS3_ERR_STATE; }
+    return CS3_OK;
+}
+
+// The forward bound of one system from what the iteration and the closing pass left (the rules of the header, in order).
+static double xp_ferr(const XpSys &s, double nxf)
+{
+    if (s.flag == XP_NONFINITE) return std::nan("");
+    if (s.iters == 0) return HUGE_VAL;
+    if (s.rate >= 1.0) return HUGE_VAL;
+    if (s.nd_prev == 0.0 && nxf == 0.0) return 0.0;
+    return std::max(XP_EPS, (s.nd_prev / nxf) / (1.0 - s.rate));
+}
+
+static int refine_xp_run(const char *who, cs3_handle h, const double *Ax_dev, const double *B_dev, double *X_dev, double *XT_dev,
+                         int64_t k, int64_t max_iters, bool trans, int32_t *iters, int32_t *flag, double *ferr, double *berr,
+                         double *rate, hipStream_t st)
+{
+    int rc = refine_xp_check(who, h, Ax_dev, B_dev, X_dev, k, max_iters);
+    if (rc) return rc;
+    const long long n = h->S.n, nnz = h->S.nnzA, batch = h->batch, nsys = batch * k;
+    if ((rc = ensure_refine_xp(h, k, trans))) return rc;
+    const auto &V = h->mem.view;
+    auto &M = h->mem.xpr;
+    const int *vp = (trans ? V.cp : V.rp).get(), *vj = (trans ? V.ci : V.rj).get(), *vmap = (trans ? V.cmap : V.rmap).get();
+    double *res = V.res.get(), *tail = M.tail.get();
+    const size_t vec_bytes = (size_t) (batch * n * k) * sizeof(double);
+    if (vec_bytes) CS3_HIP(hipMemsetAsync(tail, 0, vec_bytes, st));
+    CS3_HIP(hipMemsetAsync(M.sys.get(), 0, (size_t) nsys * sizeof(XpSys), st));       // iterating, no correction yet
+    unsigned active = (n > 0 && nsys > 0) ? 1u : 0u;
+    for (int64_t s = 0; s < max_iters && active; ++s) {
+        CS3_HIP(launch_residual_xp(vp, vj, vmap, Ax_dev, B_dev, X_dev, tail, res, nullptr, n, (int) k, nnz, batch, false, st));
+        if ((rc = run_solve(h, res, k, 0, st, trans))) return rc;                      // dx = op(A)^-1 r with the factors at hand
+        CS3_HIP(launch_xp_maxima(res, X_dev, M.sys.get(), n, (int) k, batch, st));
+        CS3_HIP(hipMemsetAsync(M.cnt.get(), 0, sizeof(unsigned), st));
+        CS3_HIP(launch_xp_control(M.sys.get(), nsys, M.cnt.get(), st));
+        CS3_HIP(launch_xp_update(X_dev, tail, res, M.sys.get(), n, (int) k, batch, st));
+        if ((rc = read_active(h, M.cnt.get(), &active, st))) return rc;
+    }
+    // the closing pass on x alone: |r_i| / s_i into res, its maxima and those of |x| into the (zeroed) words of the states
+    CS3_HIP(launch_residual_xp(vp, vj, vmap, Ax_dev, B_dev, X_dev, nullptr, res, nullptr, n, (int) k, nnz, batch, true, st));
+    CS3_HIP(launch_xp_maxima(res, X_dev, M.sys.get(), n, (int) k, batch, st));
+    if (XT_dev && vec_bytes) CS3_HIP(hipMemcpyAsync(XT_dev, tail, vec_bytes, hipMemcpyDeviceToDevice, st));
+    std::vector<XpSys> sys((size_t) nsys);
+    if (nsys) CS3_HIP(hipMemcpyAsync(sys.data(), M.sys.get(), sys.size() * sizeof(XpSys), hipMemcpyDeviceToHost, st));
+    CS3_HIP(hipStreamSynchronize(st));
+    h->dbg_syncs += 1;
+    for (long long s = 0; s < nsys; ++s) {
+        const XpSys &y = sys[(size_t) s];
+        double be, nxf;
+        std::memcpy(&be, &y.nd_bits, sizeof(double));
+        std::memcpy(&nxf, &y.nx_bits, sizeof(double));
+        if (iters) iters[s] = y.iters;
+        if (flag) flag[s] = y.flag;
+        if (ferr) ferr[s] = xp_ferr(y, nxf);
+        if (berr) berr[s] = be;
+        if (rate) rate[s] = y.rate;
+    }
+    return CS3_OK;
+}
+
+int cs3_refine_xp_dev(cs3_handle h, const double *Ax_dev, const double *B_dev, double *X_dev, double *XT_dev, int64_t k,
+                      int64_t max_iters, int64_t trans, int32_t *iters, int32_t *flag, double *ferr, double *berr, double *rate,
+                      void *stream)
+{
+    return refine_xp_run("cs3_refine_xp_dev", h, Ax_dev, B_dev, X_dev, XT_dev, k, max_iters, trans != 0, iters, flag, ferr, berr,
+                         rate, (hipStream_t) stream);
+}
+
+// The host-array form: staged as cs3_refine stages, then cs3_refine_xp_dev's steps on the null stream -- the same bits.
+int cs3_refine_xp(cs3_handle h, const double *Ax, const double *B, double *X, double *XT, int64_t k, int64_t max_iters,
+                  int64_t trans, int32_t *iters, int32_t *flag, double *ferr, double *berr, double *rate)
+{
+    int rc = refine_xp_check("cs3_refine_xp", h, Ax, B, X, k, max_iters);
+    if (rc) return rc;
+    auto &H = h->mem.host;
+    const size_t ax_count = (size_t) (h->batch * h->S.nnzA), x_count = (size_t) (h->batch * h->S.n * k);
+    CS3_HIP(H.ax.reserve(ax_count));
+    if (ax_count) CS3_HIP(hipMemcpy(H.ax.get(), Ax, ax_count * sizeof(double), hipMemcpyHostToDevice));
+    DevBuf<double> b, x, xt;
+    CS3_HIP(b.alloc(x_count));
+    CS3_HIP(x.alloc(x_count));
+    if (XT) CS3_HIP(xt.alloc(x_count));
+    if (x_count) {
+        CS3_HIP(hipMemcpy(b.get(), B, x_count * sizeof(double), hipMemcpyHostToDevice));
+        CS3_HIP(hipMemcpy(x.get(), X, x_count * sizeof(double), hipMemcpyHostToDevice));
+    }
+    if ((rc = refine_xp_run("cs3_refine_xp", h, H.ax.get(), b.get(), x.get(), XT ? xt.get() : nullptr, k, max_iters, trans != 0,
+                            iters, flag, ferr, berr, rate, nullptr)))
+        return rc;
+    if (x_count) {
+        CS3_HIP(hipMemcpy(X, x.get(), x_count * sizeof(double), hipMemcpyDeviceToHost));
+        if (XT) CS3_HIP(hipMemcpy(XT, xt.get(), x_count * sizeof(double), hipMemcpyDeviceToHost));
+    }
     return CS3_OK;
 }
 

@@ -413,4 +413,29 @@ hipError_t launch_kry_probe(const KryWork &K, int which, int j, hipStream_t st);
 // X += Z for the systems that took part in the cycle; every other column keeps its bits
 hipError_t launch_kry_axpy(const KryWork &K, double *X, hipStream_t st);
 
+// refine_xp.hip: extra-precise refinement (cs3_refine_xp*), batch * k systems in lock-step with the layouts of krylov.hip.
+constexpr int XP_BLOCK = 256;                  // threads per workgroup of every kernel of the family
+constexpr long long XP_GRID_CAP = 4096;        // workgroups (per matrix) of the residual and update kernels: grid-stride beyond
+constexpr int XP_MAX_ITERS_DEFAULT = 10;
+constexpr double XP_EPS = 0x1p-52, XP_STALL_RATIO = 0.5;
+enum XpFlag : int { XP_RUNNING = 0, XP_CONVERGED = 1, XP_STALLED = 2, XP_NONFINITE = 3 };
+struct XpSys {                    // one system
+    unsigned long long nd_bits, nx_bits;      // max |dx_i|, max |x_i| of this pass as bit patterns (zeroed by the control kernel)
+    double nd_prev, rate;         // the last applied max |dx_i|; the largest nd / nd_prev so far
+    int iters, flag;              // corrections applied; XpFlag
+    int apply, stopped;           // this pass's correction goes into x; no longer iterating
+};
+// R = B - op(A) (X + XT) in doubled precision, rounded once; S = |B| + |op(A)| |X| (XT, S may be null).  ratio: R takes
+// |r_i| / s_i instead (0 / 0 = 0), the closing pass's input to launch_xp_maxima.
+hipError_t launch_residual_xp(const int *Rp, const int *Rj, const int *Rmap, const double *Ax, const double *B, const double *X,
+                              const double *XT, double *R, double *S, long long n, int nrhs, long long nnz_a, long long batch,
+                              bool ratio, hipStream_t st);
+// per system: nd_bits = max over its column of |D|, nx_bits = of |X| (atomicMax on the bit patterns, onto what is there)
+hipError_t launch_xp_maxima(const double *D, const double *X, XpSys *sys, long long n, int nrhs, long long batch, hipStream_t st);
+// the decision of one pass per system; *active += the systems that go on
+hipError_t launch_xp_control(XpSys *sys, long long nsys, unsigned *active, hipStream_t st);
+// (x, xt) += dx in doubled precision for the systems whose apply is set; every other column keeps its bits
+hipError_t launch_xp_update(double *X, double *XT, const double *D, const XpSys *sys, long long n, int nrhs, long long batch,
+                            hipStream_t st);
+
 }  // namespace cs3

@@ -308,6 +308,73 @@ int cs3_debug_gmres_kernel(cs3_handle h, int64_t which, int64_t j, void *stream)
  * column.  CS3_ERR_STATE before any cs3_gmres* call, CS3_ERR_ARG on a null V or a count outside 0 .. restart + 1. */
 int cs3_debug_gmres_basis(cs3_handle h, double *V, int64_t nvec);
 
+/* ---- extra-precise refinement: doubled-precision residuals, berr and ferr ----
+ * Neither refinement above can make a solution more accurate than cond(A) * eps: the residual b - A x is summed in
+ * working precision, and once the true residual is below that sum's rounding error the correction A \ r is noise.  This
+ * is the extra-precise refinement of LAPACK's xGERFSX (Demmel, Hida, Kahan, Li, Mukherjee, Riedy 2006): only the
+ * residual is accumulated in doubled precision and x is carried as a head and a tail; the solves are the handle's own.
+ * For cond(A) below 1 / eps it reaches the correctly rounded solution; the componentwise backward error berr and a
+ * normwise forward error bound ferr are by-products.
+ *
+ * Layouts are cs3_refine_dev's: X, XT, B, R, S [batch][n, k] row-major, Ax [batch][nnz]; column t of matrix b is one
+ * system, index b * k + t in the result arrays.
+ *
+ * cs3_residual_xp_dev: R = B - op(A) (X + XT) accumulated in doubled precision and rounded once, S = |B| + |op(A)| |X|
+ * (S_dev may be NULL; XT_dev may be NULL = no tail).  trans != 0: op(A) = A'.  Row i, system t, the entries (a, j) of the
+ * row in cs3_residual_dev's order (ascending column through the row view; trans: storage order of column i), no
+ * floating-point contraction:
+ *     (sh, sl) = (b_i, 0);  den = |b_i|
+ *     per entry:  ph = fl(a * x_j);  pl = fma(a, x_j, -ph)               the exact error of the product
+ *                 (sh, e) = TwoSum(sh, -ph)                              Knuth's, six operations
+ *                 sl = fl(sl + fl(fl(e - pl) - fl(a * xt_j)))            without a tail: sl = fl(sl + fl(e - pl))
+ *                 den = fl(den + fl(|a| * |x_j|))
+ *     r_i = fl(sh + sl);  s_i = den
+ * One thread per (row, right-hand side), a grid-stride loop under grid_cap workgroups of `block` threads, no atomics,
+ * every output written: the same bits on every run.  Needs the analysis only (no factorisation).
+ *
+ * cs3_refine_xp_dev: X holds x0 on entry (typically from cs3_solve_dev), the tail xt starts at 0.  All batch * k systems
+ * advance in lock-step; pass s = 0 .. max_iters - 1, while any system is active:
+ *   1. r = b - op(A) (x + xt) as above, dx = op(A)^-1 r by the handle's solve (matched and perturbed handles as in
+ *      cs3_refine_dev).
+ *   2. nd = max_i |dx_i|, nx = max_i |x_i| (x before the update): maxima only, exact and independent of order.
+ *   3. Per system: nd or nx not finite: stop, flag 3, dx not applied.  With an earlier applied correction nd_prev:
+ *      rate = max(rate, nd / nd_prev), and nd > stall_ratio * nd_prev: stop, flag 2, dx not applied.  Otherwise dx is
+ *      applied, iters += 1, nd_prev = nd, and nd <= eps * nx (0 <= 0 included): stop, flag 1 (converged).
+ *   4. For the systems that apply: (s, e) = TwoSum(x, dx); t = fl(xt + e); (x, xt) = TwoSum(s, t).  The columns of a
+ *      stopped system are not touched again, bit for bit.
+ *   5. The host reads one 4-byte word, the systems still active: this synchronises `stream` (as cs3_gmres_dev does; the
+ *      call cannot be captured into a graph).
+ * Systems still active after the last pass have flag 0.  A closing pass evaluates the residual of the returned x alone
+ * (the tail dropped): berr = max_i |r_i| / s_i (0 / 0 counts as 0, non-zero over zero is +inf), nxf = max_i |x_i|.
+ * ferr, first match wins: NaN for flag 3; +inf when iters == 0; +inf when rate >= 1; 0 when nd_prev == 0 and nxf == 0
+ * (the zero solution of a zero right-hand side); otherwise max(eps, (nd_prev / nxf) / (1 - rate)), xGERFSX's
+ * geometric-series bound on the normwise relative error in the infinity norm, with eps as its floor.
+ * max_iters == 0 is valid: X untouched, iters = 0, flag = 0, ferr = +inf, berr that of x0.
+ * XT_dev, when not NULL, receives the tail: x + xt is the solution in doubled precision.
+ * iters, flag (int32), ferr, berr, rate (double): HOST arrays [batch * k], any may be NULL.
+ *
+ * Checks, in this order: null handle, a Schur handle, null Ax / B / X (cs3_residual_xp_dev: R too), k < 1,
+ * max_iters < 0: CS3_ERR_ARG; no factorisation (cs3_refine_xp* only): CS3_ERR_STATE; none needs a device.  LU and
+ * Cholesky handles, batches, matched and perturbed handles.  Work memory (the tail [batch][n, k]; per system the two
+ * maxima, nd_prev, rate, iters, flag, the apply mask) belongs to the handle, grows with k and goes with cs3_free; a
+ * second call with the same k allocates nothing.
+ * cs3_refine_xp_limits: the launch shape of the residual kernel, the default max_iters (10), eps = 2^-52,
+ *   stall_ratio = 0.5; needs no device.
+ * cs3_refine_xp, cs3_residual_xp: the host-array forms (the null stream): the same kernels, the same bits.
+ * Not offered: a capture-safe form of fixed length, a componentwise forward bound, Schur handles, residuals in more
+ * than doubled precision. */
+typedef struct { int64_t block, grid_cap, max_iters_default; double eps, stall_ratio; } cs3_refine_xp_limits_t;
+int cs3_refine_xp_limits(cs3_refine_xp_limits_t *out);
+int cs3_residual_xp_dev(cs3_handle h, const double *Ax_dev, const double *B_dev, const double *X_dev, const double *XT_dev,
+                        double *R_dev, double *S_dev, int64_t k, int64_t trans, void *stream);
+int cs3_residual_xp(cs3_handle h, const double *Ax, const double *B, const double *X, const double *XT, double *R, double *S,
+                    int64_t k, int64_t trans);
+int cs3_refine_xp_dev(cs3_handle h, const double *Ax_dev, const double *B_dev, double *X_dev, double *XT_dev,
+                      int64_t k, int64_t max_iters, int64_t trans,
+                      int32_t *iters, int32_t *flag, double *ferr, double *berr, double *rate, void *stream);
+int cs3_refine_xp(cs3_handle h, const double *Ax, const double *B, double *X, double *XT, int64_t k, int64_t max_iters,
+                  int64_t trans, int32_t *iters, int32_t *flag, double *ferr, double *berr, double *rate);
+
 /* ---- condition estimates and log-determinants from the held factors -----
  * Static diagonal pivots say nothing about how far a solution can be trusted; these are the cheap reliability signal
  * next to the factors (klu_condest, LAPACK xGECON, MATLAB condest).  Results are per matrix of the batch, [batch] each.
