@@ -293,6 +293,10 @@ int ensure_device_impl(cs3_handle h)
         f.parent = S.sn_parent[s];
         f.dbuf = 0;
         if (S.sn_class[s] == FC_BIG) { f.dbuf = dbuf_size; dbuf_size += (i64) ((f.w + 31) / 32) * 1024; }
+        if (S.sn_class[s] == FC_BIG && f.r >= (1 << 22)) {     // (launch_big_block refuses it too: this message survives)
+            set_error("a front of order " + std::to_string(f.r) + " is beyond k_big_step's 32-bit tile offsets (order < 2^22)");
+            return CS3_ERR_ARG;
+        }
     }
     D.dbuf_size = dbuf_size;
     std::vector<SolveDesc> sdesc(S.nsuper);
@@ -349,7 +353,8 @@ int ensure_device_impl(cs3_handle h)
     CS3_HIP(hipMemset(D.status, 0, (4 + (size_t) D.batch) * sizeof(int)));
     CS3_HIP(hipMemset(D.status, 0x7f, sizeof(int)));      // "clean": a handle that only imports factors never runs a prologue
     if (const char *pf = std::getenv("CS3_PROFILE")) {
-        if (pf[0] == '1') {
+        if (pf[0] == '1' || pf[0] == '2') {
+            D.tbuf_diag = pf[0] == '2';
             const size_t stamps = std::max<size_t>(1, (size_t) S.nsuper) * 8;
             if ((rc = factor_alloc(h, &D.tbuf, stamps))) return rc;
             CS3_HIP(hipMemset(D.tbuf, 0, stamps * sizeof(long long)));

@@ -314,4 +314,101 @@ __device__ __forceinline__ void schur_tiles(const double *F, At at, int r, int w
     }
 }
 
+// ---- k_big_step (kernels.hip): its descriptor in one fetch, and the addresses of a tile's loads and stores ----
+// The first 64 bytes of a front's descriptor (lpan .. w) in ONE scalar load, before any early return tests a field: field
+// by field the compiler split the fetch along the kernel's returns, each part a dependent scalar round trip of its own.
+struct DescHead { long long lpan, dbuf; int c0, r, w; };
+__device__ __forceinline__ DescHead load_desc_head(const FrontDesc *d)
+{
+    static_assert(offsetof(FrontDesc, lpan) == 0 && offsetof(FrontDesc, dbuf) == 32 && offsetof(FrontDesc, c0) == 52 &&
+                  offsetof(FrontDesc, r) == 56 && offsetof(FrontDesc, w) == 60 && sizeof(FrontDesc) >= 64, "DescHead");
+    typedef int v16i __attribute__((ext_vector_type(16), aligned(8), may_alias));
+    const v16i h = *reinterpret_cast<const v16i *>(d);
+    return {(long long) (((unsigned long long) (unsigned) h[1] << 32) | (unsigned) h[0]),
+            (long long) (((unsigned long long) (unsigned) h[9] << 32) | (unsigned) h[8]), h[13], h[14], h[15]};
+}
+
+// Addresses: ONE wave-uniform 64-bit base per operand panel, in scalar registers, plus a 32-bit byte offset per thread --
+// the thread's entry in the panel's first column group, advanced by a uniform 32-bit stride from group to group:
+// global_load v, v_off, s[base].  An offset stays inside one tile (below 64 (r + 1) doubles: 32 bits hold it for any
+// front that fits the memory; launch_big_block refuses the rest).  With a 64-bit address per load and thread
+// (v_mad_i64_i32, compare, two selects, 64-bit add) the arithmetic alone stood between the descriptor and the first load
+// for some 800 instructions, and a lone wave issues one instruction in four cycles whatever its kind.
+// (The empty asm statements only hide a value's origin from the optimiser, so that base + zext(offset) reaches
+// instruction selection in one piece and a bound stays one compare.  They change no result; what they buy was read off the
+// gfx950 assembly of ROCm 7.2's compiler, AMD clang 22.0.0git, and is to be read again after a compiler change.)
+__device__ __forceinline__ double load_at(const char *base, unsigned off)
+{
+    asm("" : "+v"(off));
+    return *reinterpret_cast<const double *>(base + off);
+}
+__device__ __forceinline__ void store_at(char *base, unsigned off, double v)
+{
+    asm("" : "+v"(off));
+    *reinterpret_cast<double *>(base + off) = v;
+}
+// A thread's bound on the column groups of a panel, 0 where it has no entry in any of them: one compare per load
+__device__ __forceinline__ int lane_limit(bool ok, int lim)
+{
+    int x = ok ? lim : 0;
+    asm("" : "+v"(x));
+    return x;
+}
+
+// What a tile of k_big_step addresses its operands with: the front as bytes, a column in bytes (ld8; as an offset: ldu),
+// the block step [kb, kb + bw) and the previous panel [kp, kp + pw), the tile's rows and columns, the thread's wave (a
+// scalar) and lane indices, and its offsets: entry (l32, h5) of a panel with 32 rows, row l64 of the tile's rows / columns.
+struct BigTile {
+    char *Fb;
+    long long ld8;
+    unsigned ldu;
+    int kb, bw, kp, pw, row0, nrow, col0, ncol, wu, l32, h5;
+    unsigned o_kj, o_row, o_col;
+};
+
+// The operand panels of the previous block step, RAW: where an entry does not exist the offset is 0 (a panel's first
+// entry always exists) and the caller masks the value where it uses it.  Entry e = tid + 256 q of a panel is
+// (e % 64, e / 64) = (l64, wu + 4 q) or (e % 32, e / 32) = (l32, h5 + 8 q).
+template <int KIND>
+__device__ __forceinline__ void big_tile_panels(const BigTile &t, bool needs_d, double (&ra)[8], double (&rb)[8], double (&rad)[4], double (&rbd)[4])
+{
+    const char *pa = t.Fb + 8ll * t.row0 + t.kp * t.ld8;       // L(row0 + l64, kp + wu + 4 q)
+    const char *pb = (KIND == CS3_LU) ? t.Fb + 8ll * t.kp + t.col0 * t.ld8 : t.Fb + 8ll * t.col0 + t.kp * t.ld8;
+    const int lim_b = lane_limit(t.l32 < t.pw, t.ncol - t.h5); // LU: entry (l32, h5 + 8 q) exists iff 8 q < lim_b
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+        const unsigned k_off = t.wu + 4 * q < t.pw ? (unsigned) (t.wu + 4 * q) * t.ldu : 0u;    // (a scalar)
+        ra[q] = load_at(pa, t.o_row + k_off);
+        rb[q] = load_at(pb, (KIND == CS3_LU) ? (8 * q < lim_b ? t.o_kj + 8 * q * t.ldu : 0u) : t.o_col + k_off);
+    }
+    if (!needs_d) return;
+    const char *pad = t.Fb + 8ll * t.kb + t.kp * t.ld8;
+    const char *pbd = (KIND == CS3_LU) ? t.Fb + 8ll * t.kp + t.kb * t.ld8 : pad;
+    const int lim_ad = lane_limit(t.l32 < t.bw, t.pw - t.h5);
+    const int lim_bd = (KIND == CS3_LU) ? lane_limit(t.l32 < t.pw, t.bw - t.h5) : lim_ad;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        rad[q] = load_at(pad, 8 * q < lim_ad ? t.o_kj + 8 * q * t.ldu : 0u);
+        rbd[q] = load_at(pbd, 8 * q < lim_bd ? t.o_kj + 8 * q * t.ldu : 0u);
+    }
+}
+
+// The tile's accumulators acc[cb][v] = F(row0 + ti, col0 + 16 cb + 4 v + mq) and, for a tile that needs the diagonal
+// block, dacc[v] = F(kb + dr, kb + j0 + 4 v + mq), RAW in the same way (o_acc, o_d: the thread's entry at cb = v = 0)
+template <class V4>
+__device__ __forceinline__ void big_tile_accumulators(const BigTile &t, bool needs_d, int ti, int dr, int mq, int j0, V4 (&acc)[4], V4 &dacc)
+{
+    const unsigned o_acc = 8u * (unsigned) ti + (unsigned) mq * t.ldu, o_d = 8u * (unsigned) dr + (unsigned) mq * t.ldu;
+    const char *pc = t.Fb + 8ll * t.row0 + t.col0 * t.ld8, *pd = t.Fb + 8ll * t.kb + t.kb * t.ld8;
+    const int lim_c = lane_limit(ti < t.nrow, t.ncol - mq);    // column 16 cb + 4 v + mq exists iff 16 cb + 4 v < lim_c
+    const int lim_d = lane_limit(dr < t.bw, t.bw - mq - j0);   // column j0 + 4 v + mq exists iff 4 v < lim_d
+#pragma unroll
+    for (int cb = 0; cb < 4; ++cb)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) acc[cb][v] = load_at(pc, 16 * cb + 4 * v < lim_c ? o_acc + (16 * cb + 4 * v) * t.ldu : 0u);
+    if (!needs_d) return;
+#pragma unroll
+    for (int v = 0; v < 4; ++v) dacc[v] = load_at(pd, 4 * v < lim_d ? o_d + (unsigned) (j0 + 4 * v) * t.ldu : 0u);
+}
+
 }  // namespace cs3

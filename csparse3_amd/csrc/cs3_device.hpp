@@ -97,6 +97,7 @@ struct DeviceFactor {
     int *status = nullptr;        // [0] first failing pivot column, 0x7f7f7f7f when clean; [3]: a hand-over between waves timed out;
                                   // [4 + b]: pivots of matrix b that the perturbation replaced (PivotCtl::count)
     long long *tbuf = nullptr;    // diagnostics (CS3_PROFILE=1): 8 shader-clock stamps per front, schedule order
+    bool tbuf_diag = false;       //   CS3_PROFILE=2: the same, with k_big_step stamping its diagonal tile instead of tile (1, 0)
     // Schur handle (cs3_analyze_schur): the held Schur complements [batch][ns, ns] row-major, the order of the Schur
     // front and the pool offset of its dense buffer (schur.hip); null / 0 on a plain handle
     double *schur = nullptr;

@@ -1402,16 +1402,23 @@ k_front_wg(const FrontDesc *__restrict__ fdesc, int first,
 // column of the factor up to block b is final in F, which is what lets the forward sweep of a
 // chunk start while later blocks are still being factorised.
 // Tile index 0 = the panel block [kb, ke); index t >= 1 = 64 rows/columns from ke + 64 (t-1).
+// What a launch costs beside the elimination (220 cycles per pivot, a dependent chain) is what stands in front of and
+// behind it on the tile that finishes last: the descriptor (one scalar load of its first 64 bytes; four waits on kernel
+// arguments remain around it), the address arithmetic until the loads are out (one uniform base per panel, 32-bit offsets), the
+// one round trip of those loads, and the panel store.  The diagonal tile carries the copy-home on top: its parked
+// entries are requested with the other loads and stored behind them.  At kb == 0 there is no previous panel, and the
+// plain trailing tiles leave at once.  The numbers are in DESIGN.md, section 7.
 template <int KIND, class Rule>
 __global__ void __launch_bounds__(256)
 k_big_step(const FrontDesc *__restrict__ fdesc, int first, int kb, double *__restrict__ pool_all,
            long long pool_stride, double *__restrict__ dbuf_all, long long dbuf_stride,
-           Rule rule, int *status, int batch, long long *tbuf)
+           Rule rule, int *status, int batch, long long *tbuf, int stamp_bi)
 {
     const double inv_tol = rule.inv_tol;
-    // diagnostics (CS3_PROFILE=1): block-column tile (1, 0) of the step kb == 64 stamps its phases into the front's slot
+    // diagnostics (CS3_PROFILE=1): block-column tile (1, 0) of the step kb == 64 stamps its phases into the front's slot;
+    // CS3_PROFILE=2: the diagonal tile (0, 0) of that step instead (stamp_bi = 0)
     const long long t_start = tbuf ? (long long) __builtin_amdgcn_s_memtime() : 0;
-#define CS3_BSTAMP(p) do { if (tbuf && kb == 64 && blockIdx.x == 1 && blockIdx.y == 0 && threadIdx.x == 0) \
+#define CS3_BSTAMP(p) do { if (tbuf && kb == 64 && blockIdx.x == stamp_bi && blockIdx.y == 0 && threadIdx.x == 0) \
         tbuf[(long long) (first + blockIdx.z / batch) * 8 + (p)] = (long long) __builtin_amdgcn_s_memtime() - t_start; } while (0)
     // ... and the block-row tile (0, 1) of the same step: slots 6 (eliminated) and 7 (stored)
 #define CS3_BSTAMP_ROW(p) do { if (tbuf && kb == 64 && blockIdx.x == 0 && blockIdx.y == 1 && threadIdx.x == 0) \
@@ -1424,7 +1431,7 @@ k_big_step(const FrontDesc *__restrict__ fdesc, int first, int kb, double *__res
     __shared__ double T[64][BIG_NB + 1];
     __shared__ int pair_ready[2];               // eliminate_pair: pivots whose multipliers wave 0 / 1 has handed over
     if (threadIdx.x < 2) pair_ready[threadIdx.x] = 0;           // (two block barriers lie between this and the first use)
-    const FrontDesc d = fdesc[first + blockIdx.z / batch];     // grid (tiles, tiles, fronts * batch)
+    const DescHead d = load_desc_head(fdesc + (first + blockIdx.z / batch));   // grid (tiles, tiles, fronts * batch); ONE fetch
     const int bz = blockIdx.z % batch;
     const int r = d.r, w = d.w;
     const int nblk = (w + BIG_NB - 1) / BIG_NB;
@@ -1434,68 +1441,57 @@ k_big_step(const FrontDesc *__restrict__ fdesc, int first, int kb, double *__res
     const int kp = kb - BIG_NB, pw = min(kb, w) - kp;          // previous panel [kp, kp + pw), if kb > 0
     double *F = pool_all + (long long) bz * pool_stride + d.lpan;
     double *dbuf = dbuf_all + (long long) bz * dbuf_stride + d.dbuf;
-    const long long ld = r;
     const int tid = threadIdx.x;
     const int bi = blockIdx.x, bj = blockIdx.y;
     const int nsl = (r - ke + 63) / 64;
     if (bi > nsl || bj > nsl) return;
     if (KIND == CS3_CHOLESKY && bi < bj) return;
-    if (kb > 0 && bi == 0 && bj == 0) {             // the diagonal block parked by the previous launch goes home:
-        const int blk = kb / BIG_NB - 1;            // nobody reads that part of F any more (for the last block
-        const int k0 = blk * BIG_NB, cw = min(BIG_NB, w - k0);      // this is the closing launch)
-        for (int e = tid; e < cw * cw; e += 256) {
-            const int i = e % cw, j = e / cw;
-            if (KIND == CS3_LU || i >= j) F[(k0 + i) + (k0 + j) * ld] = dbuf[blk * (BIG_NB * BIG_NB) + i + j * BIG_NB];
-        }
-    }
-    if (!has_panel && (bi == 0 || bj == 0)) return;
     const int row0 = (bi == 0) ? kb : ke + (bi - 1) * 64, nrow = (bi == 0) ? bw : min(64, r - row0);
     const int col0 = (bj == 0) ? kb : ke + (bj - 1) * 64, ncol = (bj == 0) ? bw : min(64, r - col0);
     const bool needs_d = has_panel && (bi == 0 || bj == 0);
+    if (kb == 0 && !needs_d) return;                // no previous panel: a plain trailing tile has nothing to apply
 
+    // ---- addresses (cs3_devfn.hpp: BigTile): one uniform base per operand panel and 32-bit offsets per thread
+    const int l64 = tid & 63;
+    BigTile t{reinterpret_cast<char *>(F), 8ll * r, 8u * (unsigned) r, kb, bw, kp, pw, row0, nrow, col0, ncol,
+              __builtin_amdgcn_readfirstlane(tid >> 6), tid & 31, tid >> 5, 0u, 8u * (unsigned) (l64 < nrow ? l64 : 0), 8u * (unsigned) (l64 < ncol ? l64 : 0)};
+    t.o_kj = 8u * (unsigned) t.l32 + (unsigned) t.h5 * t.ldu;
+    // ---- the diagonal block parked by the previous launch goes home (tile (0, 0); for the last block this is the closing
+    // launch): nobody reads that part of F any more, so the tile requests its four parked entries per thread (entry
+    // tid + 256 q = (l32, h5 + 8 q) of the block) with its other loads and stores them once all of those are out
+    const bool home = kb > 0 && bi == 0 && bj == 0;
+    const int hblk = kb / BIG_NB - 1, hk0 = hblk * BIG_NB, hcw = min(BIG_NB, w - hk0);
+    double cp[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+        if (home) cp[q] = load_at(reinterpret_cast<const char *>(dbuf + (long long) hblk * (BIG_NB * BIG_NB) + 256 * q), 8u * (unsigned) tid);
+    auto send_home = [&]() {
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            if (t.l32 < hcw && t.h5 + 8 * q < hcw && (KIND == CS3_LU || t.l32 >= t.h5 + 8 * q))
+                store_at(t.Fb + 8ll * hk0 + hk0 * t.ld8, t.o_kj + 8 * q * t.ldu, cp[q]);
+    };
+    if (!has_panel && (bi == 0 || bj == 0)) { if (home) send_home(); return; }
     // ---- every global load of this tile goes out before anything waits for one: ONE round trip.  The loads are RAW
     // (from a safe address where the entry does not exist); their masks are applied where the values are used -- with
     // the select next to the load the compiler waited for the panel operands and stored them to LDS before it issued the
-    // loads of the accumulators (two round trips; stamps: 4.9 k cycles until "loads issued").
-    auto raw = [](const double *__restrict__ p, long long off, bool ok) -> double { return p[ok ? off : 0]; };
-    double ra[8], rb[8], rad[4], rbd[4];
-    if (kb > 0) {
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            const int e = tid + 256 * q;
-            { const int i = e % 64, k = e / 64; ra[q] = raw(F, (row0 + i) + (long long) (kp + k) * ld, k < pw && i < nrow); }
-            if (KIND == CS3_LU) { const int k = e % BIG_NB, j = e / BIG_NB; rb[q] = raw(F, (kp + k) + (long long) (col0 + j) * ld, k < pw && j < ncol); }
-            else { const int j = e % 64, k = e / 64; rb[q] = raw(F, (col0 + j) + (long long) (kp + k) * ld, k < pw && j < ncol); }
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int e = tid + 256 * q;
-            { const int i = e % BIG_NB, k = e / BIG_NB; rad[q] = raw(F, (kb + i) + (long long) (kp + k) * ld, needs_d && k < pw && i < bw); }
-            if (KIND == CS3_LU) { const int k = e % BIG_NB, j = e / BIG_NB; rbd[q] = raw(F, (kp + k) + (long long) (kb + j) * ld, needs_d && k < pw && j < bw); }
-            else { const int j = e % BIG_NB, k = e / BIG_NB; rbd[q] = raw(F, (kb + j) + (long long) (kp + k) * ld, needs_d && k < pw && j < bw); }
-        }
-    }
+    // loads of the accumulators (two round trips).
+    double ra[8], rb[8], rad[4] = {0.0, 0.0, 0.0, 0.0}, rbd[4] = {0.0, 0.0, 0.0, 0.0};
+    if (kb > 0) big_tile_panels<KIND>(t, needs_d, ra, rb, rad, rbd);
     // my outputs, in the register layout of v_mfma_f64_16x16x4 with the tile transposed (A operand = U
     // panel, B operand = L panel, so that lanes % 16 run along tile ROWS and global accesses stay
     // coalesced): wave wv owns tile rows [16 wv, 16 wv + 16), acc[cb][v] = F(row0 + 16 wv + mi, col0 + 16 cb + mq + 4 v)
     const int wv = tid >> 6, mi = tid & 15, mq = (tid >> 4) & 3;
     const int ti = 16 * wv + mi;
+    const unsigned o_acc = 8u * (unsigned) ti + (unsigned) mq * t.ldu;
     double4_t acc[4];
-#pragma unroll
-    for (int cb = 0; cb < 4; ++cb)
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-            const int j = 16 * cb + mq + 4 * v;
-            acc[cb][v] = raw(F, (row0 + ti) + (long long) (col0 + j) * ld, ti < nrow && j < ncol);
-        }
     // D, same scheme: wave wv owns the 16 x 16 sub-block (wv & 1, wv >> 1): dacc[v] = D(dr, dc0 + 4 v)
     const int dr = 16 * (wv & 1) + mi, dc0 = 16 * (wv >> 1) + mq;
-    double4_t dacc;
-#pragma unroll
-    for (int v = 0; v < 4; ++v)
-        dacc[v] = raw(F, (kb + dr) + (long long) (kb + dc0 + 4 * v) * ld, needs_d && dr < bw && dc0 + 4 * v < bw);
+    double4_t dacc = {0.0, 0.0, 0.0, 0.0};
+    big_tile_accumulators(t, needs_d, ti, dr, mq, 16 * (t.wu >> 1), acc, dacc);
     __builtin_amdgcn_sched_barrier(0);
     CS3_BSTAMP(0);
+    if (home) send_home();
     // (the masks now)
 #pragma unroll
     for (int cb = 0; cb < 4; ++cb)
@@ -1548,7 +1544,7 @@ k_big_step(const FrontDesc *__restrict__ fdesc, int first, int kb, double *__res
             for (int v = 0; v < 4; ++v) {
                 const int j = 16 * cb + mq + 4 * v;
                 if (ti < nrow && j < ncol && (KIND == CS3_LU || row0 + ti >= col0 + j))
-                    F[(row0 + ti) + (long long) (col0 + j) * ld] = acc[cb][v];
+                    store_at(t.Fb + 8ll * row0 + col0 * t.ld8, o_acc + (16 * cb + 4 * v) * t.ldu, acc[cb][v]);
             }
         return;
     }
@@ -1589,6 +1585,9 @@ k_big_step(const FrontDesc *__restrict__ fdesc, int first, int kb, double *__res
         const double tv = T[32 * half + li][cbase + j];
         e[j] = stacked ? (diag_tile ? 0.0 : tv) : dv;
     }
+    // where my part of the panel goes afterwards: row (block-column tile) or column (block-row tile) tr of the tile
+    const int tr = 32 * half + li;
+    const unsigned o_tr = 8u * (row_tile ? (unsigned) tr * (unsigned) r : (unsigned) tr);
     // (perturbation: the steps past bw run with zero multipliers instead of the padding's identity pivots, which a delta
     //  above 1 would replace -- the same factors either way)
     int hits = 0;
@@ -1615,26 +1614,27 @@ k_big_step(const FrontDesc *__restrict__ fdesc, int first, int kb, double *__res
                 }
             }
         }
+        CS3_BSTAMP(5);
         return;
     }
-    const int tr = 32 * half + li;                  // my row (block-column tile) or column (block-row tile) of the tile
-    if (stacked) {
+    if (stacked) {                                  // (uniform base per column of the block, the offset from before)
+        const int cu = HC * (t.wu >> 1);              // cbase, as a scalar
         if (!row_tile) {
             if (tr < nrow) {
 #pragma unroll
                 for (int cc = 0; cc < HC; ++cc) {
-                    const int c = cbase + cc;
+                    const int c = cu + cc;
                     if (c < bw) {
                         if (KIND == CS3_LU && !(fabs(e[cc]) <= inv_tol)) flag_column(status, d.c0 + kb + c);
-                        F[(row0 + tr) + (long long) (kb + c) * ld] = e[cc];
+                        store_at(t.Fb + 8ll * row0 + (kb + cu) * t.ld8, o_tr + cc * t.ldu, e[cc]);
                     }
                 }
             }
         } else if (tr < ncol) {
 #pragma unroll
             for (int cc = 0; cc < HC; ++cc) {
-                const int c = cbase + cc;
-                if (c < bw) F[(kb + c) + (long long) (col0 + tr) * ld] = e[cc];
+                const int c = cu + cc;
+                if (c < bw) store_at(t.Fb + 8ll * (kb + cu) + col0 * t.ld8, o_tr + 8 * cc, e[cc]);
             }
         }
     }
@@ -3947,9 +3947,13 @@ static hipError_t launch_big_block(const DeviceFactor &D, const LaunchGroup &g, 
     const int start = std::max(1, kb - BIG_NB + 1);
     const int rem = g.max_r - std::min(start, g.max_r);        // largest trailing order over the group
     const int tiles = 1 + (rem + 63) / 64;
+    // k_big_step keeps a thread's byte offset inside a tile, up to 64 (r + 1) doubles, in 32 bits
+    // (unreachable with today's memories: such a front alone takes 2^47 bytes)
+    if (g.max_r >= (1 << 22)) { set_error("k_big_step: a front of order " + std::to_string(g.max_r) + " is beyond its 32-bit tile offsets"); return hipErrorInvalidValue; }
     with_rule<KIND>(pc, [&](auto rule) {
         hipLaunchKernelGGL((k_big_step<KIND, decltype(rule)>), dim3(tiles, tiles, g.count * batch), dim3(256), 0, st, D.fdesc,
-                           g.first, kb, D.pool_pm, D.pm_stride, D.dbuf, D.dbuf_size, rule, D.status, (int) batch, D.tbuf);
+                           g.first, kb, D.pool_pm, D.pm_stride, D.dbuf, D.dbuf_size, rule, D.status, (int) batch, D.tbuf,
+                           D.tbuf_diag ? 0 : 1);
     });
     CS3_LAUNCH_CHECK();
     return hipSuccess;

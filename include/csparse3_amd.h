@@ -602,7 +602,8 @@ int cs3_import_factor_dev(cs3_handle h, const double *src_dev, void *stream);
  * With CS3_PROFILE=1 in the environment every LDS-resident front records six
  * shader-clock stamps (descriptor read, zeroed, assembled, eliminated, staged,
  * stored) relative to its start; out[nsuper][8] in schedule order.  Not part
- * of the reference-facing surface. */
+ * of the reference-facing surface.  CS3_PROFILE=2: the same, except that a big
+ * front's block step stamps its diagonal tile instead of tile (1, 0). */
 int cs3_debug_front_stamps(cs3_handle h, int64_t *out);
 /* Fills the LDS of every CU with NaN bit patterns (the LDS keeps its contents between kernels): the parity tests call it
  * before the numeric entry points so that a product of a masked zero and an unwritten LDS word cannot hide. */

@@ -39,3 +39,13 @@ big = np.flatnonzero((fr > 136) & (out[:, 5] > 0))
 for j in big:
     print("big front r,w =", fr[j], fw[j], "step kb=64 tile(1,0) cycles since kernel start: loads issued %d, staged %d, updated %d, "
           "D/T in LDS %d, D factored %d, panel solved+stored %d; block-row tile (0,1): eliminated %d, stored %d" % tuple(out[j, :8]))
+# ... and of the diagonal tile (0, 0) of the same step: a second handle under CS3_PROFILE=2 (read when a handle goes to the device)
+F.close()
+os.environ["CS3_PROFILE"] = "2"
+F = hip.Factorization(m, n, Ap, Ai)
+for _ in range(5):
+    F.factor(Ax, 1e-3)
+assert L.cs3_debug_front_stamps(F._h, out.ctypes.data_as(C.POINTER(C.c_int64))) == 0
+for j in big:
+    print("big front r,w =", fr[j], fw[j], "step kb=64 tile(0,0) cycles since kernel start: loads issued (parked block requested) %d, "
+          "staged (parked block stored) %d, updated %d, D in LDS %d, D factored %d, parked %d" % tuple(out[j, :6]))
