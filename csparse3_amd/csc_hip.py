@@ -68,9 +68,10 @@ class GmresLimits(C.Structure):
 
 class RefineXpLimits(C.Structure):
     """cs3_refine_xp_limits_t: threads per workgroup and the workgroup cap of the doubled-precision residual kernel, the
-    default max_iters, eps = 2^-52 and the stall ratio of the extra-precise refinement."""
+    default max_iters, eps = 2^-52 and the stall ratio of the extra-precise refinement, the workgroup cap over the rows of
+    the maxima kernel."""
     _fields_ = [(name, C.c_int64) for name in ("block", "grid_cap", "max_iters_default")] + \
-               [(name, C.c_double) for name in ("eps", "stall_ratio")]
+               [(name, C.c_double) for name in ("eps", "stall_ratio")] + [("maxima_grid_cap", C.c_int64)]
 
 
 class SensInfo(C.Structure):

@@ -1735,6 +1735,7 @@ int cs3_refine_xp_limits(cs3_refine_xp_limits_t *out)
     out->max_iters_default = XP_MAX_ITERS_DEFAULT;
     out->eps = XP_EPS;
     out->stall_ratio = XP_STALL_RATIO;
+    out->maxima_grid_cap = XP_MAXIMA_GRID_CAP;
     return CS3_OK;
 }
 

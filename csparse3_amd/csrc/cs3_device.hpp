@@ -417,6 +417,7 @@ hipError_t launch_kry_axpy(const KryWork &K, double *X, hipStream_t st);
 // refine_xp.hip: extra-precise refinement (cs3_refine_xp*), batch * k systems in lock-step with the layouts of krylov.hip.
 constexpr int XP_BLOCK = 256;                  // threads per workgroup of every kernel of the family
 constexpr long long XP_GRID_CAP = 4096;        // workgroups (per matrix) of the residual and update kernels: grid-stride beyond
+constexpr long long XP_MAXIMA_GRID_CAP = 1024; // workgroups over the rows of k_xp_maxima (per matrix and column tile): each ends in one atomic per column
 constexpr int XP_MAX_ITERS_DEFAULT = 10;
 constexpr double XP_EPS = 0x1p-52, XP_STALL_RATIO = 0.5;
 enum XpFlag : int { XP_RUNNING = 0, XP_CONVERGED = 1, XP_STALLED = 2, XP_NONFINITE = 3 };

@@ -175,8 +175,7 @@ hipError_t launch_xp_maxima(const double *D, const double *X, XpSys *sys, long l
 {
     if (n == 0 || batch == 0) return hipSuccess;
     const int w = std::min(nrhs, XP_BLOCK), rows = XP_BLOCK / w;
-    // (1024 workgroups over the rows at the most: each ends in one atomic per column)
-    dim3 grid((unsigned) std::min<long long>((n + rows - 1) / rows, 1024), (unsigned) batch, (unsigned) ((nrhs + w - 1) / w));
+    dim3 grid((unsigned) std::min<long long>((n + rows - 1) / rows, XP_MAXIMA_GRID_CAP), (unsigned) batch, (unsigned) ((nrhs + w - 1) / w));
     hipLaunchKernelGGL(k_xp_maxima, grid, dim3(XP_BLOCK), 0, st, D, X, sys, n, nrhs);
     return hipGetLastError();
 }

@@ -359,11 +359,11 @@ int cs3_debug_gmres_basis(cs3_handle h, double *V, int64_t nvec);
  * maxima, nd_prev, rate, iters, flag, the apply mask) belongs to the handle, grows with k and goes with cs3_free; a
  * second call with the same k allocates nothing.
  * cs3_refine_xp_limits: the launch shape of the residual kernel, the default max_iters (10), eps = 2^-52,
- *   stall_ratio = 0.5; needs no device.
+ *   stall_ratio = 0.5, maxima_grid_cap = the workgroups over the rows of the maxima kernel; needs no device.
  * cs3_refine_xp, cs3_residual_xp: the host-array forms (the null stream): the same kernels, the same bits.
  * Not offered: a capture-safe form of fixed length, a componentwise forward bound, Schur handles, residuals in more
  * than doubled precision. */
-typedef struct { int64_t block, grid_cap, max_iters_default; double eps, stall_ratio; } cs3_refine_xp_limits_t;
+typedef struct { int64_t block, grid_cap, max_iters_default; double eps, stall_ratio; int64_t maxima_grid_cap; } cs3_refine_xp_limits_t;
 int cs3_refine_xp_limits(cs3_refine_xp_limits_t *out);
 int cs3_residual_xp_dev(cs3_handle h, const double *Ax_dev, const double *B_dev, const double *X_dev, const double *XT_dev,
                         double *R_dev, double *S_dev, int64_t k, int64_t trans, void *stream);

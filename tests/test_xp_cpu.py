@@ -159,7 +159,7 @@ def test_fixture_inputs_regenerate_bit_for_bit(cases, refs):
 def test_limits():
     lim = csc_hip.refine_xp_limits()
     assert lim.eps == EPS and lim.stall_ratio == 0.5 and lim.max_iters_default == 10
-    assert lim.block >= 64 and lim.block % 64 == 0 and lim.grid_cap >= 1
+    assert lim.block >= 64 and lim.block % 64 == 0 and lim.grid_cap >= 1 and lim.maxima_grid_cap >= 1
     assert csc_hip.lib().cs3_refine_xp_limits(None) == csc_hip.CS3_ERR_ARG
 
 

@@ -145,3 +145,83 @@ def plain_rounds(solve, n, Ap, Ai, Ax, b, x0, rounds=10, trans=False):
     for _ in range(rounds):
         x = x + solve(b - A @ x)
     return x
+
+
+def _max_row(v):
+    """(maximum with a NaN winning, its first row, its ratio to the runner-up of the column) of non-negative numbers.  A
+    column of one entry has ratio inf, a column with a NaN ratio nan and the row of its first NaN."""
+    v = np.asarray(v, dtype=np.float64).reshape(-1)
+    if v.size == 0:
+        return 0.0, -1, float("inf")
+    nan = np.isnan(v)
+    if nan.any():
+        return float("nan"), int(np.argmax(nan)), float("nan")
+    row = int(np.argmax(v))
+    rest = np.delete(v, row)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ratio = float("inf") if rest.size == 0 else float(np.float64(v[row]) / np.float64(rest.max()))
+    return float(v[row]), row, ratio
+
+
+def refine_xp_all(solve_all, n, Ap, Ai, AX, B, X0, max_iters=10, trans=False):
+    """All batch * k systems in lock-step, as refine_xp_run (api.cpp) drives them: AX [batch, nnz], B and X0 [batch, n, k],
+    solve_all(R [batch, n, k]) -> the corrections of the whole array in one call.  Every pass: resid_xp with the tail on
+    every system (stopped ones included), one solve_all, the maxima, the control rule and the update per system; the loop
+    ends when no system is active.  -> dict(x, xt [batch, n, k]; iters, flag, rate, ferr, berr, nd_prev [batch * k];
+    trace: one dict per pass of [batch, k] arrays nd, nx, row_d, row_x (the row of each maximum), ratio_d, ratio_x (its
+    ratio to the runner-up of the column), apply, stopped (after the pass))."""
+    AX = np.asarray(AX, dtype=np.float64).reshape(-1, int(np.asarray(Ap)[n]))
+    batch = AX.shape[0]
+    B = np.asarray(B, dtype=np.float64).reshape(batch, n, -1)
+    k = B.shape[2]
+    X = np.array(X0, dtype=np.float64).reshape(batch, n, k)
+    XT = np.zeros_like(X)
+    iters, flag = np.zeros((batch, k), dtype=np.int32), np.zeros((batch, k), dtype=np.int32)
+    rate, nd_prev = np.zeros((batch, k)), np.zeros((batch, k))
+    stopped = np.zeros((batch, k), dtype=bool)
+    trace = []
+    active = batch * k if n > 0 else 0
+    for _ in range(max_iters):
+        if not active:
+            break
+        R = np.stack([resid_xp(n, Ap, Ai, AX[m], B[m], X[m], XT[m], trans)[0] for m in range(batch)])
+        D = np.asarray(solve_all(R), dtype=np.float64).reshape(batch, n, k)
+        step = {key: np.zeros((batch, k), dtype=dt) for key, dt in (("nd", float), ("nx", float), ("row_d", np.int64),
+                                                                     ("row_x", np.int64), ("ratio_d", float),
+                                                                     ("ratio_x", float), ("apply", bool))}
+        for m in range(batch):
+            for t in range(k):
+                nd, step["row_d"][m, t], step["ratio_d"][m, t] = _max_row(np.abs(D[m, :, t]))
+                nx, step["row_x"][m, t], step["ratio_x"][m, t] = _max_row(np.abs(X[m, :, t]))
+                step["nd"][m, t], step["nx"][m, t] = nd, nx
+                if stopped[m, t]:
+                    continue
+                if not (np.isfinite(nd) and np.isfinite(nx)):
+                    flag[m, t], stopped[m, t] = 3, True
+                    continue
+                if iters[m, t] > 0:
+                    with np.errstate(divide="ignore", invalid="ignore"):
+                        q = float(np.float64(nd) / np.float64(nd_prev[m, t]))
+                    if q > rate[m, t]:
+                        rate[m, t] = q
+                    if nd > STALL_RATIO * nd_prev[m, t]:
+                        flag[m, t], stopped[m, t] = 2, True
+                        continue
+                step["apply"][m, t] = True
+                iters[m, t] += 1
+                nd_prev[m, t] = nd
+                if nd <= EPS * nx:
+                    flag[m, t], stopped[m, t] = 1, True
+            cols = np.nonzero(step["apply"][m])[0]
+            if cols.size:
+                with np.errstate(invalid="ignore", over="ignore"):
+                    s, e = two_sum(X[m][:, cols], D[m][:, cols])
+                    X[m][:, cols], XT[m][:, cols] = two_sum(s, XT[m][:, cols] + e)
+        step["stopped"] = stopped.copy()
+        trace.append(step)
+        active = int((~stopped).sum())
+    be = np.stack([berr(n, Ap, Ai, AX[m], B[m], X[m], trans) for m in range(batch)]) if n > 0 else np.zeros((batch, k))
+    fe = np.array([[ferr_rule(int(iters[m, t]), int(flag[m, t]), float(rate[m, t]), float(nd_prev[m, t]),
+                              _max_nan(np.abs(X[m, :, t]))) for t in range(k)] for m in range(batch)])
+    return dict(x=X, xt=XT, iters=iters.reshape(-1), flag=flag.reshape(-1), rate=rate.reshape(-1), ferr=fe.reshape(-1),
+                berr=be.reshape(-1), nd_prev=nd_prev.reshape(-1), trace=trace)
