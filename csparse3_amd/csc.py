@@ -51,7 +51,7 @@ class CscMat:
                       data=self.data.copy())
 
     def todense(self):
-        val = np.zeros((self.m, self.n), dtype=np.float64)
+        val = np.zeros((self.m, self.n), dtype=np.result_type(np.asarray(self.data).dtype, np.float64))     # (complex data: complex128)
         for j in range(self.n):
             for p in range(self.indptr[j], self.indptr[j + 1]):
                 val[self.indices[p], j] = self.data[p]
@@ -191,19 +191,36 @@ class CscMat:
         h.update(np.ascontiguousarray(self.indices[:nnz], dtype=np.int32).tobytes())
         return self.m, n, nnz, h.digest()
 
-    def _analysis(self, kind, order, q, match=False, schur=None):
+    def _is_complex(self):
+        return bool(np.iscomplexobj(self.data))
+
+    def _analysis(self, kind, order, q, match=False, schur=None, rotate=None):
+        cplx = self._is_complex()
         key = (kind, order, None if q is None else bytes(np.asarray(q, dtype=np.int32)), self._pattern_fingerprint(), bool(match),
-               None if schur is None else bytes(np.asarray(schur, dtype=np.int32)))
+               None if schur is None else bytes(np.asarray(schur, dtype=np.int32)), "complex128" if cplx else "float64", rotate)
         f = self._factorization
         if f is None or f[0] != key:
             if f is not None:
                 f[1].close()
-            fac = _k.Factorization(self.m, self.n, self.indptr, self.indices, kind=kind, order=order, q=q,
-                                   match_values=self.data if match else None, schur=schur)
+            if cplx:
+                assert self.m == self.n, "square matrix required"
+                fac = _k.ComplexFactorization(self.n, self.indptr, self.indices, kind=kind, order=order, q=q, rotate=rotate)
+            else:
+                fac = _k.Factorization(self.m, self.n, self.indptr, self.indices, kind=kind, order=order, q=q,
+                                       match_values=self.data if match else None, schur=schur)
             self._factorization = f = (key, fac)
         return f[1]
 
-    def lu(self, tol=0.0, order=_k.ORDER_AMD, q=None, match=False, perturb=0.0, schur=None):
+    def _complex_scope(self, **given):
+        """Complex data goes through the real-equivalent plan (csc_hip.ComplexFactorization), which packages LU, Cholesky
+        and the N / T / H solves; what it does not package says so."""
+        used = [name for name, v in given.items() if v]
+        if used:
+            raise NotImplementedError("complex matrices: %s is outside the scope of the real-equivalent plan (LU, Cholesky and "
+                                      "solves with trans 'N', 'T', 'H'); the real handle is at ComplexFactorization.real"
+                                      % ", ".join(used))
+
+    def lu(self, tol=0.0, order=_k.ORDER_AMD, q=None, match=False, perturb=0.0, schur=None, rotate=True):
         """Numeric LU on the device; the symbolic analysis is cached on the object, so calling
         lu() again after changing .data is a refactorisation with the pattern reused.
         match: permute rows by the maximum-product transversal and scale before the analysis (matrices without a strong
@@ -212,7 +229,12 @@ class CscMat:
         (a number: delta itself; True: sqrt(eps), times max |data| when match is false).  The analysis is reused whatever
         perturb is; F.perturbed() counts the replaced pivots and solutions then need F.refine / solve(perturb=...).
         schur: the variables that are not eliminated (Factorization(schur=...)): the interior is factorised and F.schur()
-        is the dense Schur complement on that set; order / q then refer to the interior."""
+        is the dense Schur complement on that set; order / q then refer to the interior.
+        Complex .data: a csc_hip.ComplexFactorization comes back (LU of the real-equivalent form, cached the same way);
+        rotate as there; match, perturb and schur raise NotImplementedError.  Real data ignores rotate."""
+        if self._is_complex():
+            self._complex_scope(match=match, perturb=perturb, schur=schur is not None)
+            return self._analysis(_k.CS3_LU, order, q, rotate=bool(rotate)).factor(self.data, tol)
         F = self._analysis(_k.CS3_LU, order, q, match, schur)
         delta = _k.perturbation_delta(perturb, self.data, match)
         if delta != F.perturbation:
@@ -221,6 +243,10 @@ class CscMat:
         return F
 
     def chol(self, order=_k.ORDER_AMD, q=None, schur=None):
+        """Numeric Cholesky on the device (complex .data: Hermitian positive definite, through ComplexFactorization)."""
+        if self._is_complex():
+            self._complex_scope(schur=schur is not None)
+            return self._analysis(_k.CS3_CHOLESKY, order, q, rotate=False).factor(self.data)
         F = self._analysis(_k.CS3_CHOLESKY, order, q, schur=schur)
         F.factor(self.data)
         return F
@@ -237,7 +263,12 @@ class CscMat:
         With perturb the solution is refined against A when pivots were replaced (Factorization.solve_refined; not
         offered together with trans); refine="gmres": by GMRES on the held factors instead of the stationary rounds.
         refine="extra": the solve is followed by the extra-precise refinement (Factorization.refine_xp, at most max_refine
-        corrections), with or without perturb, with or without trans."""
+        corrections), with or without perturb, with or without trans.
+        Complex .data: trans is "N", "T" (A^T, no conjugate; True means this) or "H"; match, perturb and a refine other
+        than the default raise NotImplementedError."""
+        if self._is_complex():
+            self._complex_scope(match=match, perturb=perturb, refine=refine != "stationary")
+            return self.lu(tol).solve(b, trans=trans)
         F = self.lu(tol, match=match, perturb=perturb)
         if refine == "extra":
             return F.refine_xp(self.data, b, max_iters=max_refine, trans=trans)[0]
@@ -250,6 +281,7 @@ class CscMat:
         """x_c = (A + dA_c) \\ b for a list of sparse modifications, `deltas` = [(rows, cols, vals), ...] (triplets of dA_c;
         duplicates add), from ONE LU factorisation of A (factorises as solve does).  -> (X [n, len(deltas)], rpiv); a
         case whose modified matrix is singular (rpiv <= sing_tol, or an exactly zero pivot) has a NaN column."""
+        self._complex_scope(solve_modified=self._is_complex())
         F = self.lu(tol)
         with F.updates_plan([(d[0], d[1]) for d in deltas]) as plan:
             vals = [np.atleast_1d(np.asarray(d[2], dtype=np.float64)) for d in deltas]
@@ -261,6 +293,7 @@ class CscMat:
         solution itself), op(A) = A' with `trans`, from ONE LU factorisation of A (factorises as solve does).  Only the
         dense Y [p, k] comes back; side "auto" solves for the fewer of k and p columns.  C is turned into the CSC form
         of C' (its rows) with csc_transpose, values included."""
+        self._complex_scope(sensitivities=self._is_complex())
         assert B.m == self.n and (C is None or C.n == self.n)
         F = self.lu(tol)
         Ct, Ctx = None, None
@@ -273,11 +306,13 @@ class CscMat:
 
     def condest(self, tol=0.0):
         """1-norm condition estimate ||A||_1 * est(||A^-1||_1) from the LU factors (factorises as solve does)."""
+        self._complex_scope(condest=self._is_complex())
         cond, _ = self.lu(tol).condest(self.data)
         return float(cond[0])
 
     def slogdet(self, tol=0.0):
         """(sign, log|det A|) from the LU factors (factorises as solve does)."""
+        self._complex_scope(slogdet=self._is_complex())
         sign, logabs = self.lu(tol).slogdet()
         return float(sign[0]), float(logabs[0])
 
@@ -305,13 +340,19 @@ def lusol(A, b, order=1, tol=0.0, match=False, perturb=0.0, max_refine=10, refin
     """x = A \\ b (cs_lusol).  match: with the maximum-product matching and scaling in front (CscMat.lu).  perturb: small
     pivots are replaced instead of rejected and the solution is refined, at most max_refine rounds (csc_lusol_f);
     refine="gmres": by GMRES on the held factors; refine="extra": extra-precise refinement (doubled-precision residuals)
-    after the solve, with or without perturb."""
+    after the solve, with or without perturb.  Complex A.data: through A.lu (the analysis is cached on A); match, perturb
+    and a refine other than the default raise NotImplementedError."""
+    if np.iscomplexobj(A.data):
+        A._complex_scope(match=match, perturb=perturb, refine=refine != "stationary")
+        return A.lu(tol, order=order).solve(b)
     return _k.csc_lusol_f(order, A.m, A.n, A.indptr, A.indices, A.data, b, tol, match=match, perturb=perturb,
                           max_refine=max_refine, refine=refine)
 
 
 def cholsol(A, b, order=1):
-    """x = A \\ b for symmetric positive definite A (cs_cholsol)."""
+    """x = A \\ b for symmetric positive definite A (cs_cholsol); complex A.data: Hermitian positive definite, through A.chol."""
+    if np.iscomplexobj(A.data):
+        return A.chol(order=order).solve(b)
     return _k.csc_cholsol_f(order, A.m, A.n, A.indptr, A.indices, A.data, b)
 
 

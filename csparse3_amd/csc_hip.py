@@ -60,6 +60,16 @@ class UnionLimits(C.Structure):
     _fields_ = [(name, C.c_int64) for name in ("block", "grid_cap", "entries_per_lane")]
 
 
+class CplxInfo(C.Structure):
+    """cs3_cplx_info: sizes of a complex plan and of the real form the handle analyses."""
+    _fields_ = [(name, C.c_int64) for name in ("n", "nnz", "batch", "rotate", "n_real", "nnz_real", "rows_without_diagonal")]
+
+
+class CplxLimits(C.Structure):
+    """cs3_cplx_limits_t: the constants that shape the launches of the complex glue kernels."""
+    _fields_ = [(name, C.c_int64) for name in ("block", "grid_cap")]
+
+
 class GmresLimits(C.Structure):
     """cs3_gmres_limits_t: the largest restart, the rows per chunk of the fixed-order reductions, the right-hand sides
     per tile of the kernels."""
@@ -250,6 +260,24 @@ def lib():
         L.cs3_union_upload.argtypes = [vp]
         L.cs3_union_values_dev.argtypes = [vp, vp, vp, vp]
         L.cs3_union_values.argtypes = [vp, _f64p, _f64p]
+        L.cs3_cplx_limits.argtypes = [C.POINTER(CplxLimits)]
+        L.cs3_cplx_plan_create.argtypes = [I64, _i32p, _i32p, I64, I64, C.POINTER(vp)]
+        L.cs3_cplx_plan_free.argtypes = [vp]
+        L.cs3_cplx_plan_info.argtypes = [vp, C.POINTER(CplxInfo)]
+        L.cs3_cplx_plan_pattern.argtypes = [vp, _i32p, _i32p]
+        L.cs3_cplx_plan_order.argtypes = [vp, I64, _i32p, _i32p]
+        L.cs3_cplx_upload.argtypes = [vp]
+        L.cs3_cplx_workspace_dev.argtypes = [vp, I64, I64, C.POINTER(vp)]
+        L.cs3_cplx_values_dev.argtypes = [vp, vp, vp, vp]
+        L.cs3_cplx_pack_dev.argtypes = [vp, I64, vp, vp, I64, vp]
+        L.cs3_cplx_unpack_dev.argtypes = [vp, I64, vp, vp, I64, I64, vp]
+        L.cs3_cplx_residual_dev.argtypes = [vp, I64, vp, vp, vp, vp, I64, vp]
+        L.cs3_cplx_rotation_dev.argtypes = [vp, C.POINTER(vp)]
+        L.cs3_cplx_values.argtypes = [vp, _f64p, _f64p]
+        L.cs3_cplx_pack.argtypes = [vp, I64, _f64p, _f64p, I64]
+        L.cs3_cplx_unpack.argtypes = [vp, I64, _f64p, _f64p, I64, I64]
+        L.cs3_cplx_residual.argtypes = [vp, I64, _f64p, _f64p, _f64p, _f64p, I64]
+        L.cs3_cplx_rotation.argtypes = [vp, _f64p]
         _lib = L
     return _lib
 
@@ -1297,6 +1325,268 @@ class UnionPlan:
         """[nmat, nnz_union] at union_ptr from the concatenated values at cat_ptr (device addresses), asynchronous on
         `stream`: one launch, no allocation, no synchronisation.  The same bits as values()."""
         _check(lib().cs3_union_values_dev(self._p, C.c_void_p(cat_ptr), C.c_void_p(union_ptr), C.c_void_p(stream)))
+
+
+# -------------------------------------------------------- complex matrices --
+
+CPLX_N, CPLX_T, CPLX_H = 0, 1, 2
+_CPLX_OPS = {"N": CPLX_N, "T": CPLX_T, "H": CPLX_H, False: CPLX_N, True: CPLX_T}
+
+
+def cplx_op(trans):
+    """"N" | "T" | "H" (or False | True for N | T, or the enum itself) -> cs3_cplx_op."""
+    if isinstance(trans, str):
+        trans = trans.upper()
+    assert trans in _CPLX_OPS or trans == CPLX_H, "trans must be 'N', 'T' or 'H'"
+    return _CPLX_OPS.get(trans, trans)
+
+
+def cplx_limits():
+    """The constants that shape the launches of the complex glue kernels (cs3_cplx_limits); needs no GPU."""
+    out = CplxLimits()
+    _check(lib().cs3_cplx_limits(C.byref(out)))
+    return out
+
+
+def _c128(a):
+    return np.ascontiguousarray(a, dtype=np.complex128)
+
+
+def _pc(a):
+    return a.ctypes.data_as(_f64p)
+
+
+class ComplexPlan:
+    """A complex CSC pattern of order n for a handle on its real-equivalent form (include/csparse3_amd.h, "complex
+    matrices"): every entry w is the block [[Re w, -Im w], [Im w, Re w]] of a real matrix of order 2n, rows and columns
+    interleaved.  pattern() and order() are what Factorization(2n, 2n, Rp, Ri, q=q2) analyses (host work, no GPU);
+    values / pack / unpack / residual are the device glue, with host-array and `_dev` forms that give the same bits.
+    rotate: rows are multiplied by s_i = conj(d_i) / max(|Re d_i|, |Im d_i|) so that the static pivots, the real parts of
+    the diagonal, are positive (an admittance matrix has a mostly imaginary diagonal).  Right-hand sides are [n], [n, k] or
+    [batch, n, k] complex128, their real forms [2n], [2n, k] or [batch, 2n, k] float64."""
+
+    def __init__(self, n, Ap, Ai, batch=1, rotate=True):
+        self._p = C.c_void_p()
+        Ap, Ai = _i32(Ap), _i32(Ai)
+        _check(lib().cs3_cplx_plan_create(n, _pi(Ap), _pi(Ai), batch, int(rotate), C.byref(self._p)))
+        inf = self.info
+        self.n, self.nnz, self.batch, self.rotate = int(inf.n), int(inf.nnz), int(inf.batch), bool(inf.rotate)
+
+    def close(self):
+        if self._p:
+            lib().cs3_cplx_plan_free(self._p)
+            self._p = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    @property
+    def info(self):
+        out = CplxInfo()
+        _check(lib().cs3_cplx_plan_info(self._p, C.byref(out)))
+        return out
+
+    def pattern(self):
+        """-> (Rp int32[2n + 1], Ri int32[4 nnz]) on the host: the pattern of the real form."""
+        Rp = np.empty(2 * self.n + 1, dtype=np.int32)
+        Ri = np.empty(4 * self.nnz, dtype=np.int32)
+        _check(lib().cs3_cplx_plan_pattern(self._p, _pi(Rp), _pi(Ri)))
+        return Rp, Ri
+
+    def order(self, order=ORDER_AMD, q=None):
+        """-> q2 int32[2n]: the fill-reducing order of the complex pattern (or q) with every index doubled into its pair."""
+        qa = None
+        if q is not None:
+            qa = _i32(q)
+            assert qa.size == self.n
+            order = ORDER_GIVEN
+        q2 = np.empty(2 * self.n, dtype=np.int32)
+        _check(lib().cs3_cplx_plan_order(self._p, order, _pi(qa), _pi(q2)))
+        return q2
+
+    def upload(self):
+        """Puts the tables on the device now (the first device call does it otherwise; do it before a graph capture)."""
+        _check(lib().cs3_cplx_upload(self._p))
+        return self
+
+    def _k(self, a):
+        per = self.batch * self.n
+        assert per > 0 and a.size % per == 0, "array does not match [batch,] n [, k]"
+        assert a.ndim == 3 or self.batch == 1, "with batch > 1 arrays are [batch, n, k]"
+        return a.size // per
+
+    @staticmethod
+    def _scaled(shape, num, den):
+        axis = 1 if len(shape) == 3 else 0
+        return tuple(s * num // den if a == axis else s for a, s in enumerate(shape))
+
+    def values(self, Az):
+        """Az: complex128 [batch, nnz] (or [nnz]).  -> float64 [batch, 4 nnz]: the values of the real form, rotated."""
+        Az = _c128(Az).reshape(-1)
+        assert Az.size >= self.batch * self.nnz
+        out = np.empty((self.batch, 4 * self.nnz), dtype=np.float64)
+        _check(lib().cs3_cplx_values(self._p, _pc(Az), _pf(out)))
+        return out
+
+    def rotation(self):
+        """-> complex128 [batch, n]: s of the last values call."""
+        s = np.empty((self.batch, self.n), dtype=np.complex128)
+        _check(lib().cs3_cplx_rotation(self._p, _pc(s)))
+        return s
+
+    def pack(self, Z, trans="N"):
+        """The real right-hand side of op(A) x = z for the handle (op N: rotated; T: conjugated; H: as it is)."""
+        Z = _c128(Z)
+        k = self._k(Z)
+        Y = np.empty(self._scaled(Z.shape, 2, 1), dtype=np.float64)
+        _check(lib().cs3_cplx_pack(self._p, cplx_op(trans), _pc(Z), _pf(Y), k))
+        return Y
+
+    def unpack(self, Y, trans="N", into=None):
+        """The complex solution from the handle's real one.  into: a complex array the result is ADDED to (a new array
+        comes back; `into` stays)."""
+        Y = _f64(Y)
+        per = 2 * self.batch * self.n
+        assert per > 0 and Y.size % per == 0, "array does not match [batch,] 2n [, k]"
+        k = Y.size // per
+        if into is None:
+            Z = np.empty(self._scaled(Y.shape, 1, 2), dtype=np.complex128)
+        else:
+            Z = np.array(into, dtype=np.complex128, order="C", copy=True)
+            assert Z.size * 2 == Y.size
+        _check(lib().cs3_cplx_unpack(self._p, cplx_op(trans), _pf(Y), _pc(Z), k, 0 if into is None else 1))
+        return Z
+
+    def residual(self, Az, b, x, trans="N"):
+        """R = b - op(A) x with the caller's values Az (complex128 [batch, nnz]), not the rotated ones."""
+        Az, b, x = _c128(Az).reshape(-1), _c128(b), _c128(x)
+        assert Az.size >= self.batch * self.nnz and b.shape == x.shape
+        R = np.empty_like(b)
+        _check(lib().cs3_cplx_residual(self._p, cplx_op(trans), _pc(Az), _pc(b), _pc(x), _pc(R), self._k(b)))
+        return R
+
+    # -- device pointers on a HIP stream: one or two launches each, nothing allocated after the first call
+    def values_dev(self, az_ptr, rx_ptr, stream=0):
+        _check(lib().cs3_cplx_values_dev(self._p, C.c_void_p(az_ptr), C.c_void_p(rx_ptr), C.c_void_p(stream)))
+
+    def pack_dev(self, z_ptr, y_ptr, k=1, trans="N", stream=0):
+        _check(lib().cs3_cplx_pack_dev(self._p, cplx_op(trans), C.c_void_p(z_ptr), C.c_void_p(y_ptr), k, C.c_void_p(stream)))
+
+    def unpack_dev(self, y_ptr, z_ptr, k=1, trans="N", accumulate=False, stream=0):
+        _check(lib().cs3_cplx_unpack_dev(self._p, cplx_op(trans), C.c_void_p(y_ptr), C.c_void_p(z_ptr), k, int(bool(accumulate)),
+                                         C.c_void_p(stream)))
+
+    def residual_dev(self, az_ptr, b_ptr, x_ptr, r_ptr, k=1, trans="N", stream=0):
+        _check(lib().cs3_cplx_residual_dev(self._p, cplx_op(trans), C.c_void_p(az_ptr), C.c_void_p(b_ptr), C.c_void_p(x_ptr),
+                                           C.c_void_p(r_ptr), k, C.c_void_p(stream)))
+
+    def rotation_dev(self):
+        """The device address of s [batch, n] complex."""
+        out = C.c_void_p()
+        _check(lib().cs3_cplx_rotation_dev(self._p, C.byref(out)))
+        return int(out.value or 0)
+
+    def workspace_dev(self, slot, count):
+        """The device address of a block of `count` doubles that the plan owns (slot 0, 1 or 2; grown only when needed)."""
+        out = C.c_void_p()
+        _check(lib().cs3_cplx_workspace_dev(self._p, slot, count, C.byref(out)))
+        return int(out.value or 0)
+
+
+class ComplexFactorization:
+    """A z = b for a complex CSC matrix: a ComplexPlan and a Factorization (`.real`: condest, slogdet, info, ... stay
+    reachable there) on the plan's real-equivalent pattern and doubled order.  Values are complex128 [batch, nnz],
+    right-hand sides [n], [n, k] or [batch, n, k].  trans: "N" A x = b, "T" A^T x = b (no conjugate), "H" A^H x = b, all on
+    the same factors.  rotate (LU only): see ComplexPlan; with it the factors are those of diag(s) A."""
+
+    def __init__(self, n, Ap, Ai, kind=CS3_LU, order=ORDER_AMD, q=None, batch=1, rotate=True):
+        assert not (rotate and kind == CS3_CHOLESKY), "rotate scales rows, which breaks the symmetry Cholesky needs: pass rotate=False"
+        self.kind, self.n, self.batch = kind, int(n), int(batch)
+        self.plan = self.real = None
+        self._ws = (0, None)
+        self.plan = ComplexPlan(n, Ap, Ai, batch, rotate)
+        self.nnz = self.plan.nnz
+        Rp, Ri = self.plan.pattern()
+        self.real = Factorization(2 * self.n, 2 * self.n, Rp, Ri, kind=kind, q=self.plan.order(order, q), batch=batch)
+
+    def close(self):
+        if self.real is not None:
+            self.real.close()
+        if self.plan is not None:
+            self.plan.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    # -- host arrays
+    def factor(self, Az, tol=0.0):
+        self.real.factor(self.plan.values(Az), tol)
+        return self
+
+    def solve(self, b, trans="N"):
+        """Solve op(A) x = b; returns a new complex array of b's shape."""
+        op = cplx_op(trans)
+        return self.plan.unpack(self.real.solve(self.plan.pack(b, op), trans=op != CPLX_N), op)
+
+    def residual(self, Az, b, x, trans="N"):
+        return self.plan.residual(Az, b, x, trans)
+
+    def refine(self, Az, b, x, steps=1, trans="N"):
+        """`steps` rounds of x += op(A) \\ (b - op(A) x) with the held factors and the values Az.  -> the refined x."""
+        op = cplx_op(trans)
+        x = _c128(x)
+        for _ in range(steps):
+            r = self.plan.residual(Az, b, x, op)
+            x = self.plan.unpack(self.real.solve(self.plan.pack(r, op), trans=op != CPLX_N), op, into=x)
+        return x
+
+    # -- device pointers on a HIP stream
+    def _workspace(self, k):
+        """(Rx, Y, X2) in the plan's workspace, for k right-hand sides: asks the plan only when k grows."""
+        if self._ws[1] is None or k > self._ws[0]:
+            per = 2 * self.batch * self.n * k
+            self._ws = (k, (self.plan.workspace_dev(0, 4 * self.batch * self.nnz), self.plan.workspace_dev(1, per),
+                            self.plan.workspace_dev(2, per)))
+        return self._ws[1]
+
+    def factor_solve_dev(self, az_ptr, b_ptr, x_ptr, k=1, tol=0.0, stream=0):
+        """(Re)factorise Az and solve A X = B: values -> pack -> the handle's fused factor + solve -> unpack, all on
+        `stream`; B [batch][n, k] complex stays, X gets the solutions.  The bits of factor() + solve().  Status through
+        factor_status()."""
+        rx, y, x2 = self._workspace(k)
+        self.plan.values_dev(az_ptr, rx, stream)
+        self.plan.pack_dev(b_ptr, y, k, CPLX_N, stream)
+        self.real.factor_solve_bx_dev(rx, y, x2, k, tol, stream)
+        self.plan.unpack_dev(x2, x_ptr, k, CPLX_N, False, stream)
+
+    def solve_dev(self, b_ptr, x_ptr, k=1, stream=0, trans="N"):
+        """op(A) X = B on the held factors; B stays, X gets the solutions (they may be the same array)."""
+        op = cplx_op(trans)
+        _, y, _ = self._workspace(k)
+        self.plan.pack_dev(b_ptr, y, k, op, stream)
+        self.real.solve_dev(y, k, stream, trans=op != CPLX_N)
+        self.plan.unpack_dev(y, x_ptr, k, op, False, stream)
+
+    def factor_status(self, stream=0):
+        self.real.factor_status(stream)
 
 
 def csc_sub_matrix(Am, Anz, Ap, Ai, Ax, rows, cols):

@@ -162,6 +162,35 @@ def jacobian_config2(seed=118):
     return jacobian_like(nbus=220, nedges=340, n_pv=38, seed=seed)
 
 
+def ybus(nbus, nedges, seed, lossless=False):
+    """Complex bus admittance matrix of a random connected network (the graph of jacobian_like): branches with
+    r ~ U(0.001, 0.01), x ~ U(0.02, 0.1), y = 1 / (r + jx), and on every bus a shunt g - jb with g ~ U(0, 0.1),
+    b ~ U(0.05, 0.5) on the diagonal (inductive, so the matrix is far from singular: condition number near 1e3).  The
+    chords beyond the spanning tree are random, so fill grows quickly with nedges - nbus.  Symmetric, not Hermitian; the diagonal is mostly
+    imaginary.  lossless: every real part is +0 -- the diagonal is purely imaginary, as for a network without
+    resistance.  -> (n, Ap, Ai, Az) with Az complex128, rows sorted, no duplicates."""
+    rng = np.random.default_rng(seed)
+    ei, ej = _connected_graph(nbus, nedges, rng)
+    r = rng.uniform(0.001, 0.01, size=len(ei))
+    x = rng.uniform(0.02, 0.1, size=len(ei))
+    y = 1.0 / (r + 1j * x)
+    shunt = rng.uniform(0.0, 0.1, size=nbus) - 1j * rng.uniform(0.05, 0.5, size=nbus)
+    diag = shunt.copy()
+    np.add.at(diag, ei, y)
+    np.add.at(diag, ej, y)
+    rows = np.concatenate([ej, ei, np.arange(nbus)])
+    cols = np.concatenate([ei, ej, np.arange(nbus)])
+    vals = np.concatenate([-y, -y, diag])
+    order = np.lexsort((rows, cols))
+    rows, cols, vals = rows[order], cols[order], vals[order]
+    if lossless:
+        vals = vals.copy()
+        vals.real = 0.0                              # (+0, never -0)
+    Ap = np.zeros(nbus + 1, dtype=np.int64)
+    np.add.at(Ap, cols + 1, 1)
+    return nbus, np.cumsum(Ap).astype(np.int32), rows.astype(np.int32), vals.astype(np.complex128)
+
+
 def grid_graph_edges(n, offsets, chord_frac, rng):
     """1-D chain with extra local ties i <-> i+k for k in offsets, plus
     chord_frac * n random long chords."""

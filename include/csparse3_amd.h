@@ -829,6 +829,98 @@ int cs3_union_upload(cs3_union p);
 int cs3_union_values_dev(cs3_union p, const double *Ax_cat_dev, double *Ax_union_dev, void *stream);
 int cs3_union_values(cs3_union p, const double *Ax_cat, double *Ax_union);
 
+/* ---- complex matrices: A z = b through a real-equivalent plan -------------
+ * A complex matrix of order n (an admittance matrix Y of Y v = i) is solved as a REAL matrix of order 2n on an ordinary
+ * handle: every entry w becomes the 2 x 2 block [[Re w, -Im w], [Im w, Re w]], rows and columns interleaved (2i, 2i + 1),
+ * so the blocks stay dense, the assembly tree is that of the complex pattern with every supernode twice as wide, and the
+ * real multiplications are those of complex arithmetic (the factors take twice the memory).  The plan holds the pattern
+ * arithmetic, the doubled order and the device glue; the handle runs unchanged behind it:
+ *     cs3_cplx_plan_create(n, Ap, Ai, batch, rotate, &p);  cs3_cplx_plan_pattern(p, Rp, Ri);  cs3_cplx_plan_order(p, order, q, q2);
+ *     cs3_analyze(kind, CS3_ORDER_GIVEN, 2 n, Rp, Ri, q2, batch, &h);
+ *     cs3_cplx_values_dev(p, Az, Rx, st);  cs3_cplx_pack_dev(p, op, B, Y, k, st);
+ *     cs3_factor_solve_bx_dev(h, Rx, tol, Y, X2, k, st);   (or cs3_factor_dev, then cs3_solve_dev / cs3_solve_t_dev on Y)
+ *     cs3_cplx_unpack_dev(p, op, X2, X, k, 0, st);
+ * A complex array is interleaved (re, im) doubles -- numpy.complex128, C's double complex -- typed const double * here and
+ * aligned to 16 bytes.
+ *
+ * ROTATION.  The static pivots of the real form are the REAL PARTS of the diagonal, and the diagonal of an admittance matrix
+ * is mostly imaginary (purely imaginary for a lossless network: the first pivot is exactly 0).  With CS3_CPLX_ROTATE_DIAG
+ * row i is multiplied by s_i = conj(d_i) / max(|Re d_i|, |Im d_i|), d_i the diagonal entry: M = diag(s) A has a real,
+ * positive diagonal, and 1 <= |s_i| <= sqrt(2).  Per matrix of the batch and row i:
+ *     d = the stored (i, i) entries added in storage order, starting from the first as stored, Re and Im separately
+ *     m = max(|Re d|, |Im d|);  s_i = (Re d / m, (-Im d) / m)
+ *     s_i = (1, +0) with CS3_CPLX_ROTATE_NONE, without a stored diagonal, and when m is 0, NaN or infinite.
+ * Only divisions and comparisons: a host reproduces s bit for bit.  s [batch][n] lives in the plan and belongs to the
+ * last values call, in stream order (before the first one it is (1, +0)).  A row scaling breaks symmetry: Cholesky
+ * handles take CS3_CPLX_ROTATE_NONE (the real form of a Hermitian positive definite matrix is symmetric positive definite).
+ *
+ * ARITHMETIC.  a * b = ((ar*br) - (ai*bi), (ar*bi) + (ai*br)): every product rounded, then the sum, nothing fused;
+ * conj() and the -Im w of a block are sign flips (a zero keeps its mirrored sign).
+ *
+ * cs3_cplx_plan_create: host work only, O(nnz + n).  Checked in this order, each failure CS3_ERR_ARG with a message: null
+ *   output; batch < 1; rotate outside the enum; n outside [0, 2^29) (2n stays in the range cs3_analyze takes); a null Ap,
+ *   Ap[0] != 0, a decreasing Ap, a null Ai with entries, a row outside [0, n); 4 nnz >= 2^31 - 1024.  Rows inside a column
+ *   need not be sorted; an entry stored twice stays two entries.
+ * cs3_cplx_plan_pattern: Rp[2n + 1], Ri[4 nnz] (either may be NULL): Rp[2j] = 4 Ap[j], Rp[2j + 1] = 4 Ap[j] + 2 len_j;
+ *   entry t of column j (row i, storage order kept) owns Rp[2j] + 2t, + 1 and Rp[2j + 1] + 2t, + 1, with rows
+ *   2i, 2i + 1, 2i, 2i + 1 and values Re w, Im w, -(Im w), Re w.
+ * cs3_cplx_plan_order: q2[2n] with q2[2t] = 2 q[t], q2[2t + 1] = 2 q[t] + 1, q = cs3_amd(order, ...) of the complex pattern,
+ *   or q_given[n] with CS3_ORDER_GIVEN (not a permutation: CS3_ERR_ARG).  Pass it on with CS3_ORDER_GIVEN.
+ * cs3_cplx_values_dev: Rx_dev [batch][4 nnz] from Az_dev [batch][nnz] complex: the rotation (one launch, only with
+ *   CS3_CPLX_ROTATE_DIAG), then w = s_i * z for every entry (one launch).  Every output entry is written once; no memset,
+ *   no atomics; after the first call (which uploads the tables, as cs3_cplx_upload does) nothing allocates or
+ *   synchronises, so the call can be captured into a graph.  Both arrays 16-byte aligned.
+ * cs3_cplx_pack_dev: Y_dev [batch][2n, k] real row-major from Z_dev [batch][n, k] complex row-major:
+ *   Y[2i, c] = Re u, Y[2i + 1, c] = Im u;    op N: u = s_i * z     op H: u = z              op T: u = conj(z)
+ * cs3_cplx_unpack_dev: the inverse, y = Y[2i, c] + j Y[2i + 1, c]:
+ *                                            op N: y               op H: conj(s_i) * y      op T: s_i * conj(y)
+ *   stored to Z, or with accumulate != 0 added to it (z + result, one addition per component).
+ *   Between the two: op N cs3_solve_dev, ops H and T cs3_solve_t_dev.  The transpose of the real form of M is the real
+ *   form of M^H, so the transposed solve of the handle solves with M^H = A^H diag(conj(s)); A^T x = b is
+ *   A^H conj(x) = conj(b).
+ * cs3_cplx_residual_dev: R = B - op(A) X on the complex CSC itself, the CALLER's values Az_dev, not the rotated ones;
+ *   B, X, R [batch][n, k] complex.  The accumulator starts at b and subtracts term by term, t = a * x (op H: conj(a) * x):
+ *   op N over row i's entries by ascending column, storage order inside a column; ops T and H over column j in storage order.
+ * cs3_cplx_rotation_dev: the plan's s [batch][n] complex on the device.
+ * cs3_cplx_workspace_dev: a block of `count` doubles that the plan owns, slot 0, 1 or 2, grown (after a device
+ *   synchronisation) only when count exceeds what the slot holds: for callers that keep no buffers of their own.
+ * cs3_cplx_values / _pack / _unpack / _residual / _rotation: the same from and to host arrays: the same kernels, the same
+ *   bits (they synchronise).  Everything that touches the device returns CS3_ERR_HIP without one.
+ * cs3_cplx_limits: the constants that shape the launches.
+ * Not offered: complex arithmetic inside the factor and sweep kernels, matching or perturbation of complex matrices, the
+ * phase of a determinant (cs3_slogdet of the handle gives 2 log|det M|). */
+typedef struct cs3_cplx_s *cs3_cplx;
+enum cs3_cplx_rotate { CS3_CPLX_ROTATE_NONE = 0, CS3_CPLX_ROTATE_DIAG = 1 };
+enum cs3_cplx_op { CS3_CPLX_N = 0, CS3_CPLX_T = 1, CS3_CPLX_H = 2 };      /* A, A^T (no conjugate), A^H */
+typedef struct cs3_cplx_info {
+    int64_t n, nnz, batch, rotate;
+    int64_t n_real, nnz_real;      /* 2 n, 4 nnz: what the handle analyses */
+    int64_t rows_without_diagonal; /* rows whose s stays (1, +0) whatever the values */
+} cs3_cplx_info;
+typedef struct cs3_cplx_limits_t {
+    int64_t block;                 /* threads of a workgroup */
+    int64_t grid_cap;              /* most workgroups of a launch: beyond grid_cap * block complex numbers a lane loops */
+} cs3_cplx_limits_t;
+int cs3_cplx_limits(cs3_cplx_limits_t *out);
+int cs3_cplx_plan_create(int64_t n, const int32_t *Ap, const int32_t *Ai, int64_t batch, int64_t rotate, cs3_cplx *out);
+int cs3_cplx_plan_free(cs3_cplx p);
+int cs3_cplx_plan_info(cs3_cplx p, cs3_cplx_info *info);
+int cs3_cplx_plan_pattern(cs3_cplx p, int32_t *Rp, int32_t *Ri);
+int cs3_cplx_plan_order(cs3_cplx p, int64_t order, const int32_t *q_given, int32_t *q2);
+int cs3_cplx_upload(cs3_cplx p);
+int cs3_cplx_workspace_dev(cs3_cplx p, int64_t slot, int64_t count, double **out);
+int cs3_cplx_values_dev(cs3_cplx p, const double *Az_dev, double *Rx_dev, void *stream);
+int cs3_cplx_pack_dev(cs3_cplx p, int64_t op, const double *Z_dev, double *Y_dev, int64_t k, void *stream);
+int cs3_cplx_unpack_dev(cs3_cplx p, int64_t op, const double *Y_dev, double *Z_dev, int64_t k, int64_t accumulate, void *stream);
+int cs3_cplx_residual_dev(cs3_cplx p, int64_t op, const double *Az_dev, const double *B_dev, const double *X_dev,
+                          double *R_dev, int64_t k, void *stream);
+int cs3_cplx_rotation_dev(cs3_cplx p, const double **s_dev);
+int cs3_cplx_values(cs3_cplx p, const double *Az, double *Rx);
+int cs3_cplx_pack(cs3_cplx p, int64_t op, const double *Z, double *Y, int64_t k);
+int cs3_cplx_unpack(cs3_cplx p, int64_t op, const double *Y, double *Z, int64_t k, int64_t accumulate);
+int cs3_cplx_residual(cs3_cplx p, int64_t op, const double *Az, const double *B, const double *X, double *R, int64_t k);
+int cs3_cplx_rotation(cs3_cplx p, double *s);
+
 #ifdef __cplusplus
 }
 #endif
