@@ -278,6 +278,19 @@ def lib():
         L.cs3_cplx_unpack.argtypes = [vp, I64, _f64p, _f64p, I64, I64]
         L.cs3_cplx_residual.argtypes = [vp, I64, _f64p, _f64p, _f64p, _f64p, I64]
         L.cs3_cplx_rotation.argtypes = [vp, _f64p]
+        L.cs3_debug_sens_tile.argtypes = [vp, I64, _f64p, I64]
+        L.cs3_cplx_sens_limits.argtypes = [C.POINTER(SensLimits)]
+        L.cs3_cplx_sens_plan.argtypes = [vp, vp, I64, _i32p, _i32p, I64, _i32p, _i32p, I64, I64, C.POINTER(vp)]
+        L.cs3_cplx_sens_free.argtypes = [vp]
+        L.cs3_cplx_sens_info.argtypes = [vp, C.POINTER(SensInfo)]
+        L.cs3_cplx_sens_solve_dev.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+        L.cs3_cplx_sens_solve.argtypes = [vp, vp, vp, _f64p, _f64p, _f64p]
+        L.cs3_debug_cplx_sens_parts.argtypes = [vp, vp, vp, I64, vp, vp, vp, vp]
+        L.cs3_cplx_plan_create_schur.argtypes = [I64, _i32p, _i32p, I64, I64, I64, _i32p, C.POINTER(vp)]
+        L.cs3_cplx_plan_schur_info.argtypes = [vp, C.POINTER(I64), _i32p]
+        L.cs3_cplx_plan_schur_order.argtypes = [vp, I64, _i32p, _i32p, _i32p]
+        L.cs3_cplx_schur_get_dev.argtypes = [vp, vp, vp, vp]
+        L.cs3_cplx_schur_get.argtypes = [vp, vp, _f64p]
         _lib = L
     return _lib
 
@@ -944,6 +957,13 @@ class Factorization:
         _check(lib().cs3_debug_sens_parts(self._h, plan._u, parts, C.c_void_p(bx_ptr), C.c_void_p(ctx_ptr), C.c_void_p(y_ptr),
                                           C.c_void_p(stream)))
 
+    def debug_sens_tile(self, shape, write=None):
+        """Diagnostics, for tests: the front of the tile buffer of the sens paths as an array of `shape` (synchronises); with
+        `write` that array goes INTO the buffer instead."""
+        a = np.empty(shape) if write is None else np.ascontiguousarray(write, dtype=np.float64).reshape(shape)
+        _check(lib().cs3_debug_sens_tile(self._h, 0 if write is None else 1, _pf(a), a.size))
+        return a
+
     def debug_alloc_counters(self):
         """(device allocations incl. graph instantiations, host synchronisations) the handle's solves have made so far."""
         a, s = I64(), I64()
@@ -1363,12 +1383,20 @@ class ComplexPlan:
     values / pack / unpack / residual are the device glue, with host-array and `_dev` forms that give the same bits.
     rotate: rows are multiplied by s_i = conj(d_i) / max(|Re d_i|, |Im d_i|) so that the static pivots, the real parts of
     the diagonal, are positive (an admittance matrix has a mostly imaginary diagonal).  Right-hand sides are [n], [n, k] or
-    [batch, n, k] complex128, their real forms [2n], [2n, k] or [batch, 2n, k] float64."""
+    [batch, n, k] complex128, their real forms [2n], [2n, k] or [batch, 2n, k] float64.
+    schur: the border of a Kron reduction (cs3_cplx_plan_create_schur): rows that are never rotated (s = 1 there), so that
+    the Schur complement of the real form is that of A itself; schur_order() and schur_info() go with it."""
 
-    def __init__(self, n, Ap, Ai, batch=1, rotate=True):
+    def __init__(self, n, Ap, Ai, batch=1, rotate=True, schur=None):
         self._p = C.c_void_p()
         Ap, Ai = _i32(Ap), _i32(Ai)
-        _check(lib().cs3_cplx_plan_create(n, _pi(Ap), _pi(Ai), batch, int(rotate), C.byref(self._p)))
+        self.ns = 0
+        if schur is None:
+            _check(lib().cs3_cplx_plan_create(n, _pi(Ap), _pi(Ai), batch, int(rotate), C.byref(self._p)))
+        else:
+            idx = _i32(schur).reshape(-1)
+            _check(lib().cs3_cplx_plan_create_schur(n, _pi(Ap), _pi(Ai), batch, int(rotate), idx.size, _pi(idx), C.byref(self._p)))
+            self.ns = int(idx.size)
         inf = self.info
         self.n, self.nnz, self.batch, self.rotate = int(inf.n), int(inf.nnz), int(inf.batch), bool(inf.rotate)
 
@@ -1412,6 +1440,27 @@ class ComplexPlan:
         q2 = np.empty(2 * self.n, dtype=np.int32)
         _check(lib().cs3_cplx_plan_order(self._p, order, _pi(qa), _pi(q2)))
         return q2
+
+    def schur_info(self):
+        """-> int32[ns]: the border in the order of S's rows and columns (Cs3Error on a plan without one)."""
+        ns = I64()
+        _check(lib().cs3_cplx_plan_schur_info(self._p, C.byref(ns), None))
+        idx = np.empty(int(ns.value), dtype=np.int32)
+        _check(lib().cs3_cplx_plan_schur_info(self._p, None, _pi(idx)))
+        return idx
+
+    def schur_order(self, order=ORDER_AMD, q=None):
+        """-> (q2_interior int32[2 (n - ns)], schur2 int32[2 ns]): the doubled order of the interior (AMD of A11, natural,
+        or q, a permutation of the interior) and the doubled border, for Factorization(..., q=q2_interior, schur=schur2)."""
+        qa = None
+        if q is not None:
+            qa = _i32(q)
+            assert qa.size == self.n - self.ns
+            order = ORDER_GIVEN
+        q2 = np.empty(2 * max(self.n - self.ns, 0), dtype=np.int32)
+        s2 = np.empty(2 * self.ns, dtype=np.int32)
+        _check(lib().cs3_cplx_plan_schur_order(self._p, order, _pi(qa), _pi(q2), _pi(s2)))
+        return q2, s2
 
     def upload(self):
         """Puts the tables on the device now (the first device call does it otherwise; do it before a graph capture)."""
@@ -1506,17 +1555,25 @@ class ComplexFactorization:
     """A z = b for a complex CSC matrix: a ComplexPlan and a Factorization (`.real`: condest, slogdet, info, ... stay
     reachable there) on the plan's real-equivalent pattern and doubled order.  Values are complex128 [batch, nnz],
     right-hand sides [n], [n, k] or [batch, n, k].  trans: "N" A x = b, "T" A^T x = b (no conjugate), "H" A^H x = b, all on
-    the same factors.  rotate (LU only): see ComplexPlan; with it the factors are those of diag(s) A."""
+    the same factors.  rotate (LU only): see ComplexPlan; with it the factors are those of diag(s) A.
+    schur: the boundary buses of a Kron reduction, not eliminated (a Schur handle on the real form).  factor() then holds
+    the complex S = A22 - A21 A11^-1 A12 in the order of the list: schur(), schur_forward(), schur_backward(); order / q refer
+    to the interior; solve() raises Cs3Error, as on every Schur handle.
+    sens_plan / sens_solve: Y = C op(A)^-1 B with sparse B and C (entries of Z-bus), see ComplexSensPlan."""
 
-    def __init__(self, n, Ap, Ai, kind=CS3_LU, order=ORDER_AMD, q=None, batch=1, rotate=True):
+    def __init__(self, n, Ap, Ai, kind=CS3_LU, order=ORDER_AMD, q=None, batch=1, rotate=True, schur=None):
         assert not (rotate and kind == CS3_CHOLESKY), "rotate scales rows, which breaks the symmetry Cholesky needs: pass rotate=False"
         self.kind, self.n, self.batch = kind, int(n), int(batch)
         self.plan = self.real = None
         self._ws = (0, None)
-        self.plan = ComplexPlan(n, Ap, Ai, batch, rotate)
-        self.nnz = self.plan.nnz
+        self.plan = ComplexPlan(n, Ap, Ai, batch, rotate, schur=schur)
+        self.nnz, self.ns = self.plan.nnz, self.plan.ns
         Rp, Ri = self.plan.pattern()
-        self.real = Factorization(2 * self.n, 2 * self.n, Rp, Ri, kind=kind, q=self.plan.order(order, q), batch=batch)
+        if schur is None:
+            self.real = Factorization(2 * self.n, 2 * self.n, Rp, Ri, kind=kind, q=self.plan.order(order, q), batch=batch)
+        else:
+            q2, s2 = self.plan.schur_order(order, q)
+            self.real = Factorization(2 * self.n, 2 * self.n, Rp, Ri, kind=kind, q=q2, batch=batch, schur=s2)
 
     def close(self):
         if self.real is not None:
@@ -1587,6 +1644,118 @@ class ComplexFactorization:
 
     def factor_status(self, stream=0):
         self.real.factor_status(stream)
+
+    # -- Kron reduction (a factorisation made with schur=...)
+    def schur_info(self):
+        return self.plan.schur_info()
+
+    def schur(self):
+        """The complex Schur complement of the last factorisation: [ns, ns], or [batch, ns, ns]; S[i, j] belongs to
+        (schur[i], schur[j]).  A Cholesky handle gives a Hermitian S."""
+        S = np.empty((self.batch, self.ns, self.ns), dtype=np.complex128)
+        _check(lib().cs3_cplx_schur_get(self.plan._p, self.real._h, _pc(S)))
+        return S[0] if self.batch == 1 else S
+
+    def schur_dev(self, s_ptr, stream=0):
+        """schur() into device memory [batch][ns, ns] complex, one launch on `stream`."""
+        _check(lib().cs3_cplx_schur_get_dev(self.plan._p, self.real._h, C.c_void_p(s_ptr), C.c_void_p(stream)))
+
+    def schur_forward(self, b):
+        """b: [n], [n, k] or [batch, n, k] complex.  -> a new array whose border rows hold b2 - A21 A11^-1 b1 (the right-hand
+        side of S x2 = g); the interior rows are the half-solved interior, to be passed on to schur_backward."""
+        return self.plan.unpack(self.real.schur_forward(self.plan.pack(b, CPLX_N)), CPLX_N)
+
+    def schur_backward(self, y):
+        """y: what schur_forward returned, with the border rows replaced by x2.  -> the solution of A x = b."""
+        return self.plan.unpack(self.real.schur_backward(self.plan.pack(y, CPLX_H)), CPLX_N)
+
+    def schur_forward_dev(self, b_ptr, y_ptr, k=1, stream=0):
+        """schur_forward on device pointers: B [batch][n, k] complex stays, Y gets the result (they may be the same)."""
+        _, x2, _ = self._workspace(k)
+        self.plan.pack_dev(b_ptr, x2, k, CPLX_N, stream)
+        self.real.schur_forward_dev(x2, k, stream)
+        self.plan.unpack_dev(x2, y_ptr, k, CPLX_N, False, stream)
+
+    def schur_backward_dev(self, y_ptr, x_ptr, k=1, stream=0):
+        """schur_backward on device pointers: Y stays, X gets the solution (they may be the same)."""
+        _, x2, _ = self._workspace(k)
+        self.plan.pack_dev(y_ptr, x2, k, CPLX_H, stream)
+        self.real.schur_backward_dev(x2, k, stream)
+        self.plan.unpack_dev(x2, x_ptr, k, CPLX_N, False, stream)
+
+    # -- sparse right-hand sides: entries of Z-bus
+    def sens_plan(self, B, Ct=None, side="auto", trans="N"):
+        """A ComplexSensPlan for Y = C op(A)^-1 B: B = (k, indptr, indices) by columns or None for I; Ct the same for the
+        ROWS of C or None for I; indices of the complex matrix."""
+        return ComplexSensPlan(self, B, Ct, side, trans)
+
+    def sens_solve(self, plan, Bz, Ctz):
+        """Y [p, k] complex128 = C op(A)^-1 B with the values Bz, Ctz (complex, in the plan's entry order; None for an
+        identity operand) on the factors at hand."""
+        Bz = _c128(Bz if Bz is not None else []).reshape(-1)
+        Ctz = _c128(Ctz if Ctz is not None else []).reshape(-1)
+        assert plan.bp is None or Bz.size >= int(plan.bp[-1])
+        assert plan.ctp is None or Ctz.size >= int(plan.ctp[-1])
+        Y = np.empty((plan.p, plan.k), dtype=np.complex128)
+        _check(lib().cs3_cplx_sens_solve(self.plan._p, self.real._h, plan._u, _pc(Bz), _pc(Ctz), _pc(Y)))
+        return Y
+
+    def sens_solve_dev(self, plan, bz_ptr, ctz_ptr, y_ptr, stream=0):
+        """sens_solve on device pointers, asynchronous on `stream`; Y [p, k] complex row-major.  After the first call with a
+        plan nothing is allocated and nothing synchronises.  The same bits as sens_solve()."""
+        _check(lib().cs3_cplx_sens_solve_dev(self.plan._p, self.real._h, plan._u, C.c_void_p(bz_ptr), C.c_void_p(ctz_ptr),
+                                             C.c_void_p(y_ptr), C.c_void_p(stream)))
+
+    def debug_sens_parts(self, plan, parts, bz_ptr, ctz_ptr, y_ptr, stream=0):
+        """Diagnostics: the steps of sens_solve_dev in the mask `parts` (1 scatter, 2 solves, 4 combine)."""
+        _check(lib().cs3_debug_cplx_sens_parts(self.plan._p, self.real._h, plan._u, parts, C.c_void_p(bz_ptr), C.c_void_p(ctz_ptr),
+                                               C.c_void_p(y_ptr), C.c_void_p(stream)))
+
+
+def cplx_sens_limits():
+    """The constants of the complex sparse right-hand-side kernels (cs3_cplx_sens_limits); needs no GPU."""
+    out = SensLimits()
+    _check(lib().cs3_cplx_sens_limits(C.byref(out)))
+    return out
+
+
+class ComplexSensPlan:
+    """The patterns of B and C' of Y = C op(A)^-1 B on a ComplexFactorization (its sens_plan): made once on the host, used
+    by every sens_solve, across refactorisations.  trans: "N", "T" or "H".  One complex solved-for column is one real
+    column of the handle's tile: side left with p rows of C plans p solves."""
+
+    def __init__(self, factorization, B, Ct=None, side="auto", trans="N"):
+        self._u = C.c_void_p()
+        n = factorization.n
+        self.k, self.bp, self.bi = (n, None, None) if B is None else (int(B[0]), _i32(B[1]), _i32(B[2]))
+        self.p, self.ctp, self.cti = (n, None, None) if Ct is None else (int(Ct[0]), _i32(Ct[1]), _i32(Ct[2]))
+        assert self.bp is None or self.bp.size == self.k + 1, "B is (ncols, indptr[ncols + 1], indices)"
+        assert self.ctp is None or self.ctp.size == self.p + 1, "Ct is (ncols, indptr[ncols + 1], indices)"
+        _check(lib().cs3_cplx_sens_plan(factorization.plan._p, factorization.real._h, self.k, _pi(self.bp), _pi(self.bi), self.p,
+                                        _pi(self.ctp), _pi(self.cti), SENS_SIDES.get(side, side), cplx_op(trans), C.byref(self._u)))
+
+    def close(self):
+        if self._u:
+            lib().cs3_cplx_sens_free(self._u)
+            self._u = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    @property
+    def info(self):
+        out = SensInfo()
+        _check(lib().cs3_cplx_sens_info(self._u, C.byref(out)))
+        return out
 
 
 def csc_sub_matrix(Am, Anz, Ap, Ai, Ax, rows, cols):

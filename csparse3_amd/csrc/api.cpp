@@ -13,6 +13,7 @@
 #include <string>
 #include <tuple>
 
+#include "cs3_cplx.hpp"
 #include "cs3_device.hpp"
 #include "cs3_hipmem.hpp"
 
@@ -162,6 +163,13 @@ struct cs3_sens_s {
     bool on_device = false;
     i64 nnz_b() const { return b_ident ? n : (i64) bi.size(); }
     i64 nnz_c() const { return c_ident ? n : (i64) cti.size(); }
+};
+
+// cs3_sens_s for a handle on the real form of a complex matrix (cs3_cplx_sens_plan): n is the COMPLEX order, the handle's is
+// 2 n; it sits in its handle's sens_plans, so the lifetime rules are those of cs3_sens_s.  The host form's copies hold
+// interleaved complex numbers.
+struct cs3_cplx_sens_s : cs3_sens_s {
+    int op = CS3_CPLX_N;
 };
 
 namespace {
@@ -2336,21 +2344,21 @@ int cs3_sens_limits(cs3_sens_limits_t *out)
 
 // One operand's pattern: pointers monotone from 0 (check 5); the indices are looked at afterwards (check 6), so that a
 // bad pointer array of either operand wins over a bad index of either.
-static int sens_check_pointers(const char *name, int64_t ncols, const int32_t *P, const int32_t *I)
+static int sens_check_pointers(const char *name, int64_t ncols, const int32_t *P, const int32_t *I, const char *who = "cs3_sens_plan")
 {
-    if (P[0] != 0) { set_error(std::string("cs3_sens_plan: ") + name + "[0] != 0"); return CS3_ERR_ARG; }
+    if (P[0] != 0) { set_error(std::string(who) + ": " + name + "[0] != 0"); return CS3_ERR_ARG; }
     for (int64_t c = 0; c < ncols; ++c)
-        if (P[c + 1] < P[c]) { set_error(std::string("cs3_sens_plan: ") + name + " not monotone at column " + std::to_string(c)); return CS3_ERR_ARG; }
-    if (P[ncols] > 0 && !I) { set_error(std::string("cs3_sens_plan: null index array behind ") + name); return CS3_ERR_ARG; }
+        if (P[c + 1] < P[c]) { set_error(std::string(who) + ": " + name + " not monotone at column " + std::to_string(c)); return CS3_ERR_ARG; }
+    if (P[ncols] > 0 && !I) { set_error(std::string(who) + ": null index array behind " + name); return CS3_ERR_ARG; }
     return CS3_OK;
 }
 
-static int sens_check_indices(const char *name, int64_t n, int64_t ncols, const int32_t *P, const int32_t *I)
+static int sens_check_indices(const char *name, int64_t n, int64_t ncols, const int32_t *P, const int32_t *I, const char *who = "cs3_sens_plan")
 {
     for (int64_t c = 0; c < ncols; ++c)
         for (int e = P[c]; e < P[c + 1]; ++e)
             if (I[e] < 0 || I[e] >= n) {
-                set_error(std::string("cs3_sens_plan: index out of range in column ") + std::to_string(c) + " of " + name);
+                set_error(std::string(who) + ": index out of range in column " + std::to_string(c) + " of " + name);
                 return CS3_ERR_ARG;
             }
     return CS3_OK;
@@ -2512,6 +2520,217 @@ int cs3_sens_solve(cs3_handle h, cs3_sens u, const double *Bx, const double *Ctx
     if ((rc = sens_run(h, u, P.bx.get(), P.ctx.get(), P.y.get(), nullptr))) return rc;
     CS3_HIP(hipMemcpy(Y, P.y.get(), ny * sizeof(double), hipMemcpyDeviceToHost));
     CS3_HIP(hipDeviceSynchronize());
+    return CS3_OK;
+}
+
+// ---- complex sparse right-hand sides: Y = C op(A)^-1 B behind a complex plan (cplxsens.hip) ----------------------------
+int cs3_cplx_sens_limits(cs3_sens_limits_t *out)
+{
+    if (!out) { set_error("cs3_cplx_sens_limits: null output"); return CS3_ERR_ARG; }
+    *out = cs3_sens_limits_t{SENS_MAX_TILE, SENS_PAD_WIDTH, 2 * CSENS_SCATTER_ROWS, SENS_SCATTER_THREADS, SENS_COMBINE_COLS,
+                             SENS_COMBINE_LANES, SENS_TBLOCK};
+    return CS3_OK;
+}
+
+int cs3_cplx_sens_plan(cs3_cplx p, cs3_handle h, int64_t k, const int32_t *Bp, const int32_t *Bi, int64_t pr, const int32_t *Ctp,
+                       const int32_t *Cti, int64_t side, int64_t op, cs3_cplx_sens *out)
+{
+    const char *who = "cs3_cplx_sens_plan";
+    const auto bad = [who](const char *msg) { set_error(std::string(who) + ": " + msg); return CS3_ERR_ARG; };
+    if (!p || !h) return bad("null plan or handle");
+    if (!out) return bad("null output");
+    *out = nullptr;
+    const int64_t n = p->n;
+    int rc;
+    if (h->S.n != 2 * n) return bad("the handle's order is not 2 n of the complex plan");
+    if (h->batch > 1) return bad("handles with batch > 1 are not supported");
+    if ((rc = refuse_schur(h, who))) return rc;
+    if (k < 1 || pr < 1 || k > INT_MAX / 2 || pr > INT_MAX / 2) return bad("k and p must be >= 1");
+    if (!Bp && !Ctp) return bad("B and C are both the identity (the dense inverse is not offered)");
+    if (!Bp && k != n) return bad("B is the identity but k != n");
+    if (!Ctp && pr != n) return bad("C is the identity but p != n");
+    if (Bp && (rc = sens_check_pointers("Bp", k, Bp, Bi, who))) return rc;
+    if (Ctp && (rc = sens_check_pointers("Ctp", pr, Ctp, Cti, who))) return rc;
+    if (Bp && (rc = sens_check_indices("B", n, k, Bp, Bi, who))) return rc;
+    if (Ctp && (rc = sens_check_indices("C'", n, pr, Ctp, Cti, who))) return rc;
+    if (side < 0 || side > 2) return bad("side must be 0 (auto), 1 (right) or 2 (left)");
+    if (!Bp && side == 1) return bad("B is the identity, side right would solve for all n columns: use side 0 or 2");
+    if (!Ctp && side == 2) return bad("C is the identity, side left would solve for all n rows: use side 0 or 1");
+    if (op != CS3_CPLX_N && op != CS3_CPLX_T && op != CS3_CPLX_H) return bad("op must be 0 (N), 1 (T) or 2 (H)");
+    cs3_cplx_sens_s *u = nullptr;
+    try {
+        u = new cs3_cplx_sens_s();
+        u->n = n; u->k = k; u->p = pr;
+        u->op = (int) op;
+        u->trans = op != CS3_CPLX_N;
+        u->b_ident = !Bp; u->c_ident = !Ctp;
+        u->side = !Bp ? 2 : !Ctp ? 1 : side ? (int) side : (pr < k ? 2 : 1);
+        if (Bp) { u->bp.assign(Bp, Bp + k + 1); u->bi.assign(Bi, Bi + Bp[k]); }
+        if (Ctp) { u->ctp.assign(Ctp, Ctp + pr + 1); u->cti.assign(Cti, Cti + Ctp[pr]); }
+        long long cap = SENS_MAX_TILE;
+        if (const char *e = std::getenv("CS3_SENS_TILE")) cap = std::min<long long>(SENS_MAX_TILE, std::max<long long>(1, std::atoll(e)));
+        u->tile_cap = (int) cap;
+        const i64 ns = (u->side == 1) ? k : pr;             // ONE real column of the [2n, w] tile per complex solved-for column
+        for (i64 c0 = 0; c0 < ns; c0 += cap) {
+            const int t = (int) std::min<i64>(cap, ns - c0);
+            const int w = (t < SENS_PAD_WIDTH && cap >= SENS_PAD_WIDTH) ? SENS_PAD_WIDTH : t;
+            u->tiles.push_back(cs3_sens_s::Tile{c0, t, w});
+            u->wmax = std::max(u->wmax, w);
+        }
+        h->sens_plans.push_back(u);
+    } catch (const std::bad_alloc &) {
+        delete u; set_error(std::string(who) + ": out of memory"); return CS3_ERR_ALLOC;
+    }
+    u->h = h;
+    *out = u;
+    return CS3_OK;
+}
+
+int cs3_cplx_sens_free(cs3_cplx_sens u)
+{
+    if (!u) return CS3_OK;
+    if (u->h) {
+        if (u->on_device) { (void) hipDeviceSynchronize(); release_plan_device(u); }
+        auto &pl = u->h->sens_plans;
+        pl.erase(std::remove(pl.begin(), pl.end(), static_cast<cs3_sens_s *>(u)), pl.end());
+    }
+    delete u;
+    return CS3_OK;
+}
+
+int cs3_cplx_sens_info(cs3_cplx_sens u, cs3_sens_info_t *out)
+{
+    if (!u || !out) { set_error("cs3_cplx_sens_info: null argument"); return CS3_ERR_ARG; }
+    *out = cs3_sens_info_t{u->k, u->p, u->side, u->op, (int64_t) u->tiles.size(), u->wmax, u->nnz_b(), u->nnz_c()};
+    return CS3_OK;
+}
+
+static int csens_check(const char *who, cs3_cplx p, cs3_handle h, cs3_cplx_sens u, const double *bz, const double *ctz, const double *Y,
+                       bool device)
+{
+    if (!p) { set_error(std::string(who) + ": null complex plan"); return CS3_ERR_ARG; }
+    int rc = sens_check(who, h, u, bz, ctz, Y);
+    if (rc) return rc;
+    if (p->n != u->n) { set_error(std::string(who) + ": the complex plan has another order than the one the plan was made with"); return CS3_ERR_ARG; }
+    const uintptr_t used = (u->b_ident ? 0 : reinterpret_cast<uintptr_t>(bz)) | (u->c_ident ? 0 : reinterpret_cast<uintptr_t>(ctz)) |
+                           reinterpret_cast<uintptr_t>(Y);
+    if (device && (used & 15)) {
+        set_error(std::string(who) + ": complex arrays must be aligned to 16 bytes");
+        return CS3_ERR_ARG;
+    }
+    return CS3_OK;
+}
+
+// sens_run with the complex kernels: per tile the scatter packs, the handle solves the real tile in place (plain for inner
+// N, transposed for T and H), the combine unpacks.  Side left solves with the transpose: inner T for op N, inner N for op
+// T, and for op H inner N between two conjugations (A^-H = conj(A^-T)).
+static int csens_run(cs3_cplx p, cs3_handle h, cs3_cplx_sens_s *u, const double *bz_dev, const double *ctz_dev, double *Y_dev,
+                     hipStream_t st, int parts = 7)
+{
+    int rc = cs3_cplx_upload(p);                            // (the tables and s = (1, +0): a plan that never saw a values call)
+    if (rc) return rc;
+    if ((rc = ensure_sens(h, u))) return rc;
+    const auto &P = u->mem;
+    const CsensOperand B{u->b_ident ? nullptr : P.bp.get(), P.bi.get(), bz_dev};
+    const CsensOperand Ct{u->c_ident ? nullptr : P.ctp.get(), P.cti.get(), ctz_dev};
+    const bool right = u->side == 1;
+    const CsensOperand &solved = right ? B : Ct, &other = right ? Ct : B;
+    const i64 ng = right ? u->p : u->k;
+    const int inner = right ? u->op : (u->op == CS3_CPLX_N ? CS3_CPLX_T : CS3_CPLX_N);
+    const CsensGlue glue{inner, (!right && u->op == CS3_CPLX_H) ? 1 : 0, p->d_s.get()};
+    double *T = h->mem.sens.t.get();
+    for (const auto &t : u->tiles) {
+        if (parts & 1) CS3_HIP(launch_csens_scatter(T, u->n, t.w, solved, t.c0, t.t, glue, st));
+        if ((parts & 2) && (rc = run_solve(h, T, t.w, 0, st, inner != CS3_CPLX_N))) return rc;
+        if (parts & 4) CS3_HIP(launch_csens_combine(T, t.w, t.t, other, ng, t.c0, u->k, !right, glue, Y_dev, st));
+    }
+    return CS3_OK;
+}
+
+int cs3_cplx_sens_solve_dev(cs3_cplx p, cs3_handle h, cs3_cplx_sens u, const double *Bz_dev, const double *Ctz_dev, double *Y_dev,
+                            void *stream)
+{
+    int rc = csens_check("cs3_cplx_sens_solve_dev", p, h, u, Bz_dev, Ctz_dev, Y_dev, true);
+    if (rc) return rc;
+    return csens_run(p, h, u, Bz_dev, Ctz_dev, Y_dev, (hipStream_t) stream);
+}
+
+int cs3_debug_cplx_sens_parts(cs3_cplx p, cs3_handle h, cs3_cplx_sens u, int64_t parts, const double *Bz_dev, const double *Ctz_dev,
+                              double *Y_dev, void *stream)
+{
+    int rc = csens_check("cs3_debug_cplx_sens_parts", p, h, u, Bz_dev, Ctz_dev, Y_dev, true);
+    if (rc) return rc;
+    if (parts < 1 || parts > 7) { set_error("cs3_debug_cplx_sens_parts: parts must be a mask of 1, 2 and 4"); return CS3_ERR_ARG; }
+    return csens_run(p, h, u, Bz_dev, Ctz_dev, Y_dev, (hipStream_t) stream, (int) parts);
+}
+
+int cs3_cplx_sens_solve(cs3_cplx p, cs3_handle h, cs3_cplx_sens u, const double *Bz, const double *Ctz, double *Y)
+{
+    int rc = csens_check("cs3_cplx_sens_solve", p, h, u, Bz, Ctz, Y, false);
+    if (rc) return rc;
+    const size_t nb = u->b_ident ? 0 : 2 * (size_t) u->nnz_b(), nc = u->c_ident ? 0 : 2 * (size_t) u->nnz_c();
+    const size_t ny = 2 * (size_t) u->p * (size_t) u->k;
+    auto &P = u->mem;
+    CS3_HIP(P.bx.reserve(nb)); CS3_HIP(P.ctx.reserve(nc)); CS3_HIP(P.y.reserve(ny));
+    if (nb) CS3_HIP(hipMemcpy(P.bx.get(), Bz, nb * sizeof(double), hipMemcpyHostToDevice));
+    if (nc) CS3_HIP(hipMemcpy(P.ctx.get(), Ctz, nc * sizeof(double), hipMemcpyHostToDevice));
+    if ((rc = csens_run(p, h, u, P.bx.get(), P.ctx.get(), P.y.get(), nullptr))) return rc;
+    CS3_HIP(hipMemcpy(Y, P.y.get(), ny * sizeof(double), hipMemcpyDeviceToHost));
+    CS3_HIP(hipDeviceSynchronize());
+    return CS3_OK;
+}
+
+// diagnostics: the handle's tile buffer (of both sens paths) to or from host memory, so that a test can look at what a
+// scatter wrote and choose what a combine reads
+int cs3_debug_sens_tile(cs3_handle h, int64_t write, double *host, int64_t count)
+{
+    int rc = guard(h); if (rc) return rc;
+    auto &T = h->mem.sens.t;
+    if (!host || count < 0 || (size_t) count > T.count()) {
+        set_error("cs3_debug_sens_tile: null array, or more doubles than the tile buffer holds (" + std::to_string(T.count()) + ")");
+        return CS3_ERR_ARG;
+    }
+    CS3_HIP(hipDeviceSynchronize());
+    if (count) CS3_HIP(write ? hipMemcpy(T.get(), host, (size_t) count * sizeof(double), hipMemcpyHostToDevice)
+                             : hipMemcpy(host, T.get(), (size_t) count * sizeof(double), hipMemcpyDeviceToHost));
+    return CS3_OK;
+}
+
+// ---- complex Schur handles: the complex S out of the real one (cplxsens.hip) -------------------------------------------
+static int cplx_schur_check(const char *who, cs3_cplx p, cs3_handle h, const double *S)
+{
+    int rc = guard(h); if (rc) return rc;
+    if (!p) { set_error(std::string(who) + ": null complex plan"); return CS3_ERR_ARG; }
+    if (h->S.schur_sn < 0) { set_error(std::string(who) + ": the handle has no Schur set (cs3_analyze_schur)"); return CS3_ERR_STATE; }
+    if (!S) { set_error(std::string(who) + ": null buffer"); return CS3_ERR_ARG; }
+    if (!h->factored) { set_error(std::string(who) + ": called before a successful factorisation"); return CS3_ERR_STATE; }
+    if (p->schur_idx.empty()) { set_error(std::string(who) + ": the plan has no border (cs3_cplx_plan_create_schur)"); return CS3_ERR_STATE; }
+    if (h->S.schur_idx.size() != 2 * p->schur_idx.size() || h->batch != p->batch) {
+        set_error(std::string(who) + ": the handle's Schur set is not the 2 ns rows of the plan's border (or the batches differ)");
+        return CS3_ERR_ARG;
+    }
+    return CS3_OK;
+}
+
+int cs3_cplx_schur_get_dev(cs3_cplx p, cs3_handle h, double *S_dev, void *stream)
+{
+    const char *who = "cs3_cplx_schur_get_dev";
+    int rc = cplx_schur_check(who, p, h, S_dev);
+    if (rc) return rc;
+    if (reinterpret_cast<uintptr_t>(S_dev) & 15) { set_error(std::string(who) + ": S_dev must be aligned to 16 bytes"); return CS3_ERR_ARG; }
+    CS3_HIP(launch_cplx_schur_gather(h->D.schur, h->batch, (long long) p->schur_idx.size(), S_dev, (hipStream_t) stream));
+    return CS3_OK;
+}
+
+int cs3_cplx_schur_get(cs3_cplx p, cs3_handle h, double *S)
+{
+    int rc = cplx_schur_check("cs3_cplx_schur_get", p, h, S);
+    if (rc) return rc;
+    const size_t count = 2 * (size_t) h->batch * p->schur_idx.size() * p->schur_idx.size();
+    DevBuf<double> s;
+    CS3_HIP(s.alloc(count));
+    CS3_HIP(launch_cplx_schur_gather(h->D.schur, h->batch, (long long) p->schur_idx.size(), s.get(), nullptr));
+    CS3_HIP(hipMemcpy(S, s.get(), count * sizeof(double), hipMemcpyDeviceToHost));
     return CS3_OK;
 }
 

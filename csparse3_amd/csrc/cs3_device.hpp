@@ -374,6 +374,30 @@ hipError_t launch_sens_scatter(double *T, long long n, int w, const SensOperand 
 hipError_t launch_sens_combine(const double *T, int w, int t, const SensOperand &op, long long ng, long long c0, long long ldy,
                                bool transposed, double *Y, hipStream_t st);
 
+// cplxsens.hip: the same around a handle on the real-equivalent form of a complex matrix (cs3_cplx_sens_*), and the
+// complex Schur complement read out of the real one (cs3_cplx_schur_get*).  The tiling constants are those above; a
+// complex row is a pair of real rows, so a scatter workgroup owns half as many.
+constexpr int CSENS_SCATTER_ROWS = SENS_SCATTER_ROWS / 2;      // complex rows (pairs of real rows) per k_csens_scatter workgroup
+constexpr int CSENS_BLOCK_LD = SENS_COMBINE_LANES + 1;         // LDS row of the transposing store, in complex numbers
+struct CsensOperand {             // SensOperand with interleaved complex values (16-byte aligned)
+    const int *p, *i;
+    const double *x;
+};
+struct CsensGlue {                // what a tile goes through around the solve: pack / unpack of cs3_cplx_op `inner`, a conjugation
+    int inner;                    //   of the solved-for values before the pack and of the solution after the unpack
+    int conj;
+    const double *s;              // the plan's rotation s [n] complex, as it stands in stream order
+};
+// T [2n, w] real = pack_inner of columns c0 .. c0 + t - 1 of `op` (n: the complex order), zero columns behind them
+hipError_t launch_csens_scatter(double *T, long long n, int w, const CsensOperand &op, long long c0, int t, const CsensGlue &g,
+                                hipStream_t st);
+// out[g, j] = sum over the entries (i, v) of column g < ng of `op` of v * unpack_inner(T[2i, j], T[2i + 1, j]), j < t; stored
+// at Y[g * ldy + c0 + j], or (transposed) at Y[(c0 + j) * ldy + g], Y complex
+hipError_t launch_csens_combine(const double *T, int w, int t, const CsensOperand &op, long long ng, long long c0, long long ldy,
+                                bool transposed, const CsensGlue &g, double *Y, hipStream_t st);
+// S [batch][ns, ns] complex from SR [batch][2 ns, 2 ns] real: S[i, j] = (SR[2i, 2j], SR[2i + 1, 2j])
+hipError_t launch_cplx_schur_gather(const double *SR, long long batch, long long ns, double *S, hipStream_t st);
+
 // krylov.hip: the vector layer of restarted GMRES on the held factors (cs3_gmres*), for batch * k systems in lock-step.
 // Every vector is [batch][n, k] row-major; system s = b * k + t is column t of matrix b.  Reductions over the rows run on
 // a FIXED partition (chunks of KRY_CHUNK rows) and the chunks are summed in index order by whoever consumes them: the

@@ -629,6 +629,11 @@ int64_t cs3_debug_updates_tiles(cs3_updates u, int32_t *first_case, int32_t *nca
  * cs3_sens_solve_dev; parts outside 1 .. 7: CS3_ERR_ARG. */
 int cs3_debug_sens_parts(cs3_handle h, cs3_sens s, int64_t parts, const double *Bx_dev, const double *Ctx_dev, double *Y_dev,
                          void *stream);
+/* diagnostics, for tests: the first `count` doubles of the handle's tile buffer (the one cs3_sens_* and cs3_cplx_sens_* solve
+ * in; it exists after the first solve with a plan) copied to `host`, or with write != 0 from `host` into it, so that a
+ * test can look at what a scatter wrote (parts = 1) and choose what a combine reads (parts = 4).  Synchronises.  More
+ * than the buffer holds: CS3_ERR_ARG. */
+int cs3_debug_sens_tile(cs3_handle h, int64_t write, double *host, int64_t count);
 /* Factorisation schedule: supernode id, front order r and width w per schedule slot. */
 int cs3_debug_schedule(cs3_handle h, int32_t *sched, int32_t *front_r, int32_t *front_w);
 /* The launch plan of an operation on this handle (op 0: factorisation, 1 / 2: forward / backward sweep, 3: the fused step =
@@ -920,6 +925,103 @@ int cs3_cplx_pack(cs3_cplx p, int64_t op, const double *Z, double *Y, int64_t k)
 int cs3_cplx_unpack(cs3_cplx p, int64_t op, const double *Y, double *Z, int64_t k, int64_t accumulate);
 int cs3_cplx_residual(cs3_cplx p, int64_t op, const double *Az, const double *B, const double *X, double *R, int64_t k);
 int cs3_cplx_rotation(cs3_cplx p, double *s);
+
+/* ---- complex sparse right-hand sides: Y = C op(A)^-1 B, entries of Z-bus ----
+ * cs3_sens_* for a complex matrix behind a complex plan: Thevenin impedances at p faulted buses, transfer impedances
+ * between a few buses, the columns of Z-bus = Y^-1 a short-circuit study needs.  The handle h holds the real form of
+ * diag(s) A (above); its sweeps run unchanged, and two kernels of their own (csrc/cplxsens.hip) scatter the complex
+ * solved-for columns into the real tile and combine the solutions with the other operand.  ONE complex solved-for column
+ * is ONE real column of a [2n, w] tile: side left with p rows of C costs p transposed solves, where cs3_sens_plan on the
+ * real form would need the real and the imaginary row of every row of C, 2p -- and could not apply s, which lives on the
+ * device.
+ *
+ * Operands as for cs3_sens_plan, in the indices of the COMPLEX matrix: B (n x k) by columns, C (pr x n) by rows as the CSC
+ * arrays of C' (no conjugate); a null Bp / Ctp is the identity.  Bz, Ctz, Y [pr, k] row-major are interleaved complex,
+ * typed double *, aligned to 16 bytes.  op is a cs3_cplx_op: A, A^T (no conjugate) or A^H.
+ *
+ * With Solve_op(r) = unpack_op(real solve(pack_op(r))), pack and unpack exactly those of cs3_cplx_pack_dev /
+ * cs3_cplx_unpack_dev, the real solve cs3_solve_dev for N and cs3_solve_t_dev for T and H, s read from the plan as it
+ * stands in stream order:
+ *     side, op            inner op     conjugate the solved-for values first, and the solution before the product
+ *     right, N / T / H    N / T / H    no
+ *     left, N             T            no
+ *     left, T             N            no
+ *     left, H             N            yes      (A^-H = conj(A^-T): conj(A)^-1 c = conj(A^-1 conj(c)))
+ *   side right: X = Solve_inner(B[:, tile]),  Y[g, c] = sum_e C[g, i_e] * x[i_e, c]   over the entries of row g of C
+ *   side left:  W = Solve_inner(C'[:, tile]), Y[r, g] = sum_e B[i_e, g] * w[i_e, r]   over the entries of column g of B
+ *   k_csens_scatter writes u = pack_inner(v) (v conjugated first where the table says so) as Re u in row 2i, Im u in row
+ *   2i + 1 of a zeroed tile; duplicates ADD in storage order, each component on its own (the first to +0); an identity
+ *   operand STORES pack_inner((1, +0)).  k_csens_combine unpacks the pair (T[2i, j], T[2i + 1, j]), conjugates where the
+ *   table says so, multiplies by the other operand's value (ARITHMETIC above); the first product starts the sum, later
+ *   ones add component by component in storage order; an identity operand hands the unpacked solution over.  No atomics:
+ *   the same bits on every run.
+ *
+ * cs3_cplx_sens_plan: host, pattern only, needs no GPU.  Checks, in this order: a null p or h (or out); a handle whose
+ *   order is not 2 n of the plan; a handle with batch > 1; a Schur handle; then those of cs3_sens_plan from "k < 1" on, in
+ *   its order and wording, and op outside the enum.  Side 0, the tiles (CS3_SENS_TILE is read by this call too), the one
+ *   tile buffer on the handle and the lifetime rules are cs3_sens_plan's: the plan survives refactorisations -- the new s
+ *   is picked up --, handle and plan may be freed in either order, after the first call nothing allocates or synchronises.
+ * cs3_cplx_sens_info: as cs3_sens_info; .trans holds op.   cs3_cplx_sens_limits: the constants of the complex kernels
+ *   (scatter_rows counts REAL rows of the tile: half as many complex rows; tblock counts complex numbers).
+ * cs3_cplx_sens_solve_dev: asynchronous on `stream`.  Checks: null arguments, a plan made for another handle, a complex
+ *   plan of another order, misaligned arrays: CS3_ERR_ARG; no successful factorisation: CS3_ERR_STATE.
+ * cs3_cplx_sens_solve: the same from host arrays (synchronises); the same bits.
+ * cs3_debug_cplx_sens_parts: the steps selected by the mask `parts` as for cs3_debug_sens_parts (1 scatter, 2 solve,
+ *   4 combine).
+ * Out of scope: batched plans, a sparse Y, skipping fronts off the elimination-tree paths of the right-hand sides; the
+ * CscMat sugar (CscMat.sensitivities refuses complex data, and a test pins that refusal: it waits for a change that may
+ * edit that test). */
+typedef struct cs3_cplx_sens_s *cs3_cplx_sens;
+int cs3_cplx_sens_limits(cs3_sens_limits_t *out);
+int cs3_cplx_sens_plan(cs3_cplx p, cs3_handle h, int64_t k, const int32_t *Bp, const int32_t *Bi, int64_t pr,
+                       const int32_t *Ctp, const int32_t *Cti, int64_t side, int64_t op, cs3_cplx_sens *out);
+int cs3_cplx_sens_free(cs3_cplx_sens s);
+int cs3_cplx_sens_info(cs3_cplx_sens s, cs3_sens_info_t *out);
+int cs3_cplx_sens_solve_dev(cs3_cplx p, cs3_handle h, cs3_cplx_sens s, const double *Bz_dev, const double *Ctz_dev,
+                            double *Y_dev, void *stream);
+int cs3_cplx_sens_solve(cs3_cplx p, cs3_handle h, cs3_cplx_sens s, const double *Bz, const double *Ctz, double *Y);
+int cs3_debug_cplx_sens_parts(cs3_cplx p, cs3_handle h, cs3_cplx_sens s, int64_t parts, const double *Bz_dev,
+                              const double *Ctz_dev, double *Y_dev, void *stream);
+
+/* ---- complex Schur handles: Kron reduction of an admittance matrix ----------
+ * Ward and network equivalents: S = A22 - A21 A11^-1 A12 of the complex matrix on its boundary buses, from a real Schur
+ * handle (cs3_analyze_schur) on the real form:
+ *     cs3_cplx_plan_create_schur(n, Ap, Ai, batch, rotate, ns, idx, &p);  cs3_cplx_plan_pattern(p, Rp, Ri);
+ *     cs3_cplx_plan_schur_order(p, order, q, q2_interior, schur2);
+ *     cs3_analyze_schur(kind, CS3_ORDER_GIVEN, 2 n, Rp, Ri, q2_interior, batch, 2 ns, schur2, &h);
+ *     cs3_cplx_values_dev(p, Az, Rx, st);  cs3_factor_dev(h, Rx, tol, st);  cs3_cplx_schur_get_dev(p, h, S, st);
+ * BORDER ROWS ARE NEVER ROTATED: their diagonal lists in the plan's tables are empty, so s_i = (1, +0) there whatever the
+ * values (they count in rows_without_diagonal).  With M = diag(s) A and s = 1 on the border,
+ * M22 - M21 M11^-1 M12 = A22 - A21 A11^-1 A12: S comes out in A's scaling with no division.  The border is never
+ * pivoted, so it needs no rotation (a zero diagonal there is no obstacle).
+ *
+ * cs3_cplx_plan_create_schur: cs3_cplx_plan_create with a border.  Its checks come first, then those of cs3_analyze_schur on
+ *   its set, in that order: a null schur_idx, ns < 1 or ns >= n, an index outside [0, n), a repeated index (named).
+ * cs3_cplx_plan_schur_info: ns and the list (either may be NULL); a plan without a border: CS3_ERR_STATE.
+ * cs3_cplx_plan_schur_order: q2_interior[2 n1], n1 = n - ns, the doubled order of the interior -- CS3_ORDER_AMD:
+ *   q = interior[cs3_amd(A11)] of the complex pattern with border rows and columns removed (what cs3_analyze_schur does
+ *   with a real pattern); CS3_ORDER_NATURAL: the interior ascending; CS3_ORDER_GIVEN: q_given[n1] -- doubled as
+ *   cs3_cplx_plan_order doubles; schur2[2 ns] = (2 b, 2 b + 1) for every border index b in the caller's order.
+ * cs3_cplx_schur_get_dev: S_dev [batch][ns, ns] complex row-major, S[i, j] = (S_R[2i, 2j], S_R[2i + 1, 2j]): the first
+ *   column of every 2 x 2 block of the handle's real Schur complement (the twin column agrees to rounding only and is not
+ *   read).  One launch on `stream`.  Checks: those of cs3_schur_get_dev, a plan without a border (CS3_ERR_STATE), a handle
+ *   whose Schur set is not 2 ns (CS3_ERR_ARG), a misaligned S_dev.  A Cholesky plan (CS3_CPLX_ROTATE_NONE, Hermitian
+ *   positive definite) gives a Hermitian S.
+ * cs3_cplx_schur_get: the same into host memory (synchronises).
+ * HALF-SOLVES are compositions of existing calls, on X2 [batch][2n, k] real:
+ *   forward:  cs3_cplx_pack_dev(p, CS3_CPLX_N, B, X2) (s * b, s = 1 on the border); cs3_schur_fwd_dev(h, X2, k);
+ *             cs3_cplx_unpack_dev(p, CS3_CPLX_N, X2, Y) (a raw join): border rows hold b2 - A21 A11^-1 b1, the interior
+ *             rows are opaque.
+ *   backward: the caller writes x2 into the border rows of Y; cs3_cplx_pack_dev(p, CS3_CPLX_H, Y, X2) (a raw split);
+ *             cs3_schur_bwd_dev(h, X2, k); cs3_cplx_unpack_dev(p, CS3_CPLX_N, X2, X): X solves A x = b.
+ * On the handle cs3_solve* stay refused, as on every Schur handle.  Out of scope: transposed half-solves; the CscMat sugar
+ * (CscMat.lu(schur=...), chol(schur=...) and schur_complement refuse complex data, and a test pins those refusals). */
+int cs3_cplx_plan_create_schur(int64_t n, const int32_t *Ap, const int32_t *Ai, int64_t batch, int64_t rotate, int64_t ns,
+                               const int32_t *schur_idx, cs3_cplx *out);
+int cs3_cplx_plan_schur_info(cs3_cplx p, int64_t *ns, int32_t *schur_idx);
+int cs3_cplx_plan_schur_order(cs3_cplx p, int64_t order, const int32_t *q_given, int32_t *q2_interior, int32_t *schur2);
+int cs3_cplx_schur_get_dev(cs3_cplx p, cs3_handle h, double *S_dev, void *stream);
+int cs3_cplx_schur_get(cs3_cplx p, cs3_handle h, double *S);
 
 #ifdef __cplusplus
 }
