@@ -98,6 +98,12 @@ class SensLimits(C.Structure):
                                                "combine_lanes", "tblock")]
 
 
+class CplxUpdatesLimits(C.Structure):
+    """cs3_cplx_updates_limits_t: the constants that shape the kernels of the complex low-rank-modified solves."""
+    _fields_ = [(name, C.c_int64) for name in ("unit_rows", "unit_threads", "apply_stage", "apply_rows", "apply_threads_min",
+                                               "max_rank", "max_tile", "max_tile_cases")]
+
+
 class Cs3Error(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("cs3 error %d: %s" % (code, msg))
@@ -286,7 +292,16 @@ def lib():
         L.cs3_cplx_sens_solve_dev.argtypes = [vp, vp, vp, vp, vp, vp, vp]
         L.cs3_cplx_sens_solve.argtypes = [vp, vp, vp, _f64p, _f64p, _f64p]
         L.cs3_debug_cplx_sens_parts.argtypes = [vp, vp, vp, I64, vp, vp, vp, vp]
-        L.cs3_cplx_plan_create_schur.argtypes = [I64, _i32p, _i32p, I64, I64, I64, _i32p, C.POINTER(vp)]
+        L.cs3_cplx_updates_limits.argtypes = [C.POINTER(CplxUpdatesLimits)]
+        L.cs3_cplx_updates_plan.argtypes = [vp, vp, I64, _i32p, _i32p, _i32p, C.POINTER(vp)]
+        L.cs3_cplx_updates_free.argtypes = [vp]
+        L.cs3_cplx_updates_info.argtypes = [vp] + [C.POINTER(I64)] * 4
+        L.cs3_debug_cplx_updates_tiles.argtypes = [vp] + [_i32p] * 4
+        L.cs3_debug_cplx_updates_tiles.restype = I64
+        L.cs3_cplx_updates_solve_dev.argtypes = [vp, vp, vp, vp, vp, C.c_double, vp, vp, vp]
+        L.cs3_cplx_updates_solve.argtypes = [vp, vp, vp, _f64p, _f64p, C.c_double, _f64p, _f64p]
+        L.cs3_debug_cplx_updates_parts.argtypes = [vp, vp, vp, I64, vp, vp, C.c_double, vp, vp, vp]
+        L.cs3_cplx_plan_create_schur.argtypes =[I64, _i32p, _i32p, I64, I64, I64, _i32p, C.POINTER(vp)]
         L.cs3_cplx_plan_schur_info.argtypes = [vp, C.POINTER(I64), _i32p]
         L.cs3_cplx_plan_schur_order.argtypes = [vp, I64, _i32p, _i32p, _i32p]
         L.cs3_cplx_schur_get_dev.argtypes = [vp, vp, vp, vp]
@@ -1559,7 +1574,8 @@ class ComplexFactorization:
     schur: the boundary buses of a Kron reduction, not eliminated (a Schur handle on the real form).  factor() then holds
     the complex S = A22 - A21 A11^-1 A12 in the order of the list: schur(), schur_forward(), schur_backward(); order / q refer
     to the interior; solve() raises Cs3Error, as on every Schur handle.
-    sens_plan / sens_solve: Y = C op(A)^-1 B with sparse B and C (entries of Z-bus), see ComplexSensPlan."""
+    sens_plan / sens_solve: Y = C op(A)^-1 B with sparse B and C (entries of Z-bus), see ComplexSensPlan.
+    updates_plan / solve_updates: (A + dA_c) x = b for many sparse complex dA_c (outages, faults), see ComplexUpdatesPlan."""
 
     def __init__(self, n, Ap, Ai, kind=CS3_LU, order=ORDER_AMD, q=None, batch=1, rotate=True, schur=None):
         assert not (rotate and kind == CS3_CHOLESKY), "rotate scales rows, which breaks the symmetry Cholesky needs: pass rotate=False"
@@ -1710,6 +1726,85 @@ class ComplexFactorization:
         """Diagnostics: the steps of sens_solve_dev in the mask `parts` (1 scatter, 2 solves, 4 combine)."""
         _check(lib().cs3_debug_cplx_sens_parts(self.plan._p, self.real._h, plan._u, parts, C.c_void_p(bz_ptr), C.c_void_p(ctz_ptr),
                                                C.c_void_p(y_ptr), C.c_void_p(stream)))
+
+
+    # -- low-rank-modified systems: outages, faults and switching on an admittance matrix
+    def updates_plan(self, cases):
+        """A ComplexUpdatesPlan for a list of modifications of A: `cases` is a list of (rows, cols) index arrays, one pair per
+        case, in the indices of the complex matrix (or the flat triple (cp, ci, cj)); at most 16 distinct rows and 16
+        distinct columns per case."""
+        return ComplexUpdatesPlan(self, cases)
+
+    def solve_updates(self, plan, cz, b, sing_tol=0.0):
+        """x_c = (A + dA_c)^-1 b for every case of `plan` on the factors at hand; cz holds the complex values of all
+        triplets in the plan's order.  -> (X [n, ncases] complex128, rpiv [ncases]).  A case with rpiv[c] <= sing_tol
+        (sing_tol > 0), an exactly zero pivot or a NaN has a (NaN, NaN) column in X; the others are unaffected."""
+        cz, b = _c128(cz).reshape(-1), _c128(b).reshape(-1)
+        assert cz.size >= int(plan.cp[-1]) and b.size == self.n
+        X = np.empty((self.n, plan.ncases), dtype=np.complex128)
+        rpiv = np.empty(plan.ncases, dtype=np.float64)
+        _check(lib().cs3_cplx_updates_solve(self.plan._p, self.real._h, plan._u, _pc(cz), _pc(b), sing_tol, _pc(X), _pf(rpiv)))
+        return X, rpiv
+
+    def solve_updates_dev(self, plan, cz_ptr, b_ptr, x_ptr, rpiv_ptr=0, sing_tol=0.0, stream=0):
+        """solve_updates on device pointers, asynchronous on `stream`; X [n, ncases] complex row-major.  After the first
+        call with a plan nothing is allocated and nothing synchronises.  The same bits as solve_updates()."""
+        _check(lib().cs3_cplx_updates_solve_dev(self.plan._p, self.real._h, plan._u, C.c_void_p(cz_ptr), C.c_void_p(b_ptr), sing_tol,
+                                                C.c_void_p(x_ptr), C.c_void_p(rpiv_ptr), C.c_void_p(stream)))
+
+    def debug_updates_parts(self, plan, parts, cz_ptr, b_ptr, x_ptr, rpiv_ptr=0, sing_tol=0.0, stream=0):
+        """Diagnostics: the steps of solve_updates_dev in the mask `parts` (1 x0 and units, 2 solves, 4 capacitance + apply)."""
+        _check(lib().cs3_debug_cplx_updates_parts(self.plan._p, self.real._h, plan._u, parts, C.c_void_p(cz_ptr), C.c_void_p(b_ptr),
+                                                  sing_tol, C.c_void_p(x_ptr), C.c_void_p(rpiv_ptr), C.c_void_p(stream)))
+
+
+def cplx_updates_limits():
+    """The constants of the complex low-rank-modified solves (cs3_cplx_updates_limits); needs no GPU."""
+    out = CplxUpdatesLimits()
+    _check(lib().cs3_cplx_updates_limits(C.byref(out)))
+    return out
+
+
+class ComplexUpdatesPlan:
+    """The pattern of a list of sparse complex modifications dA_c (ComplexFactorization.updates_plan): made once on the
+    host, used by every solve_updates, across refactorisations.  One touched bus is one real column of the handle's tile."""
+
+    def __init__(self, factorization, cases):
+        self._u = C.c_void_p()
+        self.cp, self.ci, self.cj = _flat_cases(cases)
+        self.ncases = len(self.cp) - 1
+        _check(lib().cs3_cplx_updates_plan(factorization.plan._p, factorization.real._h, self.ncases, _pi(self.cp), _pi(self.ci),
+                                           _pi(self.cj), C.byref(self._u)))
+
+    def close(self):
+        if self._u:
+            lib().cs3_cplx_updates_free(self._u)
+            self._u = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    @property
+    def info(self):
+        out = [I64() for _ in range(4)]
+        _check(lib().cs3_cplx_updates_info(self._u, *[C.byref(o) for o in out]))
+        return UpdatesInfo(*[int(o.value) for o in out])
+
+    def tiles(self):
+        """-> int32 [ntiles, 4]: first case, cases, touched rows and solve width of every tile (diagnostic)."""
+        nt = self.info.ntiles
+        arrs = [np.empty(nt, dtype=np.int32) for _ in range(4)]
+        assert lib().cs3_debug_cplx_updates_tiles(self._u, *[_pi(a) for a in arrs]) == nt
+        return np.stack(arrs, axis=1)
 
 
 def cplx_sens_limits():

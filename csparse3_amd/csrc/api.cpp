@@ -172,6 +172,13 @@ struct cs3_cplx_sens_s : cs3_sens_s {
     int op = CS3_CPLX_N;
 };
 
+// cs3_updates_s for a handle on the real form of a complex matrix (cs3_cplx_updates_plan): n is the COMPLEX order, the
+// handle's is 2 n; it sits in its handle's plans, so the lifetime rules are those of cs3_updates_s.  mem.y holds 16 complex
+// numbers per case, mem.cx the host form's interleaved values.
+struct cs3_cplx_updates_s : cs3_updates_s {
+    const cs3_cplx_s *p = nullptr;            // the complex plan it was made with (compared, never followed)
+};
+
 namespace {
 
 // One array of the DeviceFactor: the block joins h->mem.factor, *field points at it.
@@ -2088,7 +2095,8 @@ int cs3_slogdet(cs3_handle h, double *sign, double *logabs)
 // in their order cut into tiles (a case joins the current tile unless the union of touched rows would pass the tile
 // width, or the tile already has UPD_MAX_TILE_CASES cases); per tile the touched rows in order of first use = the columns
 // of its Z.  A row that cases of two tiles touch is a column of both.
-static int updates_build(cs3_updates_s &u, int64_t n, int64_t ncases, const int32_t *cp, const int32_t *ci, const int32_t *cj)
+static int updates_build(cs3_updates_s &u, int64_t n, int64_t ncases, const int32_t *cp, const int32_t *ci, const int32_t *cj,
+                         const char *who = "cs3_updates_plan")
 {
     u.n = n; u.ncases = ncases; u.ntrip = cp[ncases];
     u.cp.assign(cp, cp + ncases + 1);
@@ -2102,7 +2110,7 @@ static int updates_build(cs3_updates_s &u, int64_t n, int64_t ncases, const int3
         std::sort(rows.begin(), rows.end()); rows.erase(std::unique(rows.begin(), rows.end()), rows.end());
         std::sort(cols.begin(), cols.end()); cols.erase(std::unique(cols.begin(), cols.end()), cols.end());
         if (rows.size() > (size_t) UPD_MAX_RANK || cols.size() > (size_t) UPD_MAX_RANK) {
-            set_error("cs3_updates_plan: case " + std::to_string(c) + " touches " + std::to_string(rows.size()) + " rows and " +
+            set_error(std::string(who) + ": case " + std::to_string(c) + " touches " + std::to_string(rows.size()) + " rows and " +
                       std::to_string(cols.size()) + " columns (at most 16 of each)");
             return CS3_ERR_ARG;
         }
@@ -2156,6 +2164,24 @@ static int updates_build(cs3_updates_s &u, int64_t n, int64_t ncases, const int3
     return CS3_OK;
 }
 
+// The case lists of a plan (cp non-null): ncases, cp monotone from 0, the index arrays and their range, in this order.
+static int updates_check_lists(const char *who_, int64_t n, int64_t ncases, const int32_t *cp, const int32_t *ci, const int32_t *cj)
+{
+    const std::string who(who_);
+    if (ncases < 1 || ncases > INT_MAX / 2) { set_error(who + ": ncases must be >= 1"); return CS3_ERR_ARG; }
+    if (cp[0] != 0) { set_error(who + ": cp[0] != 0"); return CS3_ERR_ARG; }
+    for (int64_t c = 0; c < ncases; ++c)
+        if (cp[c + 1] < cp[c]) { set_error(who + ": cp not monotone at case " + std::to_string(c)); return CS3_ERR_ARG; }
+    if (cp[ncases] > 0 && (!ci || !cj)) { set_error(who + ": null index arrays"); return CS3_ERR_ARG; }
+    for (int64_t c = 0; c < ncases; ++c)
+        for (int p = cp[c]; p < cp[c + 1]; ++p)
+            if (ci[p] < 0 || ci[p] >= n || cj[p] < 0 || cj[p] >= n) {
+                set_error(who + ": index out of range in case " + std::to_string(c));
+                return CS3_ERR_ARG;
+            }
+    return CS3_OK;
+}
+
 int cs3_updates_plan(cs3_handle h, int64_t ncases, const int32_t *cp, const int32_t *ci, const int32_t *cj, cs3_updates *out)
 {
     int rc = guard(h); if (rc) return rc;
@@ -2163,18 +2189,8 @@ int cs3_updates_plan(cs3_handle h, int64_t ncases, const int32_t *cp, const int3
     *out = nullptr;
     if ((rc = refuse_schur(h, "cs3_updates_plan"))) return rc;
     if (!cp) { set_error("cs3_updates_plan: null case pointers"); return CS3_ERR_ARG; }
-    if (ncases < 1 || ncases > INT_MAX / 2) { set_error("cs3_updates_plan: ncases must be >= 1"); return CS3_ERR_ARG; }
-    if (cp[0] != 0) { set_error("cs3_updates_plan: cp[0] != 0"); return CS3_ERR_ARG; }
-    for (int64_t c = 0; c < ncases; ++c)
-        if (cp[c + 1] < cp[c]) { set_error("cs3_updates_plan: cp not monotone at case " + std::to_string(c)); return CS3_ERR_ARG; }
-    if (cp[ncases] > 0 && (!ci || !cj)) { set_error("cs3_updates_plan: null index arrays"); return CS3_ERR_ARG; }
     const int64_t n = h->S.n;
-    for (int64_t c = 0; c < ncases; ++c)
-        for (int p = cp[c]; p < cp[c + 1]; ++p)
-            if (ci[p] < 0 || ci[p] >= n || cj[p] < 0 || cj[p] >= n) {
-                set_error("cs3_updates_plan: index out of range in case " + std::to_string(c));
-                return CS3_ERR_ARG;
-            }
+    if ((rc = updates_check_lists("cs3_updates_plan", n, ncases, cp, ci, cj))) return rc;
     cs3_updates_s *u = nullptr;
     try {
         u = new cs3_updates_s();
@@ -2693,6 +2709,185 @@ int cs3_debug_sens_tile(cs3_handle h, int64_t write, double *host, int64_t count
     CS3_HIP(hipDeviceSynchronize());
     if (count) CS3_HIP(write ? hipMemcpy(T.get(), host, (size_t) count * sizeof(double), hipMemcpyHostToDevice)
                              : hipMemcpy(host, T.get(), (size_t) count * sizeof(double), hipMemcpyDeviceToHost));
+    return CS3_OK;
+}
+
+// ---- complex low-rank-modified systems (A + dA_c) v = i behind a complex plan (cplxupd.hip) ---------------------------
+int cs3_cplx_updates_limits(cs3_cplx_updates_limits_t *out)
+{
+    if (!out) { set_error("cs3_cplx_updates_limits: null output"); return CS3_ERR_ARG; }
+    *out = cs3_cplx_updates_limits_t{CUPD_UNIT_ROWS, CUPD_UNIT_THREADS, CUPD_APPLY_STAGE, CUPD_APPLY_ROWS, CUPD_APPLY_NT_MIN,
+                                     UPD_MAX_RANK, UPD_MAX_TILE, UPD_MAX_TILE_CASES};
+    return CS3_OK;
+}
+
+int cs3_cplx_updates_plan(cs3_cplx p, cs3_handle h, int64_t ncases, const int32_t *cp, const int32_t *ci, const int32_t *cj,
+                          cs3_cplx_updates *out)
+{
+    const char *who = "cs3_cplx_updates_plan";
+    const auto bad = [who](const char *msg) { set_error(std::string(who) + ": " + msg); return CS3_ERR_ARG; };
+    if (!p || !h) return bad("null plan or handle");
+    if (!out) return bad("null output");
+    *out = nullptr;
+    if (!cp) return bad("null case pointers");
+    const int64_t n = p->n;
+    int rc;
+    if (h->S.n != 2 * n) return bad("the handle's order is not 2 n of the complex plan");
+    if ((rc = updates_check_lists(who, n, ncases, cp, ci, cj))) return rc;
+    cs3_cplx_updates_s *u = nullptr;
+    try {
+        u = new cs3_cplx_updates_s();
+        if ((rc = updates_build(*u, n, ncases, cp, ci, cj, who))) { delete u; return rc; }
+        if (h->batch > 1 || p->batch > 1) { delete u; return bad("plans and handles with batch > 1 are not supported"); }
+        if (!p->schur_idx.empty()) { delete u; return bad("not available on a complex plan with a border (cs3_cplx_plan_create_schur)"); }
+        if ((rc = refuse_schur(h, who))) { delete u; return rc; }
+        h->plans.push_back(u);
+    } catch (const std::bad_alloc &) {
+        delete u; set_error(std::string(who) + ": out of memory"); return CS3_ERR_ALLOC;
+    }
+    u->h = h;
+    u->p = p;
+    *out = u;
+    return CS3_OK;
+}
+
+int cs3_cplx_updates_free(cs3_cplx_updates u)
+{
+    if (!u) return CS3_OK;
+    if (u->h) {
+        if (u->on_device) { (void) hipDeviceSynchronize(); release_plan_device(u); }
+        auto &pl = u->h->plans;
+        pl.erase(std::remove(pl.begin(), pl.end(), static_cast<cs3_updates_s *>(u)), pl.end());
+    }
+    delete u;
+    return CS3_OK;
+}
+
+int cs3_cplx_updates_info(cs3_cplx_updates u, int64_t *ncases, int64_t *nrows_unique, int64_t *max_rank, int64_t *ntiles)
+{
+    if (!u) { set_error("cs3_cplx_updates_info: null plan"); return CS3_ERR_ARG; }
+    return cs3_updates_info(u, ncases, nrows_unique, max_rank, ntiles);
+}
+
+int64_t cs3_debug_cplx_updates_tiles(cs3_cplx_updates u, int32_t *first_case, int32_t *ncases, int32_t *nrows, int32_t *width)
+{
+    if (!u) { set_error("cs3_debug_cplx_updates_tiles: null plan"); return CS3_ERR_ARG; }
+    return cs3_debug_updates_tiles(u, first_case, ncases, nrows, width);
+}
+
+static int cupd_check(const char *who_, cs3_cplx p, cs3_handle h, cs3_cplx_updates u, const double *cz, const double *b, const double *X,
+                      bool device)
+{
+    const std::string who(who_);
+    if (!p) { set_error(who + ": null complex plan"); return CS3_ERR_ARG; }
+    int rc = guard(h); if (rc) return rc;
+    if (!u) { set_error(who + ": null plan"); return CS3_ERR_ARG; }
+    if (!b || !X || (u->ntrip > 0 && !cz)) { set_error(who + ": null argument"); return CS3_ERR_ARG; }
+    if (u->h != h) { set_error(who + ": the plan was made for another handle"); return CS3_ERR_ARG; }
+    if (u->p != p) { set_error(who + ": the plan was made for another complex plan"); return CS3_ERR_ARG; }
+    const uintptr_t used = reinterpret_cast<uintptr_t>(cz) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(X);
+    if (device && (used & 15)) { set_error(who + ": complex arrays must be aligned to 16 bytes"); return CS3_ERR_ARG; }
+    if (!h->factored) { set_error(who + ": no successful factorisation"); return CS3_ERR_STATE; }
+    return CS3_OK;
+}
+
+// Tables of the plan in HBM, x0 [2n] (the real path's, a stable address) and the handle's tile buffer for Z [2n][widest
+// tile], room for the widest tile in the sweep buffers: later calls neither allocate nor synchronise.
+static int ensure_cupd(cs3_handle h, cs3_cplx_updates_s *u)
+{
+    int wmax = 1;
+    for (const auto &t : u->tiles) wmax = std::max(wmax, t.t_solve);
+    if (!u->on_device) {
+        static bool prepared = false;
+        if (!prepared) { CS3_HIP(prepare_cupd_kernels()); prepared = true; }
+        auto &P = u->mem;
+        CS3_HIP(P.cases.upload(u->cases));
+        CS3_HIP(P.cp.upload(u->cp));
+        CS3_HIP(P.tpos.upload(u->tpos));
+        CS3_HIP(P.unit.upload(u->unit_row));
+        CS3_HIP(P.y.alloc((size_t) u->ncases * 2 * UPD_MAX_RANK));
+        CS3_HIP(P.flag.alloc((size_t) u->ncases));
+        CS3_HIP(P.rpiv.alloc((size_t) u->ncases));
+        h->dbg_allocs += 7;
+        u->on_device = true;
+    }
+    const size_t n2 = std::max<size_t>(2, (size_t) h->S.n);
+    auto &x0 = h->mem.upd.x0;
+    if (!x0.get()) { CS3_HIP(x0.alloc(n2)); h->dbg_allocs += 1; }
+    auto &T = h->mem.sens.t;
+    if (T.count() < n2 * (size_t) wmax) {
+        if (T.get()) {                                     // a wider plan than any before: the old tile may still be in use
+            CS3_HIP(hipDeviceSynchronize());
+            h->dbg_syncs += 1;
+        }
+        CS3_HIP(T.alloc(n2 * (size_t) wmax));
+        h->dbg_allocs += 1;
+    }
+    return ensure_rhs_capacity(h, wmax);
+}
+
+// updates_run with the complex kernels.  parts (diagnostics): 1 x0 and the units, 2 the tiles' solves, 4 capacitance + apply.
+static int cupd_run(cs3_cplx p, cs3_handle h, cs3_cplx_updates_s *u, const double *cz_dev, const double *b_dev, double sing_tol,
+                    double *X_dev, double *rpiv_dev, hipStream_t st, int parts = 7)
+{
+    int rc = cs3_cplx_upload(p);                            // (the tables and s = (1, +0): a plan that never saw a values call)
+    if (rc) return rc;
+    if ((rc = ensure_cupd(h, u))) return rc;
+    const i64 n = u->n;
+    const auto &P = u->mem;
+    const UpdTables T{P.cases.get(), P.cp.get(), P.tpos.get(), P.y.get(), P.flag.get()};
+    double *rpiv = rpiv_dev ? rpiv_dev : P.rpiv.get();
+    double *Z = h->mem.sens.t.get(), *x0 = h->mem.upd.x0.get();
+    if (n > 0 && (parts & 1)) {
+        if ((rc = cs3_cplx_pack_dev(p, CS3_CPLX_N, b_dev, x0, 1, st))) return rc;
+        if ((rc = run_solve(h, x0, 1, 0, st))) return rc;
+    }
+    for (const auto &t : u->tiles) {
+        if (n > 0 && t.t > 0) {
+            if (parts & 1) CS3_HIP(launch_cupd_units(Z, n, t.t_solve, P.unit.get() + t.unit0, p->d_s.get(), st));
+            if ((parts & 2) && (rc = run_solve(h, Z, t.t_solve, 0, st))) return rc;
+        }
+        if (parts & 4) {
+            CS3_HIP(launch_cupd_capacitance(T, cz_dev, Z, t.t_solve, x0, t.c0, t.nc, sing_tol, rpiv, st));
+            CS3_HIP(launch_cupd_apply(T, Z, t.t_solve, x0, n, t.c0, t.nc, t.rmax, u->ncases, X_dev, st));
+        }
+    }
+    return CS3_OK;
+}
+
+int cs3_cplx_updates_solve_dev(cs3_cplx p, cs3_handle h, cs3_cplx_updates u, const double *cz_dev, const double *b_dev, double sing_tol,
+                               double *X_dev, double *rpiv_dev, void *stream)
+{
+    int rc = cupd_check("cs3_cplx_updates_solve_dev", p, h, u, cz_dev, b_dev, X_dev, true);
+    if (rc) return rc;
+    return cupd_run(p, h, u, cz_dev, b_dev, sing_tol, X_dev, rpiv_dev, (hipStream_t) stream);
+}
+
+int cs3_debug_cplx_updates_parts(cs3_cplx p, cs3_handle h, cs3_cplx_updates u, int64_t parts, const double *cz_dev, const double *b_dev,
+                                 double sing_tol, double *X_dev, double *rpiv_dev, void *stream)
+{
+    int rc = cupd_check("cs3_debug_cplx_updates_parts", p, h, u, cz_dev, b_dev, X_dev, true);
+    if (rc) return rc;
+    if (parts < 1 || parts > 7) { set_error("cs3_debug_cplx_updates_parts: parts must be a mask of 1, 2 and 4"); return CS3_ERR_ARG; }
+    return cupd_run(p, h, u, cz_dev, b_dev, sing_tol, X_dev, rpiv_dev, (hipStream_t) stream, (int) parts);
+}
+
+int cs3_cplx_updates_solve(cs3_cplx p, cs3_handle h, cs3_cplx_updates u, const double *cz, const double *b, double sing_tol, double *X,
+                           double *rpiv)
+{
+    int rc = cupd_check("cs3_cplx_updates_solve", p, h, u, cz, b, X, false);
+    if (rc) return rc;
+    const size_t n = (size_t) u->n, nc = (size_t) u->ncases, nt = (size_t) u->ntrip;
+    CS3_HIP(u->mem.cx.reserve(2 * nt));
+    DevBuf<double> bx;                                     // b [n], then X [n, ncases], complex, for this call
+    CS3_HIP(bx.alloc(2 * n * (nc + 1)));
+    double *d_b = bx.get(), *d_x = d_b + 2 * n;
+    if (nt) CS3_HIP(hipMemcpy(u->mem.cx.get(), cz, 2 * nt * sizeof(double), hipMemcpyHostToDevice));
+    if (n) CS3_HIP(hipMemcpy(d_b, b, 2 * n * sizeof(double), hipMemcpyHostToDevice));
+    if ((rc = cupd_run(p, h, u, u->mem.cx.get(), d_b, sing_tol, d_x, nullptr, nullptr))) return rc;
+    if (n) CS3_HIP(hipMemcpy(X, d_x, 2 * n * nc * sizeof(double), hipMemcpyDeviceToHost));
+    if (rpiv) CS3_HIP(hipMemcpy(rpiv, u->mem.rpiv.get(), nc * sizeof(double), hipMemcpyDeviceToHost));
+    CS3_HIP(hipDeviceSynchronize());
     return CS3_OK;
 }
 

@@ -398,6 +398,24 @@ hipError_t launch_csens_combine(const double *T, int w, int t, const CsensOperan
 // S [batch][ns, ns] complex from SR [batch][2 ns, 2 ns] real: S[i, j] = (SR[2i, 2j], SR[2i + 1, 2j])
 hipError_t launch_cplx_schur_gather(const double *SR, long long batch, long long ns, double *S, hipStream_t st);
 
+// cplxupd.hip: many low-rank-modified COMPLEX systems (A + dA_c) v = i around a handle on the real-equivalent form
+// (cs3_cplx_updates_*).  Plan, cases and tiles are those of updates.hip with n = the complex order (UpdCase, UpdTables;
+// y is [ncases][16] complex here); a complex row is a pair of real rows of the tile Z [2n, t].
+constexpr int CUPD_UNIT_ROWS = 8;              // complex rows (pairs of real rows) per k_cupd_units workgroup
+constexpr int CUPD_UNIT_THREADS = 256;         //   ... and its threads (a thread owns columns j, j + 256, ...)
+constexpr int CUPD_APPLY_STAGE = 4;            // complex rows of Z in LDS at a time: 2 x 4 x 1024 x 8 B = 64 KB at the full width
+constexpr int CUPD_APPLY_ROWS = 64;            // complex rows per k_cupd_apply workgroup
+constexpr int CUPD_APPLY_NT_MIN = 1024;        // threads of the smallest k_cupd_apply workgroup
+hipError_t prepare_cupd_kernels();
+// Z [2n, t]: column j = pack_N(e_{unit_row[j]}) with the rotation s [n] complex (a negative row: a zero column)
+hipError_t launch_cupd_units(double *Z, long long n, int t, const int *unit_row, const double *s, hipStream_t st);
+// the cases c0 .. c0 + nc - 1 of one tile: y, rpiv, flag from the solved tile Z [2n, t] and x0 [n] complex; cz interleaved
+hipError_t launch_cupd_capacitance(const UpdTables &T, const double *cz, const double *Z, int t, const double *x0, int c0, int nc,
+                                   double sing_tol, double *rpiv, hipStream_t st);
+// columns c0 .. c0 + nc - 1 of X [n, ldx] complex; rmax = the largest rank among them
+hipError_t launch_cupd_apply(const UpdTables &T, const double *Z, int t, const double *x0, long long n, int c0, int nc, int rmax,
+                             long long ldx, double *X, hipStream_t st);
+
 // krylov.hip: the vector layer of restarted GMRES on the held factors (cs3_gmres*), for batch * k systems in lock-step.
 // Every vector is [batch][n, k] row-major; system s = b * k + t is column t of matrix b.  Reductions over the rows run on
 // a FIXED partition (chunks of KRY_CHUNK rows) and the chunks are summed in index order by whoever consumes them: the

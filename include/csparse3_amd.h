@@ -983,6 +983,78 @@ int cs3_cplx_sens_solve(cs3_cplx p, cs3_handle h, cs3_cplx_sens s, const double 
 int cs3_debug_cplx_sens_parts(cs3_cplx p, cs3_handle h, cs3_cplx_sens s, int64_t parts, const double *Bz_dev,
                               const double *Ctz_dev, double *Y_dev, void *stream);
 
+/* ---- complex low-rank-modified systems (Y + dY_c) v = i on the held factors -
+ * Branch-outage, fault and switching studies on an admittance matrix: cs3_updates_* (above) for a complex matrix behind
+ * a complex plan, on the factors its real-form handle holds.  ONE complex solved-for column is ONE real column of the
+ * tile Z [2n, t], real part in rows 2i, imaginary part in rows 2i + 1: the unit right-hand side pack_N(e_row) is
+ * (Re s_row, Im s_row) in the pair of that row, so Z = A^-1 E_R comes out of the handle's unchanged many-right-hand-side
+ * solve.  dA_c is never rotated, s never leaves the device, a case may touch 16 complex rows and 16 complex columns, and a
+ * tile of 1024 columns holds 1024 buses.
+ *
+ * Case c is a sparse complex dA_c given as triplets (i, j, v); duplicates of one (i, j) inside a case ADD, in triplet
+ * order, component by component, starting from +0.  R_c (r <= 16) its distinct rows ascending, C_c (s <= 16) its distinct
+ * columns ascending, D_c the dense r x s block, x0 = A^-1 b, Z = A^-1 E_R:
+ *     G_c = Z[C_c, R_c]   S_c = I_r + D_c G_c   y_c = S_c^-1 (D_c x0[C_c])   x_c = x0 - Z[:, R_c] y_c
+ * ARITHMETIC, on separate real and imaginary parts, fp contraction off, no atomics:
+ *   product   a b = (ar br - ai bi, ar bi + ai br): four rounded products, then the two sums
+ *   quotient  a / b: den = br br + bi bi;  ((ar br + ai bi) / den, (ai br - ar bi) / den)
+ *   S_c[i, k] starts at (1, +0) on the diagonal and (+0, +0) off it and adds the products D[i, a] G[a, k] over ascending
+ *   a, each component on its own; the right-hand side starts at (+0, +0) and adds D[i, a] x0[C_a] likewise.
+ *   Elimination by rows with partial pivoting on LAPACK's complex measure cabs1(z) = |Re z| + |Im z| (izamax): the
+ *   largest candidate of rows k .. r - 1 of column k, ties to the lowest row, a NaN above every number; the rows are
+ *   swapped with their right-hand side entry; l = S[i, k] / pivot (quotient), S[i, j] -= l S[k, j] (product, then the
+ *   two differences) for j > k and the right-hand side.  Back substitution from the last row: y_k = rhs_k / S[k, k]
+ *   (quotient), rhs_i -= S[i, k] y_k for i < k.
+ *   x_c[i] = x0[i] minus the products Z[i, R_j] y_j over ascending j, each component on its own.
+ * rpiv[c] = min_k cabs1(pivot_k) / max(1, max cabs1(S_c)); 1.0 for an empty case, NaN when a NaN is met.  A case is
+ * flagged on an exactly zero pivot column, on rpiv[c] <= sing_tol when sing_tol > 0, or on a NaN: its column of X is
+ * filled with (NaN, NaN); the other cases of the call are unaffected.  An empty case returns, bit for bit, what pack_N, the
+ * handle's solve and unpack_N give for b.  Only op N is built.
+ *
+ * Complex arrays (cz, b, X [n, ncases] row-major) are interleaved, typed double *, and aligned to 16 bytes on the device.
+ * cs3_cplx_updates_plan: host, pattern only, needs no GPU; indices are those of the COMPLEX matrix.  Cases and tiles are
+ *   exactly those cs3_updates_plan builds for the same lists with n = the complex order (CS3_UPD_TILE is read by this call
+ *   too).  Checks, in this order, each CS3_ERR_ARG: null pointers; a handle whose order is not 2 n of the plan;
+ *   ncases < 1; cp not monotone (from 0); null index arrays when there are triplets; an index outside [0, n); a case with
+ *   more than 16 distinct rows or columns (the message names the case); a plan or handle with batch > 1; a plan or handle
+ *   with a border (Schur).
+ * cs3_cplx_updates_info, cs3_debug_cplx_updates_tiles: as cs3_updates_info, cs3_debug_updates_tiles.
+ * cs3_cplx_updates_limits: the constants that shape the kernels; needs no GPU.
+ * cs3_cplx_updates_solve_dev: cz_dev[cp[ncases]] the values in the plan's triplet order; b_dev[n]; X_dev [n, ncases];
+ *   rpiv_dev[ncases] real, may be NULL.  Asynchronous on `stream`; s is read from the plan as it stands in stream order.
+ *   Checks: null arguments, a plan made for another handle or another complex plan, misaligned arrays: CS3_ERR_ARG; no
+ *   successful factorisation: CS3_ERR_STATE.  LU (rotated or not) and Cholesky handles both work; dA_c need not be
+ *   Hermitian.  Workspace: the handle's tile buffer (the one cs3_sens_* use), 2 n x 1024 doubles at most, 2 n doubles of
+ *   x0, a few hundred bytes per case on the plan, allocated by the first call; later calls neither allocate nor
+ *   synchronise.
+ * cs3_cplx_updates_solve: the same from host arrays (synchronises); the same bits.
+ * cs3_debug_cplx_updates_parts: the steps selected by the mask `parts` (1: x0 and the unit right-hand sides, 2: the
+ *   tiles' solves, 4: capacitance and apply), for tests.
+ * A plan survives refactorisations (the new s is picked up).  Plans and handle may be freed in either order, as for
+ * cs3_updates_plan.
+ * Out of scope: ops T and H; batched and Schur handles; several base right-hand sides per call; more than 16 distinct
+ * rows or columns; exploiting the sparsity of the unit columns in the sweeps; the CscMat sugar (CscMat.solve_modified
+ * refuses complex data, and a test pins that refusal). */
+typedef struct cs3_cplx_updates_s *cs3_cplx_updates;
+typedef struct cs3_cplx_updates_limits_t {
+    int64_t unit_rows, unit_threads;        /* k_cupd_units: complex rows per workgroup, its threads */
+    int64_t apply_stage, apply_rows;        /* k_cupd_apply: complex rows of Z in LDS at a time, complex rows per workgroup */
+    int64_t apply_threads_min;              /*   ... and the threads of its smallest workgroup */
+    int64_t max_rank, max_tile, max_tile_cases;
+} cs3_cplx_updates_limits_t;
+int cs3_cplx_updates_limits(cs3_cplx_updates_limits_t *out);
+int cs3_cplx_updates_plan(cs3_cplx p, cs3_handle h, int64_t ncases, const int32_t *cp, const int32_t *ci, const int32_t *cj,
+                          cs3_cplx_updates *out);
+int cs3_cplx_updates_free(cs3_cplx_updates u);
+int cs3_cplx_updates_info(cs3_cplx_updates u, int64_t *ncases, int64_t *nrows_unique, int64_t *max_rank, int64_t *ntiles);
+int64_t cs3_debug_cplx_updates_tiles(cs3_cplx_updates u, int32_t *first_case, int32_t *ncases, int32_t *nrows, int32_t *width);
+int cs3_cplx_updates_solve_dev(cs3_cplx p, cs3_handle h, cs3_cplx_updates u, const double *cz_dev, const double *b_dev,
+                               double sing_tol, double *X_dev, double *rpiv_dev, void *stream);
+int cs3_cplx_updates_solve(cs3_cplx p, cs3_handle h, cs3_cplx_updates u, const double *cz, const double *b,
+                           double sing_tol, double *X, double *rpiv);
+int cs3_debug_cplx_updates_parts(cs3_cplx p, cs3_handle h, cs3_cplx_updates u, int64_t parts, const double *cz_dev,
+                                 const double *b_dev, double sing_tol, double *X_dev, double *rpiv_dev, void *stream);
+
 /* ---- complex Schur handles: Kron reduction of an admittance matrix ----------
  * Ward and network equivalents: S = A22 - A21 A11^-1 A12 of the complex matrix on its boundary buses, from a real Schur
  * handle (cs3_analyze_schur) on the real form:
