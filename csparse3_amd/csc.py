@@ -316,6 +316,22 @@ class CscMat:
         sign, logabs = self.lu(tol).slogdet()
         return float(sign[0]), float(logabs[0])
 
+    def selected_inverse(self, kind="lu", tol=0.0, trans=False):
+        """The entries of A^-1 on the pattern of A, as a CscMat with A's pattern (with `trans`: of (A^-1)'), by selected
+        inversion on the LU (kind "lu") or Cholesky ("chol") factors (factorises as solve does)."""
+        self._complex_scope(selected_inverse=self._is_complex())
+        assert kind in ("lu", "chol")
+        F = self.lu(tol) if kind == "lu" else self.chol()
+        nz = int(self.indptr[self.n])
+        return CscMat(self.m, self.n, indptr=self.indptr.copy(), indices=self.indices[:nz].copy(), data=F.inverse_entries(trans=trans))
+
+    def inverse_diagonal(self, kind="lu", tol=0.0):
+        """diag(A^-1) [n] by selected inversion on the LU or Cholesky factors (factorises as solve does)."""
+        self._complex_scope(inverse_diagonal=self._is_complex())
+        assert kind in ("lu", "chol")
+        F = self.lu(tol) if kind == "lu" else self.chol()
+        return F.inverse_diagonal()
+
 
 def _sub_matrix_cols(Ap, Ai, Ax, cols):
     """Whole columns `cols` of a CSC matrix with their original row indices (csc_sub_matrix_cols, csc_numba.py:505-538):

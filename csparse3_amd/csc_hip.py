@@ -98,6 +98,19 @@ class SensLimits(C.Structure):
                                                "combine_lanes", "tblock")]
 
 
+class SelinvLimits(C.Structure):
+    """cs3_selinv_limits_t: the front orders at which the selected inversion changes kernel, and its tile sizes."""
+    _fields_ = [(name, C.c_int64) for name in ("lds_max_order", "wave_max_order", "gemm_tile", "diag_block")]
+
+
+class SelinvInfo(C.Structure):
+    """cs3_selinv_info_t: doubles of Z per matrix, fronts inside and beyond the LDS, launches of one selected inversion."""
+    _fields_ = [(name, C.c_int64) for name in ("zpool_doubles", "nfronts_small", "nfronts_big", "nlaunches")]
+
+    def __repr__(self):
+        return "SelinvInfo(%s)" % ", ".join("%s=%d" % (f, getattr(self, f)) for f, _ in self._fields_)
+
+
 class CplxUpdatesLimits(C.Structure):
     """cs3_cplx_updates_limits_t: the constants that shape the kernels of the complex low-rank-modified solves."""
     _fields_ = [(name, C.c_int64) for name in ("unit_rows", "unit_threads", "apply_stage", "apply_rows", "apply_threads_min",
@@ -225,6 +238,16 @@ def lib():
         L.cs3_sens_solve.argtypes = [vp, vp, _f64p, _f64p, _f64p]
         L.cs3_debug_sens_parts.argtypes = [vp, vp, I64, vp, vp, vp, vp]
         L.cs3_debug_live_device_buffers.argtypes = []
+        L.cs3_selinv_limits.argtypes = [C.POINTER(SelinvLimits)]
+        L.cs3_selinv_dev.argtypes = [vp, vp]
+        L.cs3_selinv_info.argtypes = [vp, C.POINTER(SelinvInfo)]
+        L.cs3_selinv_entries_dev.argtypes = [vp, I64, vp, vp]
+        L.cs3_selinv_diag_dev.argtypes = [vp, vp, vp]
+        L.cs3_selinv_entries.argtypes = [vp, I64, _f64p]
+        L.cs3_selinv_diag.argtypes = [vp, _f64p]
+        L.cs3_selinv_factors.argtypes = [vp, I64, _f64p, _f64p]
+        L.cs3_debug_selinv_plan.argtypes = [vp, _i32p, _i32p, C.POINTER(I64), C.POINTER(I64)]
+        L.cs3_debug_selinv_plan.restype = I64
         L.cs3_debug_live_device_buffers.restype = I64
         L.cs3_export_factor_dev.argtypes = [vp, vp, vp]
         L.cs3_import_factor_dev.argtypes = [vp, vp, vp]
@@ -480,6 +503,13 @@ def sens_limits():
     """The constants of the sparse right-hand-side path (cs3_sens_limits); needs no GPU."""
     out = SensLimits()
     _check(lib().cs3_sens_limits(C.byref(out)))
+    return out
+
+
+def selinv_limits():
+    """The constants of the selected inversion (cs3_selinv_limits); needs no GPU."""
+    out = SelinvLimits()
+    _check(lib().cs3_selinv_limits(C.byref(out)))
     return out
 
 
@@ -978,6 +1008,53 @@ class Factorization:
         a = np.empty(shape) if write is None else np.ascontiguousarray(write, dtype=np.float64).reshape(shape)
         _check(lib().cs3_debug_sens_tile(self._h, 0 if write is None else 1, _pf(a), a.size))
         return a
+
+    # -- selected inversion: A^-1 on the pattern of L + U from the held factors
+    def selinv(self, stream=0):
+        """Compute Z = A^-1 on the pattern of L + U into memory the handle owns, asynchronously on `stream` (one pass over
+        the assembly tree, parents first).  Any later factorisation invalidates it."""
+        _check(lib().cs3_selinv_dev(self._h, C.c_void_p(stream or 0)))
+
+    def selinv_info(self):
+        """-> SelinvInfo: sizes of the plan of the selected inversion; needs no GPU."""
+        out = SelinvInfo()
+        _check(lib().cs3_selinv_info(self._h, C.byref(out)))
+        return out
+
+    def selinv_plan(self):
+        """Diagnostics -> (front, launch, entry_map, diag_map): supernodes in the order they are computed, the launch of
+        each, the offset in Z of A^-1(Ai[p], j) per entry of A and of A^-1(i, i) per i; needs no GPU."""
+        ns = int(self.info.nsuper)
+        front, launch = np.empty(ns, dtype=np.int32), np.empty(ns, dtype=np.int32)
+        emap, dmap = np.empty(self.nnz, dtype=np.int64), np.empty(self.n, dtype=np.int64)
+        got = lib().cs3_debug_selinv_plan(self._h, _pi(front), _pi(launch), emap.ctypes.data_as(C.POINTER(I64)),
+                                          dmap.ctypes.data_as(C.POINTER(I64)))
+        if got < 0:
+            _check(CS3_ERR_ARG)
+        assert got == ns
+        return front, launch, emap, dmap
+
+    def inverse_entries(self, trans=False):
+        """A^-1 at the stored positions of A: [batch, nnz] (1-D for one matrix), entry p of column j = A^-1(Ai[p], j), with
+        `trans` A^-1(j, Ai[p]).  Runs selinv() first when the handle holds no inverse of the current factors."""
+        Zx = np.empty((self.batch, self.nnz))
+        _check(lib().cs3_selinv_entries(self._h, 1 if trans else 0, _pf(Zx)))
+        return Zx[0] if self.batch == 1 else Zx
+
+    def inverse_diagonal(self):
+        """diag(A^-1) in the caller's labels: [batch, n] (1-D for one matrix); computes like inverse_entries."""
+        d = np.empty((self.batch, self.n))
+        _check(lib().cs3_selinv_diag(self._h, _pf(d)))
+        return d[0] if self.batch == 1 else d
+
+    def inverse_on_factors(self, b=0):
+        """-> (Zl, Zu): Z = (Q' A Q)^-1 of matrix b at the positions of factors()' (Lp, Li) and (Up, Ui), in their labels
+        (Zu None for Cholesky); computes like inverse_entries."""
+        inf = self.info
+        Zl = np.empty(inf.nnz_l)
+        Zu = np.empty(inf.nnz_u) if self.kind == CS3_LU else None
+        _check(lib().cs3_selinv_factors(self._h, b, _pf(Zl), _pf(Zu)))
+        return Zl, Zu
 
     def debug_alloc_counters(self):
         """(device allocations incl. graph instantiations, host synchronisations) the handle's solves have made so far."""

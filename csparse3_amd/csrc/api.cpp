@@ -57,6 +57,14 @@ struct cs3_handle_s {
     int fused_same_x = 0;
     long long fail_col = -1;
     bool inverses_valid = false;      // inverted diagonal blocks (many-RHS GEMM sweeps) match the current factors
+    // selected inversion (cs3_selinv_*): the plan and the extraction maps, built from S on first use (ensure_selinv_plan);
+    // selinv_valid: mem.selinv.z holds Z of the current factors (every factor entry point clears it)
+    struct Selinv {
+        bool planned = false;
+        SelinvPlan plan;
+        std::vector<i64> entry, entry_t, diag;    // zpool offsets: A^-1(Ai[p], j), A^-1(j, Ai[p]) per entry of A; A^-1(i, i)
+    } selinv;
+    bool selinv_valid = false;
     std::vector<i32> Ap_host, Ai_host;
     // A matched handle (cs3_analyze_matched): S analyses B = P (Dr A Dc), Ap_host / Ai_host keep the pattern of A.
     struct Matching {
@@ -108,6 +116,9 @@ struct cs3_handle_s {
         struct { DevBuf<double> dr, dc; DevBuf<int> rq, erow, ecol; } match;
         // ensure_device on a Schur handle (schur.hip): the held Schur complements S [batch][ns, ns]
         DevBuf<double> schur;
+        // ensure_selinv (selinv.hip): zpool [batch][zpool_doubles], X and Y of the big fronts [batch][work_doubles], the
+        // fronts in top-down order, the extraction maps (those on the CSC factors: cs3_selinv_factors), the host forms' results
+        struct { DevBuf<double> z, work, out; DevBuf<SelFront> fronts; DevBuf<i64> entry, entry_t, diag, lmap, umap; } selinv;
     } mem;
     // diagnostics (cs3_debug_alloc_counters): device allocations / graph instantiations and host synchronisations made by the
     // solves and the paths on top of them
@@ -240,6 +251,7 @@ void release_device(cs3_handle h)
     h->fj.destroy();
     h->mem = cs3_handle_s::Memory();
     h->kry_work = KryWork();
+    h->selinv_valid = false;
     h->D = DeviceFactor();                  // (no pointer of it outlives its block; nrhs_cap = 0)
     h->on_device = false;
 }
@@ -543,6 +555,7 @@ int run_factor(cs3_handle h, const double *ax_dev, double tol, hipStream_t st)
     h->factored = true;
     h->factor_ran = true;
     h->inverses_valid = false;
+    h->selinv_valid = false;
     return CS3_OK;
 }
 
@@ -676,6 +689,7 @@ int run_factor_solve(cs3_handle h, const double *ax_dev, const double *b_dev, do
     h->factored = true;
     h->factor_ran = true;
     h->inverses_valid = nrhs >= 16;                                // a many-RHS fused call leaves them current
+    h->selinv_valid = false;
     return CS3_OK;
 }
 
@@ -1180,6 +1194,7 @@ int cs3_import_factor_dev(cs3_handle h, const double *src_dev, void *stream)
                                  (size_t) D.batch, hipMemcpyDeviceToDevice, (hipStream_t) stream));
     h->factored = true;
     h->inverses_valid = false;
+    h->selinv_valid = false;
     h->fail_col = -1;
     return CS3_OK;
 }
@@ -2350,6 +2365,194 @@ int cs3_updates_solve(cs3_handle h, cs3_updates u, const double *cx, const doubl
 }
 
 // ---- sparse right-hand sides: Y = C op(A)^-1 B on the held factors (sens.hip) ------------------------------------------
+/* ---- selected inversion: A^-1 on the pattern of L + U (selinv.hip, selinv.cpp) ---- */
+
+// What every cs3_selinv_* call refuses, and why (no device needed)
+static int selinv_refuse(cs3_handle h, const char *who)
+{
+    if (int rc = refuse_schur(h, who)) return rc;
+    if (h->match.on) {
+        set_error(std::string(who) + ": not available for a matched handle (the row permutation makes the pattern of the factors unsymmetric)");
+        return CS3_ERR_ARG;
+    }
+    if (h->S.il_len > 0) {
+        set_error(std::string(who) + ": not available for a matrix-interleaved batch (128 or more matrices)");
+        return CS3_ERR_ARG;
+    }
+    return CS3_OK;
+}
+
+// The plan and the maps of the entries of A and of the diagonal, from the analysis alone
+static int ensure_selinv_plan(cs3_handle h)
+{
+    auto &Q = h->selinv;
+    if (Q.planned) return CS3_OK;
+    const Symbolic &S = h->S;
+    try {
+        build_selinv_plan(S, Q.plan);
+        Q.entry.resize((size_t) S.nnzA); Q.entry_t.resize((size_t) S.nnzA); Q.diag.resize((size_t) S.n);
+        for (i64 j = 0; j < S.n; ++j) {
+            Q.diag[j] = selinv_position(S, Q.plan, S.pinv[j], S.pinv[j]);
+            for (i64 p = h->Ap_host[j]; p < h->Ap_host[j + 1]; ++p) {
+                const i64 k = S.pinv[h->Ai_host[p]], l = S.pinv[j];
+                Q.entry[p] = selinv_position(S, Q.plan, k, l);
+                Q.entry_t[p] = selinv_position(S, Q.plan, l, k);
+                if (Q.entry[p] < 0 || Q.entry_t[p] < 0) { set_error("cs3_selinv: an entry of A lies outside the symbolic structure"); return CS3_ERR_STATE; }
+            }
+        }
+    } catch (const std::exception &e) { set_error(e.what()); return CS3_ERR_ALLOC; }
+    Q.planned = true;
+    return CS3_OK;
+}
+
+static int ensure_selinv(cs3_handle h)
+{
+    int rc = ensure_selinv_plan(h);
+    if (rc) return rc;
+    auto &M = h->mem.selinv;
+    if (M.fronts.get()) return CS3_OK;
+    const auto &Q = h->selinv;
+    CS3_HIP(prepare_selinv_kernels());
+    CS3_HIP(M.z.alloc((size_t) (h->batch * Q.plan.zpool_doubles)));
+    CS3_HIP(M.work.alloc((size_t) (h->batch * Q.plan.work_doubles)));
+    CS3_HIP(M.entry.upload(Q.entry));
+    CS3_HIP(M.entry_t.upload(Q.entry_t));
+    CS3_HIP(M.diag.upload(Q.diag));
+    CS3_HIP(M.fronts.upload(Q.plan.fronts));
+    return CS3_OK;
+}
+
+// checks 1 to 3 of the header, in its order
+static int selinv_check(cs3_handle h, const char *who, bool null_output)
+{
+    int rc = guard(h); if (rc) return rc;
+    if (null_output) { set_error(std::string(who) + ": null output"); return CS3_ERR_ARG; }
+    if ((rc = selinv_refuse(h, who))) return rc;
+    if (!h->factored) { set_error(std::string(who) + ": called before a successful factorisation"); return CS3_ERR_STATE; }
+    return CS3_OK;
+}
+
+int cs3_selinv_limits(cs3_selinv_limits_t *out)
+{
+    if (!out) { set_error("cs3_selinv_limits: null output"); return CS3_ERR_ARG; }
+    out->lds_max_order = SELINV_LDS_R; out->wave_max_order = SELINV_WAVE_R;
+    out->gemm_tile = SELINV_TILE; out->diag_block = SELINV_DIAG;
+    return CS3_OK;
+}
+
+int cs3_selinv_info(cs3_handle h, cs3_selinv_info_t *out)
+{
+    int rc = guard(h); if (rc) return rc;
+    if (!out) { set_error("cs3_selinv_info: null output"); return CS3_ERR_ARG; }
+    if ((rc = selinv_refuse(h, "cs3_selinv_info"))) return rc;
+    if ((rc = ensure_selinv_plan(h))) return rc;
+    const SelinvPlan &P = h->selinv.plan;
+    out->zpool_doubles = P.zpool_doubles; out->nfronts_small = P.nsmall; out->nfronts_big = P.nbig; out->nlaunches = P.nlaunches;
+    return CS3_OK;
+}
+
+int64_t cs3_debug_selinv_plan(cs3_handle h, int32_t *front, int32_t *launch, int64_t *entry_map, int64_t *diag_map)
+{
+    if (guard(h) || selinv_refuse(h, "cs3_debug_selinv_plan") || ensure_selinv_plan(h)) return -1;
+    const auto &Q = h->selinv;
+    if (front) std::copy(Q.plan.front_sn.begin(), Q.plan.front_sn.end(), front);
+    if (launch) std::copy(Q.plan.front_launch.begin(), Q.plan.front_launch.end(), launch);
+    if (entry_map) std::copy(Q.entry.begin(), Q.entry.end(), entry_map);
+    if (diag_map) std::copy(Q.diag.begin(), Q.diag.end(), diag_map);
+    return (int64_t) Q.plan.front_sn.size();
+}
+
+int cs3_selinv_dev(cs3_handle h, void *stream)
+{
+    int rc = selinv_check(h, "cs3_selinv_dev", false); if (rc) return rc;
+    if ((rc = ensure_selinv(h))) return rc;
+    const DeviceFactor &D = h->D;
+    const SelinvPlan &P = h->selinv.plan;
+    const SelinvView V{D.pool_pm, D.pm_stride, h->mem.selinv.z.get(), h->mem.selinv.work.get(), P.zpool_doubles, P.work_doubles,
+                       h->mem.selinv.fronts.get(), D.rel_idx, h->batch};
+    for (const SelinvGroup &g : P.groups) CS3_HIP(launch_selinv_group(D.kind, V, g, (hipStream_t) stream));
+    h->selinv_valid = true;
+    return CS3_OK;
+}
+
+// out_dev [batch][count] through `map`, from the Z that cs3_selinv_dev left (check 4 of the header)
+static int selinv_get_dev(cs3_handle h, const char *who, const DevBuf<i64> &map, int64_t count, double *out_dev, hipStream_t st)
+{
+    if (!h->selinv_valid) { set_error(std::string(who) + ": no selected inverse of the current factors (call cs3_selinv_dev after the factorisation)"); return CS3_ERR_STATE; }
+    CS3_HIP(launch_selinv_gather(h->mem.selinv.z.get(), h->selinv.plan.zpool_doubles, (const long long *) map.get(), out_dev, count, h->batch, st));
+    return CS3_OK;
+}
+
+int cs3_selinv_entries_dev(cs3_handle h, int64_t trans, double *Zx_dev, void *stream)
+{
+    int rc = selinv_check(h, "cs3_selinv_entries_dev", !Zx_dev && h && h->S.nnzA > 0); if (rc) return rc;
+    return selinv_get_dev(h, "cs3_selinv_entries_dev", trans ? h->mem.selinv.entry_t : h->mem.selinv.entry, h->S.nnzA, Zx_dev, (hipStream_t) stream);
+}
+
+int cs3_selinv_diag_dev(cs3_handle h, double *d_dev, void *stream)
+{
+    int rc = selinv_check(h, "cs3_selinv_diag_dev", !d_dev && h && h->S.n > 0); if (rc) return rc;
+    return selinv_get_dev(h, "cs3_selinv_diag_dev", h->mem.selinv.diag, h->S.n, d_dev, (hipStream_t) stream);
+}
+
+// The host forms: Z is computed when the handle does not hold that of the current factors, then read through `map`
+static int selinv_get_host(cs3_handle h, const DevBuf<i64> &map, int64_t count, long long nmat, const double *z, double *out)
+{
+    auto &M = h->mem.selinv;
+    CS3_HIP(M.out.reserve((size_t) (nmat * count)));
+    CS3_HIP(launch_selinv_gather(z, h->selinv.plan.zpool_doubles, (const long long *) map.get(), M.out.get(), count, nmat, nullptr));
+    CS3_HIP(hipMemcpy(out, M.out.get(), (size_t) (nmat * count) * sizeof(double), hipMemcpyDeviceToHost));
+    return CS3_OK;
+}
+
+int cs3_selinv_entries(cs3_handle h, int64_t trans, double *Zx)
+{
+    int rc = selinv_check(h, "cs3_selinv_entries", !Zx && h && h->S.nnzA > 0); if (rc) return rc;
+    if (!h->selinv_valid && (rc = cs3_selinv_dev(h, nullptr))) return rc;
+    auto &M = h->mem.selinv;
+    return selinv_get_host(h, trans ? M.entry_t : M.entry, h->S.nnzA, h->batch, M.z.get(), Zx);
+}
+
+int cs3_selinv_diag(cs3_handle h, double *d)
+{
+    int rc = selinv_check(h, "cs3_selinv_diag", !d && h && h->S.n > 0); if (rc) return rc;
+    if (!h->selinv_valid && (rc = cs3_selinv_dev(h, nullptr))) return rc;
+    auto &M = h->mem.selinv;
+    return selinv_get_host(h, M.diag, h->S.n, h->batch, M.z.get(), d);
+}
+
+int cs3_selinv_factors(cs3_handle h, int64_t b, double *Zl, double *Zu)
+{
+    int rc = guard(h); if (rc) return rc;
+    if (!Zl && !Zu) { set_error("cs3_selinv_factors: null output"); return CS3_ERR_ARG; }
+    if (b < 0 || b >= h->batch) { set_error("cs3_selinv_factors: batch index out of range"); return CS3_ERR_ARG; }
+    if (h->S.kind == CS3_CHOLESKY && Zu) { set_error("cs3_selinv_factors: Cholesky has no U"); return CS3_ERR_ARG; }
+    if ((rc = selinv_check(h, "cs3_selinv_factors", false))) return rc;
+    if (!h->selinv_valid && (rc = cs3_selinv_dev(h, nullptr))) return rc;
+    const Symbolic &S = h->S;
+    auto &M = h->mem.selinv;
+    if (!M.lmap.get()) {                                       // Z at the positions of the CSC factors, in their (pivot-order) labels
+        try { build_csc_factors(h->S); }
+        catch (const std::exception &e) { set_error(e.what()); return CS3_ERR_ALLOC; }
+        std::vector<i64> lmap(S.Li.size()), umap(S.Ui.size());
+        for (i64 j = 0; j < S.n; ++j) {
+            for (i64 p = S.Lp[j]; p < S.Lp[j + 1]; ++p) lmap[p] = selinv_position(S, h->selinv.plan, S.Li[p], j);
+            if (S.kind == CS3_LU)
+                for (i64 p = S.Up[j]; p < S.Up[j + 1]; ++p) umap[p] = selinv_position(S, h->selinv.plan, S.Ui[p], j);
+        }
+        if (std::count(lmap.begin(), lmap.end(), -1) || std::count(umap.begin(), umap.end(), -1)) {
+            set_error("cs3_selinv_factors: an entry of the factors lies outside the symbolic structure");
+            return CS3_ERR_STATE;
+        }
+        CS3_HIP(M.umap.upload(umap));
+        CS3_HIP(M.lmap.upload(lmap));
+    }
+    const double *z = M.z.get() + b * h->selinv.plan.zpool_doubles;
+    if (Zl && (rc = selinv_get_host(h, M.lmap, (int64_t) S.Li.size(), 1, z, Zl))) return rc;
+    if (Zu && (rc = selinv_get_host(h, M.umap, (int64_t) S.Ui.size(), 1, z, Zu))) return rc;
+    return CS3_OK;
+}
+
 int cs3_sens_limits(cs3_sens_limits_t *out)
 {
     if (!out) { set_error("cs3_sens_limits: null output"); return CS3_ERR_ARG; }

@@ -374,6 +374,56 @@ hipError_t launch_sens_scatter(double *T, long long n, int w, const SensOperand 
 hipError_t launch_sens_combine(const double *T, int w, int t, const SensOperand &op, long long ng, long long c0, long long ldy,
                                bool transposed, double *Y, hipStream_t st);
 
+// selinv.hip / selinv.cpp: selected inversion, A^-1 on the pattern of L + U from the held factors (cs3_selinv_*).
+// Every front gets a dense r x r column-major block Zfront of a second pool (zpool) holding Z = (Q' A Q)^-1 on its
+// structure; fronts run parents first, a front gathers its update block from its parent's Zfront.
+constexpr int SELINV_WAVE_R = 32;              // fronts up to this order: one wave each, four per workgroup
+constexpr int SELINV_LDS_R = 136;              // ... up to this order: one workgroup each, the r x r image in LDS
+constexpr int SELINV_TILE = 16;                // edge of an MFMA output tile (one wave computes one)
+constexpr int SELINV_DIAG = 64;                // big fronts: pivots per chunk of the triangular solves
+constexpr int SELINV_SLICE = 16;               // big fronts: vectors (rows of X, columns of Y and of the identity) per workgroup
+enum SelinvClass : int { SELINV_WAVE = 0, SELINV_LDS = 1, SELINV_BIG = 2 };
+struct SelFront {                 // one front as the kernels read it, in top-down schedule order
+    long long lpan, upan;         // pool offsets of the panels
+    long long z, zpar;            // zpool offsets of its Zfront and of its parent's
+    long long wk;                 // big fronts: offset of X (c x w, ld c) in the work buffer, Y (w x c, ld w) behind it
+    long long rel;                // first entry of its row map in rel_idx
+    int r, w, rpar;               // order, pivots, the parent's order
+    int u_sk, u_sj;
+    int pad;
+};
+struct SelinvGroup {              // the fronts of one level and class: one launch (big fronts: three)
+    int cls, first, count, max_r;
+    int launch;                   // index of its first launch
+    unsigned grid_prep, grid_cross, grid_pivot;      // big fronts: workgroups per front of the three launches
+};
+struct SelinvPlan {
+    std::vector<SelFront> fronts;
+    std::vector<i32> front_sn;                // supernode of every entry of `fronts`
+    std::vector<i32> front_launch;            // index of the (first) launch that computes it
+    std::vector<SelinvGroup> groups;
+    std::vector<i64> z_off;                   // per supernode: zpool offset of its Zfront
+    i64 zpool_doubles = 0, work_doubles = 0;
+    i64 nsmall = 0, nbig = 0, nlaunches = 0;
+};
+void build_selinv_plan(const Symbolic &S, SelinvPlan &P);
+// zpool offset of Z(k, l), k and l in pivot order; -1 when (k, l) is outside the pattern of L + U
+i64 selinv_position(const Symbolic &S, const SelinvPlan &P, i64 k, i64 l);
+hipError_t prepare_selinv_kernels();
+struct SelinvView {               // device arrays of one call
+    const double *pool;           // DeviceFactor::pool_pm
+    long long pool_stride;
+    double *zpool, *work;
+    long long z_stride, work_stride;
+    const SelFront *fronts;
+    const int *rel_idx;
+    long long batch;
+};
+hipError_t launch_selinv_group(int kind, const SelinvView &V, const SelinvGroup &g, hipStream_t st);
+// out [batch][count] = zpool[b][map[e]]
+hipError_t launch_selinv_gather(const double *zpool, long long z_stride, const long long *map, double *out, long long count,
+                                long long batch, hipStream_t st);
+
 // cplxsens.hip: the same around a handle on the real-equivalent form of a complex matrix (cs3_cplx_sens_*), and the
 // complex Schur complement read out of the real one (cs3_cplx_schur_get*).  The tiling constants are those above; a
 // complex row is a pair of real rows, so a scatter workgroup owns half as many.

@@ -522,6 +522,54 @@ int cs3_sens_info(cs3_sens s, cs3_sens_info_t *out);
 int cs3_sens_solve_dev(cs3_handle h, cs3_sens s, const double *Bx_dev, const double *Ctx_dev, double *Y_dev, void *stream);
 int cs3_sens_solve(cs3_handle h, cs3_sens s, const double *Bx, const double *Ctx, double *Y);
 
+/* ---- selected inversion: A^-1 on the pattern of L + U from the held factors -----
+ * Many entries of A^-1 at about the cost of a factorisation: the diagonal (fault levels at every bus from diag(Z-bus),
+ * variances of a state estimate), the entries on the pattern of A (Thevenin impedances of all branches,
+ * Z_ii + Z_jj - Z_ij - Z_ji), the entries on the pattern of the factors.  With B = Q' A Q = L U in pivot order and
+ * Z = B^-1, a front with pivots P and update rows C, X = L21 L11^-1 and Y = U11^-1 U12 satisfies (Takahashi)
+ *     Z_CP = -Z_CC X,   Z_PC = -Y Z_CC,   Z_PP = U11^-1 L11^-1 - Y Z_CP,
+ * and Z_CC lies inside the parent's front: one pass over the assembly tree, parents first, gives Z on the whole
+ * pattern of L + U (explicit zeros of amalgamated fronts included).  Cholesky: U = L'.  The handle keeps one dense
+ * r x r block per front (cs3_selinv_info_t.zpool_doubles per matrix); a batch below 128 runs in the same launches.
+ *
+ * cs3_selinv_limits: the orders up to which a front runs as one wave and inside the LDS of one workgroup, the edge of
+ *   the matrix-core tiles, the pivots per chunk of the big fronts' triangular solves.  Needs no device.
+ * cs3_selinv_dev: computes Z of the current factors into memory the handle owns, asynchronously on `stream`.  The first
+ *   call builds the plan and allocates; later calls issue launches only (no host read, no synchronisation).
+ * cs3_selinv_info: sizes of the plan (built on first use from the analysis alone: needs no device).
+ * cs3_selinv_entries_dev: Zx_dev [batch][nnz(A)], entry p of column j: A^-1(Ai[p], j); trans != 0: A^-1(j, Ai[p]).
+ * cs3_selinv_diag_dev: d_dev [batch][n], d[i] = A^-1(i, i) in the caller's labels.
+ * cs3_selinv_entries, cs3_selinv_diag: the same into host memory (synchronise); they compute Z first when the handle does
+ *   not hold that of the current factors.
+ * cs3_selinv_factors: matrix b of the batch on the patterns cs3_get_factors returns, in its (pivot-order) labels:
+ *   Zl[p] = Z(Li[p], j) for entry p of column j of L (its unit diagonal maps to the diagonal of Z), Zu[p] = Z(Ui[p], j).
+ *   Either may be NULL; Zu must be NULL for Cholesky.  Host form, computes Z when needed.
+ * cs3_debug_selinv_plan: returns the number of fronts and, for arrays that are not null, the supernodes in the order they
+ *   are computed (parents first), the index of the launch that computes each, the offset in the handle's block of Z of
+ *   A^-1(Ai[p], j) for every entry of A and of A^-1(i, i) for every i.  Needs no device.  -1: error.
+ *
+ * Checks, in this order, none of which needs a device: a null handle or null output: CS3_ERR_ARG; a Schur handle, a
+ * matched handle (cs3_analyze_matched: the row permutation makes the pattern unsymmetric) or a matrix-interleaved batch
+ * (128 or more matrices): CS3_ERR_ARG with a message that names the reason; no successful factorisation: CS3_ERR_STATE;
+ * a *_dev getter before cs3_selinv_dev, or after any later factorisation (cs3_factor*, the fused steps and
+ * cs3_import_factor_dev invalidate Z): CS3_ERR_STATE.  Solves, estimates and refinements leave Z alone.
+ * With static pivot perturbation the result is the inverse of what the factors represent, not of A.
+ * The same factors give the same bits on every run, and a matrix of a batch the bits it gets alone.
+ *
+ * Out of scope: complex handles; matched, Schur and matrix-interleaved handles; entries outside the pattern of L + U; a
+ * variant for transposed handles (trans on the getter covers it); sharding. */
+typedef struct cs3_selinv_limits_t { int64_t lds_max_order, wave_max_order, gemm_tile, diag_block; } cs3_selinv_limits_t;
+typedef struct cs3_selinv_info_t { int64_t zpool_doubles, nfronts_small, nfronts_big, nlaunches; } cs3_selinv_info_t;
+int cs3_selinv_limits(cs3_selinv_limits_t *out);
+int cs3_selinv_dev(cs3_handle h, void *stream);
+int cs3_selinv_info(cs3_handle h, cs3_selinv_info_t *out);
+int cs3_selinv_entries_dev(cs3_handle h, int64_t trans, double *Zx_dev, void *stream);
+int cs3_selinv_diag_dev(cs3_handle h, double *d_dev, void *stream);
+int cs3_selinv_entries(cs3_handle h, int64_t trans, double *Zx);
+int cs3_selinv_diag(cs3_handle h, double *d);
+int cs3_selinv_factors(cs3_handle h, int64_t b, double *Zl, double *Zu);
+int64_t cs3_debug_selinv_plan(cs3_handle h, int32_t *front, int32_t *launch, int64_t *entry_map, int64_t *diag_map);
+
 /* ---- Schur complements: factor the interior, return the dense border -----
  * A partial factorisation, as cuDSS, PARDISO, MUMPS and SuperLU_DIST offer it: the caller names ns variables that are NOT
  * eliminated (boundary buses of a network equivalent, the constraint rows of a saddle-point system [[H, G'], [G, 0]], the
