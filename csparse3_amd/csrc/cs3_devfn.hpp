@@ -100,6 +100,15 @@ __device__ __forceinline__ void flag_column(int *status, int col)
     atomicMin(status, col);
 }
 
+// A lane's first rejected column, kept beside its stores instead of a flag_column between them (k_big_step): the columns
+// are offered upward and the first hit wins, so bad_col is the lane's smallest rejected column.  status is an atomicMin
+// over columns: one flag_column(bad_col) per lane leaves the same word as one call per rejected column.
+__device__ __forceinline__ void first_rejected(bool rej, int col, bool &bad, int &bad_col)
+{
+    bad_col = (rej & !bad) ? col : bad_col;
+    bad = bad | rej;
+}
+
 // ---- multipliers handed from wave to wave through LDS (eliminate_pair in k_big_step, the shared fronts of forest.hip) ----
 // The producer stores a vector of multipliers, then the number of pivots handed over so far; the consumer polls that number.
 // LDS operations of one wave complete in order, so no fence sits on the producer's pivot chain (a release fence per pivot

@@ -1407,7 +1407,9 @@ k_front_wg(const FrontDesc *__restrict__ fdesc, int first,
 // arguments remain around it), the address arithmetic until the loads are out (one uniform base per panel, 32-bit offsets), the
 // one round trip of those loads, and the panel store.  The diagonal tile carries the copy-home on top: its parked
 // entries are requested with the other loads and stored behind them.  At kb == 0 there is no previous panel, and the
-// plain trailing tiles leave at once.  The numbers are in DESIGN.md, section 7.
+// plain trailing tiles leave at once.  The pivot checks of the diagonal and block-column tiles stand beside the stores,
+// not between them: a lane keeps a plain running minimum (first_rejected in cs3_devfn.hpp; no __any, the compiler itself
+// sinks the selects behind the one branch) and calls flag_column once, behind its last store.  Numbers: DESIGN.md, section 7.
 template <int KIND, class Rule>
 __global__ void __launch_bounds__(256)
 k_big_step(const FrontDesc *__restrict__ fdesc, int first, int kb, double *__restrict__ pool_all,
@@ -1595,47 +1597,46 @@ k_big_step(const FrontDesc *__restrict__ fdesc, int first, int kb, double *__res
                          Rule::on ? bw : (1 << 30), rule, hits);
     CS3_BSTAMP(4);
     CS3_BSTAMP_ROW(6);
+    const int cu = HC * (t.wu >> 1);                // cbase, as a scalar
+    bool bad = false;                               // (the pivot checks: beside the stores, reported once; see the header)
+    int bad_col = 0;
     if (diag_tile) {                                // park the factored block, check its pivots
         double *db = dbuf + (long long) (kb / BIG_NB) * (BIG_NB * BIG_NB);
         if (lane == 0) count_perturbed(rule, bz, hits);         // (the parked copy is the stored one: each wave its own 16 pivots)
         if (lane < bw) {
+            unsigned o_db = 8u * (unsigned) lane;   // (uniform base, one 32-bit offset, the column in the immediate)
+            asm("" : "+v"(o_db));
+            double *dl = reinterpret_cast<double *>(reinterpret_cast<char *>(db + cu * BIG_NB) + o_db);
+#pragma unroll
+            for (int jj = 0; jj < HC; ++jj)
+                if (cu + jj < bw) dl[jj * BIG_NB] = e[jj];           // = db[lane + (cu + jj) * BIG_NB]
+            const int lj = lane - cu;               // my row, counted from my first column
 #pragma unroll
             for (int jj = 0; jj < HC; ++jj) {
-                const int j = cbase + jj;
-                if (j < bw) {
-                    const double v = e[jj];
-                    if (KIND == CS3_LU) {
-                        if (lane > j) { if (!(fabs(v) <= inv_tol)) flag_column(status, d.c0 + kb + j); }
-                        else if (lane == j) { if (!(fabs(v) > 0.0) || !(fabs(v) < 1.0e300)) flag_column(status, d.c0 + kb + j); }
-                    } else if (lane == j) {
-                        if (!(v > 0.0)) flag_column(status, d.c0 + kb + j);
-                    }
-                    db[lane + j * BIG_NB] = v;
-                }
+                const double v = e[jj], av = fabs(v);
+                const bool rej = (KIND == CS3_LU) ? ((lj > jj) & !(av <= inv_tol)) | ((lj == jj) & (!(av > 0.0) | !(av < 1.0e300))) : (lj == jj) & !(v > 0.0);
+                first_rejected(rej & (cu + jj < bw), cu + jj, bad, bad_col);
             }
         }
+        if (bad) flag_column(status, d.c0 + kb + bad_col);
         CS3_BSTAMP(5);
         return;
     }
     if (stacked) {                                  // (uniform base per column of the block, the offset from before)
-        const int cu = HC * (t.wu >> 1);              // cbase, as a scalar
         if (!row_tile) {
             if (tr < nrow) {
 #pragma unroll
-                for (int cc = 0; cc < HC; ++cc) {
-                    const int c = cu + cc;
-                    if (c < bw) {
-                        if (KIND == CS3_LU && !(fabs(e[cc]) <= inv_tol)) flag_column(status, d.c0 + kb + c);
-                        store_at(t.Fb + 8ll * row0 + (kb + cu) * t.ld8, o_tr + cc * t.ldu, e[cc]);
-                    }
-                }
+                for (int cc = 0; cc < HC; ++cc)
+                    if (cu + cc < bw) store_at(t.Fb + 8ll * row0 + (kb + cu) * t.ld8, o_tr + cc * t.ldu, e[cc]);
+#pragma unroll
+                for (int cc = 0; KIND == CS3_LU && cc < HC; ++cc)
+                    first_rejected(!(fabs(e[cc]) <= inv_tol) & (cu + cc < bw), cu + cc, bad, bad_col);
             }
+            if (bad) flag_column(status, d.c0 + kb + bad_col);
         } else if (tr < ncol) {
 #pragma unroll
-            for (int cc = 0; cc < HC; ++cc) {
-                const int c = cu + cc;
-                if (c < bw) store_at(t.Fb + 8ll * (kb + cu) + col0 * t.ld8, o_tr + 8 * cc, e[cc]);
-            }
+            for (int cc = 0; cc < HC; ++cc)
+                if (cu + cc < bw) store_at(t.Fb + 8ll * (kb + cu) + col0 * t.ld8, o_tr + 8 * cc, e[cc]);
         }
     }
     CS3_BSTAMP(5);
@@ -1643,7 +1644,6 @@ k_big_step(const FrontDesc *__restrict__ fdesc, int first, int kb, double *__res
 #undef CS3_BSTAMP
 #undef CS3_BSTAMP_ROW
 }
-
 
 // ------------------------------------------------------ supernodal solves --
 // X is [n, nrhs] row-major in pivot order; blockIdx.z = right-hand side,
