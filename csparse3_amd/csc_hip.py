@@ -117,6 +117,11 @@ class CplxUpdatesLimits(C.Structure):
                                                "max_rank", "max_tile", "max_tile_cases")]
 
 
+class CplxSelinvLimits(C.Structure):
+    """cs3_cplx_selinv_limits_t: threads per workgroup and the workgroup cap of the complex selected-inverse getters."""
+    _fields_ = [(name, C.c_int64) for name in ("block", "grid_cap")]
+
+
 class Cs3Error(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("cs3 error %d: %s" % (code, msg))
@@ -329,6 +334,14 @@ def lib():
         L.cs3_cplx_plan_schur_order.argtypes = [vp, I64, _i32p, _i32p, _i32p]
         L.cs3_cplx_schur_get_dev.argtypes = [vp, vp, vp, vp]
         L.cs3_cplx_schur_get.argtypes = [vp, vp, _f64p]
+        L.cs3_cplx_selinv_limits.argtypes = [C.POINTER(CplxSelinvLimits)]
+        L.cs3_cplx_selinv_entries_dev.argtypes = [vp, vp, I64, vp, vp]
+        L.cs3_cplx_selinv_diag_dev.argtypes = [vp, vp, vp, vp]
+        L.cs3_cplx_selinv_thevenin_dev.argtypes = [vp, vp, vp, vp]
+        L.cs3_cplx_selinv_entries.argtypes = [vp, vp, I64, _f64p]
+        L.cs3_cplx_selinv_diag.argtypes = [vp, vp, _f64p]
+        L.cs3_cplx_selinv_thevenin.argtypes = [vp, vp, _f64p]
+        L.cs3_debug_cplx_selinv_maps.argtypes = [vp, vp] + [C.POINTER(I64)] * 3
         _lib = L
     return _lib
 
@@ -1652,7 +1665,9 @@ class ComplexFactorization:
     the complex S = A22 - A21 A11^-1 A12 in the order of the list: schur(), schur_forward(), schur_backward(); order / q refer
     to the interior; solve() raises Cs3Error, as on every Schur handle.
     sens_plan / sens_solve: Y = C op(A)^-1 B with sparse B and C (entries of Z-bus), see ComplexSensPlan.
-    updates_plan / solve_updates: (A + dA_c) x = b for many sparse complex dA_c (outages, faults), see ComplexUpdatesPlan."""
+    updates_plan / solve_updates: (A + dA_c) x = b for many sparse complex dA_c (outages, faults), see ComplexUpdatesPlan.
+    selinv / inverse_entries / inverse_diagonal / thevenin: A^-1 on the pattern of A from the selected inverse of the real
+    form (diag(Z-bus), the Thevenin impedance of every branch)."""
 
     def __init__(self, n, Ap, Ai, kind=CS3_LU, order=ORDER_AMD, q=None, batch=1, rotate=True, schur=None):
         assert not (rotate and kind == CS3_CHOLESKY), "rotate scales rows, which breaks the symmetry Cholesky needs: pass rotate=False"
@@ -1833,6 +1848,66 @@ class ComplexFactorization:
         """Diagnostics: the steps of solve_updates_dev in the mask `parts` (1 x0 and units, 2 solves, 4 capacitance + apply)."""
         _check(lib().cs3_debug_cplx_updates_parts(self.plan._p, self.real._h, plan._u, parts, C.c_void_p(cz_ptr), C.c_void_p(b_ptr),
                                                   sing_tol, C.c_void_p(x_ptr), C.c_void_p(rpiv_ptr), C.c_void_p(stream)))
+
+    # -- selected inversion: Z = A^-1 on the pattern of A, diag(Z-bus), the Thevenin table of the branches
+    def selinv(self, stream=0):
+        """The selected inverse of the real form on the factors at hand (Factorization.selinv), asynchronously on `stream`;
+        the `_dev` getters below read it."""
+        self.real.selinv(stream)
+        return self
+
+    def selinv_maps(self):
+        """-> (entry int64 [nnz, 2], entry_t [nnz, 2], diag [n, 2]): where the getters read the real selected inverse, as
+        offsets in the handle's block of Z per matrix (diagnostic; from the analysis alone, needs no GPU)."""
+        entry, entry_t = (np.empty((self.nnz, 2), dtype=np.int64) for _ in range(2))
+        diag = np.empty((self.n, 2), dtype=np.int64)
+        p64 = C.POINTER(I64)
+        _check(lib().cs3_debug_cplx_selinv_maps(self.plan._p, self.real._h, entry.ctypes.data_as(p64), entry_t.ctypes.data_as(p64),
+                                                diag.ctypes.data_as(p64)))
+        return entry, entry_t, diag
+
+    def _zshape(self, count):
+        return (count,) if self.batch == 1 else (self.batch, count)
+
+    def inverse_entries(self, trans=False):
+        """-> complex128 [nnz] (or [batch, nnz]): A^-1(Ai[e], j) for every stored entry e of column j; with `trans`
+        A^-1(j, Ai[e]).  Runs selinv() first when the handle holds no inverse of the current factors."""
+        Zz = np.empty(self._zshape(self.nnz), dtype=np.complex128)
+        _check(lib().cs3_cplx_selinv_entries(self.plan._p, self.real._h, 1 if trans else 0, _pc(Zz)))
+        return Zz
+
+    def inverse_diagonal(self):
+        """-> complex128 [n] (or [batch, n]): A^-1(i, i), the driving-point impedances of an admittance matrix."""
+        d = np.empty(self._zshape(self.n), dtype=np.complex128)
+        _check(lib().cs3_cplx_selinv_diag(self.plan._p, self.real._h, _pc(d)))
+        return d
+
+    def thevenin(self):
+        """-> complex128 [nnz] (or [batch, nnz]): ((Z_ii + Z_jj) - Z_ij) - Z_ji of Z = A^-1 for every stored entry (i, j),
+        the Thevenin impedance between the ends of a branch."""
+        T = np.empty(self._zshape(self.nnz), dtype=np.complex128)
+        _check(lib().cs3_cplx_selinv_thevenin(self.plan._p, self.real._h, _pc(T)))
+        return T
+
+    def inverse_entries_dev(self, z_ptr, trans=False, stream=0):
+        """inverse_entries into device memory [batch][nnz] complex (16-byte aligned), one launch on `stream`, after
+        selinv().  After the first call nothing is allocated and nothing synchronises.  The same bits."""
+        _check(lib().cs3_cplx_selinv_entries_dev(self.plan._p, self.real._h, 1 if trans else 0, C.c_void_p(z_ptr), C.c_void_p(stream)))
+
+    def inverse_diagonal_dev(self, d_ptr, stream=0):
+        """inverse_diagonal into device memory [batch][n] complex, as inverse_entries_dev."""
+        _check(lib().cs3_cplx_selinv_diag_dev(self.plan._p, self.real._h, C.c_void_p(d_ptr), C.c_void_p(stream)))
+
+    def thevenin_dev(self, t_ptr, stream=0):
+        """thevenin into device memory [batch][nnz] complex, as inverse_entries_dev."""
+        _check(lib().cs3_cplx_selinv_thevenin_dev(self.plan._p, self.real._h, C.c_void_p(t_ptr), C.c_void_p(stream)))
+
+
+def cplx_selinv_limits():
+    """The constants of the complex selected-inverse getters (cs3_cplx_selinv_limits); needs no GPU."""
+    out = CplxSelinvLimits()
+    _check(lib().cs3_cplx_selinv_limits(C.byref(out)))
+    return out
 
 
 def cplx_updates_limits():

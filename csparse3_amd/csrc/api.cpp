@@ -63,6 +63,11 @@ struct cs3_handle_s {
         bool planned = false;
         SelinvPlan plan;
         std::vector<i64> entry, entry_t, diag;    // zpool offsets: A^-1(Ai[p], j), A^-1(j, Ai[p]) per entry of A; A^-1(i, i)
+        // a handle on the real form of a complex matrix (ensure_cselinv_plan): the same in pairs (real part, imaginary
+        // part) per entry and per row of the COMPLEX matrix, and (row, column) of every complex entry
+        bool cplanned = false;
+        std::vector<i64> centry, centry_t, cdiag;
+        std::vector<i32> cij;
     } selinv;
     bool selinv_valid = false;
     std::vector<i32> Ap_host, Ai_host;
@@ -119,6 +124,9 @@ struct cs3_handle_s {
         // ensure_selinv (selinv.hip): zpool [batch][zpool_doubles], X and Y of the big fronts [batch][work_doubles], the
         // fronts in top-down order, the extraction maps (those on the CSC factors: cs3_selinv_factors), the host forms' results
         struct { DevBuf<double> z, work, out; DevBuf<SelFront> fronts; DevBuf<i64> entry, entry_t, diag, lmap, umap; } selinv;
+        // ensure_cselinv (cplxselinv.hip, a handle on the real form of a complex matrix): the same maps in pairs per entry
+        // and per row of the COMPLEX matrix ([.][2], CselinvMaps), row and column of every complex entry
+        struct { DevBuf<i64> entry, entry_t, diag; DevBuf<i32> ij; } cselinv;
     } mem;
     // diagnostics (cs3_debug_alloc_counters): device allocations / graph instantiations and host synchronisations made by the
     // solves and the paths on top of them
@@ -3130,6 +3138,182 @@ int cs3_cplx_schur_get(cs3_cplx p, cs3_handle h, double *S)
     CS3_HIP(launch_cplx_schur_gather(h->D.schur, h->batch, (long long) p->schur_idx.size(), s.get(), nullptr));
     CS3_HIP(hipMemcpy(S, s.get(), count * sizeof(double), hipMemcpyDeviceToHost));
     return CS3_OK;
+}
+
+// ---- complex selected inversion: Z = A^-1 out of the real form's selected inverse (cplxselinv.hip) ---------------------
+int cs3_cplx_selinv_limits(cs3_cplx_selinv_limits_t *out)
+{
+    if (!out) { set_error("cs3_cplx_selinv_limits: null output"); return CS3_ERR_ARG; }
+    out->block = CSELINV_BLOCK; out->grid_cap = CSELINV_GRID_CAP;
+    return CS3_OK;
+}
+
+// checks 1 to 6 of the header, in its order; none needs a device
+static int cselinv_check(const char *who_, cs3_cplx p, cs3_handle h, const double *out, bool device, bool plan_only = false)
+{
+    const std::string who(who_);
+    if (!p) { set_error(who + ": null complex plan"); return CS3_ERR_ARG; }
+    int rc = guard(h); if (rc) return rc;
+    if (!out && !plan_only) { set_error(who + ": null output"); return CS3_ERR_ARG; }
+    if (h->S.n != 2 * p->n || h->S.nnzA != 4 * p->nnz || h->batch != p->batch) {
+        set_error(who + ": the handle is not one on the real form of the complex plan (its order is not 2 n, its entries are not 4 nnz, "
+                        "or the batches differ)");
+        return CS3_ERR_ARG;
+    }
+    if ((rc = selinv_refuse(h, who_))) return rc;
+    if (plan_only) return CS3_OK;                          // (cs3_debug_cplx_selinv_maps: the analysis alone)
+    if (device && (reinterpret_cast<uintptr_t>(out) & 15)) { set_error(who + ": complex arrays must be aligned to 16 bytes"); return CS3_ERR_ARG; }
+    if (!h->factored) { set_error(who + ": called before a successful factorisation"); return CS3_ERR_STATE; }
+    if (device && !h->selinv_valid) {
+        set_error(who + ": no selected inverse of the current factors (call cs3_selinv_dev after the factorisation)");
+        return CS3_ERR_STATE;
+    }
+    return CS3_OK;
+}
+
+// The maps of the complex layer, once per handle and from the analysis alone (no device): the real maps of
+// ensure_selinv_plan at the positions Rp[2j] + 2t, + 1 and Rp[2j + 1] + 2t of the real pattern, in pairs, and the one
+// position they do not hold, (2i + 1, 2i).  The handle's pattern is compared with the real form of the plan's while they are
+// built, so that the kernels read the handle's tables only.
+static int ensure_cselinv_plan(cs3_cplx p, cs3_handle h, const char *who_)
+{
+    auto &Q = h->selinv;
+    if (Q.cplanned) return CS3_OK;
+    const std::string who(who_);
+    int rc = ensure_selinv_plan(h);
+    if (rc) return rc;
+    const Symbolic &S = h->S;
+    const i64 n = p->n, nnz = p->nnz;
+    const i32 *Ap = p->Ap.data(), *Ai = p->Ai.data(), *Rp = h->Ap_host.data(), *Ri = h->Ai_host.data();
+    try {
+        Q.centry.assign((size_t) (2 * nnz), -1); Q.centry_t.assign((size_t) (2 * nnz), -1); Q.cdiag.assign((size_t) (2 * n), -1);
+        Q.cij.assign((size_t) (2 * nnz), 0);
+        for (i64 j = 0; j < n; ++j) {
+            const i64 r0 = 4LL * Ap[j], r1 = 2LL * Ap[j] + 2LL * Ap[j + 1];
+            bool same = Rp[2 * j] == r0 && Rp[2 * j + 1] == r1;
+            for (i64 e = Ap[j]; same && e < Ap[j + 1]; ++e) {
+                const i64 lo = r0 + 2 * (e - Ap[j]), hi = r1 + 2 * (e - Ap[j]);
+                const i32 i = Ai[e];
+                same = Ri[lo] == 2 * i && Ri[lo + 1] == 2 * i + 1 && Ri[hi] == 2 * i && Ri[hi + 1] == 2 * i + 1;
+                Q.centry[2 * e] = Q.entry[lo];     Q.centry[2 * e + 1] = Q.entry[lo + 1];       // ZR(2i, 2j), ZR(2i + 1, 2j)
+                Q.centry_t[2 * e] = Q.entry_t[lo]; Q.centry_t[2 * e + 1] = Q.entry_t[hi];       // ZR(2j, 2i), ZR(2j + 1, 2i)
+                Q.cij[2 * e] = i; Q.cij[2 * e + 1] = (i32) j;
+            }
+            if (!same) {
+                set_error(who + ": the handle's pattern is not the real form of the complex plan's (cs3_cplx_plan_pattern), column " +
+                          std::to_string(j));
+                return CS3_ERR_ARG;
+            }
+            Q.cdiag[2 * j] = Q.diag[2 * j];
+            Q.cdiag[2 * j + 1] = selinv_position(S, Q.plan, S.pinv[2 * j + 1], S.pinv[2 * j]);
+            if (Q.cdiag[2 * j] < 0 || Q.cdiag[2 * j + 1] < 0) {
+                set_error(who + ": the imaginary part of Z(" + std::to_string(j) + ", " + std::to_string(j) + ") lies outside the symbolic "
+                          "structure (complex row " + std::to_string(j) + " has no stored diagonal)");
+                return CS3_ERR_STATE;
+            }
+        }
+    } catch (const std::exception &e) { set_error(e.what()); return CS3_ERR_ALLOC; }
+    Q.cplanned = true;
+    return CS3_OK;
+}
+
+static int ensure_cselinv(cs3_cplx p, cs3_handle h, const char *who)
+{
+    auto &M = h->mem.cselinv;
+    if (M.ij.get()) return CS3_OK;
+    int rc = ensure_cselinv_plan(p, h, who);
+    if (rc) return rc;
+    const auto &Q = h->selinv;
+    CS3_HIP(M.entry.upload(Q.centry));
+    CS3_HIP(M.entry_t.upload(Q.centry_t));
+    CS3_HIP(M.diag.upload(Q.cdiag));
+    CS3_HIP(M.ij.upload(Q.cij));                           // (last: what marks the maps as uploaded)
+    return CS3_OK;
+}
+
+int cs3_debug_cplx_selinv_maps(cs3_cplx p, cs3_handle h, int64_t *entry, int64_t *entry_t, int64_t *diag)
+{
+    const char *who = "cs3_debug_cplx_selinv_maps";
+    int rc = cselinv_check(who, p, h, nullptr, false, true);
+    if (rc) return rc;
+    if ((rc = ensure_cselinv_plan(p, h, who))) return rc;
+    const auto &Q = h->selinv;
+    if (entry) std::copy(Q.centry.begin(), Q.centry.end(), entry);
+    if (entry_t) std::copy(Q.centry_t.begin(), Q.centry_t.end(), entry_t);
+    if (diag) std::copy(Q.cdiag.begin(), Q.cdiag.end(), diag);
+    return CS3_OK;
+}
+
+enum CselinvWhat : int { CSELINV_ENTRIES = 0, CSELINV_ENTRIES_T = 1, CSELINV_DIAG = 2, CSELINV_THEVENIN = 3 };
+
+static int cselinv_run(cs3_cplx p, cs3_handle h, const char *who, int what, double *out_dev, hipStream_t st)
+{
+    int rc = cs3_cplx_upload(p);                            // (the tables and s = (1, +0): a plan that never saw a values call)
+    if (rc) return rc;
+    if ((rc = ensure_cselinv(p, h, who))) return rc;
+    const auto &M = h->mem.cselinv;
+    const CselinvMaps maps{(const long long *) M.entry.get(), (const long long *) M.entry_t.get(), (const long long *) M.diag.get(),
+                           M.ij.get()};
+    const double *z = h->mem.selinv.z.get(), *s = p->d_s.get();
+    const long long zs = h->selinv.plan.zpool_doubles;
+    if (what == CSELINV_DIAG) CS3_HIP(launch_cselinv_diag(z, zs, maps, s, p->n, p->batch, out_dev, st));
+    else if (what == CSELINV_THEVENIN) CS3_HIP(launch_cselinv_thevenin(z, zs, maps, s, p->n, p->nnz, p->batch, out_dev, st));
+    else CS3_HIP(launch_cselinv_entries(z, zs, maps, what == CSELINV_ENTRIES_T, s, p->n, p->nnz, p->batch, out_dev, st));
+    return CS3_OK;
+}
+
+// The host forms: ZR is computed when the handle does not hold that of the current factors; the result is staged through
+// the block the real host getters use.
+static int cselinv_host(cs3_cplx p, cs3_handle h, const char *who, int what, double *out)
+{
+    int rc = cselinv_check(who, p, h, out, false);
+    if (rc) return rc;
+    if (!h->selinv_valid && (rc = cs3_selinv_dev(h, nullptr))) return rc;
+    const size_t count = 2 * (size_t) p->batch * (size_t) (what == CSELINV_DIAG ? p->n : p->nnz);
+    auto &stage = h->mem.selinv.out;
+    CS3_HIP(stage.reserve(count));
+    if ((rc = cselinv_run(p, h, who, what, stage.get(), nullptr))) return rc;
+    CS3_HIP(hipMemcpy(out, stage.get(), count * sizeof(double), hipMemcpyDeviceToHost));
+    return CS3_OK;
+}
+
+int cs3_cplx_selinv_entries_dev(cs3_cplx p, cs3_handle h, int64_t trans, double *Zz_dev, void *stream)
+{
+    const char *who = "cs3_cplx_selinv_entries_dev";
+    int rc = cselinv_check(who, p, h, Zz_dev, true);
+    if (rc) return rc;
+    return cselinv_run(p, h, who, trans ? CSELINV_ENTRIES_T : CSELINV_ENTRIES, Zz_dev, (hipStream_t) stream);
+}
+
+int cs3_cplx_selinv_diag_dev(cs3_cplx p, cs3_handle h, double *d_dev, void *stream)
+{
+    const char *who = "cs3_cplx_selinv_diag_dev";
+    int rc = cselinv_check(who, p, h, d_dev, true);
+    if (rc) return rc;
+    return cselinv_run(p, h, who, CSELINV_DIAG, d_dev, (hipStream_t) stream);
+}
+
+int cs3_cplx_selinv_thevenin_dev(cs3_cplx p, cs3_handle h, double *T_dev, void *stream)
+{
+    const char *who = "cs3_cplx_selinv_thevenin_dev";
+    int rc = cselinv_check(who, p, h, T_dev, true);
+    if (rc) return rc;
+    return cselinv_run(p, h, who, CSELINV_THEVENIN, T_dev, (hipStream_t) stream);
+}
+
+int cs3_cplx_selinv_entries(cs3_cplx p, cs3_handle h, int64_t trans, double *Zz)
+{
+    return cselinv_host(p, h, "cs3_cplx_selinv_entries", trans ? CSELINV_ENTRIES_T : CSELINV_ENTRIES, Zz);
+}
+
+int cs3_cplx_selinv_diag(cs3_cplx p, cs3_handle h, double *d)
+{
+    return cselinv_host(p, h, "cs3_cplx_selinv_diag", CSELINV_DIAG, d);
+}
+
+int cs3_cplx_selinv_thevenin(cs3_cplx p, cs3_handle h, double *T)
+{
+    return cselinv_host(p, h, "cs3_cplx_selinv_thevenin", CSELINV_THEVENIN, T);
 }
 
 // The same on data that already lives in HBM: nothing crosses PCIe and nothing synchronises.  The caller knows the

@@ -424,6 +424,26 @@ hipError_t launch_selinv_group(int kind, const SelinvView &V, const SelinvGroup 
 hipError_t launch_selinv_gather(const double *zpool, long long z_stride, const long long *map, double *out, long long count,
                                 long long batch, hipStream_t st);
 
+// cplxselinv.hip: Z = A^-1 of a complex matrix out of the zpool of the handle on its real-equivalent form
+// (cs3_cplx_selinv_*).  Per matrix Z(i, j) = (ZR(2i, 2j), ZR(2i + 1, 2j)) * s_j with the complex plan's rotation s.
+constexpr int CSELINV_BLOCK = 256;             // threads per workgroup, one complex number per lane
+constexpr int CSELINV_GRID_CAP = 2048;         // workgroups: grid-stride beyond
+struct CselinvMaps {              // device tables of the handle, pairs stored side by side (one 16-byte or 8-byte load)
+    const long long *entry;       // [nnz][2] zpool offsets of ZR(2i, 2j), ZR(2i + 1, 2j) for entry e = (i, j) of the complex matrix
+    const long long *entry_t;     // [nnz][2] ... of ZR(2j, 2i), ZR(2j + 1, 2i)
+    const long long *diag;        // [n][2]   ... of ZR(2i, 2i), ZR(2i + 1, 2i)
+    const int *ij;                // [nnz][2] (i, j)
+};
+// out [batch][nnz] complex: Z(i, j), or with trans Z(j, i); s [batch][n] complex
+hipError_t launch_cselinv_entries(const double *zpool, long long z_stride, const CselinvMaps &M, bool trans, const double *s,
+                                  long long n, long long nnz, long long batch, double *out, hipStream_t st);
+// out [batch][n] complex: Z(i, i)
+hipError_t launch_cselinv_diag(const double *zpool, long long z_stride, const CselinvMaps &M, const double *s, long long n,
+                               long long batch, double *out, hipStream_t st);
+// out [batch][nnz] complex: ((Z(i, i) + Z(j, j)) - Z(i, j)) - Z(j, i)
+hipError_t launch_cselinv_thevenin(const double *zpool, long long z_stride, const CselinvMaps &M, const double *s, long long n,
+                                   long long nnz, long long batch, double *out, hipStream_t st);
+
 // cplxsens.hip: the same around a handle on the real-equivalent form of a complex matrix (cs3_cplx_sens_*), and the
 // complex Schur complement read out of the real one (cs3_cplx_schur_get*).  The tiling constants are those above; a
 // complex row is a pair of real rows, so a scatter workgroup owns half as many.

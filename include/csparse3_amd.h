@@ -556,8 +556,9 @@ int cs3_sens_solve(cs3_handle h, cs3_sens s, const double *Bx, const double *Ctx
  * With static pivot perturbation the result is the inverse of what the factors represent, not of A.
  * The same factors give the same bits on every run, and a matrix of a batch the bits it gets alone.
  *
- * Out of scope: complex handles; matched, Schur and matrix-interleaved handles; entries outside the pattern of L + U; a
- * variant for transposed handles (trans on the getter covers it); sharding. */
+ * A handle on the real form of a complex matrix: see "complex selected inversion" below (cs3_cplx_selinv_*).
+ * Out of scope: matched, Schur and matrix-interleaved handles; entries outside the pattern of L + U; a variant for
+ * transposed handles (trans on the getter covers it); sharding. */
 typedef struct cs3_selinv_limits_t { int64_t lds_max_order, wave_max_order, gemm_tile, diag_block; } cs3_selinv_limits_t;
 typedef struct cs3_selinv_info_t { int64_t zpool_doubles, nfronts_small, nfronts_big, nlaunches; } cs3_selinv_info_t;
 int cs3_selinv_limits(cs3_selinv_limits_t *out);
@@ -1142,6 +1143,73 @@ int cs3_cplx_plan_schur_info(cs3_cplx p, int64_t *ns, int32_t *schur_idx);
 int cs3_cplx_plan_schur_order(cs3_cplx p, int64_t order, const int32_t *q_given, int32_t *q2_interior, int32_t *schur2);
 int cs3_cplx_schur_get_dev(cs3_cplx p, cs3_handle h, double *S_dev, void *stream);
 int cs3_cplx_schur_get(cs3_cplx p, cs3_handle h, double *S);
+
+/* ---- complex selected inversion: entries, diagonal and Thevenin table of Z-bus ----
+ * Z = A^-1 of a complex matrix on its own pattern, from the factors the real-form handle holds: the driving-point
+ * impedances diag(Z-bus) of every bus (fault levels), the transfer impedances of every branch, and the Thevenin impedance
+ * Z_ii + Z_jj - Z_ij - Z_ji seen between the ends of every branch.  A composition, like the complex sections above:
+ *     cs3_cplx_values_dev(p, Az, Rx, st);  cs3_factor_dev(h, Rx, tol, st);  cs3_selinv_dev(h, st);
+ *     cs3_cplx_selinv_diag_dev(p, h, d, st);  cs3_cplx_selinv_thevenin_dev(p, h, T, st);
+ * Computing the real selected inverse stays cs3_selinv_dev on the handle; the calls here read it.
+ *
+ * DEFINITIONS.  p is a complex plan of order n on the pattern (Ap, Ai), batch nb; h the handle analysed from
+ * cs3_cplx_plan_pattern / cs3_cplx_plan_order, order 2 n.  ZR(a, b) is entry (a, b) of the inverse that cs3_selinv_dev(h)
+ * left on the handle, in the caller's real-form labels.  s [nb][n] is the plan's rotation as it stands in stream order,
+ * (1, +0) everywhere with CS3_CPLX_ROTATE_NONE.  The handle factorises the real form of M = diag(s) A, and
+ * A^-1 = M^-1 diag(s).  Per matrix of the batch:
+ *   Minv(i, j) = (ZR(2i, 2j), ZR(2i + 1, 2j)): the first column of the 2 x 2 block, as cs3_cplx_schur_get_dev reads S (the
+ *     twin column agrees to rounding only and is not read).
+ *   Z(i, j) = Minv(i, j) * s_j, by the ARITHMETIC rule above: four rounded products, then the two sums, nothing fused.
+ *     The product is always made, also when s_j = (1, +0), as cs3_cplx_values_dev makes its own.
+ *   entries:   Zz[e] = Z(Ai[e], j) for entry e of column j; with trans != 0, Zz[e] = Z(j, Ai[e]), rotated by s of row
+ *     Ai[e] of the entry.  An entry stored twice gets the same value twice.
+ *   diagonal:  d[i] = Z(i, i).
+ *   Thevenin:  T[e] = ((Z(i, i) + Z(j, j)) - Z(i, j)) - Z(j, i) with i = Ai[e], in this order, component by component,
+ *     every Z the rounded product above.  A diagonal entry gives whatever that formula gives.
+ * All positions (2i, 2j) and (2i + 1, 2j) of stored entries and of their transposes lie in the structure of L + U, and
+ * (2i + 1, 2i) does whenever row i has a stored diagonal or 2i, 2i + 1 share a supernode.  If a needed position is outside
+ * the structure (only conceivable for a row without a stored diagonal), the first call that needs the maps returns
+ * CS3_ERR_STATE with a message that names the complex row; nothing is read out of bounds.
+ * The same factors and the same s give the same bits on every run, and a matrix of a batch the bits it gets alone.
+ *
+ * cs3_cplx_selinv_limits: threads per workgroup and the workgroup cap of the three kernels (one complex number per lane,
+ *   grid-stride beyond block * grid_cap numbers).  Needs no device.
+ * cs3_cplx_selinv_entries_dev: Zz_dev [nb][nnz] complex.  cs3_cplx_selinv_diag_dev: d_dev [nb][n] complex.
+ * cs3_cplx_selinv_thevenin_dev: T_dev [nb][nnz] complex, one fused launch.
+ *   Asynchronous on `stream`, one launch each; s is read in stream order, so a refactorisation through
+ *   cs3_cplx_values_dev is picked up.  They need a valid ZR exactly as the real *_dev getters do.  Complex arrays are
+ *   interleaved doubles, aligned to 16 bytes on the device.  The first call builds the maps (pairs of the handle's own
+ *   selinv maps, and the n offsets of ZR(2i + 1, 2i)) and puts them on the device; later calls neither allocate nor
+ *   synchronise.  The maps belong to the handle and go with cs3_free; plan and handle may be freed in either order.
+ * cs3_cplx_selinv_entries, cs3_cplx_selinv_diag, cs3_cplx_selinv_thevenin: the same into host memory (synchronise); they
+ *   compute ZR first when the handle does not hold that of the current factors.  The same bits.
+ * cs3_debug_cplx_selinv_maps: for arrays that are not null, the offsets in the handle's block of Z of the pairs
+ *   entry [nnz][2] = ZR(2i, 2j), ZR(2i + 1, 2j), entry_t [nnz][2] = ZR(2j, 2i), ZR(2j + 1, 2i) for every entry (i, j), and
+ *   diag [n][2] = ZR(2i, 2i), ZR(2i + 1, 2i).  Checks 1 to 3 below (no output to check); from the analysis alone, needs
+ *   no device and no factorisation.
+ *
+ * Checks, in this order, none of which needs a device: (1) a null plan, handle or output: CS3_ERR_ARG; (2) a handle
+ * whose order is not 2 n of the plan, whose entry count is not 4 nnz, or whose batch differs: CS3_ERR_ARG; (3) the
+ * refusals of cs3_selinv_* with their wording (Schur, matched, 128 matrices or more), so a plan with a border is refused
+ * through its handle; (4) a misaligned device output: CS3_ERR_ARG; (5) no successful factorisation: CS3_ERR_STATE; (6) a
+ * *_dev getter without a valid ZR: CS3_ERR_STATE.  A handle of the right sizes whose pattern is not the real form of
+ * the plan's is refused when the maps are built (CS3_ERR_ARG).
+ * LU handles (rotated or not) and Cholesky handles (CS3_CPLX_ROTATE_NONE, Hermitian positive definite) both work; the
+ * Cholesky Z is Hermitian to rounding.
+ *
+ * Out of scope: complex arithmetic inside the selinv kernels (the real form does twice the work and holds Z twice);
+ * entries outside the pattern of L + U; a getter on the complex factors' own pattern; op H (the conjugate of trans);
+ * matched, Schur and matrix-interleaved handles; a Thevenin getter for real handles; the CscMat sugar
+ * (CscMat.selected_inverse and inverse_diagonal refuse complex data, and a test pins that refusal). */
+typedef struct cs3_cplx_selinv_limits_t { int64_t block, grid_cap; } cs3_cplx_selinv_limits_t;
+int cs3_cplx_selinv_limits(cs3_cplx_selinv_limits_t *out);
+int cs3_cplx_selinv_entries_dev(cs3_cplx p, cs3_handle h, int64_t trans, double *Zz_dev, void *stream);
+int cs3_cplx_selinv_diag_dev(cs3_cplx p, cs3_handle h, double *d_dev, void *stream);
+int cs3_cplx_selinv_thevenin_dev(cs3_cplx p, cs3_handle h, double *T_dev, void *stream);
+int cs3_cplx_selinv_entries(cs3_cplx p, cs3_handle h, int64_t trans, double *Zz);
+int cs3_cplx_selinv_diag(cs3_cplx p, cs3_handle h, double *d);
+int cs3_cplx_selinv_thevenin(cs3_cplx p, cs3_handle h, double *T);
+int cs3_debug_cplx_selinv_maps(cs3_cplx p, cs3_handle h, int64_t *entry, int64_t *entry_t, int64_t *diag);
 
 #ifdef __cplusplus
 }
