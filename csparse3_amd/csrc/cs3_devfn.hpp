@@ -378,8 +378,11 @@ struct BigTile {
 // The operand panels of the previous block step, RAW: where an entry does not exist the offset is 0 (a panel's first
 // entry always exists) and the caller masks the value where it uses it.  Entry e = tid + 256 q of a panel is
 // (e % 64, e / 64) = (l64, wu + 4 q) or (e % 32, e / 32) = (l32, h5 + 8 q).
-template <int KIND>
-__device__ __forceinline__ void big_tile_panels(const BigTile &t, bool needs_d, double (&ra)[8], double (&rb)[8], double (&rad)[4], double (&rbd)[4])
+// The 64-wide panels of a tile: ra (A: the L panel of the tile's rows) and rb (B: the U panel of its columns; Cholesky:
+// the L panel of its columns).  A block-column tile asks for ra only and a block-row tile for rb only: the other panel of
+// theirs is the diagonal block's (big_diag_panels), entry for entry.
+template <int KIND, bool A, bool B>
+__device__ __forceinline__ void big_tile_panels(const BigTile &t, double (&ra)[8], double (&rb)[8])
 {
     const char *pa = t.Fb + 8ll * t.row0 + t.kp * t.ld8;       // L(row0 + l64, kp + wu + 4 q)
     const char *pb = (KIND == CS3_LU) ? t.Fb + 8ll * t.kp + t.col0 * t.ld8 : t.Fb + 8ll * t.col0 + t.kp * t.ld8;
@@ -387,10 +390,16 @@ __device__ __forceinline__ void big_tile_panels(const BigTile &t, bool needs_d, 
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
         const unsigned k_off = t.wu + 4 * q < t.pw ? (unsigned) (t.wu + 4 * q) * t.ldu : 0u;    // (a scalar)
-        ra[q] = load_at(pa, t.o_row + k_off);
-        rb[q] = load_at(pb, (KIND == CS3_LU) ? (8 * q < lim_b ? t.o_kj + 8 * q * t.ldu : 0u) : t.o_col + k_off);
+        if (A) ra[q] = load_at(pa, t.o_row + k_off);
+        if (B) rb[q] = load_at(pb, (KIND == CS3_LU) ? (8 * q < lim_b ? t.o_kj + 8 * q * t.ldu : 0u) : t.o_col + k_off);
     }
-    if (!needs_d) return;
+}
+
+// The 32-wide panels of the diagonal block D = F[kb:ke, kb:ke], for the tiles that need it: rad (L(kb + l32, kp + h5 + 8 q))
+// and rbd (U(kp + l32, kb + h5 + 8 q); Cholesky: rad again)
+template <int KIND>
+__device__ __forceinline__ void big_diag_panels(const BigTile &t, double (&rad)[4], double (&rbd)[4])
+{
     const char *pad = t.Fb + 8ll * t.kb + t.kp * t.ld8;
     const char *pbd = (KIND == CS3_LU) ? t.Fb + 8ll * t.kp + t.kb * t.ld8 : pad;
     const int lim_ad = lane_limit(t.l32 < t.bw, t.pw - t.h5);
@@ -402,22 +411,198 @@ __device__ __forceinline__ void big_tile_panels(const BigTile &t, bool needs_d, 
     }
 }
 
-// The tile's accumulators acc[cb][v] = F(row0 + ti, col0 + 16 cb + 4 v + mq) and, for a tile that needs the diagonal
-// block, dacc[v] = F(kb + dr, kb + j0 + 4 v + mq), RAW in the same way (o_acc, o_d: the thread's entry at cb = v = 0)
-template <class V4>
-__device__ __forceinline__ void big_tile_accumulators(const BigTile &t, bool needs_d, int ti, int dr, int mq, int j0, V4 (&acc)[4], V4 &dacc)
+// NCB of the tile's accumulators, the column blocks cb0 .. cb0 + NCB - 1 (cb0 a scalar): acc[c][v] = F(row0 + ti,
+// col0 + 16 (cb0 + c) + 4 v + mq), RAW in the same way (o_acc: the thread's entry at cb = v = 0).  A plain trailing tile
+// takes all four, a block-column tile the two that its 32 columns fill, a wave of a block-row tile the two it is dealt.
+template <int NCB, class V4>
+__device__ __forceinline__ void big_tile_accumulators(const BigTile &t, int ti, int mq, int cb0, V4 (&acc)[NCB])
 {
-    const unsigned o_acc = 8u * (unsigned) ti + (unsigned) mq * t.ldu, o_d = 8u * (unsigned) dr + (unsigned) mq * t.ldu;
-    const char *pc = t.Fb + 8ll * t.row0 + t.col0 * t.ld8, *pd = t.Fb + 8ll * t.kb + t.kb * t.ld8;
-    const int lim_c = lane_limit(ti < t.nrow, t.ncol - mq);    // column 16 cb + 4 v + mq exists iff 16 cb + 4 v < lim_c
+    const unsigned o_acc = 8u * (unsigned) ti + (unsigned) mq * t.ldu;
+    const char *pc = t.Fb + 8ll * t.row0 + t.col0 * t.ld8;
+    const int lim_c = lane_limit(ti < t.nrow, t.ncol - mq - 16 * cb0);   // column 16 (cb0 + c) + 4 v + mq exists iff 16 c + 4 v < lim_c
+#pragma unroll
+    for (int c = 0; c < NCB; ++c)
+#pragma unroll
+        for (int v = 0; v < 4; ++v)
+            acc[c][v] = load_at(pc, 16 * c + 4 * v < lim_c ? o_acc + (unsigned) (16 * (cb0 + c) + 4 * v) * t.ldu : 0u);
+}
+
+// ... and of the diagonal block, for a tile that needs it: dacc[v] = F(kb + dr, kb + j0 + 4 v + mq)
+template <class V4>
+__device__ __forceinline__ void big_diag_accumulator(const BigTile &t, int dr, int mq, int j0, V4 &dacc)
+{
+    const unsigned o_d = 8u * (unsigned) dr + (unsigned) mq * t.ldu;
+    const char *pd = t.Fb + 8ll * t.kb + t.kb * t.ld8;
     const int lim_d = lane_limit(dr < t.bw, t.bw - mq - j0);   // column j0 + 4 v + mq exists iff 4 v < lim_d
 #pragma unroll
-    for (int cb = 0; cb < 4; ++cb)
-#pragma unroll
-        for (int v = 0; v < 4; ++v) acc[cb][v] = load_at(pc, 16 * cb + 4 * v < lim_c ? o_acc + (16 * cb + 4 * v) * t.ldu : 0u);
-    if (!needs_d) return;
-#pragma unroll
     for (int v = 0; v < 4; ++v) dacc[v] = load_at(pd, 4 * v < lim_d ? o_d + (unsigned) (j0 + 4 * v) * t.ldu : 0u);
+}
+
+// The LDS of k_big_step as its panel tiles use it: As[k][i] = -L(row0 + i, kp + k), Bs[k][j] = U(kp + k, col0 + j), Ad / Bd
+// the same for the diagonal block, D the block itself and T the tile that is stacked under it
+struct BigLds {
+    double (&As)[BIG_NB][64 + 1], (&Bs)[BIG_NB][64 + 1], (&Ad)[BIG_NB][BIG_NB + 1], (&Bd)[BIG_NB][BIG_NB + 1];
+    double (&D)[BIG_NB][BIG_NB + 1], (&T)[64][BIG_NB + 1];
+};
+
+// A panel tile of k_big_step (the diagonal tile, a block-column tile: bj == 0, or a block-row tile) up to the point where
+// the updated diagonal block D (identity-padded past bw) and the tile T meet in LDS: the update of the previous panel,
+// for the 16 x 16 blocks that the 32-wide panel uses and no others.  Every kind issues ALL of its loads before its first
+// wait (the kernel's header says why):
+//   diagonal tile (0, 0)  D alone: its two 32-wide panels and one accumulator, 8 MFMAs per wave (it has no tile of its own:
+//                         T is only read for bi > 0 or bj > 0), and the copy-home of the parked block (send_home)
+//   block-column tile     D, and its 32 columns: the L panel of its rows and acc[0 .. 1].  Its U panel IS D's (col0 = kb,
+//                         ncol = bw: Bs would repeat Bd entry for entry), so the tile MFMAs read Bd: 16 + 8 per wave
+//   block-row tile (LU)   D, and its 32 rows: the U panel of its columns and two accumulators per wave -- wave wv takes row
+//                         block wv & 1 (the rows of its D sub-block: ONE B operand feeds both) and the column blocks
+//                         2 (wv >> 1), 2 (wv >> 1) + 1, and writes them to T[col][row] itself.  Its L panel is D's
+//                         (row0 = kb, nrow = bw): Ad.  16 + 8 MFMAs in every wave
+// Every entry's sum keeps its terms, their order (k0 upward, the MFMA's own order inside a group of four), its operand
+// roles (A = U, B = -L) and the zero padding past pw whichever wave forms it: the bits are those of the full 64 x 64 tile
+// path that the plain trailing tiles take.  In the block-column and block-row tiles the D chain stands in the k loop beside
+// the two tile chains (three independent accumulators per step), not behind them.  stamp(p): the profiling stamps 0 .. 2.
+template <int KIND, class Home, class Stamp>
+__device__ __forceinline__ void big_panel_tile(const BigTile &t, const BigLds &s, int tid, bool diag, bool col, Home send_home, Stamp stamp)
+{
+    auto &As = s.As; auto &Bs = s.Bs; auto &Ad = s.Ad; auto &Bd = s.Bd; auto &D = s.D; auto &T = s.T;
+    const int kb = t.kb, bw = t.bw, pw = t.pw, nrow = t.nrow, ncol = t.ncol;
+    const int wv = tid >> 6, mi = tid & 15, mq = (tid >> 4) & 3;
+    const int ti = 16 * wv + mi;                    // tile row of the block-column tile's accumulators
+    // D: wave wv owns the 16 x 16 sub-block (wv & 1, wv >> 1): dacc[v] = D(dr, dc0 + 4 v)
+    const int dr = 16 * (wv & 1) + mi, dc0 = 16 * (wv >> 1) + mq;
+    double rad[4] = {0.0, 0.0, 0.0, 0.0}, rbd[4] = {0.0, 0.0, 0.0, 0.0};
+    cs3_double4 dacc = {0.0, 0.0, 0.0, 0.0};
+    auto mask_d = [&]() {
+#pragma unroll
+        for (int v = 0; v < 4; ++v)
+            if (!(dr < bw && dc0 + 4 * v < bw)) dacc[v] = 0.0;
+    };
+    auto stage_d = [&]() {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int e = tid + 256 * q;
+            { const int i = e % BIG_NB, k = e / BIG_NB; Ad[k][i] = (k < pw && i < bw) ? -rad[q] : 0.0; }
+            if (KIND == CS3_LU) { const int k = e % BIG_NB, j = e / BIG_NB; Bd[k][j] = (k < pw && j < bw) ? rbd[q] : 0.0; }
+            else { const int j = e % BIG_NB, k = e / BIG_NB; Bd[k][j] = (k < pw && j < bw) ? rbd[q] : 0.0; }
+        }
+    };
+    auto put_d = [&]() {                            // the updated D, identity-padded past bw
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+            const int j = dc0 + 4 * v;
+            D[dr][j] = (dr < bw && j < bw) ? dacc[v] : (dr == j ? 1.0 : 0.0);
+        }
+    };
+    if (diag) {                                     // ---- diagonal tile
+        if (kb > 0) big_diag_panels<KIND>(t, rad, rbd);
+        big_diag_accumulator(t, dr, mq, 16 * (t.wu >> 1), dacc);
+        __builtin_amdgcn_sched_barrier(0);
+        stamp(0);
+        send_home();
+        mask_d();
+        if (kb > 0) stage_d();
+        __syncthreads();
+        stamp(1);
+        if (kb > 0) {
+#pragma unroll
+            for (int k0 = 0; k0 < BIG_NB; k0 += 4)
+                dacc = __builtin_amdgcn_mfma_f64_16x16x4f64(Bd[k0 + mq][16 * (wv >> 1) + mi], Ad[k0 + mq][dr], dacc, 0, 0, 0);
+        }
+        stamp(2);
+        put_d();
+    } else if (col) {                               // ---- block-column tile: D and T[row][col], 32 columns
+        double ra[8], rb[8];                        // (rb stays unused)
+        cs3_double4 acc[2];
+        if (kb > 0) {
+            big_tile_panels<KIND, true, false>(t, ra, rb);
+            big_diag_panels<KIND>(t, rad, rbd);
+        }
+        big_tile_accumulators<2>(t, ti, mq, 0, acc);
+        big_diag_accumulator(t, dr, mq, 16 * (t.wu >> 1), dacc);
+        __builtin_amdgcn_sched_barrier(0);
+        stamp(0);
+#pragma unroll
+        for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+            for (int v = 0; v < 4; ++v) {
+                const int j = 16 * cb + mq + 4 * v;
+                if (!(ti < nrow && j < ncol)) acc[cb][v] = 0.0;
+            }
+        mask_d();
+        if (kb > 0) {
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+                const int e = tid + 256 * q;
+                const int i = e % 64, k = e / 64;
+                As[k][i] = (k < pw && i < nrow) ? -ra[q] : 0.0;     // negated: the MFMA accumulates acc += U' (-L)'
+            }
+            stage_d();
+        }
+        __syncthreads();
+        stamp(1);
+        if (kb > 0) {
+#pragma unroll
+            for (int k0 = 0; k0 < BIG_NB; k0 += 4) {
+                const double bl = As[k0 + mq][ti];
+                const double au0 = Bd[k0 + mq][mi], au1 = Bd[k0 + mq][16 + mi];
+                const double aud = Bd[k0 + mq][16 * (wv >> 1) + mi], bld = Ad[k0 + mq][dr];
+                acc[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(au0, bl, acc[0], 0, 0, 0);
+                acc[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(au1, bl, acc[1], 0, 0, 0);
+                dacc = __builtin_amdgcn_mfma_f64_16x16x4f64(aud, bld, dacc, 0, 0, 0);
+            }
+        }
+        stamp(2);
+        put_d();
+#pragma unroll
+        for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+            for (int v = 0; v < 4; ++v) T[ti][16 * cb + mq + 4 * v] = acc[cb][v];
+    } else if constexpr (KIND == CS3_LU) {          // ---- block-row tile: D and T[col][row], 32 rows
+        const int cb0 = 2 * (t.wu >> 1);            // my column blocks cb0, cb0 + 1; my rows are D's: dr
+        double ra[8], rb[8];                        // (ra stays unused)
+        cs3_double4 acc[2];
+        if (kb > 0) {
+            big_tile_panels<KIND, false, true>(t, ra, rb);
+            big_diag_panels<KIND>(t, rad, rbd);
+        }
+        big_tile_accumulators<2>(t, dr, mq, cb0, acc);
+        big_diag_accumulator(t, dr, mq, 16 * (t.wu >> 1), dacc);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int c = 0; c < 2; ++c)
+#pragma unroll
+            for (int v = 0; v < 4; ++v) {
+                const int j = 16 * (cb0 + c) + mq + 4 * v;
+                if (!(dr < nrow && j < ncol)) acc[c][v] = 0.0;
+            }
+        mask_d();
+        if (kb > 0) {
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+                const int e = tid + 256 * q;
+                const int k = e % BIG_NB, j = e / BIG_NB;
+                Bs[k][j] = (k < pw && j < ncol) ? rb[q] : 0.0;
+            }
+            stage_d();
+        }
+        __syncthreads();
+        if (kb > 0) {
+#pragma unroll
+            for (int k0 = 0; k0 < BIG_NB; k0 += 4) {
+                const double bl = Ad[k0 + mq][dr];              // -L(kb + dr, k0 + mq): the tile's rows are D's
+                const double au0 = Bs[k0 + mq][16 * cb0 + mi], au1 = Bs[k0 + mq][16 * cb0 + 16 + mi];
+                const double aud = Bd[k0 + mq][16 * (wv >> 1) + mi];
+                acc[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(au0, bl, acc[0], 0, 0, 0);
+                acc[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(au1, bl, acc[1], 0, 0, 0);
+                dacc = __builtin_amdgcn_mfma_f64_16x16x4f64(aud, bl, dacc, 0, 0, 0);
+            }
+        }
+        put_d();
+#pragma unroll
+        for (int c = 0; c < 2; ++c)
+#pragma unroll
+            for (int v = 0; v < 4; ++v) T[16 * (cb0 + c) + mq + 4 * v][dr] = acc[c][v];
+    }
 }
 
 }  // namespace cs3

@@ -1402,6 +1402,15 @@ k_front_wg(const FrontDesc *__restrict__ fdesc, int first,
 // column of the factor up to block b is final in F, which is what lets the forward sweep of a
 // chunk start while later blocks are still being factorised.
 // Tile index 0 = the panel block [kb, ke); index t >= 1 = 64 rows/columns from ke + 64 (t-1).
+// The three panel tiles, which end the launch, load and multiply only the blocks their 32-wide panel uses: the diagonal
+// tile D alone, a block-column tile two of the four column blocks (with D's U panel as its own), a block-row tile its
+// eight blocks dealt to all four waves (with D's L panel as its own); the D chain runs beside the tile chains.  The
+// comment at the branch on the tile's kind has the details.  Loads per thread: diagonal tile 16 (it was 52 with the full
+// 64 x 64 tile path), block-column and block-row tile 28 (48); MFMAs per wave 8 and 24 (40; block-row tile: 40 in two
+// waves, 8 in the others).  On the root step kb = 64 of the 50k Jacobian the diagonal tile parks its block at 15.2 k cycles
+// instead of 21.3 k and the block-column tile stores at 17.0 k instead of 20.5 k: it now ends the launch, the block-row
+// tile in front of it (16.1 k).  From "D and T meet in LDS" on nothing changed: 6.9 k cycles for the 32 pivots, 1.8 to
+// 2.5 k for the stores and the checks.
 // What a launch costs beside the elimination (220 cycles per pivot, a dependent chain) is what stands in front of and
 // behind it on the tile that finishes last: the descriptor (one scalar load of its first 64 bytes; four waits on kernel
 // arguments remain around it), the address arithmetic until the loads are out (one uniform base per panel, 32-bit offsets), the
@@ -1478,34 +1487,46 @@ k_big_step(const FrontDesc *__restrict__ fdesc, int first, int kb, double *__res
     // (from a safe address where the entry does not exist); their masks are applied where the values are used -- with
     // the select next to the load the compiler waited for the panel operands and stored them to LDS before it issued the
     // loads of the accumulators (two round trips).
-    double ra[8], rb[8], rad[4] = {0.0, 0.0, 0.0, 0.0}, rbd[4] = {0.0, 0.0, 0.0, 0.0};
-    if (kb > 0) big_tile_panels<KIND>(t, needs_d, ra, rb, rad, rbd);
+    // The tile's kind decides what it loads and multiplies (bi, bj are uniform: one branch per workgroup, in front of
+    // the loads), and every kind issues ALL of its loads before its first wait:
+    //   plain trailing tile   the two 64-wide panels, 64 x 64 accumulators, 32 MFMAs per wave; stores and leaves
+    //   diagonal tile (0, 0)  D alone: its two 32-wide panels and one accumulator, 8 MFMAs per wave (it has no tile of
+    //                         its own: T is only read for bi > 0 or bj > 0)
+    //   block-column tile     D, and its 32 columns: the L panel of its rows and acc[0 .. 1].  Its U panel IS D's (col0 =
+    //                         kb, ncol = bw: Bs would repeat Bd entry for entry), so the tile MFMAs read Bd: 16 + 8 per wave
+    //   block-row tile (LU)   D, and its 32 rows: the U panel of its columns and two accumulators per wave -- wave wv takes
+    //                         row block wv & 1 (the rows of its D sub-block: ONE B operand feeds both) and the column
+    //                         blocks 2 (wv >> 1), 2 (wv >> 1) + 1.  Its L panel is D's (row0 = kb, nrow = bw): Ad.  16 + 8
+    // Every entry's sum keeps its terms, their order (k0 upward, the MFMA's own order inside a group of four), its operand
+    // roles (A = U, B = -L) and the zero padding past pw whichever wave forms it: the bits are those of the full tile.
+    // In the block-column and block-row tiles the D chain stands in the k loop beside the two tile chains (three
+    // independent accumulators per step), not behind them.
+    // To be read again in the gfx950 assembly of all three instances after a change here or a compiler change:
+    //   * global loads before a path's first s_waitcnt vmcnt: plain tile 32; block-column and block-row tile 16 + 12
+    //     (Cholesky, whose two D panels are one: 12 + 12); diagonal tile 4 parked entries + 8 + 4 (Cholesky 4 + 4 + 4)
+    //   * v_mfma_f64_16x16x4_f64 of a block-column / block-row tile: 24, as (tile, tile, D) per k step, none behind the others
+    //   * no scratch, 75 528 bytes of LDS, two workgroups per CU (tools/kernel_resources.py)
+    //
     // my outputs, in the register layout of v_mfma_f64_16x16x4 with the tile transposed (A operand = U
     // panel, B operand = L panel, so that lanes % 16 run along tile ROWS and global accesses stay
     // coalesced): wave wv owns tile rows [16 wv, 16 wv + 16), acc[cb][v] = F(row0 + 16 wv + mi, col0 + 16 cb + mq + 4 v)
     const int wv = tid >> 6, mi = tid & 15, mq = (tid >> 4) & 3;
     const int ti = 16 * wv + mi;
-    const unsigned o_acc = 8u * (unsigned) ti + (unsigned) mq * t.ldu;
-    double4_t acc[4];
-    // D, same scheme: wave wv owns the 16 x 16 sub-block (wv & 1, wv >> 1): dacc[v] = D(dr, dc0 + 4 v)
-    const int dr = 16 * (wv & 1) + mi, dc0 = 16 * (wv >> 1) + mq;
-    double4_t dacc = {0.0, 0.0, 0.0, 0.0};
-    big_tile_accumulators(t, needs_d, ti, dr, mq, 16 * (t.wu >> 1), acc, dacc);
-    __builtin_amdgcn_sched_barrier(0);
-    CS3_BSTAMP(0);
-    if (home) send_home();
-    // (the masks now)
+    if (!needs_d) {                                 // ---- plain trailing tile (kb > 0)
+        const unsigned o_acc = 8u * (unsigned) ti + (unsigned) mq * t.ldu;
+        double ra[8], rb[8];
+        double4_t acc[4];
+        big_tile_panels<KIND, true, true>(t, ra, rb);
+        big_tile_accumulators<4>(t, ti, mq, 0, acc);
+        __builtin_amdgcn_sched_barrier(0);
+        // (the masks now)
 #pragma unroll
-    for (int cb = 0; cb < 4; ++cb)
+        for (int cb = 0; cb < 4; ++cb)
 #pragma unroll
-        for (int v = 0; v < 4; ++v) {
-            const int j = 16 * cb + mq + 4 * v;
-            if (!(ti < nrow && j < ncol)) acc[cb][v] = 0.0;
-        }
-#pragma unroll
-    for (int v = 0; v < 4; ++v)
-        if (!(needs_d && dr < bw && dc0 + 4 * v < bw)) dacc[v] = 0.0;
-    if (kb > 0) {
+            for (int v = 0; v < 4; ++v) {
+                const int j = 16 * cb + mq + 4 * v;
+                if (!(ti < nrow && j < ncol)) acc[cb][v] = 0.0;
+            }
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
             const int e = tid + 256 * q;
@@ -1513,19 +1534,7 @@ k_big_step(const FrontDesc *__restrict__ fdesc, int first, int kb, double *__res
             if (KIND == CS3_LU) { const int k = e % BIG_NB, j = e / BIG_NB; Bs[k][j] = (k < pw && j < ncol) ? rb[q] : 0.0; }
             else { const int j = e % 64, k = e / 64; Bs[k][j] = (k < pw && j < ncol) ? rb[q] : 0.0; }
         }
-        if (needs_d) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int e = tid + 256 * q;
-                { const int i = e % BIG_NB, k = e / BIG_NB; Ad[k][i] = (k < pw && i < bw) ? -rad[q] : 0.0; }
-                if (KIND == CS3_LU) { const int k = e % BIG_NB, j = e / BIG_NB; Bd[k][j] = (k < pw && j < bw) ? rbd[q] : 0.0; }
-                else { const int j = e % BIG_NB, k = e / BIG_NB; Bd[k][j] = (k < pw && j < bw) ? rbd[q] : 0.0; }
-            }
-        }
-    }
-    __syncthreads();
-    CS3_BSTAMP(1);
-    if (kb > 0) {
+        __syncthreads();
 #pragma unroll
         for (int k0 = 0; k0 < BIG_NB; k0 += 4) {
             const double bl = As[k0 + mq][ti];                  // B operand: -L(row ti, k0 + mq), lane mi + 16 mq
@@ -1533,13 +1542,6 @@ k_big_step(const FrontDesc *__restrict__ fdesc, int first, int kb, double *__res
             for (int cb = 0; cb < 4; ++cb)                      // A operand: U(k0 + mq, column 16 cb + mi)
                 acc[cb] = __builtin_amdgcn_mfma_f64_16x16x4f64(Bs[k0 + mq][16 * cb + mi], bl, acc[cb], 0, 0, 0);
         }
-        if (needs_d) {
-#pragma unroll
-            for (int k0 = 0; k0 < BIG_NB; k0 += 4)
-                dacc = __builtin_amdgcn_mfma_f64_16x16x4f64(Bd[k0 + mq][16 * (wv >> 1) + mi], Ad[k0 + mq][dr], dacc, 0, 0, 0);
-        }
-    }
-    if (!needs_d) {                                 // plain trailing tile: store and leave
 #pragma unroll
         for (int cb = 0; cb < 4; ++cb)
 #pragma unroll
@@ -1550,25 +1552,23 @@ k_big_step(const FrontDesc *__restrict__ fdesc, int first, int kb, double *__res
             }
         return;
     }
-    CS3_BSTAMP(2);
-
-    // ---- the updated D (identity-padded past bw) and my tile meet in LDS
-#pragma unroll
-    for (int v = 0; v < 4; ++v) {
-        const int j = dc0 + 4 * v;
-        D[dr][j] = (dr < bw && j < bw) ? dacc[v] : (dr == j ? 1.0 : 0.0);
-    }
-    if (bi > 0) {                                   // block-column tile: T[row][col], 32 columns
-#pragma unroll
-        for (int cb = 0; cb < 2; ++cb)
-#pragma unroll
-            for (int v = 0; v < 4; ++v) T[ti][16 * cb + mq + 4 * v] = acc[cb][v];
-    } else if (bj > 0 && wv < 2) {                  // block-row tile: T[col][row], 32 rows
-#pragma unroll
-        for (int cb = 0; cb < 4; ++cb)
-#pragma unroll
-            for (int v = 0; v < 4; ++v) T[16 * cb + mq + 4 * v][ti] = acc[cb][v];
-    }
+    // ---- the three panel tiles.  D, same scheme: wave wv owns the 16 x 16 sub-block (wv & 1, wv >> 1): dacc[v] = D(dr, dc0 + 4 v)
+    // ---- the three panel tiles (cs3_devfn.hpp: big_panel_tile, one path per kind): the update of the previous panel for
+    // the blocks that the 32-wide panel uses, which leaves the updated D (identity-padded past bw) and the tile T in LDS.
+    // The diagonal tile stores its parked entries home behind its loads; stamps 0 .. 2: loads issued, staged, updated.
+    // (bi, bj are uniform: the branch on the kind costs a scalar compare per workgroup.  The three paths share no register:
+    //  each declares the operands it loads, which took the kernel from 115 to 105 VGPRs.  A path ends in front of the
+    //  barrier below and nothing but LDS carries over: the elimination reads D and T and reuses As / Bs for the hand-over
+    //  of its multipliers -- As is read by the block-column tile's MFMAs and Bs by the block-row tile's, both in front of
+    //  that barrier.)
+    const BigLds lds{As, Bs,                        // the 64-wide panels: -L of my rows (block-column tile), U of my columns (block-row tile)
+                     Ad, Bd,                        // the panels of the diagonal block: every panel tile
+                     D, T};                         // what the elimination below reads
+    const bool diag = bi == 0 && bj == 0, col = bj == 0;
+    big_panel_tile<KIND>(t, lds, tid, diag, col,
+                         [&]() { if (home) send_home(); },
+                         [&](int p) { CS3_BSTAMP(p); });
+    // ---- the updated D and my tile have met in LDS
     __syncthreads();
     CS3_BSTAMP(3);
     // all four waves carry on: waves 0 and 1 take 32 stacked tile rows each with columns 0..15 of the block, waves 2 and 3
@@ -1615,7 +1615,7 @@ k_big_step(const FrontDesc *__restrict__ fdesc, int first, int kb, double *__res
             for (int jj = 0; jj < HC; ++jj) {
                 const double v = e[jj], av = fabs(v);
                 const bool rej = (KIND == CS3_LU) ? ((lj > jj) & !(av <= inv_tol)) | ((lj == jj) & (!(av > 0.0) | !(av < 1.0e300))) : (lj == jj) & !(v > 0.0);
-                first_rejected(rej & (cu + jj < bw), cu + jj, bad, bad_col);
+                first_rejected(rej, cu + jj, bad, bad_col);     // (lj >= jj and lane < bw: column cu + jj exists)
             }
         }
         if (bad) flag_column(status, d.c0 + kb + bad_col);
