@@ -1,5 +1,6 @@
 // C ABI of the library (include/csparse3_amd.h): handle management, HBM
 // residency, hipGraph capture of the level schedules, host <-> device copies.
+// (The applications on a factorised handle -- updates, sparse right-hand sides, selected inversion -- are in apps.cpp.)
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -8,14 +9,11 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <map>
 #include <stdexcept>
 #include <string>
-#include <tuple>
 
 #include "cs3_cplx.hpp"
-#include "cs3_device.hpp"
-#include "cs3_hipmem.hpp"
+#include "cs3_handle.hpp"
 
 using namespace cs3;
 
@@ -26,177 +24,6 @@ thread_local std::string g_error;
 namespace cs3 {
 void set_error(const std::string &msg) { g_error = msg; }
 }
-
-// Captured graphs, one cache per handle, keyed by what a capture bakes in: (operation, trans, nrhs, the caller's X when
-// its address is inside the graph, else null).
-//   - GRAPH_FACTOR: one graph (trans false, nrhs 0), dropped when inv_tol or the perturbation delta changes.
-//   - GRAPH_SOLVE per (trans, nrhs): unbounded.  With fused permutations (X baked in) per (trans, nrhs, X): at most 8 per
-//     trans -- the 9th clears that class (callers that rotate buffers).
-//   - GRAPH_FUSED (factor + overlapped forward + backward) per nrhs: unbounded.  The same with the closing permutation
-//     inside the graph (no eager launch behind it: 5 us) per (nrhs, X): at most 4, and only from the third call in a row
-//     with the same X (fused_last_x / fused_same_x).  A change of inv_tol or delta drops every fused-step graph.
-//   - ensure_rhs_capacity drops every solve and fused-step graph (the buffers they read move).
-//   - GRAPH_SCHUR_FWD / GRAPH_SCHUR_BWD (the half-solves of a Schur handle) per nrhs: unbounded, X never baked in.
-// A graph that may still be running on another stream is destroyed only after a hipDeviceSynchronize.
-enum GraphOp { GRAPH_FACTOR, GRAPH_SOLVE, GRAPH_FUSED, GRAPH_SCHUR_FWD, GRAPH_SCHUR_BWD };
-using GraphKey = std::tuple<int, bool, int, const void *>;     // (GraphOp, trans, nrhs, X)
-
-struct cs3_handle_s {
-    Symbolic S;
-    DeviceFactor D;
-    long long batch = 1;
-    bool on_device = false, factored = false;
-    bool factor_ran = false;          // a numeric factorisation was enqueued on this handle (its counters mean something)
-    bool use_graph = true;
-    hipStream_t cap_stream = nullptr;
-    ForkJoin fj;
-    std::map<GraphKey, hipGraphExec_t> graphs;
-    PivotCtl factor_ctl{0.0, 0.0, nullptr}, fused_ctl{0.0, 0.0, nullptr};     // what the factor / fused-step graphs were captured with
-    double perturb_delta = 0.0;       // cs3_set_pivot_perturbation: LU pivots with |p| < delta become +delta (0: off)
-    const void *fused_last_x = nullptr;
-    int fused_same_x = 0;
-    long long fail_col = -1;
-    bool inverses_valid = false;      // inverted diagonal blocks (many-RHS GEMM sweeps) match the current factors
-    // selected inversion (cs3_selinv_*): the plan and the extraction maps, built from S on first use (ensure_selinv_plan);
-    // selinv_valid: mem.selinv.z holds Z of the current factors (every factor entry point clears it)
-    struct Selinv {
-        bool planned = false;
-        SelinvPlan plan;
-        std::vector<i64> entry, entry_t, diag;    // zpool offsets: A^-1(Ai[p], j), A^-1(j, Ai[p]) per entry of A; A^-1(i, i)
-        // a handle on the real form of a complex matrix (ensure_cselinv_plan): the same in pairs (real part, imaginary
-        // part) per entry and per row of the COMPLEX matrix, and (row, column) of every complex entry
-        bool cplanned = false;
-        std::vector<i64> centry, centry_t, cdiag;
-        std::vector<i32> cij;
-    } selinv;
-    bool selinv_valid = false;
-    std::vector<i32> Ap_host, Ai_host;
-    // A matched handle (cs3_analyze_matched): S analyses B = P (Dr A Dc), Ap_host / Ai_host keep the pattern of A.
-    struct Matching {
-        bool on = false;
-        std::vector<i32> rowperm;             // row of A matched to column j = row j of B
-        std::vector<double> dr, dc;
-        double t_match = 0.0;                 // host seconds of the matching
-        double parity = 1.0, log_shift = 0.0; // det A = parity det B exp(log_shift): sign of rowperm, -(sum log dr + sum log dc)
-    } match;
-    std::vector<cs3_updates_s *> plans;       // the plans made for this handle (cs3_updates_plan)
-    std::vector<cs3_sens_s *> sens_plans;     // ... and by cs3_sens_plan
-    KryWork kry_work{};                       // the work arrays of the last cs3_gmres* call (views of mem.kry)
-    // Every HBM block of the handle, one group per feature that builds it; release_device drops them all at once.  A
-    // new feature declares its DevBuf in a group here and allocates it in its ensure_*: nothing else has to know.
-    struct Memory {
-        // ensure_device: the arrays behind D's pointers (allocated together, die together) ...
-        std::vector<DevBuf<unsigned char>> factor;
-        // ... but for the sweep buffers D.cv, D.xp, D.bigv, D.gv, which grow with nrhs (ensure_rhs_capacity)
-        DevBuf<double> cv, xp, bigv, gv;
-        // ensure_row_view / ensure_col_view (residuals, refinement): the analysed pattern by rows, the same by columns
-        // (transposed products), the residual R [batch][n][k] (grows), the bits of max |dx|
-        struct { DevBuf<int> rp, rj, rmap, cp, ci, cmap; DevBuf<double> res; DevBuf<unsigned long long> maxbits; } view;
-        // ensure_krylov (krylov.hip, cs3_gmres*): (restart + 1) basis vectors, w and the vector that goes through the
-        // solves, all [batch][n, k]; per system its state, R, the rotations, g, y; the partial sums of the reductions and
-        // their sums; the counters of active systems.  All grow with k and restart.
-        struct {
-            DevBuf<double> v, w, z, small, parts;
-            DevBuf<KrySys> sys;
-            DevBuf<unsigned> cnt;
-        } kry;
-        // ensure_refine_xp (refine_xp.hip, cs3_refine_xp*): the tail of the iterate [batch][n, k], one state per system,
-        // the counter of active systems.  Grow with k.  (The residual / correction vector is view.res.)
-        struct { DevBuf<double> tail; DevBuf<XpSys> sys; DevBuf<unsigned> cnt; } xpr;
-        // ensure_estimator (estimate.hip): X [batch][n] (stable address: the solves on it replay the cached graphs), the
-        // sign vectors [2][batch][n], one state per matrix, the chunks of the partial reductions, the two "wants" counters
-        struct { DevBuf<double> x; DevBuf<signed char> s; DevBuf<EstState> state; DevBuf<EstPart> parts; DevBuf<unsigned> cnt; } est;
-        // the host forms of condest / slogdet stage through these: values of A, results [2][batch]
-        struct { DevBuf<double> ax, out; } host;
-        DevBuf<i64> diag;             // ensure_diag_map (log-determinants): virtual pool offset of every pivot's diagonal
-        // cs3_get_factors: where the entries of L and U sit in the pool, and their values gathered
-        struct { DevBuf<i64> lmap, umap; DevBuf<double> lx, ux; } exp;
-        // ensure_updates (updates.hip): the tile of A^-1 columns Z [n][widest tile so far] (grows) and x0 [n] (stable
-        // addresses: the solves on them replay the cached graphs)
-        struct { DevBuf<double> z, x0; } upd;
-        // ensure_sens (sens.hip): the tile of right-hand sides T [n][widest solve width so far] (grows; a stable address:
-        // the solves on it replay the cached graphs)
-        struct { DevBuf<double> t; } sens;
-        // ensure_match (matching.hip): the scalings, the row of A behind every pivot row, row and column of every entry
-        struct { DevBuf<double> dr, dc; DevBuf<int> rq, erow, ecol; } match;
-        // ensure_device on a Schur handle (schur.hip): the held Schur complements S [batch][ns, ns]
-        DevBuf<double> schur;
-        // ensure_selinv (selinv.hip): zpool [batch][zpool_doubles], X and Y of the big fronts [batch][work_doubles], the
-        // fronts in top-down order, the extraction maps (those on the CSC factors: cs3_selinv_factors), the host forms' results
-        struct { DevBuf<double> z, work, out; DevBuf<SelFront> fronts; DevBuf<i64> entry, entry_t, diag, lmap, umap; } selinv;
-        // ensure_cselinv (cplxselinv.hip, a handle on the real form of a complex matrix): the same maps in pairs per entry
-        // and per row of the COMPLEX matrix ([.][2], CselinvMaps), row and column of every complex entry
-        struct { DevBuf<i64> entry, entry_t, diag; DevBuf<i32> ij; } cselinv;
-    } mem;
-    // diagnostics (cs3_debug_alloc_counters): device allocations / graph instantiations and host synchronisations made by the
-    // solves and the paths on top of them
-    long long dbg_allocs = 0, dbg_syncs = 0;
-};
-
-// One list of sparse modifications dA_c of a handle's matrix, pattern only (cs3_updates_plan).  Cases are grouped into
-// TILES: consecutive cases whose union of touched rows fits the tile width; a tile is one many-RHS solve.
-struct cs3_updates_s {
-    cs3_handle h = nullptr;                   // null once the handle has been freed: the plan can then only be freed
-    i64 n = 0, ncases = 0, ntrip = 0, nrows_unique = 0, max_rank = 0;
-    int tile_cap = UPD_MAX_TILE;
-    std::vector<UpdCase> cases;
-    std::vector<i32> cp;
-    std::vector<unsigned char> tpos;
-    struct Tile {
-        int c0, nc;                           // its cases
-        int t, t_solve;                       // touched rows, and the width it is solved at (t rounded up; zero columns behind t)
-        int rmax;                             // largest rank among its cases
-        i64 unit0;                            // its slice of unit_row (t_solve entries)
-    };
-    std::vector<Tile> tiles;
-    std::vector<i32> unit_row;                // row of the unit entry of every tile column, -1: a zero column
-    // device copies (uploaded by the first solve), per-case results, the host form's copy of the triplet values
-    struct Memory {
-        DevBuf<UpdCase> cases;
-        DevBuf<int> cp, unit, flag;
-        DevBuf<unsigned char> tpos;
-        DevBuf<double> y, rpiv, cx;
-    } mem;
-    bool on_device = false;
-};
-
-// The patterns of B and C' of one Y = C op(A)^-1 B, the side it is evaluated from and its tiles (cs3_sens_plan).
-struct cs3_sens_s {
-    cs3_handle h = nullptr;                   // null once the handle has been freed: the plan can then only be freed
-    i64 n = 0, k = 0, p = 0;
-    int side = 1;                             // 1: solve for columns of B, 2: for rows of C
-    bool trans = false;
-    bool b_ident = false, c_ident = false;
-    int tile_cap = SENS_MAX_TILE, wmax = 1;
-    std::vector<i32> bp, bi, ctp, cti;        // empty for an identity operand
-    struct Tile {
-        i64 c0;                               // first solved-for column
-        int t, w;                             // its columns, and the width it is solved at (zero columns behind t)
-    };
-    std::vector<Tile> tiles;
-    // device copies (uploaded by the first solve); the host form's copies of the values and of Y
-    struct Memory {
-        DevBuf<int> bp, bi, ctp, cti;
-        DevBuf<double> bx, ctx, y;
-    } mem;
-    bool on_device = false;
-    i64 nnz_b() const { return b_ident ? n : (i64) bi.size(); }
-    i64 nnz_c() const { return c_ident ? n : (i64) cti.size(); }
-};
-
-// cs3_sens_s for a handle on the real form of a complex matrix (cs3_cplx_sens_plan): n is the COMPLEX order, the handle's is
-// 2 n; it sits in its handle's sens_plans, so the lifetime rules are those of cs3_sens_s.  The host form's copies hold
-// interleaved complex numbers.
-struct cs3_cplx_sens_s : cs3_sens_s {
-    int op = CS3_CPLX_N;
-};
-
-// cs3_updates_s for a handle on the real form of a complex matrix (cs3_cplx_updates_plan): n is the COMPLEX order, the
-// handle's is 2 n; it sits in its handle's plans, so the lifetime rules are those of cs3_updates_s.  mem.y holds 16 complex
-// numbers per case, mem.cx the host form's interleaved values.
-struct cs3_cplx_updates_s : cs3_updates_s {
-    const cs3_cplx_s *p = nullptr;            // the complex plan it was made with (compared, never followed)
-};
 
 namespace {
 
@@ -237,23 +64,10 @@ int drop_graphs(cs3_handle h, Pred drop, bool synced = false)
 
 bool graph_op_is(const GraphKey &k, int op) { return std::get<0>(k) == op; }
 
-void release_plan_device(cs3_updates_s *u)
-{
-    u->mem = cs3_updates_s::Memory();
-    u->on_device = false;
-}
-
-void release_plan_device(cs3_sens_s *u)
-{
-    u->mem = cs3_sens_s::Memory();
-    u->on_device = false;
-}
-
 // Frees every HBM allocation of the handle (ensure_device's error path and cs3_free).
 void release_device(cs3_handle h)
 {
-    for (cs3_updates_s *u : h->plans) release_plan_device(u);
-    for (cs3_sens_s *u : h->sens_plans) release_plan_device(u);
+    for (HeldPlan *u : h->plans) u->drop_device();
     (void) drop_graphs(h, [](const GraphKey &) { return true; }, true);     // (cs3_free has synchronised)
     if (h->cap_stream) { (void) hipStreamDestroy(h->cap_stream); h->cap_stream = nullptr; }
     h->fj.destroy();
@@ -415,7 +229,9 @@ int ensure_device_impl(cs3_handle h)
     return CS3_OK;
 }
 
-int ensure_rhs_capacity(cs3_handle h, long long nrhs)
+}  // namespace
+
+int cs3::ensure_rhs_capacity(cs3_handle h, long long nrhs)
 {
     DeviceFactor &D = h->D;
     if (nrhs <= D.nrhs_cap) return CS3_OK;
@@ -435,6 +251,8 @@ int ensure_rhs_capacity(cs3_handle h, long long nrhs)
     D.nrhs_cap = nrhs;
     return CS3_OK;
 }
+
+namespace {
 
 // Capture `body` (kernel launches on h->cap_stream) into an executable graph.
 template <class Body>
@@ -508,12 +326,11 @@ hipError_t launch_match_permute(cs3_handle h, const double *src, double *dst, in
     return launch_match_rows(src, dst, rows_of_a ? M.rq : D.q, rows_of_a ? M.dr : M.dc, D.n, nrhs, D.batch, !into_pivot_order, st);
 }
 
-// The sweeps of one call: launch groups and their descriptors.  One right-hand side on a handle with a bottom forest
-// follows the factor schedule (the forest, then the levels above it) with descriptors of its own.  (The forest's sweeps
-// have no transposed form: a transposed solve takes the level schedule whatever nrhs is.)
+}  // namespace
+
 // A Schur handle holds the factors of A with A22 replaced by A22 - S + I: whatever would silently answer for that matrix
 // is refused.
-int refuse_schur(cs3_handle h, const char *who)
+int cs3::refuse_schur(cs3_handle h, const char *who)
 {
     if (h->S.schur_sn < 0) return CS3_OK;
     set_error(std::string(who) + ": not available on a Schur handle (cs3_analyze_schur) -- its factors are those of A with A22 replaced "
@@ -521,11 +338,16 @@ int refuse_schur(cs3_handle h, const char *who)
     return CS3_ERR_ARG;
 }
 
+namespace {
+
 // One half-solve of a Schur handle: the caller's X (rows of A) into D.xp, one direction of the unchanged sweeps, back.
 // Forward: the Schur rows end up as b2 - A21 A11^-1 b1, the interior rows half-solved.  Backward, entered with x2 in the
 // Schur rows: x1 = U11^-1 (y1 - U12 x2).  The sweeps are replayed from a graph per (direction, nrhs).
 int run_schur_sweep(cs3_handle h, const char *who, double *x_dev, long long k, bool forward, hipStream_t st);
 
+// The sweeps of one call: launch groups and their descriptors.  One right-hand side on a handle with a bottom forest
+// follows the factor schedule (the forest, then the levels above it) with descriptors of its own.  (The forest's sweeps
+// have no transposed form: a transposed solve takes the level schedule whatever nrhs is.)
 SweepCall select_sweep_schedule(cs3_handle h, int nrhs, bool trans = false)
 {
     const bool forest = nrhs == 1 && !trans && !h->S.sub_forest.empty();
@@ -594,10 +416,12 @@ int read_status(cs3_handle h, hipStream_t st)
     return CS3_ERR_NOT_SPD;
 }
 
+}  // namespace
+
 // mode 0: full solve with permutations; 1: lsolve only; 2: usolve only (in pivot order, on X itself).
 // trans (LU): A' X = B; the forward sweep solves with U', the backward sweep with L' (mode 1: utsolve, 2: ltsolve).
 // On a Cholesky handle A' = A and trans changes nothing.
-int run_solve(cs3_handle h, double *x_dev, long long k, int mode, hipStream_t st, bool trans = false)
+int cs3::run_solve(cs3_handle h, double *x_dev, long long k, int mode, hipStream_t st, bool trans)
 {
     if (int rc = refuse_schur(h, "solves and one-sided sweeps")) return rc;
     if (!h->factored) { set_error("solve before a successful factorisation"); return CS3_ERR_STATE; }
@@ -632,6 +456,8 @@ int run_solve(cs3_handle h, double *x_dev, long long k, int mode, hipStream_t st
     else if (!fused) CS3_HIP(launch_permute(D, D.xp, x_dev, nrhs, true, st));
     return CS3_OK;
 }
+
+namespace {
 
 int run_schur_sweep(cs3_handle h, const char *who, double *x_dev, long long k, bool forward, hipStream_t st)
 {
@@ -723,13 +549,13 @@ int check_parent(const char *who, int64_t n, const int32_t *parent)
     return CS3_OK;
 }
 
-int guard(cs3_handle h)
+}  // namespace
+
+int cs3::guard(cs3_handle h)
 {
     if (!h) { set_error("null handle"); return CS3_ERR_ARG; }
     return CS3_OK;
 }
-
-}  // namespace
 
 extern "C" {
 
@@ -988,8 +814,7 @@ int cs3_free(cs3_handle h)
         (void) hipDeviceSynchronize();
         release_device(h);
     }
-    for (cs3_updates_s *u : h->plans) u->h = nullptr;      // (their device arrays went with release_device)
-    for (cs3_sens_s *u : h->sens_plans) u->h = nullptr;
+    for (HeldPlan *u : h->plans) u->h = nullptr;            // (their device arrays went with release_device)
     delete h;
     return CS3_OK;
 }
@@ -2113,160 +1938,6 @@ int cs3_slogdet(cs3_handle h, double *sign, double *logabs)
     return CS3_OK;
 }
 
-// ---- many low-rank-modified systems (A + dA_c) x = b on the held factors (updates.hip) ---------------------------------
-// Plan: per case its distinct rows R_c and columns C_c (ascending) and the entry of D_c every triplet adds to; the cases
-// in their order cut into tiles (a case joins the current tile unless the union of touched rows would pass the tile
-// width, or the tile already has UPD_MAX_TILE_CASES cases); per tile the touched rows in order of first use = the columns
-// of its Z.  A row that cases of two tiles touch is a column of both.
-static int updates_build(cs3_updates_s &u, int64_t n, int64_t ncases, const int32_t *cp, const int32_t *ci, const int32_t *cj,
-                         const char *who = "cs3_updates_plan")
-{
-    u.n = n; u.ncases = ncases; u.ntrip = cp[ncases];
-    u.cp.assign(cp, cp + ncases + 1);
-    u.cases.assign((size_t) ncases, UpdCase());
-    u.tpos.assign((size_t) u.ntrip, 0);
-    std::vector<i32> rows, cols;
-    std::vector<char> seen((size_t) n, 0);
-    for (int64_t c = 0; c < ncases; ++c) {
-        rows.assign(ci + cp[c], ci + cp[c + 1]);
-        cols.assign(cj + cp[c], cj + cp[c + 1]);
-        std::sort(rows.begin(), rows.end()); rows.erase(std::unique(rows.begin(), rows.end()), rows.end());
-        std::sort(cols.begin(), cols.end()); cols.erase(std::unique(cols.begin(), cols.end()), cols.end());
-        if (rows.size() > (size_t) UPD_MAX_RANK || cols.size() > (size_t) UPD_MAX_RANK) {
-            set_error(std::string(who) + ": case " + std::to_string(c) + " touches " + std::to_string(rows.size()) + " rows and " +
-                      std::to_string(cols.size()) + " columns (at most 16 of each)");
-            return CS3_ERR_ARG;
-        }
-        UpdCase &uc = u.cases[(size_t) c];
-        std::memset(&uc, 0, sizeof(uc));
-        uc.r = (int) rows.size(); uc.s = (int) cols.size();
-        for (size_t a = 0; a < cols.size(); ++a) uc.col[a] = cols[a];
-        for (int p = cp[c]; p < cp[c + 1]; ++p) {
-            const int ri = (int) (std::lower_bound(rows.begin(), rows.end(), ci[p]) - rows.begin());
-            const int cc = (int) (std::lower_bound(cols.begin(), cols.end(), cj[p]) - cols.begin());
-            u.tpos[(size_t) p] = (unsigned char) (ri * UPD_MAX_RANK + cc);
-        }
-        u.max_rank = std::max<i64>(u.max_rank, std::max(uc.r, uc.s));
-        for (i32 r : rows) if (!seen[(size_t) r]) { seen[(size_t) r] = 1; u.nrows_unique += 1; }
-    }
-    int tile = UPD_MAX_TILE;
-    if (const char *e = std::getenv("CS3_UPD_TILE")) tile = (int) std::min<long long>(UPD_MAX_TILE, std::max<long long>(1, std::atoll(e)));
-    u.tile_cap = std::max<int>(tile, (int) u.max_rank);           // every case fits a tile of its own
-    std::vector<i32> pos((size_t) n, -1);                          // column of a row in the current tile
-    std::vector<i32> cur;                                          // the current tile's rows
-    cs3_updates_s::Tile t{0, 0, 0, 0, 0, 0};
-    auto close_tile = [&]() {
-        t.t = (int) cur.size();
-        t.t_solve = std::min(u.tile_cap, (t.t + 63) / 64 * 64);   // few distinct widths: one captured graph per width
-        t.unit0 = (i64) u.unit_row.size();
-        u.unit_row.insert(u.unit_row.end(), cur.begin(), cur.end());
-        u.unit_row.insert(u.unit_row.end(), (size_t) (t.t_solve - t.t), -1);
-        u.tiles.push_back(t);
-        for (i32 r : cur) pos[(size_t) r] = -1;
-        cur.clear();
-    };
-    for (int64_t c = 0; c < ncases; ++c) {
-        rows.assign(ci + cp[c], ci + cp[c + 1]);
-        std::sort(rows.begin(), rows.end()); rows.erase(std::unique(rows.begin(), rows.end()), rows.end());
-        int fresh = 0;
-        for (i32 r : rows) fresh += pos[(size_t) r] < 0;
-        if (t.nc > 0 && ((int) cur.size() + fresh > u.tile_cap || t.nc == UPD_MAX_TILE_CASES)) {
-            close_tile();
-            t = cs3_updates_s::Tile{(int) c, 0, 0, 0, 0, 0};
-        }
-        UpdCase &uc = u.cases[(size_t) c];
-        for (size_t k = 0; k < rows.size(); ++k) {
-            i32 &p = pos[(size_t) rows[k]];
-            if (p < 0) { p = (i32) cur.size(); cur.push_back(rows[k]); }
-            uc.zcol[k] = (unsigned short) p;
-        }
-        t.nc += 1;
-        t.rmax = std::max(t.rmax, uc.r);
-    }
-    close_tile();
-    return CS3_OK;
-}
-
-// The case lists of a plan (cp non-null): ncases, cp monotone from 0, the index arrays and their range, in this order.
-static int updates_check_lists(const char *who_, int64_t n, int64_t ncases, const int32_t *cp, const int32_t *ci, const int32_t *cj)
-{
-    const std::string who(who_);
-    if (ncases < 1 || ncases > INT_MAX / 2) { set_error(who + ": ncases must be >= 1"); return CS3_ERR_ARG; }
-    if (cp[0] != 0) { set_error(who + ": cp[0] != 0"); return CS3_ERR_ARG; }
-    for (int64_t c = 0; c < ncases; ++c)
-        if (cp[c + 1] < cp[c]) { set_error(who + ": cp not monotone at case " + std::to_string(c)); return CS3_ERR_ARG; }
-    if (cp[ncases] > 0 && (!ci || !cj)) { set_error(who + ": null index arrays"); return CS3_ERR_ARG; }
-    for (int64_t c = 0; c < ncases; ++c)
-        for (int p = cp[c]; p < cp[c + 1]; ++p)
-            if (ci[p] < 0 || ci[p] >= n || cj[p] < 0 || cj[p] >= n) {
-                set_error(who + ": index out of range in case " + std::to_string(c));
-                return CS3_ERR_ARG;
-            }
-    return CS3_OK;
-}
-
-int cs3_updates_plan(cs3_handle h, int64_t ncases, const int32_t *cp, const int32_t *ci, const int32_t *cj, cs3_updates *out)
-{
-    int rc = guard(h); if (rc) return rc;
-    if (!out) { set_error("cs3_updates_plan: null output"); return CS3_ERR_ARG; }
-    *out = nullptr;
-    if ((rc = refuse_schur(h, "cs3_updates_plan"))) return rc;
-    if (!cp) { set_error("cs3_updates_plan: null case pointers"); return CS3_ERR_ARG; }
-    const int64_t n = h->S.n;
-    if ((rc = updates_check_lists("cs3_updates_plan", n, ncases, cp, ci, cj))) return rc;
-    cs3_updates_s *u = nullptr;
-    try {
-        u = new cs3_updates_s();
-        if ((rc = updates_build(*u, n, ncases, cp, ci, cj))) { delete u; return rc; }
-        if (h->batch > 1) {
-            delete u;
-            set_error("cs3_updates_plan: handles with batch > 1 are not supported");
-            return CS3_ERR_ARG;
-        }
-        h->plans.push_back(u);
-    } catch (const std::bad_alloc &) {
-        delete u; set_error("cs3_updates_plan: out of memory"); return CS3_ERR_ALLOC;
-    }
-    u->h = h;
-    *out = u;
-    return CS3_OK;
-}
-
-int cs3_updates_free(cs3_updates u)
-{
-    if (!u) return CS3_OK;
-    if (u->h) {
-        if (u->on_device) { (void) hipDeviceSynchronize(); release_plan_device(u); }
-        auto &pl = u->h->plans;
-        pl.erase(std::remove(pl.begin(), pl.end(), u), pl.end());
-    }
-    delete u;
-    return CS3_OK;
-}
-
-int cs3_updates_info(cs3_updates u, int64_t *ncases, int64_t *nrows_unique, int64_t *max_rank, int64_t *ntiles)
-{
-    if (!u) { set_error("cs3_updates_info: null plan"); return CS3_ERR_ARG; }
-    if (ncases) *ncases = u->ncases;
-    if (nrows_unique) *nrows_unique = u->nrows_unique;
-    if (max_rank) *max_rank = u->max_rank;
-    if (ntiles) *ntiles = (int64_t) u->tiles.size();
-    return CS3_OK;
-}
-
-int64_t cs3_debug_updates_tiles(cs3_updates u, int32_t *first_case, int32_t *ncases, int32_t *nrows, int32_t *width)
-{
-    if (!u) { set_error("cs3_debug_updates_tiles: null plan"); return CS3_ERR_ARG; }
-    for (size_t k = 0; k < u->tiles.size(); ++k) {
-        const auto &t = u->tiles[k];
-        if (first_case) first_case[k] = t.c0;
-        if (ncases) ncases[k] = t.nc;
-        if (nrows) nrows[k] = t.t;
-        if (width) width[k] = t.t_solve;
-    }
-    return (int64_t) u->tiles.size();
-}
-
 int64_t cs3_debug_live_device_buffers(void) { return (int64_t) g_live_device_buffers.load(); }
 
 int cs3_debug_alloc_counters(cs3_handle h, int64_t *allocs, int64_t *syncs)
@@ -2274,831 +1945,6 @@ int cs3_debug_alloc_counters(cs3_handle h, int64_t *allocs, int64_t *syncs)
     int rc = guard(h); if (rc) return rc;
     if (allocs) *allocs = h->dbg_allocs;
     if (syncs) *syncs = h->dbg_syncs;
-    return CS3_OK;
-}
-
-static int updates_check(const char *who, cs3_handle h, cs3_updates u, const double *cx, const double *b, const double *X)
-{
-    int rc = guard(h); if (rc) return rc;
-    if (!u) { set_error(std::string(who) + ": null plan"); return CS3_ERR_ARG; }
-    if (!b || !X || (u->ntrip > 0 && !cx)) { set_error(std::string(who) + ": null argument"); return CS3_ERR_ARG; }
-    if (u->h != h) { set_error(std::string(who) + ": the plan was made for another handle"); return CS3_ERR_ARG; }
-    if (!h->factored) { set_error(std::string(who) + ": no successful factorisation"); return CS3_ERR_STATE; }
-    return CS3_OK;
-}
-
-// Tables of the plan in HBM, the handle's Z and x0, room for the widest tile in the sweep buffers: everything a call
-// needs, so that later calls neither allocate nor synchronise.
-static int ensure_updates(cs3_handle h, cs3_updates_s *u)
-{
-    int wmax = 1;
-    for (const auto &t : u->tiles) wmax = std::max(wmax, t.t_solve);
-    if (!u->on_device) {
-        static bool prepared = false;
-        if (!prepared) { CS3_HIP(prepare_updates_kernels()); prepared = true; }
-        auto &P = u->mem;
-        CS3_HIP(P.cases.upload(u->cases));
-        CS3_HIP(P.cp.upload(u->cp));
-        CS3_HIP(P.tpos.upload(u->tpos));
-        CS3_HIP(P.unit.upload(u->unit_row));
-        CS3_HIP(P.y.alloc((size_t) u->ncases * UPD_MAX_RANK));
-        CS3_HIP(P.flag.alloc((size_t) u->ncases));
-        CS3_HIP(P.rpiv.alloc((size_t) u->ncases));
-        h->dbg_allocs += 7;
-        u->on_device = true;
-    }
-    auto &U = h->mem.upd;
-    const size_t n1 = std::max<size_t>(1, (size_t) h->S.n);
-    if (!U.x0.get()) { CS3_HIP(U.x0.alloc(n1)); h->dbg_allocs += 1; }
-    if (U.z.count() < n1 * (size_t) wmax) {
-        if (U.z.get()) {                                   // a wider plan than any before: the old tile may still be in use
-            CS3_HIP(hipDeviceSynchronize());
-            h->dbg_syncs += 1;
-        }
-        CS3_HIP(U.z.alloc(n1 * (size_t) wmax));
-        h->dbg_allocs += 1;
-    }
-    return ensure_rhs_capacity(h, wmax);
-}
-
-static int updates_run(cs3_handle h, cs3_updates_s *u, const double *cx_dev, const double *b_dev, double sing_tol, double *X_dev,
-                       double *rpiv_dev, hipStream_t st)
-{
-    int rc = ensure_updates(h, u);
-    if (rc) return rc;
-    const i64 n = h->S.n;
-    const auto &P = u->mem;
-    const UpdTables T{P.cases.get(), P.cp.get(), P.tpos.get(), P.y.get(), P.flag.get()};
-    double *rpiv = rpiv_dev ? rpiv_dev : P.rpiv.get();
-    double *Z = h->mem.upd.z.get(), *x0 = h->mem.upd.x0.get();
-    if (n > 0) {
-        CS3_HIP(hipMemcpyAsync(x0, b_dev, (size_t) n * sizeof(double), hipMemcpyDeviceToDevice, st));
-        if ((rc = run_solve(h, x0, 1, 0, st))) return rc;
-    }
-    for (const auto &t : u->tiles) {
-        if (n > 0 && t.t > 0) {
-            CS3_HIP(launch_upd_units(Z, n, t.t_solve, P.unit.get() + t.unit0, st));
-            if ((rc = run_solve(h, Z, t.t_solve, 0, st))) return rc;
-        }
-        CS3_HIP(launch_upd_capacitance(T, cx_dev, Z, t.t_solve, x0, t.c0, t.nc, sing_tol, rpiv, st));
-        CS3_HIP(launch_upd_apply(T, Z, t.t_solve, x0, n, t.c0, t.nc, t.rmax, u->ncases, X_dev, st));
-    }
-    return CS3_OK;
-}
-
-int cs3_updates_solve_dev(cs3_handle h, cs3_updates u, const double *cx_dev, const double *b_dev, double sing_tol, double *X_dev,
-                          double *rpiv_dev, void *stream)
-{
-    int rc = updates_check("cs3_updates_solve_dev", h, u, cx_dev, b_dev, X_dev);
-    if (rc) return rc;
-    return updates_run(h, u, cx_dev, b_dev, sing_tol, X_dev, rpiv_dev, (hipStream_t) stream);
-}
-
-int cs3_updates_solve(cs3_handle h, cs3_updates u, const double *cx, const double *b, double sing_tol, double *X, double *rpiv)
-{
-    int rc = updates_check("cs3_updates_solve", h, u, cx, b, X);
-    if (rc) return rc;
-    const size_t n = (size_t) h->S.n, nc = (size_t) u->ncases, nt = (size_t) u->ntrip;
-    CS3_HIP(u->mem.cx.reserve(nt));
-    DevBuf<double> bx;                                     // b [n], then X [n, ncases], for this call
-    CS3_HIP(bx.alloc(n * (nc + 1)));
-    double *d_b = bx.get(), *d_x = d_b + n;
-    if (nt) CS3_HIP(hipMemcpy(u->mem.cx.get(), cx, nt * sizeof(double), hipMemcpyHostToDevice));
-    if (n) CS3_HIP(hipMemcpy(d_b, b, n * sizeof(double), hipMemcpyHostToDevice));
-    if ((rc = updates_run(h, u, u->mem.cx.get(), d_b, sing_tol, d_x, nullptr, nullptr))) return rc;
-    if (n) CS3_HIP(hipMemcpy(X, d_x, n * nc * sizeof(double), hipMemcpyDeviceToHost));
-    if (rpiv) CS3_HIP(hipMemcpy(rpiv, u->mem.rpiv.get(), nc * sizeof(double), hipMemcpyDeviceToHost));
-    CS3_HIP(hipDeviceSynchronize());
-    return CS3_OK;
-}
-
-// ---- sparse right-hand sides: Y = C op(A)^-1 B on the held factors (sens.hip) ------------------------------------------
-/* ---- selected inversion: A^-1 on the pattern of L + U (selinv.hip, selinv.cpp) ---- */
-
-// What every cs3_selinv_* call refuses, and why (no device needed)
-static int selinv_refuse(cs3_handle h, const char *who)
-{
-    if (int rc = refuse_schur(h, who)) return rc;
-    if (h->match.on) {
-        set_error(std::string(who) + ": not available for a matched handle (the row permutation makes the pattern of the factors unsymmetric)");
-        return CS3_ERR_ARG;
-    }
-    if (h->S.il_len > 0) {
-        set_error(std::string(who) + ": not available for a matrix-interleaved batch (128 or more matrices)");
-        return CS3_ERR_ARG;
-    }
-    return CS3_OK;
-}
-
-// The plan and the maps of the entries of A and of the diagonal, from the analysis alone
-static int ensure_selinv_plan(cs3_handle h)
-{
-    auto &Q = h->selinv;
-    if (Q.planned) return CS3_OK;
-    const Symbolic &S = h->S;
-    try {
-        build_selinv_plan(S, Q.plan);
-        Q.entry.resize((size_t) S.nnzA); Q.entry_t.resize((size_t) S.nnzA); Q.diag.resize((size_t) S.n);
-        for (i64 j = 0; j < S.n; ++j) {
-            Q.diag[j] = selinv_position(S, Q.plan, S.pinv[j], S.pinv[j]);
-            for (i64 p = h->Ap_host[j]; p < h->Ap_host[j + 1]; ++p) {
-                const i64 k = S.pinv[h->Ai_host[p]], l = S.pinv[j];
-                Q.entry[p] = selinv_position(S, Q.plan, k, l);
-                Q.entry_t[p] = selinv_position(S, Q.plan, l, k);
-                if (Q.entry[p] < 0 || Q.entry_t[p] < 0) { set_error("cs3_selinv: an entry of A lies outside the symbolic structure"); return CS3_ERR_STATE; }
-            }
-        }
-    } catch (const std::exception &e) { set_error(e.what()); return CS3_ERR_ALLOC; }
-    Q.planned = true;
-    return CS3_OK;
-}
-
-static int ensure_selinv(cs3_handle h)
-{
-    int rc = ensure_selinv_plan(h);
-    if (rc) return rc;
-    auto &M = h->mem.selinv;
-    if (M.fronts.get()) return CS3_OK;
-    const auto &Q = h->selinv;
-    CS3_HIP(prepare_selinv_kernels());
-    CS3_HIP(M.z.alloc((size_t) (h->batch * Q.plan.zpool_doubles)));
-    CS3_HIP(M.work.alloc((size_t) (h->batch * Q.plan.work_doubles)));
-    CS3_HIP(M.entry.upload(Q.entry));
-    CS3_HIP(M.entry_t.upload(Q.entry_t));
-    CS3_HIP(M.diag.upload(Q.diag));
-    CS3_HIP(M.fronts.upload(Q.plan.fronts));
-    return CS3_OK;
-}
-
-// checks 1 to 3 of the header, in its order
-static int selinv_check(cs3_handle h, const char *who, bool null_output)
-{
-    int rc = guard(h); if (rc) return rc;
-    if (null_output) { set_error(std::string(who) + ": null output"); return CS3_ERR_ARG; }
-    if ((rc = selinv_refuse(h, who))) return rc;
-    if (!h->factored) { set_error(std::string(who) + ": called before a successful factorisation"); return CS3_ERR_STATE; }
-    return CS3_OK;
-}
-
-int cs3_selinv_limits(cs3_selinv_limits_t *out)
-{
-    if (!out) { set_error("cs3_selinv_limits: null output"); return CS3_ERR_ARG; }
-    out->lds_max_order = SELINV_LDS_R; out->wave_max_order = SELINV_WAVE_R;
-    out->gemm_tile = SELINV_TILE; out->diag_block = SELINV_DIAG;
-    return CS3_OK;
-}
-
-int cs3_selinv_info(cs3_handle h, cs3_selinv_info_t *out)
-{
-    int rc = guard(h); if (rc) return rc;
-    if (!out) { set_error("cs3_selinv_info: null output"); return CS3_ERR_ARG; }
-    if ((rc = selinv_refuse(h, "cs3_selinv_info"))) return rc;
-    if ((rc = ensure_selinv_plan(h))) return rc;
-    const SelinvPlan &P = h->selinv.plan;
-    out->zpool_doubles = P.zpool_doubles; out->nfronts_small = P.nsmall; out->nfronts_big = P.nbig; out->nlaunches = P.nlaunches;
-    return CS3_OK;
-}
-
-int64_t cs3_debug_selinv_plan(cs3_handle h, int32_t *front, int32_t *launch, int64_t *entry_map, int64_t *diag_map)
-{
-    if (guard(h) || selinv_refuse(h, "cs3_debug_selinv_plan") || ensure_selinv_plan(h)) return -1;
-    const auto &Q = h->selinv;
-    if (front) std::copy(Q.plan.front_sn.begin(), Q.plan.front_sn.end(), front);
-    if (launch) std::copy(Q.plan.front_launch.begin(), Q.plan.front_launch.end(), launch);
-    if (entry_map) std::copy(Q.entry.begin(), Q.entry.end(), entry_map);
-    if (diag_map) std::copy(Q.diag.begin(), Q.diag.end(), diag_map);
-    return (int64_t) Q.plan.front_sn.size();
-}
-
-int cs3_selinv_dev(cs3_handle h, void *stream)
-{
-    int rc = selinv_check(h, "cs3_selinv_dev", false); if (rc) return rc;
-    if ((rc = ensure_selinv(h))) return rc;
-    const DeviceFactor &D = h->D;
-    const SelinvPlan &P = h->selinv.plan;
-    const SelinvView V{D.pool_pm, D.pm_stride, h->mem.selinv.z.get(), h->mem.selinv.work.get(), P.zpool_doubles, P.work_doubles,
-                       h->mem.selinv.fronts.get(), D.rel_idx, h->batch};
-    for (const SelinvGroup &g : P.groups) CS3_HIP(launch_selinv_group(D.kind, V, g, (hipStream_t) stream));
-    h->selinv_valid = true;
-    return CS3_OK;
-}
-
-// out_dev [batch][count] through `map`, from the Z that cs3_selinv_dev left (check 4 of the header)
-static int selinv_get_dev(cs3_handle h, const char *who, const DevBuf<i64> &map, int64_t count, double *out_dev, hipStream_t st)
-{
-    if (!h->selinv_valid) { set_error(std::string(who) + ": no selected inverse of the current factors (call cs3_selinv_dev after the factorisation)"); return CS3_ERR_STATE; }
-    CS3_HIP(launch_selinv_gather(h->mem.selinv.z.get(), h->selinv.plan.zpool_doubles, (const long long *) map.get(), out_dev, count, h->batch, st));
-    return CS3_OK;
-}
-
-int cs3_selinv_entries_dev(cs3_handle h, int64_t trans, double *Zx_dev, void *stream)
-{
-    int rc = selinv_check(h, "cs3_selinv_entries_dev", !Zx_dev && h && h->S.nnzA > 0); if (rc) return rc;
-    return selinv_get_dev(h, "cs3_selinv_entries_dev", trans ? h->mem.selinv.entry_t : h->mem.selinv.entry, h->S.nnzA, Zx_dev, (hipStream_t) stream);
-}
-
-int cs3_selinv_diag_dev(cs3_handle h, double *d_dev, void *stream)
-{
-    int rc = selinv_check(h, "cs3_selinv_diag_dev", !d_dev && h && h->S.n > 0); if (rc) return rc;
-    return selinv_get_dev(h, "cs3_selinv_diag_dev", h->mem.selinv.diag, h->S.n, d_dev, (hipStream_t) stream);
-}
-
-// The host forms: Z is computed when the handle does not hold that of the current factors, then read through `map`
-static int selinv_get_host(cs3_handle h, const DevBuf<i64> &map, int64_t count, long long nmat, const double *z, double *out)
-{
-    auto &M = h->mem.selinv;
-    CS3_HIP(M.out.reserve((size_t) (nmat * count)));
-    CS3_HIP(launch_selinv_gather(z, h->selinv.plan.zpool_doubles, (const long long *) map.get(), M.out.get(), count, nmat, nullptr));
-    CS3_HIP(hipMemcpy(out, M.out.get(), (size_t) (nmat * count) * sizeof(double), hipMemcpyDeviceToHost));
-    return CS3_OK;
-}
-
-int cs3_selinv_entries(cs3_handle h, int64_t trans, double *Zx)
-{
-    int rc = selinv_check(h, "cs3_selinv_entries", !Zx && h && h->S.nnzA > 0); if (rc) return rc;
-    if (!h->selinv_valid && (rc = cs3_selinv_dev(h, nullptr))) return rc;
-    auto &M = h->mem.selinv;
-    return selinv_get_host(h, trans ? M.entry_t : M.entry, h->S.nnzA, h->batch, M.z.get(), Zx);
-}
-
-int cs3_selinv_diag(cs3_handle h, double *d)
-{
-    int rc = selinv_check(h, "cs3_selinv_diag", !d && h && h->S.n > 0); if (rc) return rc;
-    if (!h->selinv_valid && (rc = cs3_selinv_dev(h, nullptr))) return rc;
-    auto &M = h->mem.selinv;
-    return selinv_get_host(h, M.diag, h->S.n, h->batch, M.z.get(), d);
-}
-
-int cs3_selinv_factors(cs3_handle h, int64_t b, double *Zl, double *Zu)
-{
-    int rc = guard(h); if (rc) return rc;
-    if (!Zl && !Zu) { set_error("cs3_selinv_factors: null output"); return CS3_ERR_ARG; }
-    if (b < 0 || b >= h->batch) { set_error("cs3_selinv_factors: batch index out of range"); return CS3_ERR_ARG; }
-    if (h->S.kind == CS3_CHOLESKY && Zu) { set_error("cs3_selinv_factors: Cholesky has no U"); return CS3_ERR_ARG; }
-    if ((rc = selinv_check(h, "cs3_selinv_factors", false))) return rc;
-    if (!h->selinv_valid && (rc = cs3_selinv_dev(h, nullptr))) return rc;
-    const Symbolic &S = h->S;
-    auto &M = h->mem.selinv;
-    if (!M.lmap.get()) {                                       // Z at the positions of the CSC factors, in their (pivot-order) labels
-        try { build_csc_factors(h->S); }
-        catch (const std::exception &e) { set_error(e.what()); return CS3_ERR_ALLOC; }
-        std::vector<i64> lmap(S.Li.size()), umap(S.Ui.size());
-        for (i64 j = 0; j < S.n; ++j) {
-            for (i64 p = S.Lp[j]; p < S.Lp[j + 1]; ++p) lmap[p] = selinv_position(S, h->selinv.plan, S.Li[p], j);
-            if (S.kind == CS3_LU)
-                for (i64 p = S.Up[j]; p < S.Up[j + 1]; ++p) umap[p] = selinv_position(S, h->selinv.plan, S.Ui[p], j);
-        }
-        if (std::count(lmap.begin(), lmap.end(), -1) || std::count(umap.begin(), umap.end(), -1)) {
-            set_error("cs3_selinv_factors: an entry of the factors lies outside the symbolic structure");
-            return CS3_ERR_STATE;
-        }
-        CS3_HIP(M.umap.upload(umap));
-        CS3_HIP(M.lmap.upload(lmap));
-    }
-    const double *z = M.z.get() + b * h->selinv.plan.zpool_doubles;
-    if (Zl && (rc = selinv_get_host(h, M.lmap, (int64_t) S.Li.size(), 1, z, Zl))) return rc;
-    if (Zu && (rc = selinv_get_host(h, M.umap, (int64_t) S.Ui.size(), 1, z, Zu))) return rc;
-    return CS3_OK;
-}
-
-int cs3_sens_limits(cs3_sens_limits_t *out)
-{
-    if (!out) { set_error("cs3_sens_limits: null output"); return CS3_ERR_ARG; }
-    *out = cs3_sens_limits_t{SENS_MAX_TILE, SENS_PAD_WIDTH, SENS_SCATTER_ROWS, SENS_SCATTER_THREADS, SENS_COMBINE_COLS,
-                             SENS_COMBINE_LANES, SENS_TBLOCK};
-    return CS3_OK;
-}
-
-// One operand's pattern: pointers monotone from 0 (check 5); the indices are looked at afterwards (check 6), so that a
-// bad pointer array of either operand wins over a bad index of either.
-static int sens_check_pointers(const char *name, int64_t ncols, const int32_t *P, const int32_t *I, const char *who = "cs3_sens_plan")
-{
-    if (P[0] != 0) { set_error(std::string(who) + ": " + name + "[0] != 0"); return CS3_ERR_ARG; }
-    for (int64_t c = 0; c < ncols; ++c)
-        if (P[c + 1] < P[c]) { set_error(std::string(who) + ": " + name + " not monotone at column " + std::to_string(c)); return CS3_ERR_ARG; }
-    if (P[ncols] > 0 && !I) { set_error(std::string(who) + ": null index array behind " + name); return CS3_ERR_ARG; }
-    return CS3_OK;
-}
-
-static int sens_check_indices(const char *name, int64_t n, int64_t ncols, const int32_t *P, const int32_t *I, const char *who = "cs3_sens_plan")
-{
-    for (int64_t c = 0; c < ncols; ++c)
-        for (int e = P[c]; e < P[c + 1]; ++e)
-            if (I[e] < 0 || I[e] >= n) {
-                set_error(std::string(who) + ": index out of range in column " + std::to_string(c) + " of " + name);
-                return CS3_ERR_ARG;
-            }
-    return CS3_OK;
-}
-
-int cs3_sens_plan(cs3_handle h, int64_t k, const int32_t *Bp, const int32_t *Bi, int64_t p, const int32_t *Ctp, const int32_t *Cti,
-                  int64_t side, int64_t trans, cs3_sens *out)
-{
-    int rc = guard(h); if (rc) return rc;
-    if (!out) { set_error("cs3_sens_plan: null output"); return CS3_ERR_ARG; }
-    *out = nullptr;
-    const int64_t n = h->S.n;
-    if (k < 1 || p < 1 || k > INT_MAX / 2 || p > INT_MAX / 2) { set_error("cs3_sens_plan: k and p must be >= 1"); return CS3_ERR_ARG; }
-    if (!Bp && !Ctp) { set_error("cs3_sens_plan: B and C are both the identity (the dense inverse is not offered)"); return CS3_ERR_ARG; }
-    if (!Bp && k != n) { set_error("cs3_sens_plan: B is the identity but k != n"); return CS3_ERR_ARG; }
-    if (!Ctp && p != n) { set_error("cs3_sens_plan: C is the identity but p != n"); return CS3_ERR_ARG; }
-    if (Bp && (rc = sens_check_pointers("Bp", k, Bp, Bi))) return rc;
-    if (Ctp && (rc = sens_check_pointers("Ctp", p, Ctp, Cti))) return rc;
-    if (Bp && (rc = sens_check_indices("B", n, k, Bp, Bi))) return rc;
-    if (Ctp && (rc = sens_check_indices("C'", n, p, Ctp, Cti))) return rc;
-    if (side < 0 || side > 2) { set_error("cs3_sens_plan: side must be 0 (auto), 1 (right) or 2 (left)"); return CS3_ERR_ARG; }
-    if (!Bp && side == 1) { set_error("cs3_sens_plan: B is the identity, side right would solve for all n columns: use side 0 or 2"); return CS3_ERR_ARG; }
-    if (!Ctp && side == 2) { set_error("cs3_sens_plan: C is the identity, side left would solve for all n rows: use side 0 or 1"); return CS3_ERR_ARG; }
-    if (h->batch > 1) { set_error("cs3_sens_plan: handles with batch > 1 are not supported"); return CS3_ERR_ARG; }
-    if ((rc = refuse_schur(h, "cs3_sens_plan"))) return rc;
-    cs3_sens_s *u = nullptr;
-    try {
-        u = new cs3_sens_s();
-        u->n = n; u->k = k; u->p = p;
-        u->trans = trans != 0;
-        u->b_ident = !Bp; u->c_ident = !Ctp;
-        u->side = !Bp ? 2 : !Ctp ? 1 : side ? (int) side : (p < k ? 2 : 1);
-        if (Bp) { u->bp.assign(Bp, Bp + k + 1); u->bi.assign(Bi, Bi + Bp[k]); }
-        if (Ctp) { u->ctp.assign(Ctp, Ctp + p + 1); u->cti.assign(Cti, Cti + Ctp[p]); }
-        long long cap = SENS_MAX_TILE;
-        if (const char *e = std::getenv("CS3_SENS_TILE")) cap = std::min<long long>(SENS_MAX_TILE, std::max<long long>(1, std::atoll(e)));
-        u->tile_cap = (int) cap;
-        // full tiles at the tile width; the last at its own, padded to SENS_PAD_WIDTH where the tile width allows it
-        const i64 ns = (u->side == 1) ? k : p;
-        for (i64 c0 = 0; c0 < ns; c0 += cap) {
-            const int t = (int) std::min<i64>(cap, ns - c0);
-            const int w = (t < SENS_PAD_WIDTH && cap >= SENS_PAD_WIDTH) ? SENS_PAD_WIDTH : t;
-            u->tiles.push_back(cs3_sens_s::Tile{c0, t, w});
-            u->wmax = std::max(u->wmax, w);
-        }
-        h->sens_plans.push_back(u);
-    } catch (const std::bad_alloc &) {
-        delete u; set_error("cs3_sens_plan: out of memory"); return CS3_ERR_ALLOC;
-    }
-    u->h = h;
-    *out = u;
-    return CS3_OK;
-}
-
-int cs3_sens_free(cs3_sens u)
-{
-    if (!u) return CS3_OK;
-    if (u->h) {
-        if (u->on_device) { (void) hipDeviceSynchronize(); release_plan_device(u); }
-        auto &pl = u->h->sens_plans;
-        pl.erase(std::remove(pl.begin(), pl.end(), u), pl.end());
-    }
-    delete u;
-    return CS3_OK;
-}
-
-int cs3_sens_info(cs3_sens u, cs3_sens_info_t *out)
-{
-    if (!u || !out) { set_error("cs3_sens_info: null argument"); return CS3_ERR_ARG; }
-    *out = cs3_sens_info_t{u->k, u->p, u->side, u->trans ? 1 : 0, (int64_t) u->tiles.size(), u->wmax, u->nnz_b(), u->nnz_c()};
-    return CS3_OK;
-}
-
-static int sens_check(const char *who, cs3_handle h, cs3_sens u, const double *bx, const double *ctx, const double *Y)
-{
-    int rc = guard(h); if (rc) return rc;
-    if (!u) { set_error(std::string(who) + ": null plan"); return CS3_ERR_ARG; }
-    if (!Y || (!u->b_ident && u->nnz_b() > 0 && !bx) || (!u->c_ident && u->nnz_c() > 0 && !ctx)) {
-        set_error(std::string(who) + ": null argument");
-        return CS3_ERR_ARG;
-    }
-    if (u->h != h) { set_error(std::string(who) + ": the plan was made for another handle"); return CS3_ERR_ARG; }
-    if (!h->factored) { set_error(std::string(who) + ": no successful factorisation"); return CS3_ERR_STATE; }
-    return CS3_OK;
-}
-
-// Tables of the plan in HBM, the handle's tile buffer, room for the widest tile in the sweep buffers: everything a call
-// needs, so that later calls neither allocate nor synchronise.
-static int ensure_sens(cs3_handle h, cs3_sens_s *u)
-{
-    if (!u->on_device) {
-        auto &P = u->mem;
-        if (!u->b_ident) { CS3_HIP(P.bp.upload(u->bp)); CS3_HIP(P.bi.upload(u->bi)); h->dbg_allocs += 2; }
-        if (!u->c_ident) { CS3_HIP(P.ctp.upload(u->ctp)); CS3_HIP(P.cti.upload(u->cti)); h->dbg_allocs += 2; }
-        u->on_device = true;
-    }
-    auto &T = h->mem.sens.t;
-    const size_t need = std::max<size_t>(1, (size_t) h->S.n) * (size_t) u->wmax;
-    if (T.count() < need) {
-        if (T.get()) {                                     // a wider plan than any before: the old tile may still be in use
-            CS3_HIP(hipDeviceSynchronize());
-            h->dbg_syncs += 1;
-        }
-        CS3_HIP(T.alloc(need));
-        h->dbg_allocs += 1;
-    }
-    return ensure_rhs_capacity(h, u->wmax);
-}
-
-// Per tile: scatter the solved-for columns, solve in place, combine with the other operand.  Side left solves with the
-// transpose of op(A) and writes the transposed block.  parts (diagnostics): 1 the scatter, 2 the solve, 4 the combine.
-static int sens_run(cs3_handle h, cs3_sens_s *u, const double *bx_dev, const double *ctx_dev, double *Y_dev, hipStream_t st,
-                    int parts = 7)
-{
-    int rc = ensure_sens(h, u);
-    if (rc) return rc;
-    const i64 n = h->S.n;
-    const auto &P = u->mem;
-    const SensOperand B{u->b_ident ? nullptr : P.bp.get(), P.bi.get(), bx_dev};
-    const SensOperand Ct{u->c_ident ? nullptr : P.ctp.get(), P.cti.get(), ctx_dev};
-    const bool right = u->side == 1;
-    const SensOperand &solved = right ? B : Ct, &other = right ? Ct : B;
-    const i64 ng = right ? u->p : u->k;
-    double *T = h->mem.sens.t.get();
-    for (const auto &t : u->tiles) {
-        if (parts & 1) CS3_HIP(launch_sens_scatter(T, n, t.w, solved, t.c0, t.t, st));
-        if ((parts & 2) && (rc = run_solve(h, T, t.w, 0, st, right ? u->trans : !u->trans))) return rc;
-        if (parts & 4) CS3_HIP(launch_sens_combine(T, t.w, t.t, other, ng, t.c0, u->k, !right, Y_dev, st));
-    }
-    return CS3_OK;
-}
-
-int cs3_sens_solve_dev(cs3_handle h, cs3_sens u, const double *Bx_dev, const double *Ctx_dev, double *Y_dev, void *stream)
-{
-    int rc = sens_check("cs3_sens_solve_dev", h, u, Bx_dev, Ctx_dev, Y_dev);
-    if (rc) return rc;
-    return sens_run(h, u, Bx_dev, Ctx_dev, Y_dev, (hipStream_t) stream);
-}
-
-int cs3_debug_sens_parts(cs3_handle h, cs3_sens u, int64_t parts, const double *Bx_dev, const double *Ctx_dev, double *Y_dev,
-                         void *stream)
-{
-    int rc = sens_check("cs3_debug_sens_parts", h, u, Bx_dev, Ctx_dev, Y_dev);
-    if (rc) return rc;
-    if (parts < 1 || parts > 7) { set_error("cs3_debug_sens_parts: parts must be a mask of 1, 2 and 4"); return CS3_ERR_ARG; }
-    return sens_run(h, u, Bx_dev, Ctx_dev, Y_dev, (hipStream_t) stream, (int) parts);
-}
-
-int cs3_sens_solve(cs3_handle h, cs3_sens u, const double *Bx, const double *Ctx, double *Y)
-{
-    int rc = sens_check("cs3_sens_solve", h, u, Bx, Ctx, Y);
-    if (rc) return rc;
-    const size_t nb = u->b_ident ? 0 : (size_t) u->nnz_b(), nc = u->c_ident ? 0 : (size_t) u->nnz_c();
-    const size_t ny = (size_t) u->p * (size_t) u->k;
-    auto &P = u->mem;
-    CS3_HIP(P.bx.reserve(nb)); CS3_HIP(P.ctx.reserve(nc)); CS3_HIP(P.y.reserve(ny));
-    if (nb) CS3_HIP(hipMemcpy(P.bx.get(), Bx, nb * sizeof(double), hipMemcpyHostToDevice));
-    if (nc) CS3_HIP(hipMemcpy(P.ctx.get(), Ctx, nc * sizeof(double), hipMemcpyHostToDevice));
-    if ((rc = sens_run(h, u, P.bx.get(), P.ctx.get(), P.y.get(), nullptr))) return rc;
-    CS3_HIP(hipMemcpy(Y, P.y.get(), ny * sizeof(double), hipMemcpyDeviceToHost));
-    CS3_HIP(hipDeviceSynchronize());
-    return CS3_OK;
-}
-
-// ---- complex sparse right-hand sides: Y = C op(A)^-1 B behind a complex plan (cplxsens.hip) ----------------------------
-int cs3_cplx_sens_limits(cs3_sens_limits_t *out)
-{
-    if (!out) { set_error("cs3_cplx_sens_limits: null output"); return CS3_ERR_ARG; }
-    *out = cs3_sens_limits_t{SENS_MAX_TILE, SENS_PAD_WIDTH, 2 * CSENS_SCATTER_ROWS, SENS_SCATTER_THREADS, SENS_COMBINE_COLS,
-                             SENS_COMBINE_LANES, SENS_TBLOCK};
-    return CS3_OK;
-}
-
-int cs3_cplx_sens_plan(cs3_cplx p, cs3_handle h, int64_t k, const int32_t *Bp, const int32_t *Bi, int64_t pr, const int32_t *Ctp,
-                       const int32_t *Cti, int64_t side, int64_t op, cs3_cplx_sens *out)
-{
-    const char *who = "cs3_cplx_sens_plan";
-    const auto bad = [who](const char *msg) { set_error(std::string(who) + ": " + msg); return CS3_ERR_ARG; };
-    if (!p || !h) return bad("null plan or handle");
-    if (!out) return bad("null output");
-    *out = nullptr;
-    const int64_t n = p->n;
-    int rc;
-    if (h->S.n != 2 * n) return bad("the handle's order is not 2 n of the complex plan");
-    if (h->batch > 1) return bad("handles with batch > 1 are not supported");
-    if ((rc = refuse_schur(h, who))) return rc;
-    if (k < 1 || pr < 1 || k > INT_MAX / 2 || pr > INT_MAX / 2) return bad("k and p must be >= 1");
-    if (!Bp && !Ctp) return bad("B and C are both the identity (the dense inverse is not offered)");
-    if (!Bp && k != n) return bad("B is the identity but k != n");
-    if (!Ctp && pr != n) return bad("C is the identity but p != n");
-    if (Bp && (rc = sens_check_pointers("Bp", k, Bp, Bi, who))) return rc;
-    if (Ctp && (rc = sens_check_pointers("Ctp", pr, Ctp, Cti, who))) return rc;
-    if (Bp && (rc = sens_check_indices("B", n, k, Bp, Bi, who))) return rc;
-    if (Ctp && (rc = sens_check_indices("C'", n, pr, Ctp, Cti, who))) return rc;
-    if (side < 0 || side > 2) return bad("side must be 0 (auto), 1 (right) or 2 (left)");
-    if (!Bp && side == 1) return bad("B is the identity, side right would solve for all n columns: use side 0 or 2");
-    if (!Ctp && side == 2) return bad("C is the identity, side left would solve for all n rows: use side 0 or 1");
-    if (op != CS3_CPLX_N && op != CS3_CPLX_T && op != CS3_CPLX_H) return bad("op must be 0 (N), 1 (T) or 2 (H)");
-    cs3_cplx_sens_s *u = nullptr;
-    try {
-        u = new cs3_cplx_sens_s();
-        u->n = n; u->k = k; u->p = pr;
-        u->op = (int) op;
-        u->trans = op != CS3_CPLX_N;
-        u->b_ident = !Bp; u->c_ident = !Ctp;
-        u->side = !Bp ? 2 : !Ctp ? 1 : side ? (int) side : (pr < k ? 2 : 1);
-        if (Bp) { u->bp.assign(Bp, Bp + k + 1); u->bi.assign(Bi, Bi + Bp[k]); }
-        if (Ctp) { u->ctp.assign(Ctp, Ctp + pr + 1); u->cti.assign(Cti, Cti + Ctp[pr]); }
-        long long cap = SENS_MAX_TILE;
-        if (const char *e = std::getenv("CS3_SENS_TILE")) cap = std::min<long long>(SENS_MAX_TILE, std::max<long long>(1, std::atoll(e)));
-        u->tile_cap = (int) cap;
-        const i64 ns = (u->side == 1) ? k : pr;             // ONE real column of the [2n, w] tile per complex solved-for column
-        for (i64 c0 = 0; c0 < ns; c0 += cap) {
-            const int t = (int) std::min<i64>(cap, ns - c0);
-            const int w = (t < SENS_PAD_WIDTH && cap >= SENS_PAD_WIDTH) ? SENS_PAD_WIDTH : t;
-            u->tiles.push_back(cs3_sens_s::Tile{c0, t, w});
-            u->wmax = std::max(u->wmax, w);
-        }
-        h->sens_plans.push_back(u);
-    } catch (const std::bad_alloc &) {
-        delete u; set_error(std::string(who) + ": out of memory"); return CS3_ERR_ALLOC;
-    }
-    u->h = h;
-    *out = u;
-    return CS3_OK;
-}
-
-int cs3_cplx_sens_free(cs3_cplx_sens u)
-{
-    if (!u) return CS3_OK;
-    if (u->h) {
-        if (u->on_device) { (void) hipDeviceSynchronize(); release_plan_device(u); }
-        auto &pl = u->h->sens_plans;
-        pl.erase(std::remove(pl.begin(), pl.end(), static_cast<cs3_sens_s *>(u)), pl.end());
-    }
-    delete u;
-    return CS3_OK;
-}
-
-int cs3_cplx_sens_info(cs3_cplx_sens u, cs3_sens_info_t *out)
-{
-    if (!u || !out) { set_error("cs3_cplx_sens_info: null argument"); return CS3_ERR_ARG; }
-    *out = cs3_sens_info_t{u->k, u->p, u->side, u->op, (int64_t) u->tiles.size(), u->wmax, u->nnz_b(), u->nnz_c()};
-    return CS3_OK;
-}
-
-static int csens_check(const char *who, cs3_cplx p, cs3_handle h, cs3_cplx_sens u, const double *bz, const double *ctz, const double *Y,
-                       bool device)
-{
-    if (!p) { set_error(std::string(who) + ": null complex plan"); return CS3_ERR_ARG; }
-    int rc = sens_check(who, h, u, bz, ctz, Y);
-    if (rc) return rc;
-    if (p->n != u->n) { set_error(std::string(who) + ": the complex plan has another order than the one the plan was made with"); return CS3_ERR_ARG; }
-    const uintptr_t used = (u->b_ident ? 0 : reinterpret_cast<uintptr_t>(bz)) | (u->c_ident ? 0 : reinterpret_cast<uintptr_t>(ctz)) |
-                           reinterpret_cast<uintptr_t>(Y);
-    if (device && (used & 15)) {
-        set_error(std::string(who) + ": complex arrays must be aligned to 16 bytes");
-        return CS3_ERR_ARG;
-    }
-    return CS3_OK;
-}
-
-// sens_run with the complex kernels: per tile the scatter packs, the handle solves the real tile in place (plain for inner
-// N, transposed for T and H), the combine unpacks.  Side left solves with the transpose: inner T for op N, inner N for op
-// T, and for op H inner N between two conjugations (A^-H = conj(A^-T)).
-static int csens_run(cs3_cplx p, cs3_handle h, cs3_cplx_sens_s *u, const double *bz_dev, const double *ctz_dev, double *Y_dev,
-                     hipStream_t st, int parts = 7)
-{
-    int rc = cs3_cplx_upload(p);                            // (the tables and s = (1, +0): a plan that never saw a values call)
-    if (rc) return rc;
-    if ((rc = ensure_sens(h, u))) return rc;
-    const auto &P = u->mem;
-    const CsensOperand B{u->b_ident ? nullptr : P.bp.get(), P.bi.get(), bz_dev};
-    const CsensOperand Ct{u->c_ident ? nullptr : P.ctp.get(), P.cti.get(), ctz_dev};
-    const bool right = u->side == 1;
-    const CsensOperand &solved = right ? B : Ct, &other = right ? Ct : B;
-    const i64 ng = right ? u->p : u->k;
-    const int inner = right ? u->op : (u->op == CS3_CPLX_N ? CS3_CPLX_T : CS3_CPLX_N);
-    const CsensGlue glue{inner, (!right && u->op == CS3_CPLX_H) ? 1 : 0, p->d_s.get()};
-    double *T = h->mem.sens.t.get();
-    for (const auto &t : u->tiles) {
-        if (parts & 1) CS3_HIP(launch_csens_scatter(T, u->n, t.w, solved, t.c0, t.t, glue, st));
-        if ((parts & 2) && (rc = run_solve(h, T, t.w, 0, st, inner != CS3_CPLX_N))) return rc;
-        if (parts & 4) CS3_HIP(launch_csens_combine(T, t.w, t.t, other, ng, t.c0, u->k, !right, glue, Y_dev, st));
-    }
-    return CS3_OK;
-}
-
-int cs3_cplx_sens_solve_dev(cs3_cplx p, cs3_handle h, cs3_cplx_sens u, const double *Bz_dev, const double *Ctz_dev, double *Y_dev,
-                            void *stream)
-{
-    int rc = csens_check("cs3_cplx_sens_solve_dev", p, h, u, Bz_dev, Ctz_dev, Y_dev, true);
-    if (rc) return rc;
-    return csens_run(p, h, u, Bz_dev, Ctz_dev, Y_dev, (hipStream_t) stream);
-}
-
-int cs3_debug_cplx_sens_parts(cs3_cplx p, cs3_handle h, cs3_cplx_sens u, int64_t parts, const double *Bz_dev, const double *Ctz_dev,
-                              double *Y_dev, void *stream)
-{
-    int rc = csens_check("cs3_debug_cplx_sens_parts", p, h, u, Bz_dev, Ctz_dev, Y_dev, true);
-    if (rc) return rc;
-    if (parts < 1 || parts > 7) { set_error("cs3_debug_cplx_sens_parts: parts must be a mask of 1, 2 and 4"); return CS3_ERR_ARG; }
-    return csens_run(p, h, u, Bz_dev, Ctz_dev, Y_dev, (hipStream_t) stream, (int) parts);
-}
-
-int cs3_cplx_sens_solve(cs3_cplx p, cs3_handle h, cs3_cplx_sens u, const double *Bz, const double *Ctz, double *Y)
-{
-    int rc = csens_check("cs3_cplx_sens_solve", p, h, u, Bz, Ctz, Y, false);
-    if (rc) return rc;
-    const size_t nb = u->b_ident ? 0 : 2 * (size_t) u->nnz_b(), nc = u->c_ident ? 0 : 2 * (size_t) u->nnz_c();
-    const size_t ny = 2 * (size_t) u->p * (size_t) u->k;
-    auto &P = u->mem;
-    CS3_HIP(P.bx.reserve(nb)); CS3_HIP(P.ctx.reserve(nc)); CS3_HIP(P.y.reserve(ny));
-    if (nb) CS3_HIP(hipMemcpy(P.bx.get(), Bz, nb * sizeof(double), hipMemcpyHostToDevice));
-    if (nc) CS3_HIP(hipMemcpy(P.ctx.get(), Ctz, nc * sizeof(double), hipMemcpyHostToDevice));
-    if ((rc = csens_run(p, h, u, P.bx.get(), P.ctx.get(), P.y.get(), nullptr))) return rc;
-    CS3_HIP(hipMemcpy(Y, P.y.get(), ny * sizeof(double), hipMemcpyDeviceToHost));
-    CS3_HIP(hipDeviceSynchronize());
-    return CS3_OK;
-}
-
-// diagnostics: the handle's tile buffer (of both sens paths) to or from host memory, so that a test can look at what a
-// scatter wrote and choose what a combine reads
-int cs3_debug_sens_tile(cs3_handle h, int64_t write, double *host, int64_t count)
-{
-    int rc = guard(h); if (rc) return rc;
-    auto &T = h->mem.sens.t;
-    if (!host || count < 0 || (size_t) count > T.count()) {
-        set_error("cs3_debug_sens_tile: null array, or more doubles than the tile buffer holds (" + std::to_string(T.count()) + ")");
-        return CS3_ERR_ARG;
-    }
-    CS3_HIP(hipDeviceSynchronize());
-    if (count) CS3_HIP(write ? hipMemcpy(T.get(), host, (size_t) count * sizeof(double), hipMemcpyHostToDevice)
-                             : hipMemcpy(host, T.get(), (size_t) count * sizeof(double), hipMemcpyDeviceToHost));
-    return CS3_OK;
-}
-
-// ---- complex low-rank-modified systems (A + dA_c) v = i behind a complex plan (cplxupd.hip) ---------------------------
-int cs3_cplx_updates_limits(cs3_cplx_updates_limits_t *out)
-{
-    if (!out) { set_error("cs3_cplx_updates_limits: null output"); return CS3_ERR_ARG; }
-    *out = cs3_cplx_updates_limits_t{CUPD_UNIT_ROWS, CUPD_UNIT_THREADS, CUPD_APPLY_STAGE, CUPD_APPLY_ROWS, CUPD_APPLY_NT_MIN,
-                                     UPD_MAX_RANK, UPD_MAX_TILE, UPD_MAX_TILE_CASES};
-    return CS3_OK;
-}
-
-int cs3_cplx_updates_plan(cs3_cplx p, cs3_handle h, int64_t ncases, const int32_t *cp, const int32_t *ci, const int32_t *cj,
-                          cs3_cplx_updates *out)
-{
-    const char *who = "cs3_cplx_updates_plan";
-    const auto bad = [who](const char *msg) { set_error(std::string(who) + ": " + msg); return CS3_ERR_ARG; };
-    if (!p || !h) return bad("null plan or handle");
-    if (!out) return bad("null output");
-    *out = nullptr;
-    if (!cp) return bad("null case pointers");
-    const int64_t n = p->n;
-    int rc;
-    if (h->S.n != 2 * n) return bad("the handle's order is not 2 n of the complex plan");
-    if ((rc = updates_check_lists(who, n, ncases, cp, ci, cj))) return rc;
-    cs3_cplx_updates_s *u = nullptr;
-    try {
-        u = new cs3_cplx_updates_s();
-        if ((rc = updates_build(*u, n, ncases, cp, ci, cj, who))) { delete u; return rc; }
-        if (h->batch > 1 || p->batch > 1) { delete u; return bad("plans and handles with batch > 1 are not supported"); }
-        if (!p->schur_idx.empty()) { delete u; return bad("not available on a complex plan with a border (cs3_cplx_plan_create_schur)"); }
-        if ((rc = refuse_schur(h, who))) { delete u; return rc; }
-        h->plans.push_back(u);
-    } catch (const std::bad_alloc &) {
-        delete u; set_error(std::string(who) + ": out of memory"); return CS3_ERR_ALLOC;
-    }
-    u->h = h;
-    u->p = p;
-    *out = u;
-    return CS3_OK;
-}
-
-int cs3_cplx_updates_free(cs3_cplx_updates u)
-{
-    if (!u) return CS3_OK;
-    if (u->h) {
-        if (u->on_device) { (void) hipDeviceSynchronize(); release_plan_device(u); }
-        auto &pl = u->h->plans;
-        pl.erase(std::remove(pl.begin(), pl.end(), static_cast<cs3_updates_s *>(u)), pl.end());
-    }
-    delete u;
-    return CS3_OK;
-}
-
-int cs3_cplx_updates_info(cs3_cplx_updates u, int64_t *ncases, int64_t *nrows_unique, int64_t *max_rank, int64_t *ntiles)
-{
-    if (!u) { set_error("cs3_cplx_updates_info: null plan"); return CS3_ERR_ARG; }
-    return cs3_updates_info(u, ncases, nrows_unique, max_rank, ntiles);
-}
-
-int64_t cs3_debug_cplx_updates_tiles(cs3_cplx_updates u, int32_t *first_case, int32_t *ncases, int32_t *nrows, int32_t *width)
-{
-    if (!u) { set_error("cs3_debug_cplx_updates_tiles: null plan"); return CS3_ERR_ARG; }
-    return cs3_debug_updates_tiles(u, first_case, ncases, nrows, width);
-}
-
-static int cupd_check(const char *who_, cs3_cplx p, cs3_handle h, cs3_cplx_updates u, const double *cz, const double *b, const double *X,
-                      bool device)
-{
-    const std::string who(who_);
-    if (!p) { set_error(who + ": null complex plan"); return CS3_ERR_ARG; }
-    int rc = guard(h); if (rc) return rc;
-    if (!u) { set_error(who + ": null plan"); return CS3_ERR_ARG; }
-    if (!b || !X || (u->ntrip > 0 && !cz)) { set_error(who + ": null argument"); return CS3_ERR_ARG; }
-    if (u->h != h) { set_error(who + ": the plan was made for another handle"); return CS3_ERR_ARG; }
-    if (u->p != p) { set_error(who + ": the plan was made for another complex plan"); return CS3_ERR_ARG; }
-    const uintptr_t used = reinterpret_cast<uintptr_t>(cz) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(X);
-    if (device && (used & 15)) { set_error(who + ": complex arrays must be aligned to 16 bytes"); return CS3_ERR_ARG; }
-    if (!h->factored) { set_error(who + ": no successful factorisation"); return CS3_ERR_STATE; }
-    return CS3_OK;
-}
-
-// Tables of the plan in HBM, x0 [2n] (the real path's, a stable address) and the handle's tile buffer for Z [2n][widest
-// tile], room for the widest tile in the sweep buffers: later calls neither allocate nor synchronise.
-static int ensure_cupd(cs3_handle h, cs3_cplx_updates_s *u)
-{
-    int wmax = 1;
-    for (const auto &t : u->tiles) wmax = std::max(wmax, t.t_solve);
-    if (!u->on_device) {
-        static bool prepared = false;
-        if (!prepared) { CS3_HIP(prepare_cupd_kernels()); prepared = true; }
-        auto &P = u->mem;
-        CS3_HIP(P.cases.upload(u->cases));
-        CS3_HIP(P.cp.upload(u->cp));
-        CS3_HIP(P.tpos.upload(u->tpos));
-        CS3_HIP(P.unit.upload(u->unit_row));
-        CS3_HIP(P.y.alloc((size_t) u->ncases * 2 * UPD_MAX_RANK));
-        CS3_HIP(P.flag.alloc((size_t) u->ncases));
-        CS3_HIP(P.rpiv.alloc((size_t) u->ncases));
-        h->dbg_allocs += 7;
-        u->on_device = true;
-    }
-    const size_t n2 = std::max<size_t>(2, (size_t) h->S.n);
-    auto &x0 = h->mem.upd.x0;
-    if (!x0.get()) { CS3_HIP(x0.alloc(n2)); h->dbg_allocs += 1; }
-    auto &T = h->mem.sens.t;
-    if (T.count() < n2 * (size_t) wmax) {
-        if (T.get()) {                                     // a wider plan than any before: the old tile may still be in use
-            CS3_HIP(hipDeviceSynchronize());
-            h->dbg_syncs += 1;
-        }
-        CS3_HIP(T.alloc(n2 * (size_t) wmax));
-        h->dbg_allocs += 1;
-    }
-    return ensure_rhs_capacity(h, wmax);
-}
-
-// updates_run with the complex kernels.  parts (diagnostics): 1 x0 and the units, 2 the tiles' solves, 4 capacitance + apply.
-static int cupd_run(cs3_cplx p, cs3_handle h, cs3_cplx_updates_s *u, const double *cz_dev, const double *b_dev, double sing_tol,
-                    double *X_dev, double *rpiv_dev, hipStream_t st, int parts = 7)
-{
-    int rc = cs3_cplx_upload(p);                            // (the tables and s = (1, +0): a plan that never saw a values call)
-    if (rc) return rc;
-    if ((rc = ensure_cupd(h, u))) return rc;
-    const i64 n = u->n;
-    const auto &P = u->mem;
-    const UpdTables T{P.cases.get(), P.cp.get(), P.tpos.get(), P.y.get(), P.flag.get()};
-    double *rpiv = rpiv_dev ? rpiv_dev : P.rpiv.get();
-    double *Z = h->mem.sens.t.get(), *x0 = h->mem.upd.x0.get();
-    if (n > 0 && (parts & 1)) {
-        if ((rc = cs3_cplx_pack_dev(p, CS3_CPLX_N, b_dev, x0, 1, st))) return rc;
-        if ((rc = run_solve(h, x0, 1, 0, st))) return rc;
-    }
-    for (const auto &t : u->tiles) {
-        if (n > 0 && t.t > 0) {
-            if (parts & 1) CS3_HIP(launch_cupd_units(Z, n, t.t_solve, P.unit.get() + t.unit0, p->d_s.get(), st));
-            if ((parts & 2) && (rc = run_solve(h, Z, t.t_solve, 0, st))) return rc;
-        }
-        if (parts & 4) {
-            CS3_HIP(launch_cupd_capacitance(T, cz_dev, Z, t.t_solve, x0, t.c0, t.nc, sing_tol, rpiv, st));
-            CS3_HIP(launch_cupd_apply(T, Z, t.t_solve, x0, n, t.c0, t.nc, t.rmax, u->ncases, X_dev, st));
-        }
-    }
-    return CS3_OK;
-}
-
-int cs3_cplx_updates_solve_dev(cs3_cplx p, cs3_handle h, cs3_cplx_updates u, const double *cz_dev, const double *b_dev, double sing_tol,
-                               double *X_dev, double *rpiv_dev, void *stream)
-{
-    int rc = cupd_check("cs3_cplx_updates_solve_dev", p, h, u, cz_dev, b_dev, X_dev, true);
-    if (rc) return rc;
-    return cupd_run(p, h, u, cz_dev, b_dev, sing_tol, X_dev, rpiv_dev, (hipStream_t) stream);
-}
-
-int cs3_debug_cplx_updates_parts(cs3_cplx p, cs3_handle h, cs3_cplx_updates u, int64_t parts, const double *cz_dev, const double *b_dev,
-                                 double sing_tol, double *X_dev, double *rpiv_dev, void *stream)
-{
-    int rc = cupd_check("cs3_debug_cplx_updates_parts", p, h, u, cz_dev, b_dev, X_dev, true);
-    if (rc) return rc;
-    if (parts < 1 || parts > 7) { set_error("cs3_debug_cplx_updates_parts: parts must be a mask of 1, 2 and 4"); return CS3_ERR_ARG; }
-    return cupd_run(p, h, u, cz_dev, b_dev, sing_tol, X_dev, rpiv_dev, (hipStream_t) stream, (int) parts);
-}
-
-int cs3_cplx_updates_solve(cs3_cplx p, cs3_handle h, cs3_cplx_updates u, const double *cz, const double *b, double sing_tol, double *X,
-                           double *rpiv)
-{
-    int rc = cupd_check("cs3_cplx_updates_solve", p, h, u, cz, b, X, false);
-    if (rc) return rc;
-    const size_t n = (size_t) u->n, nc = (size_t) u->ncases, nt = (size_t) u->ntrip;
-    CS3_HIP(u->mem.cx.reserve(2 * nt));
-    DevBuf<double> bx;                                     // b [n], then X [n, ncases], complex, for this call
-    CS3_HIP(bx.alloc(2 * n * (nc + 1)));
-    double *d_b = bx.get(), *d_x = d_b + 2 * n;
-    if (nt) CS3_HIP(hipMemcpy(u->mem.cx.get(), cz, 2 * nt * sizeof(double), hipMemcpyHostToDevice));
-    if (n) CS3_HIP(hipMemcpy(d_b, b, 2 * n * sizeof(double), hipMemcpyHostToDevice));
-    if ((rc = cupd_run(p, h, u, u->mem.cx.get(), d_b, sing_tol, d_x, nullptr, nullptr))) return rc;
-    if (n) CS3_HIP(hipMemcpy(X, d_x, 2 * n * nc * sizeof(double), hipMemcpyDeviceToHost));
-    if (rpiv) CS3_HIP(hipMemcpy(rpiv, u->mem.rpiv.get(), nc * sizeof(double), hipMemcpyDeviceToHost));
-    CS3_HIP(hipDeviceSynchronize());
     return CS3_OK;
 }
 
@@ -3138,182 +1984,6 @@ int cs3_cplx_schur_get(cs3_cplx p, cs3_handle h, double *S)
     CS3_HIP(launch_cplx_schur_gather(h->D.schur, h->batch, (long long) p->schur_idx.size(), s.get(), nullptr));
     CS3_HIP(hipMemcpy(S, s.get(), count * sizeof(double), hipMemcpyDeviceToHost));
     return CS3_OK;
-}
-
-// ---- complex selected inversion: Z = A^-1 out of the real form's selected inverse (cplxselinv.hip) ---------------------
-int cs3_cplx_selinv_limits(cs3_cplx_selinv_limits_t *out)
-{
-    if (!out) { set_error("cs3_cplx_selinv_limits: null output"); return CS3_ERR_ARG; }
-    out->block = CSELINV_BLOCK; out->grid_cap = CSELINV_GRID_CAP;
-    return CS3_OK;
-}
-
-// checks 1 to 6 of the header, in its order; none needs a device
-static int cselinv_check(const char *who_, cs3_cplx p, cs3_handle h, const double *out, bool device, bool plan_only = false)
-{
-    const std::string who(who_);
-    if (!p) { set_error(who + ": null complex plan"); return CS3_ERR_ARG; }
-    int rc = guard(h); if (rc) return rc;
-    if (!out && !plan_only) { set_error(who + ": null output"); return CS3_ERR_ARG; }
-    if (h->S.n != 2 * p->n || h->S.nnzA != 4 * p->nnz || h->batch != p->batch) {
-        set_error(who + ": the handle is not one on the real form of the complex plan (its order is not 2 n, its entries are not 4 nnz, "
-                        "or the batches differ)");
-        return CS3_ERR_ARG;
-    }
-    if ((rc = selinv_refuse(h, who_))) return rc;
-    if (plan_only) return CS3_OK;                          // (cs3_debug_cplx_selinv_maps: the analysis alone)
-    if (device && (reinterpret_cast<uintptr_t>(out) & 15)) { set_error(who + ": complex arrays must be aligned to 16 bytes"); return CS3_ERR_ARG; }
-    if (!h->factored) { set_error(who + ": called before a successful factorisation"); return CS3_ERR_STATE; }
-    if (device && !h->selinv_valid) {
-        set_error(who + ": no selected inverse of the current factors (call cs3_selinv_dev after the factorisation)");
-        return CS3_ERR_STATE;
-    }
-    return CS3_OK;
-}
-
-// The maps of the complex layer, once per handle and from the analysis alone (no device): the real maps of
-// ensure_selinv_plan at the positions Rp[2j] + 2t, + 1 and Rp[2j + 1] + 2t of the real pattern, in pairs, and the one
-// position they do not hold, (2i + 1, 2i).  The handle's pattern is compared with the real form of the plan's while they are
-// built, so that the kernels read the handle's tables only.
-static int ensure_cselinv_plan(cs3_cplx p, cs3_handle h, const char *who_)
-{
-    auto &Q = h->selinv;
-    if (Q.cplanned) return CS3_OK;
-    const std::string who(who_);
-    int rc = ensure_selinv_plan(h);
-    if (rc) return rc;
-    const Symbolic &S = h->S;
-    const i64 n = p->n, nnz = p->nnz;
-    const i32 *Ap = p->Ap.data(), *Ai = p->Ai.data(), *Rp = h->Ap_host.data(), *Ri = h->Ai_host.data();
-    try {
-        Q.centry.assign((size_t) (2 * nnz), -1); Q.centry_t.assign((size_t) (2 * nnz), -1); Q.cdiag.assign((size_t) (2 * n), -1);
-        Q.cij.assign((size_t) (2 * nnz), 0);
-        for (i64 j = 0; j < n; ++j) {
-            const i64 r0 = 4LL * Ap[j], r1 = 2LL * Ap[j] + 2LL * Ap[j + 1];
-            bool same = Rp[2 * j] == r0 && Rp[2 * j + 1] == r1;
-            for (i64 e = Ap[j]; same && e < Ap[j + 1]; ++e) {
-                const i64 lo = r0 + 2 * (e - Ap[j]), hi = r1 + 2 * (e - Ap[j]);
-                const i32 i = Ai[e];
-                same = Ri[lo] == 2 * i && Ri[lo + 1] == 2 * i + 1 && Ri[hi] == 2 * i && Ri[hi + 1] == 2 * i + 1;
-                Q.centry[2 * e] = Q.entry[lo];     Q.centry[2 * e + 1] = Q.entry[lo + 1];       // ZR(2i, 2j), ZR(2i + 1, 2j)
-                Q.centry_t[2 * e] = Q.entry_t[lo]; Q.centry_t[2 * e + 1] = Q.entry_t[hi];       // ZR(2j, 2i), ZR(2j + 1, 2i)
-                Q.cij[2 * e] = i; Q.cij[2 * e + 1] = (i32) j;
-            }
-            if (!same) {
-                set_error(who + ": the handle's pattern is not the real form of the complex plan's (cs3_cplx_plan_pattern), column " +
-                          std::to_string(j));
-                return CS3_ERR_ARG;
-            }
-            Q.cdiag[2 * j] = Q.diag[2 * j];
-            Q.cdiag[2 * j + 1] = selinv_position(S, Q.plan, S.pinv[2 * j + 1], S.pinv[2 * j]);
-            if (Q.cdiag[2 * j] < 0 || Q.cdiag[2 * j + 1] < 0) {
-                set_error(who + ": the imaginary part of Z(" + std::to_string(j) + ", " + std::to_string(j) + ") lies outside the symbolic "
-                          "structure (complex row " + std::to_string(j) + " has no stored diagonal)");
-                return CS3_ERR_STATE;
-            }
-        }
-    } catch (const std::exception &e) { set_error(e.what()); return CS3_ERR_ALLOC; }
-    Q.cplanned = true;
-    return CS3_OK;
-}
-
-static int ensure_cselinv(cs3_cplx p, cs3_handle h, const char *who)
-{
-    auto &M = h->mem.cselinv;
-    if (M.ij.get()) return CS3_OK;
-    int rc = ensure_cselinv_plan(p, h, who);
-    if (rc) return rc;
-    const auto &Q = h->selinv;
-    CS3_HIP(M.entry.upload(Q.centry));
-    CS3_HIP(M.entry_t.upload(Q.centry_t));
-    CS3_HIP(M.diag.upload(Q.cdiag));
-    CS3_HIP(M.ij.upload(Q.cij));                           // (last: what marks the maps as uploaded)
-    return CS3_OK;
-}
-
-int cs3_debug_cplx_selinv_maps(cs3_cplx p, cs3_handle h, int64_t *entry, int64_t *entry_t, int64_t *diag)
-{
-    const char *who = "cs3_debug_cplx_selinv_maps";
-    int rc = cselinv_check(who, p, h, nullptr, false, true);
-    if (rc) return rc;
-    if ((rc = ensure_cselinv_plan(p, h, who))) return rc;
-    const auto &Q = h->selinv;
-    if (entry) std::copy(Q.centry.begin(), Q.centry.end(), entry);
-    if (entry_t) std::copy(Q.centry_t.begin(), Q.centry_t.end(), entry_t);
-    if (diag) std::copy(Q.cdiag.begin(), Q.cdiag.end(), diag);
-    return CS3_OK;
-}
-
-enum CselinvWhat : int { CSELINV_ENTRIES = 0, CSELINV_ENTRIES_T = 1, CSELINV_DIAG = 2, CSELINV_THEVENIN = 3 };
-
-static int cselinv_run(cs3_cplx p, cs3_handle h, const char *who, int what, double *out_dev, hipStream_t st)
-{
-    int rc = cs3_cplx_upload(p);                            // (the tables and s = (1, +0): a plan that never saw a values call)
-    if (rc) return rc;
-    if ((rc = ensure_cselinv(p, h, who))) return rc;
-    const auto &M = h->mem.cselinv;
-    const CselinvMaps maps{(const long long *) M.entry.get(), (const long long *) M.entry_t.get(), (const long long *) M.diag.get(),
-                           M.ij.get()};
-    const double *z = h->mem.selinv.z.get(), *s = p->d_s.get();
-    const long long zs = h->selinv.plan.zpool_doubles;
-    if (what == CSELINV_DIAG) CS3_HIP(launch_cselinv_diag(z, zs, maps, s, p->n, p->batch, out_dev, st));
-    else if (what == CSELINV_THEVENIN) CS3_HIP(launch_cselinv_thevenin(z, zs, maps, s, p->n, p->nnz, p->batch, out_dev, st));
-    else CS3_HIP(launch_cselinv_entries(z, zs, maps, what == CSELINV_ENTRIES_T, s, p->n, p->nnz, p->batch, out_dev, st));
-    return CS3_OK;
-}
-
-// The host forms: ZR is computed when the handle does not hold that of the current factors; the result is staged through
-// the block the real host getters use.
-static int cselinv_host(cs3_cplx p, cs3_handle h, const char *who, int what, double *out)
-{
-    int rc = cselinv_check(who, p, h, out, false);
-    if (rc) return rc;
-    if (!h->selinv_valid && (rc = cs3_selinv_dev(h, nullptr))) return rc;
-    const size_t count = 2 * (size_t) p->batch * (size_t) (what == CSELINV_DIAG ? p->n : p->nnz);
-    auto &stage = h->mem.selinv.out;
-    CS3_HIP(stage.reserve(count));
-    if ((rc = cselinv_run(p, h, who, what, stage.get(), nullptr))) return rc;
-    CS3_HIP(hipMemcpy(out, stage.get(), count * sizeof(double), hipMemcpyDeviceToHost));
-    return CS3_OK;
-}
-
-int cs3_cplx_selinv_entries_dev(cs3_cplx p, cs3_handle h, int64_t trans, double *Zz_dev, void *stream)
-{
-    const char *who = "cs3_cplx_selinv_entries_dev";
-    int rc = cselinv_check(who, p, h, Zz_dev, true);
-    if (rc) return rc;
-    return cselinv_run(p, h, who, trans ? CSELINV_ENTRIES_T : CSELINV_ENTRIES, Zz_dev, (hipStream_t) stream);
-}
-
-int cs3_cplx_selinv_diag_dev(cs3_cplx p, cs3_handle h, double *d_dev, void *stream)
-{
-    const char *who = "cs3_cplx_selinv_diag_dev";
-    int rc = cselinv_check(who, p, h, d_dev, true);
-    if (rc) return rc;
-    return cselinv_run(p, h, who, CSELINV_DIAG, d_dev, (hipStream_t) stream);
-}
-
-int cs3_cplx_selinv_thevenin_dev(cs3_cplx p, cs3_handle h, double *T_dev, void *stream)
-{
-    const char *who = "cs3_cplx_selinv_thevenin_dev";
-    int rc = cselinv_check(who, p, h, T_dev, true);
-    if (rc) return rc;
-    return cselinv_run(p, h, who, CSELINV_THEVENIN, T_dev, (hipStream_t) stream);
-}
-
-int cs3_cplx_selinv_entries(cs3_cplx p, cs3_handle h, int64_t trans, double *Zz)
-{
-    return cselinv_host(p, h, "cs3_cplx_selinv_entries", trans ? CSELINV_ENTRIES_T : CSELINV_ENTRIES, Zz);
-}
-
-int cs3_cplx_selinv_diag(cs3_cplx p, cs3_handle h, double *d)
-{
-    return cselinv_host(p, h, "cs3_cplx_selinv_diag", CSELINV_DIAG, d);
-}
-
-int cs3_cplx_selinv_thevenin(cs3_cplx p, cs3_handle h, double *T)
-{
-    return cselinv_host(p, h, "cs3_cplx_selinv_thevenin", CSELINV_THEVENIN, T);
 }
 
 // The same on data that already lives in HBM: nothing crosses PCIe and nothing synchronises.  The caller knows the

@@ -7,7 +7,7 @@
 //     out[g, j] = sum_e v_e * unpack_inner(T[2 i_e, j], T[2 i_e + 1, j])                         k_csens_combine
 //
 // One complex solved-for column is ONE real column of the tile: side left with p rows of C costs p solves, where the real
-// sens path on the real form would need the real and the imaginary row of every row of C, 2p.  api.cpp drives it per tile
+// sens path on the real form would need the real and the imaginary row of every row of C, 2p.  apps.cpp drives it per tile
 // and picks `inner` and the conjugations (include/csparse3_amd.h, "complex sparse right-hand sides").
 //
 // Arithmetic is that of cplxplan.hip: a complex product is four rounded products, then the two sums; a conjugate is a sign

@@ -6,7 +6,7 @@
 //     S_c = I + D_c Z[C_c, R_c],   y_c = S_c^-1 D_c x0[C_c],   x_c = x0 - Z[:, R_c] y_c          (complex)
 //
 // M is the real form of diag(s) A, and pack_N(e_row) = (Re s_row, Im s_row) in the pair of that row: M^-1 of it is
-// A^-1 e_row with no rotation of dA_c anywhere.  api.cpp drives it per tile as it drives updates.hip: k_cupd_units writes
+// A^-1 e_row with no rotation of dA_c anywhere.  apps.cpp drives it per tile as it drives updates.hip: k_cupd_units writes
 // the right-hand sides, the handle's many-RHS solve turns them into the tile of Z in place, k_cupd_capacitance forms and
 // solves the small systems, k_cupd_apply writes their columns of X.  Plan, cases and tiles are those of updates.hip.
 //

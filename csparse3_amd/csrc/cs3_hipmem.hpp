@@ -1,5 +1,5 @@
-// Device memory of the host layer (api.cpp, substrate.hip's host functions): the one place that allocates and frees HBM,
-// the error macro and the device check that go with it.  Host code only.
+// Device memory of the host layer (api.cpp, apps.cpp, substrate.hip's host functions): the one place that allocates and
+// frees HBM, the error macro and the device check that go with it.  Host code only.
 #pragma once
 #include <hip/hip_runtime_api.h>
 

@@ -5,7 +5,7 @@
 //     T = op(A)^-1 T  (side left: op(A)^-T T)                              the handle's solve, in place
 //     out[g, j] = sum_e v_e T[i_e, j]   over the entries of column g of the OTHER operand      k_sens_combine
 //
-// api.cpp drives it per tile of at most 1024 solved-for columns.  Side right solves for columns of B and combines with the
+// apps.cpp drives it per tile of at most 1024 solved-for columns.  Side right solves for columns of B and combines with the
 // rows of C (out = Y[g, c0 + j]); side left solves for rows of C and combines with the columns of B (out = Y[c0 + j, g],
 // stored through LDS so that both the reads of T and the stores to Y are contiguous).
 //

@@ -4,7 +4,7 @@
 //     Z = A^-1 E_R          the columns of A^-1 of the touched rows, one TILE of at most 1024 of them at a time
 //     S_c = I + D_c Z[C_c, R_c],   y_c = S_c^-1 D_c x0[C_c],   x_c = x0 - Z[:, R_c] y_c
 //
-// api.cpp drives it per tile: k_upd_units writes the unit right-hand sides, the handle's many-RHS solve turns them into
+// apps.cpp drives it per tile: k_upd_units writes the unit right-hand sides, the handle's many-RHS solve turns them into
 // the tile of Z in place, k_upd_capacitance forms and solves the small systems of the tile's cases, k_upd_apply writes
 // their columns of X.  The tables the kernels read (UpdTables) are built once per plan on the host.
 //

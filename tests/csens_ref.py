@@ -1,5 +1,5 @@
 """NumPy restatement of the complex sparse right-hand-side path (cs3_cplx_sens_*: csrc/cplxsens.hip and csens_run in
-csrc/api.cpp) and of complex Schur handles (cs3_cplx_plan_create_schur, cs3_cplx_schur_get).
+csrc/apps.cpp) and of complex Schur handles (cs3_cplx_plan_create_schur, cs3_cplx_schur_get).
 
 scatter and combine work on SEPARATE real and imaginary float64 arrays, every product and every sum a NumPy call of its
 own in the order the header states (cplx_ref.cmul; NumPy's complex multiplication is never used); the real solve between

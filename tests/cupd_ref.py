@@ -1,5 +1,5 @@
 """NumPy restatement of the complex low-rank-modified solves (cs3_cplx_updates_*: csrc/cplxupd.hip and cupd_run in
-csrc/api.cpp), on SEPARATE real and imaginary float64 arrays with every product, quotient and sum a NumPy call of its own
+csrc/apps.cpp), on SEPARATE real and imaginary float64 arrays with every product, quotient and sum a NumPy call of its own
 in the order the header states (cplx_ref.cmul, cdiv below; NumPy's complex arithmetic is never used in the restatement).
 The real solve between the steps is a callback, as in csens_ref: numpy.linalg.solve on the dense real form for the tests
 without a GPU, the handle's own solve_dev for the GPU tests.  The dense reference at the end is NumPy complex128: it is

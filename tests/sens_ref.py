@@ -1,5 +1,5 @@
 """NumPy / SciPy restatement of the sparse right-hand-side path (cs3_sens_*: csrc/sens.hip and cs3_sens_plan in
-csrc/api.cpp): how a plan groups its solved-for columns into tiles, which side it picks, and Y = C op(A)^-1 B computed
+csrc/apps.cpp): how a plan groups its solved-for columns into tiles, which side it picks, and Y = C op(A)^-1 B computed
 both ways -- from the right, C @ splu(op(A)).solve(B), and from the left, (splu(op(A)').solve(C'))' @ B.
 
 An operand is an Op(ncols, indptr, indices, values): B by columns (n x ncols), C by rows, i.e. the CSC arrays of C'."""

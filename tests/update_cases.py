@@ -1,4 +1,4 @@
-"""Case lists that put the low-rank-modified solves (cs3_updates_*: csrc/updates.hip and updates_build in csrc/api.cpp)
+"""Case lists that put the low-rank-modified solves (cs3_updates_*: csrc/updates.hip and updates_build in csrc/apps.cpp)
 at their engineered edges, for tests/test_update_cases_cpu.py and tests/test_gpu_update_edges.py.
 
 What the kernels do with a case (updates.hip): k_upd_capacitance gives a wave to a case, forms S = I + D G in LDS with
