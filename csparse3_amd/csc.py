@@ -332,6 +332,38 @@ class CscMat:
         F = self.lu(tol) if kind == "lu" else self.chol()
         return F.inverse_diagonal()
 
+    @staticmethod
+    def _rows_of(C):
+        """A CscMat (p x n) as the CSC form of its transpose, (p, indptr, indices) and the values: its rows."""
+        _, p, Ctp, Cti, Ctx = _k.csc_transpose(C.m, C.n, C.indptr, C.indices, C.data)
+        return (p, Ctp, Cti), Ctx
+
+    def quad_forms(self, C, B=None, kind="lu", tol=0.0):
+        """t_i = c_i' A^-1 b_i for the rows c_i of a sparse C and b_i of a sparse B (CscMat, m x n; None: B = C), by
+        selected inversion on the LU (kind "lu") or Cholesky ("chol") factors (factorises as solve does): every pair of
+        columns of one row pair must lie on the pattern of the factors.  With an incidence matrix as C: Z_ii + Z_jj - Z_ij
+        - Z_ji of every branch.  C and B are turned into their rows with csc_transpose, values included."""
+        self._complex_scope(quad_forms=self._is_complex())
+        assert kind in ("lu", "chol")
+        assert C.n == self.n and (B is None or (B.n == self.n and B.m == C.m))
+        F = self.lu(tol) if kind == "lu" else self.chol()
+        Ct, Cx = self._rows_of(C)
+        Bt, Bx = (None, None) if B is None else self._rows_of(B)
+        with F.quad_plan(Ct, Bt) as plan:
+            return F.quad_forms(plan, Cx, Bx)
+
+    def normalized_residuals(self, H, w, r, crit_tol=1e-8):
+        """The largest-normalised-residual test of a state estimate whose gain matrix G = H' W H this is: H (CscMat, m x n)
+        the measurement Jacobian, w [m] the weights, r [m] the residuals.  By selected inversion on the Cholesky factors.
+        -> (rn, info) as Factorization.normalized_residuals: rn_i = |r_i| / sqrt(1/w_i - h_i' G^-1 h_i), 0 for a critical
+        measurement (1 - w_i h_i' G^-1 h_i <= crit_tol); info holds omega, t, worst, worst_row, J and critical."""
+        self._complex_scope(normalized_residuals=self._is_complex())
+        assert H.n == self.n
+        F = self.chol()
+        Ht, Hx = self._rows_of(H)
+        with F.quad_plan(Ht) as plan:
+            return F.normalized_residuals(plan, Hx, w, r, crit_tol)
+
 
 def _sub_matrix_cols(Ap, Ai, Ax, cols):
     """Whole columns `cols` of a CSC matrix with their original row indices (csc_sub_matrix_cols, csc_numba.py:505-538):

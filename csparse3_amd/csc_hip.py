@@ -111,6 +111,20 @@ class SelinvInfo(C.Structure):
         return "SelinvInfo(%s)" % ", ".join("%s=%d" % (f, getattr(self, f)) for f, _ in self._fields_)
 
 
+class QuadLimits(C.Structure):
+    """cs3_quad_limits_t: the term counts at which a row of the bilinear forms changes class, and the kernels' sizes."""
+    _fields_ = [(name, C.c_int64) for name in ("lane_max_terms", "wave_max_terms", "block", "lane_chunk", "reduce_rows")]
+
+
+class QuadInfo(C.Structure):
+    """cs3_quad_info_t: rows, entries of C and B, terms, whether B = C, and the rows per class of a QuadPlan."""
+    _fields_ = [(name, C.c_int64) for name in ("m", "nnz_c", "nnz_b", "nterms", "same_operand", "rows_lane", "rows_wave",
+                                               "rows_workgroup")]
+
+    def __repr__(self):
+        return "QuadInfo(%s)" % ", ".join("%s=%d" % (f, getattr(self, f)) for f, _ in self._fields_)
+
+
 class CplxUpdatesLimits(C.Structure):
     """cs3_cplx_updates_limits_t: the constants that shape the kernels of the complex low-rank-modified solves."""
     _fields_ = [(name, C.c_int64) for name in ("unit_rows", "unit_threads", "apply_stage", "apply_rows", "apply_threads_min",
@@ -254,6 +268,15 @@ def lib():
         L.cs3_debug_selinv_plan.argtypes = [vp, _i32p, _i32p, C.POINTER(I64), C.POINTER(I64)]
         L.cs3_debug_selinv_plan.restype = I64
         L.cs3_debug_live_device_buffers.restype = I64
+        L.cs3_quad_limits.argtypes = [C.POINTER(QuadLimits)]
+        L.cs3_quad_plan.argtypes = [vp, I64, _i32p, _i32p, _i32p, _i32p, C.POINTER(vp)]
+        L.cs3_quad_free.argtypes = [vp]
+        L.cs3_quad_info.argtypes = [vp, C.POINTER(QuadInfo)]
+        L.cs3_quad_dev.argtypes = [vp, vp, vp, vp, vp, vp]
+        L.cs3_quad.argtypes = [vp, vp, _f64p, _f64p, _f64p]
+        L.cs3_quad_normres_dev.argtypes = [vp, vp, vp, vp, vp, C.c_double, vp, vp, vp, vp, vp]
+        L.cs3_quad_normres.argtypes = [vp, vp, _f64p, _f64p, _f64p, C.c_double, _f64p, _f64p, _f64p, _f64p]
+        L.cs3_debug_quad_plan.argtypes = [vp, _i32p, C.POINTER(I64), C.POINTER(I64)]
         L.cs3_export_factor_dev.argtypes = [vp, vp, vp]
         L.cs3_import_factor_dev.argtypes = [vp, vp, vp]
         L.cs3_get_factors.argtypes = [vp, I64, _i32p, _i32p, _f64p, _i32p, _i32p, _f64p]
@@ -524,6 +547,63 @@ def selinv_limits():
     out = SelinvLimits()
     _check(lib().cs3_selinv_limits(C.byref(out)))
     return out
+
+
+def quad_limits():
+    """The constants of the bilinear forms on the selected inverse (cs3_quad_limits); needs no GPU."""
+    out = QuadLimits()
+    _check(lib().cs3_quad_limits(C.byref(out)))
+    return out
+
+
+class QuadPlan:
+    """The term map of m bilinear forms t_i = c_i' A^-1 b_i on a handle's selected inverse (Factorization.quad_plan): made
+    once on the host from the analysis alone, used by every quad_forms / normalized_residuals of that handle, across
+    refactorisations."""
+
+    def __init__(self, factorization, Ct, Bt=None):
+        self._u = C.c_void_p()
+        self.m, self.ctp, self.cti = int(Ct[0]), _i32(Ct[1]), _i32(Ct[2])
+        assert self.ctp.size == self.m + 1, "Ct is (nrows, indptr[nrows + 1], indices)"
+        self.btp, self.bti = (None, None) if Bt is None else (_i32(Bt[1]), _i32(Bt[2]))
+        assert Bt is None or (int(Bt[0]) == self.m and self.btp.size == self.m + 1), "Bt is (nrows, indptr[nrows + 1], indices), nrows that of Ct"
+        self.nnz_c = int(self.ctp[-1])
+        self.nnz_b = self.nnz_c if Bt is None else int(self.btp[-1])
+        _check(lib().cs3_quad_plan(factorization._h, self.m, _pi(self.ctp), _pi(self.cti), _pi(self.btp), _pi(self.bti),
+                                   C.byref(self._u)))
+
+    def close(self):
+        if self._u:
+            lib().cs3_quad_free(self._u)
+            self._u = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    @property
+    def info(self):
+        out = QuadInfo()
+        _check(lib().cs3_quad_info(self._u, C.byref(out)))
+        return out
+
+    def debug_plan(self):
+        """Diagnostics -> (row_class [m], term_ptr [m + 1], term_pos [terms]): the class of every row (0 lane, 1 wave,
+        2 workgroup) and the offsets in the handle's block of Z of its terms, a-major; needs no GPU."""
+        row_class = np.empty(self.m, dtype=np.int32)
+        term_ptr = np.empty(self.m + 1, dtype=np.int64)
+        term_pos = np.empty(int(self.info.nterms), dtype=np.int64)
+        _check(lib().cs3_debug_quad_plan(self._u, _pi(row_class), term_ptr.ctypes.data_as(C.POINTER(I64)),
+                                         term_pos.ctypes.data_as(C.POINTER(I64))))
+        return row_class, term_ptr, term_pos
 
 
 class SensPlan:
@@ -1068,6 +1148,60 @@ class Factorization:
         Zu = np.empty(inf.nnz_u) if self.kind == CS3_LU else None
         _check(lib().cs3_selinv_factors(self._h, b, _pf(Zl), _pf(Zu)))
         return Zl, Zu
+
+    # -- bilinear forms on the selected inverse: t_i = c_i' A^-1 b_i, the bad-data test of a state estimate
+    def quad_plan(self, Ct, Bt=None):
+        """Plan for t_i = c_i' A^-1 b_i, i < m: `Ct` = (m, indptr, indices) the CSC pattern of C' (C by rows), `Bt` the same
+        for B; None: B = C, pattern and values.  Every pair of a row's columns must lie on the pattern of L + U (the pairs
+        of one row of H always do for A = H' W H).  Needs no GPU.  -> QuadPlan (.info, .close(), context manager)."""
+        return QuadPlan(self, Ct, Bt)
+
+    def _quad_values(self, a, count):
+        a = _f64(a).reshape(self.batch, -1)
+        assert a.shape[1] == count, "values are [batch, %d] in the plan's entry order" % count
+        return a
+
+    def quad_forms(self, plan, Cx, Bx=None):
+        """t [batch, m] (1-D for one matrix) from the held selected inverse: Cx / Bx the values [batch, nnz] in the plan's
+        entry order (Bx is ignored for a plan with B = C).  Runs selinv() first when the handle holds no inverse of the
+        current factors."""
+        Cx = self._quad_values(Cx, plan.nnz_c)
+        Bx = None if plan.btp is None else self._quad_values(Bx, plan.nnz_b)
+        t = np.empty((self.batch, plan.m))
+        _check(lib().cs3_quad(self._h, plan._u, _pf(Cx), _pf(Bx), _pf(t)))
+        return t[0] if self.batch == 1 else t
+
+    def quad_forms_dev(self, plan, cx_ptr, bx_ptr, t_ptr, stream=0):
+        """quad_forms on device pointers, asynchronous on `stream`, after selinv(); t [batch, m].  After the first call with
+        a plan nothing is allocated and nothing synchronises.  The same bits as quad_forms()."""
+        _check(lib().cs3_quad_dev(self._h, plan._u, C.c_void_p(cx_ptr), C.c_void_p(bx_ptr or 0), C.c_void_p(t_ptr),
+                                  C.c_void_p(stream or 0)))
+
+    def normalized_residuals(self, plan, Hx, w, r, crit_tol=1e-8):
+        """The largest-normalised-residual test on a handle that holds the factors of G = H' W H, `plan` made from the
+        rows of H (B = C): t_i = h_i' G^-1 h_i, omega_i = 1/w_i - t_i, rn_i = |r_i| / sqrt(omega_i), and rn_i = 0 for a
+        critical measurement (1 - w_i t_i <= crit_tol).  Hx [batch, nnz], w and r [batch, m].
+        -> (rn, info), info = {"omega", "t", "worst", "worst_row", "J", "critical"}; J = sum w r^2.  Arrays are 1-D and the
+        others scalars for one matrix, [batch, ...] otherwise.  Ties take the lowest row; a NaN rn ranks first."""
+        Hx = self._quad_values(Hx, plan.nnz_c)
+        w, r = self._quad_values(w, plan.m), self._quad_values(r, plan.m)
+        t, omega, rn = (np.empty((self.batch, plan.m)) for _ in range(3))
+        summary = np.empty((self.batch, 4))
+        _check(lib().cs3_quad_normres(self._h, plan._u, _pf(Hx), _pf(w), _pf(r), float(crit_tol), _pf(t), _pf(omega), _pf(rn),
+                                      _pf(summary)))
+        info = {"omega": omega, "t": t, "worst": summary[:, 0].copy(), "worst_row": summary[:, 1].astype(np.int64),
+                "J": summary[:, 2].copy(), "critical": summary[:, 3].astype(np.int64)}
+        if self.batch == 1:
+            rn = rn[0]
+            info = {k: (v[0] if v.ndim == 2 else v[0].item()) for k, v in info.items()}
+        return rn, info
+
+    def normalized_residuals_dev(self, plan, hx_ptr, w_ptr, r_ptr, crit_tol, summary_ptr, t_ptr=0, omega_ptr=0, rn_ptr=0, stream=0):
+        """normalized_residuals on device pointers, asynchronous on `stream`, after selinv(): summary [batch, 4] = (worst,
+        worst_row, J, critical) as doubles; t, omega, rn [batch, m] are written where a pointer is given.  The same bits."""
+        _check(lib().cs3_quad_normres_dev(self._h, plan._u, C.c_void_p(hx_ptr), C.c_void_p(w_ptr), C.c_void_p(r_ptr), float(crit_tol),
+                                          C.c_void_p(t_ptr or 0), C.c_void_p(omega_ptr or 0), C.c_void_p(rn_ptr or 0),
+                                          C.c_void_p(summary_ptr), C.c_void_p(stream or 0)))
 
     def debug_alloc_counters(self):
         """(device allocations incl. graph instantiations, host synchronisations) the handle's solves have made so far."""

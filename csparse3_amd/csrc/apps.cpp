@@ -1,6 +1,6 @@
 // The applications on a factorised handle (include/csparse3_amd.h): low-rank-modified solves (cs3_updates_*), sparse
-// right-hand sides (cs3_sens_*), selected inversion (cs3_selinv_*), and the complex forms of all three behind a complex
-// plan and a handle on its real form.  Host drivers only: plans, checks, workspace, and the order of the launches; the
+// right-hand sides (cs3_sens_*), selected inversion (cs3_selinv_*), the complex forms of all three behind a complex plan
+// and a handle on its real form, and the bilinear forms on the selected inverse (cs3_quad_*).  Host drivers only: plans, checks, workspace, and the order of the launches; the
 // solves themselves are the handle's (run_solve in api.cpp).
 #include <hip/hip_runtime_api.h>
 
@@ -691,6 +691,112 @@ int cselinv_host(cs3_cplx p, cs3_handle h, const char *who, int what, double *ou
     return CS3_OK;
 }
 
+// ---- bilinear forms on the selected inverse: t_i = c_i' A^-1 b_i (quadform.hip) -------------------------------------------
+// The term map (per row, a-major, the zpool offset of Z(pinv Cti[a], pinv Bti[b])), the class of every row by its term
+// count, and the rows in class order.  The pattern has passed the pointer and index checks.
+int quad_build(cs3_handle h, cs3_quad_s &u, int64_t m, const int32_t *Ctp, const int32_t *Cti, const int32_t *Btp, const int32_t *Bti,
+               const char *who)
+{
+    const Symbolic &S = h->S;
+    const SelinvPlan &P = h->selinv.plan;
+    u.m = m; u.same = !Btp;
+    if (!Btp) { Btp = Ctp; Bti = Cti; }
+    u.nnz_c = Ctp[m]; u.nnz_b = Btp[m];
+    u.term_ptr.assign((size_t) m + 1, 0);
+    for (i64 i = 0; i < m; ++i) {
+        u.term_ptr[i + 1] = u.term_ptr[i] + (i64) (Ctp[i + 1] - Ctp[i]) * (i64) (Btp[i + 1] - Btp[i]);
+        if (u.term_ptr[i + 1] >= (i64) INT_MAX - 1023) return bad_arg(who, "2^31 - 1024 terms or more (a row has nnz(c) * nnz(b))");
+    }
+    u.term_pos.resize((size_t) u.term_ptr[m]);
+    u.row_class.resize((size_t) m);
+    std::vector<i32> order[3];
+    for (i64 i = 0; i < m; ++i) {
+        i64 at = u.term_ptr[i];
+        for (i32 a = Ctp[i]; a < Ctp[i + 1]; ++a)
+            for (i32 b = Btp[i]; b < Btp[i + 1]; ++b) {
+                const i64 pos = selinv_position(S, P, S.pinv[Cti[a]], S.pinv[Bti[b]]);
+                if (pos < 0) {
+                    set_error(std::string(who) + ": row " + std::to_string(i) + " pairs columns " + std::to_string(Cti[a]) + " and " +
+                              std::to_string(Bti[b]) + ", an entry of A^-1 outside the pattern of L + U");
+                    return CS3_ERR_ARG;
+                }
+                u.term_pos[(size_t) at++] = pos;
+            }
+        const i64 nt = u.term_ptr[i + 1] - u.term_ptr[i];
+        u.row_class[i] = nt <= QUAD_LANE_TERMS ? 0 : nt <= QUAD_WAVE_TERMS ? 1 : 2;
+        order[u.row_class[i]].push_back((i32) i);
+    }
+    // lanes of one wave run as long as their longest row: the lane rows go by ascending term count
+    std::stable_sort(order[0].begin(), order[0].end(),
+                     [&](i32 x, i32 y) { return u.term_ptr[x + 1] - u.term_ptr[x] < u.term_ptr[y + 1] - u.term_ptr[y]; });
+    u.rows.reserve((size_t) m);
+    for (const auto &cls : order)
+        for (i32 i : cls)
+            u.rows.push_back(QuadRow{u.term_ptr[i], Ctp[i], Ctp[i + 1] - Ctp[i], Btp[i], Btp[i + 1] - Btp[i], i, 0});
+    QuadShape &G = u.shape;
+    G.n_lane = (i64) order[0].size(); G.n_wave = (i64) order[1].size(); G.n_wg = (i64) order[2].size();
+    G.blk_wave = (unsigned) ((G.n_lane + QUAD_BLOCK - 1) / QUAD_BLOCK);
+    G.blk_wg = G.blk_wave + (unsigned) ((G.n_wave + 3) / 4);
+    G.blocks = G.blk_wg + (unsigned) G.n_wg;
+    return CS3_OK;
+}
+
+// the checks of cs3_quad_dev in the header's order; `device`: the caller's forms need Z of the current factors
+int quad_check(const char *who, cs3_handle h, cs3_quad_s *u, bool null_argument, bool device)
+{
+    int rc = guard(h); if (rc) return rc;
+    if (!u || null_argument) return bad_arg(who, "null argument");
+    if (u->h != h) return bad_arg(who, "the plan was made for another handle");
+    if (!h->factored) { set_error(std::string(who) + ": no successful factorisation"); return CS3_ERR_STATE; }
+    if (device && !h->selinv_valid) {
+        set_error(std::string(who) + ": no selected inverse of the current factors (call cs3_selinv_dev after the factorisation)");
+        return CS3_ERR_STATE;
+    }
+    return CS3_OK;
+}
+
+// Tables of the plan in HBM, t for the calls that want none, the partials of the residual reduction: everything a call
+// needs, so that later calls neither allocate nor synchronise.
+int ensure_quad(cs3_handle h, cs3_quad_s *u)
+{
+    if (u->on_device) return CS3_OK;
+    auto &M = u->mem;
+    CS3_HIP(M.rows.upload(u->rows));
+    CS3_HIP(M.pos.upload(u->term_pos));
+    CS3_HIP(M.t.alloc((size_t) (h->batch * u->m)));
+    CS3_HIP(M.parts.alloc((size_t) (4 * h->batch * ((u->m + QUAD_BLOCK - 1) / QUAD_BLOCK))));
+    h->dbg_allocs += 4;
+    u->on_device = true;
+    return CS3_OK;
+}
+
+int quad_run(cs3_handle h, cs3_quad_s *u, const double *cx_dev, const double *bx_dev, double *t_dev, hipStream_t st)
+{
+    if (int rc = ensure_quad(h, u)) return rc;
+    if (u->same) bx_dev = cx_dev;
+    CS3_HIP(launch_quad_forms(h->mem.selinv.z.get(), h->selinv.plan.zpool_doubles, u->mem.rows.get(), (const long long *) u->mem.pos.get(),
+                              u->shape, cx_dev, u->nnz_c, bx_dev, u->nnz_b, u->m, h->batch, t_dev, st));
+    return CS3_OK;
+}
+
+int quad_normres_run(cs3_handle h, cs3_quad_s *u, const double *hx_dev, const double *w_dev, const double *r_dev, double crit_tol,
+                     double *t_dev, double *omega_dev, double *rn_dev, double *summary_dev, hipStream_t st)
+{
+    if (int rc = ensure_quad(h, u)) return rc;
+    if (!t_dev) t_dev = u->mem.t.get();
+    if (int rc = quad_run(h, u, hx_dev, hx_dev, t_dev, st)) return rc;
+    CS3_HIP(launch_quad_normres(t_dev, w_dev, r_dev, crit_tol, u->m, h->batch, omega_dev, rn_dev, u->mem.parts.get(), summary_dev, st));
+    return CS3_OK;
+}
+
+// host array -> a block of the plan (grow-only)
+int quad_stage(DevBuf<double> &buf, const double *src, size_t count)
+{
+    CS3_HIP(buf.reserve(count));
+    if (count) CS3_HIP(hipMemcpy(buf.get(), src, count * sizeof(double), hipMemcpyHostToDevice));
+    return CS3_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1041,6 +1147,115 @@ int cs3_cplx_selinv_diag(cs3_cplx p, cs3_handle h, double *d)
 int cs3_cplx_selinv_thevenin(cs3_cplx p, cs3_handle h, double *T)
 {
     return cselinv_host(p, h, "cs3_cplx_selinv_thevenin", CSELINV_THEVENIN, T);
+}
+
+// ---- bilinear forms on the selected inverse -------------------------------------------------------------------------------
+int cs3_quad_limits(cs3_quad_limits_t *out)
+{
+    if (!out) { set_error("cs3_quad_limits: null output"); return CS3_ERR_ARG; }
+    *out = cs3_quad_limits_t{QUAD_LANE_TERMS, QUAD_WAVE_TERMS, QUAD_BLOCK, QUAD_CHUNK, QUAD_BLOCK};
+    return CS3_OK;
+}
+
+int cs3_quad_plan(cs3_handle h, int64_t m, const int32_t *Ctp, const int32_t *Cti, const int32_t *Btp, const int32_t *Bti, cs3_quadplan *out)
+{
+    const char *who = "cs3_quad_plan";
+    int rc = guard(h); if (rc) return rc;
+    if (!out) return bad_arg(who, "null output");
+    *out = nullptr;
+    if (!Ctp) return bad_arg(who, "null row pointers of C");
+    if (m < 1 || m > (1LL << 30)) return bad_arg(who, "m must be between 1 and 2^30");
+    if ((rc = sens_check_pointers(who, "Ctp", m, Ctp, Cti))) return rc;
+    if (Btp && (rc = sens_check_pointers(who, "Btp", m, Btp, Bti))) return rc;
+    if ((rc = sens_check_indices(who, "C'", h->S.n, m, Ctp, Cti))) return rc;
+    if (Btp && (rc = sens_check_indices(who, "B'", h->S.n, m, Btp, Bti))) return rc;
+    if ((rc = selinv_refuse(h, who))) return rc;
+    if ((rc = ensure_selinv_plan(h))) return rc;
+    try {
+        std::unique_ptr<cs3_quad_s> u(new cs3_quad_s());
+        if ((rc = quad_build(h, *u, m, Ctp, Cti, Btp, Bti, who))) return rc;
+        h->plans.push_back(u.get());
+        u->h = h;
+        *out = u.release();
+    } catch (const std::bad_alloc &) {
+        set_error(std::string(who) + ": out of memory"); return CS3_ERR_ALLOC;
+    }
+    return CS3_OK;
+}
+
+int cs3_quad_free(cs3_quadplan q) { return plan_free(q); }
+
+int cs3_quad_info(cs3_quadplan q, cs3_quad_info_t *out)
+{
+    if (!q || !out) return bad_arg("cs3_quad_info", "null argument");
+    *out = cs3_quad_info_t{q->m, q->nnz_c, q->nnz_b, q->term_ptr[(size_t) q->m], q->same ? 1 : 0, q->shape.n_lane, q->shape.n_wave,
+                           q->shape.n_wg};
+    return CS3_OK;
+}
+
+int cs3_debug_quad_plan(cs3_quadplan q, int32_t *row_class, int64_t *term_ptr, int64_t *term_pos)
+{
+    if (!q) return bad_arg("cs3_debug_quad_plan", "null plan");
+    if (row_class) std::copy(q->row_class.begin(), q->row_class.end(), row_class);
+    if (term_ptr) std::copy(q->term_ptr.begin(), q->term_ptr.end(), term_ptr);
+    if (term_pos) std::copy(q->term_pos.begin(), q->term_pos.end(), term_pos);
+    return CS3_OK;
+}
+
+int cs3_quad_dev(cs3_handle h, cs3_quadplan q, const double *Cx_dev, const double *Bx_dev, double *t_dev, void *stream)
+{
+    int rc = quad_check("cs3_quad_dev", h, q, q && (!t_dev || (q->nnz_c > 0 && !Cx_dev) || (!q->same && q->nnz_b > 0 && !Bx_dev)), true);
+    if (rc) return rc;
+    return quad_run(h, q, Cx_dev, Bx_dev, t_dev, (hipStream_t) stream);
+}
+
+int cs3_quad(cs3_handle h, cs3_quadplan q, const double *Cx, const double *Bx, double *t)
+{
+    int rc = quad_check("cs3_quad", h, q, q && (!t || (q->nnz_c > 0 && !Cx) || (!q->same && q->nnz_b > 0 && !Bx)), false);
+    if (rc) return rc;
+    if (!h->selinv_valid && (rc = cs3_selinv_dev(h, nullptr))) return rc;
+    auto &M = q->mem;
+    const size_t nt = (size_t) (h->batch * q->m);
+    if ((rc = quad_stage(M.cx, Cx, (size_t) (h->batch * q->nnz_c)))) return rc;
+    if (!q->same && (rc = quad_stage(M.bx, Bx, (size_t) (h->batch * q->nnz_b)))) return rc;
+    CS3_HIP(M.out.reserve(nt));
+    if ((rc = quad_run(h, q, M.cx.get(), M.bx.get(), M.out.get(), nullptr))) return rc;
+    CS3_HIP(hipMemcpy(t, M.out.get(), nt * sizeof(double), hipMemcpyDeviceToHost));
+    CS3_HIP(hipDeviceSynchronize());
+    return CS3_OK;
+}
+
+int cs3_quad_normres_dev(cs3_handle h, cs3_quadplan q, const double *Hx_dev, const double *w_dev, const double *r_dev, double crit_tol,
+                         double *t_dev, double *omega_dev, double *rn_dev, double *summary_dev, void *stream)
+{
+    const char *who = "cs3_quad_normres_dev";
+    int rc = quad_check(who, h, q, q && (!summary_dev || !w_dev || !r_dev || (q->nnz_c > 0 && !Hx_dev)), true);
+    if (rc) return rc;
+    if (!q->same) return bad_arg(who, "the plan has a B of its own (the normalised residuals need B = C)");
+    return quad_normres_run(h, q, Hx_dev, w_dev, r_dev, crit_tol, t_dev, omega_dev, rn_dev, summary_dev, (hipStream_t) stream);
+}
+
+int cs3_quad_normres(cs3_handle h, cs3_quadplan q, const double *Hx, const double *w, const double *r, double crit_tol, double *t,
+                     double *omega, double *rn, double *summary)
+{
+    const char *who = "cs3_quad_normres";
+    int rc = quad_check(who, h, q, q && (!summary || !w || !r || (q->nnz_c > 0 && !Hx)), false);
+    if (rc) return rc;
+    if (!q->same) return bad_arg(who, "the plan has a B of its own (the normalised residuals need B = C)");
+    if (!h->selinv_valid && (rc = cs3_selinv_dev(h, nullptr))) return rc;
+    auto &M = q->mem;
+    const size_t nm = (size_t) (h->batch * q->m), ns = 4 * (size_t) h->batch;
+    if ((rc = quad_stage(M.cx, Hx, (size_t) (h->batch * q->nnz_c)))) return rc;
+    if ((rc = quad_stage(M.w, w, nm)) || (rc = quad_stage(M.r, r, nm))) return rc;
+    CS3_HIP(M.out.reserve(3 * nm + ns));                   // t, omega, rn, summary
+    double *o = M.out.get();
+    if ((rc = quad_normres_run(h, q, M.cx.get(), M.w.get(), M.r.get(), crit_tol, o, o + nm, o + 2 * nm, o + 3 * nm, nullptr))) return rc;
+    if (t) CS3_HIP(hipMemcpy(t, o, nm * sizeof(double), hipMemcpyDeviceToHost));
+    if (omega) CS3_HIP(hipMemcpy(omega, o + nm, nm * sizeof(double), hipMemcpyDeviceToHost));
+    if (rn) CS3_HIP(hipMemcpy(rn, o + 2 * nm, nm * sizeof(double), hipMemcpyDeviceToHost));
+    CS3_HIP(hipMemcpy(summary, o + 3 * nm, ns * sizeof(double), hipMemcpyDeviceToHost));
+    CS3_HIP(hipDeviceSynchronize());
+    return CS3_OK;
 }
 
 }  // extern "C"

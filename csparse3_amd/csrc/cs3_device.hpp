@@ -444,6 +444,31 @@ hipError_t launch_cselinv_diag(const double *zpool, long long z_stride, const Cs
 hipError_t launch_cselinv_thevenin(const double *zpool, long long z_stride, const CselinvMaps &M, const double *s, long long n,
                                    long long nnz, long long batch, double *out, hipStream_t st);
 
+// quadform.hip: bilinear forms t_i = c_i' A^-1 b_i on the zpool that cs3_selinv_dev left (cs3_quad_*), and the normalised
+// residuals of a state estimate on top of them (cs3_quad_normres*).
+constexpr int QUAD_BLOCK = 256;                // threads per workgroup of all three kernels (four waves)
+constexpr int QUAD_LANE_TERMS = 32;            // rows with at most this many terms: one lane each
+constexpr int QUAD_WAVE_TERMS = 1024;          // ... up to this many: one wave each, four per workgroup; beyond: one workgroup each
+constexpr int QUAD_CHUNK = 8;                  // lane class: positions loaded together before their entries of Z
+struct QuadRow {                  // one row as k_quad_forms reads it, in class order (lane rows, wave rows, workgroup rows)
+    long long term0;              // its first term in the position table
+    int c0, nc, b0, nb;           // its entries of C and of B in the value arrays (term u: entry u / nb of C, u % nb of B)
+    int row;                      // the caller's row index
+    int pad;
+};
+struct QuadShape {                // rows per class and the first workgroup of the wave and workgroup classes
+    long long n_lane, n_wave, n_wg;
+    unsigned blk_wave, blk_wg, blocks;
+};
+// t [batch][m]: t[b][row] = sum over the row's terms u of (cx[c0 + u / nb] * zpool[pos[term0 + u]]) * bx[b0 + u % nb]
+hipError_t launch_quad_forms(const double *zpool, long long z_stride, const QuadRow *rows, const long long *pos, const QuadShape &G,
+                             const double *cx, long long cx_stride, const double *bx, long long bx_stride, long long m,
+                             long long batch, double *t, hipStream_t st);
+// omega, rn [batch][m] (either may be null), summary [batch][4] = (max rn, its row, sum w r^2, critical rows) from t, w, r
+// [batch][m]; parts [batch][ceil(m / QUAD_BLOCK)][4] is the workspace between the two launches
+hipError_t launch_quad_normres(const double *t, const double *w, const double *r, double crit_tol, long long m, long long batch,
+                               double *omega, double *rn, double *parts, double *summary, hipStream_t st);
+
 // cplxsens.hip: the same around a handle on the real-equivalent form of a complex matrix (cs3_cplx_sens_*), and the
 // complex Schur complement read out of the real one (cs3_cplx_schur_get*).  The tiling constants are those above; a
 // complex row is a pair of real rows, so a scatter workgroup owns half as many.

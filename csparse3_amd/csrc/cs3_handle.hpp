@@ -191,6 +191,27 @@ protected:
 };
 struct cs3_cplx_sens_s : cs3_sens_s {};
 
+// The term map of m bilinear forms t_i = c_i' A^-1 b_i on a handle's selected inverse (cs3_quad_plan): per row, in the
+// caller's order, its class and its terms' zpool offsets (a-major); the rows again in class order as the kernel reads them.
+// The offsets come from the analysis alone, so a plan survives refactorisations.
+struct cs3_quad_s : cs3::HeldPlan {
+    cs3::i64 m = 0, nnz_c = 0, nnz_b = 0;     // nnz_b == nnz_c and every (b0, nb) == (c0, nc) when B = C
+    bool same = false;                        // B = C: one value array
+    std::vector<cs3::i32> row_class;          // per row: 0 lane, 1 wave, 2 workgroup
+    std::vector<cs3::i64> term_ptr, term_pos; // [m + 1], [term_ptr[m]]
+    std::vector<cs3::QuadRow> rows;           // class order; lane rows by ascending term count (stable)
+    cs3::QuadShape shape{};
+    // device copies (uploaded by the first call) and what the calls stage through: t when the caller wants none and the
+    // partials of the normalised residuals (allocated with the tables); the host forms' values, weights, residuals, results
+    struct Memory {
+        cs3::DevBuf<cs3::QuadRow> rows;
+        cs3::DevBuf<cs3::i64> pos;
+        cs3::DevBuf<double> t, parts, cx, bx, w, r, out;
+    } mem;
+protected:
+    void reset_memory() override { mem = Memory(); }
+};
+
 // What apps.cpp calls of api.cpp.
 namespace cs3 {
 

@@ -304,3 +304,49 @@ def dense_block_matrix(n=700, nd=300, seed=1):
     bi, bj = np.meshgrid(idx, idx, indexing="ij")
     ei, ej = _unique_edges(n, np.concatenate([ei, bi.ravel()]), np.concatenate([ej, bj.ravel()]))
     return _graph_to_matrix(n, ei, ej, rng)
+
+
+def se_case(nbus, nedges, seed, inj_share=0.5, ncrit=2):
+    """Measurement Jacobian of a DC-type state estimate (states: the nbus bus angles) on _connected_graph.
+
+    The last `ncrit` buses are pendant: each hangs on one branch off a bus of the meshed part (nbus - ncrit buses,
+    nedges - ncrit branches).  Rows, in this order: one flow row per branch, (b, -b) at its two buses, b = 1/x,
+    x ~ U(0.5, 2) (scaled so that cond_1 of H' W H stays below 1e4 at a few hundred buses); then one row per bus of the meshed part -- an injection row (the sum of its branches' b at the bus,
+    -b at each neighbour: degree + 1 entries) on a share `inj_share` of them, a magnitude row (a single 1) on the rest.
+    The buses that carry a pendant branch have magnitude rows and a pendant bus has no row of its own, so the flow row of
+    a pendant branch is the only row that sees its pendant bus: a designed critical measurement.  Weights w = 10^U(0, 2).
+    -> (m, n, Hp, Hi, Hx, w, critical_rows): H is m x n in CSC, rows sorted, no duplicates."""
+    rng = np.random.default_rng(seed)
+    nb = nbus - ncrit
+    assert ncrit >= 1 and nb >= 2 and nedges - ncrit >= nb - 1
+    ei, ej = _connected_graph(nb, nedges - ncrit, rng)
+    is_inj = rng.random(nb) < inj_share
+    hosts = rng.choice(np.flatnonzero(~is_inj) if (~is_inj).sum() >= ncrit else np.arange(nb), size=ncrit, replace=False)
+    is_inj[hosts] = False
+    ei = np.concatenate([ei, hosts]).astype(np.int64)
+    ej = np.concatenate([ej, nb + np.arange(ncrit)]).astype(np.int64)
+    nbr = len(ei)
+    b = 1.0 / rng.uniform(0.5, 2.0, size=nbr)
+    flow = np.arange(nbr)
+    rows = [flow, flow]
+    cols = [ei, ej]
+    vals = [b, -b]
+    bus_row = nbr + np.arange(nb)
+    diag = np.zeros(nbus)
+    np.add.at(diag, ei, b)
+    np.add.at(diag, ej, b)
+    inj = np.flatnonzero(is_inj)
+    rows.append(bus_row[inj]); cols.append(inj); vals.append(diag[inj])
+    for me, other in ((ei, ej), (ej, ei)):
+        k = np.flatnonzero((me < nb) & is_inj[np.minimum(me, nb - 1)])
+        rows.append(bus_row[me[k]]); cols.append(other[k]); vals.append(-b[k])
+    mag = np.flatnonzero(~is_inj)
+    rows.append(bus_row[mag]); cols.append(mag); vals.append(np.ones(len(mag)))
+    rows, cols, vals = np.concatenate(rows), np.concatenate(cols), np.concatenate(vals)
+    m = nbr + nb
+    order = np.lexsort((rows, cols))
+    Hp = np.zeros(nbus + 1, dtype=np.int64)
+    np.add.at(Hp, cols + 1, 1)
+    w = 10.0 ** rng.uniform(0.0, 2.0, size=m)
+    return (m, nbus, np.cumsum(Hp).astype(np.int32), rows[order].astype(np.int32), vals[order].astype(np.float64), w,
+            np.arange(nbr - ncrit, nbr))

@@ -571,6 +571,85 @@ int cs3_selinv_diag(cs3_handle h, double *d);
 int cs3_selinv_factors(cs3_handle h, int64_t b, double *Zl, double *Zu);
 int64_t cs3_debug_selinv_plan(cs3_handle h, int32_t *front, int32_t *launch, int64_t *entry_map, int64_t *diag_map);
 
+/* ---- bilinear forms on the selected inverse: t_i = c_i' A^-1 b_i, the bad-data test of a state estimate -----
+ * After a state estimate has been solved with the gain matrix G = H' W H, the largest-normalised-residual test needs
+ * Omega_ii = 1/w_i - h_i' G^-1 h_i for every measurement row h_i of H.  Every pair of columns that occurs in one row of H is
+ * an entry of H' W H, so all of diag(H G^-1 H') is a short sum over entries that cs3_selinv_dev has already computed: m
+ * gathers, not m solves.  The same form with the incidence rows c_l of a real network gives Z_ii + Z_jj - Z_ij - Z_ji of
+ * every branch (the self-PTDF and LODF denominators).  In general: m sparse row pairs (c_i, b_i) whose index pairs all lie
+ * on the pattern of L + U, and
+ *     t_i = sum over the entries a of c_i and b of b_i of (c_a * Z(Cti[a], Bti[b])) * b_b,   Z = A^-1,
+ * read from the held selected inverse in one launch.
+ *
+ * (m, Ctp, Cti) is the CSC pattern of C', that is the rows of C, as cs3_sens_plan takes Ct; (m, Btp, Bti) the same for B.
+ * Btp == NULL: B = C, pattern and values (one value array at solve time).  Rows may be unsorted, empty (t_i = +0) or hold a
+ * column twice: the terms simply add.
+ *
+ * cs3_quad_limits: the term counts up to which a row is summed by one lane and by one wave (beyond: by one workgroup), the
+ *   threads per workgroup, the positions a lane loads together, the rows per workgroup of the residual reduction.  No
+ *   launch has a grid cap: the grids grow with the rows.  Needs no device.
+ * cs3_quad_plan: host, from the analysis alone, needs no device.  Checks, in this order: a null handle, out pointer or
+ *   Ctp, m < 1 or m > 2^30; pointer arrays not monotone from 0 (or a null index array behind one); an index outside
+ *   [0, n); a Schur, matched or matrix-interleaved handle (the refusals of cs3_selinv_*); 2^31 - 1024 terms or more
+ *   (a row has nnz(c_i) * nnz(b_i)); a pair (Cti[a], Bti[b]) outside the pattern of L + U, where the message names the row
+ *   and the two columns: all CS3_ERR_ARG.  The plan stores, per row and a-major (all b of the first a, then the second a),
+ *   the offset of Z(Cti[a], Bti[b]) in the handle's block of Z, and the rows sorted into the three classes.
+ * cs3_quad_info: m, nnz(C), nnz(B), the terms, whether B = C, the rows per class.
+ * cs3_quad_dev: Cx_dev / Bx_dev [batch][nnz] the values in the plan's entry order (Bx_dev is ignored when B = C), t_dev
+ *   [batch][m].  Asynchronous on `stream`.  Checks, in this order: null arguments, a plan made for another handle (or whose
+ *   handle was freed): CS3_ERR_ARG; no successful factorisation: CS3_ERR_STATE; no selected inverse of the current factors
+ *   (before cs3_selinv_dev, or after any later factorisation): CS3_ERR_STATE.  The first call with a plan uploads its
+ *   tables; later calls neither allocate nor synchronise.
+ * cs3_quad: the same from host arrays (synchronises); computes Z first when the handle does not hold that of the current
+ *   factors; the same bits.
+ * cs3_quad_normres_dev (plans with B = C only, CS3_ERR_ARG otherwise): with Hx_dev [batch][nnz] the values of the rows,
+ *   w_dev and r_dev [batch][m] the weights and the residuals, per row
+ *       t_i as above,  omega_i = 1/w_i - t_i,  rn_i = |r_i| / sqrt(omega_i),
+ *   but rn_i = 0 where 1 - w_i t_i <= crit_tol: a critical measurement, whose residual carries no information.
+ *   summary_dev [batch][4] = (the largest rn, its row as a double, J = sum w_i (r_i r_i) over all rows, the number of
+ *   critical rows).  Ties take the lowest row; a NaN rn ranks above every number.  Any of t_dev, omega_dev, rn_dev may be
+ *   NULL.  Two launches beyond the forms: per-workgroup partials over 256 consecutive rows, then one closing workgroup
+ *   per matrix.  Checks and state rules of cs3_quad_dev.
+ * cs3_quad_normres: the same from and to host arrays (t, omega, rn may be NULL); computes Z first when needed.
+ * cs3_debug_quad_plan: for arrays that are not null, the class of every row (0 lane, 1 wave, 2 workgroup), term_ptr
+ *   [m + 1] and the offsets term_pos [term_ptr[m]].  Needs no device.
+ *
+ * Every sum has a fixed order, (c * z) * b with both products rounded, and there are no atomics: the same bits on every run,
+ * from both forms, and for a matrix of a batch the bits it gets alone.  A lane-class row adds its terms in order; a
+ * wave-class row gives lane l the terms l, l + 64, ... in order, then adds lane l + off into lane l for off = 32, 16, ..., 1;
+ * a workgroup-class row does the same with thread j of 256 taking terms j, j + 256, ..., then adds the four waves in order.
+ * The reductions of cs3_quad_normres* use the same tree over rows 256 g + j, and thread j of the closing workgroup takes
+ * the partials j, j + 256, ... in order.
+ * A plan survives refactorisations of its handle.  Plans and handle may be freed in either order: freeing the handle
+ * releases the device memory of its plans, which can then only be freed.
+ *
+ * Out of scope: a complex form (complex C and B behind a complex plan); matched, Schur and matrix-interleaved handles; pairs
+ * outside the pattern of L + U;
+ * off-diagonal entries of C A^-1 B' (cs3_sens_* covers them); removing the bad measurement and estimating again
+ * (cs3_updates_* is the tool); sharding. */
+/* (the plan's type is cs3_quadplan: cs3_quad is the host form of the call) */
+typedef struct cs3_quad_s *cs3_quadplan;
+typedef struct cs3_quad_limits_t {
+    int64_t lane_max_terms;    /* rows with at most this many terms: one lane each */
+    int64_t wave_max_terms;    /* ... up to this many: one wave each; beyond: one workgroup each */
+    int64_t block;             /* threads per workgroup of every kernel */
+    int64_t lane_chunk;        /* lane class: positions loaded together before their entries of Z */
+    int64_t reduce_rows;       /* rows per workgroup of the partial reduction of cs3_quad_normres* */
+} cs3_quad_limits_t;
+typedef struct cs3_quad_info_t { int64_t m, nnz_c, nnz_b, nterms, same_operand, rows_lane, rows_wave, rows_workgroup; } cs3_quad_info_t;
+int cs3_quad_limits(cs3_quad_limits_t *out);
+int cs3_quad_plan(cs3_handle h, int64_t m, const int32_t *Ctp, const int32_t *Cti, const int32_t *Btp, const int32_t *Bti,
+                  cs3_quadplan *out);
+int cs3_quad_free(cs3_quadplan q);
+int cs3_quad_info(cs3_quadplan q, cs3_quad_info_t *out);
+int cs3_quad_dev(cs3_handle h, cs3_quadplan q, const double *Cx_dev, const double *Bx_dev, double *t_dev, void *stream);
+int cs3_quad(cs3_handle h, cs3_quadplan q, const double *Cx, const double *Bx, double *t);
+int cs3_quad_normres_dev(cs3_handle h, cs3_quadplan q, const double *Hx_dev, const double *w_dev, const double *r_dev, double crit_tol,
+                         double *t_dev, double *omega_dev, double *rn_dev, double *summary_dev, void *stream);
+int cs3_quad_normres(cs3_handle h, cs3_quadplan q, const double *Hx, const double *w, const double *r, double crit_tol, double *t,
+                     double *omega, double *rn, double *summary);
+int cs3_debug_quad_plan(cs3_quadplan q, int32_t *row_class, int64_t *term_ptr, int64_t *term_pos);
+
 /* ---- Schur complements: factor the interior, return the dense border -----
  * A partial factorisation, as cuDSS, PARDISO, MUMPS and SuperLU_DIST offer it: the caller names ns variables that are NOT
  * eliminated (boundary buses of a network equivalent, the constraint rows of a saddle-point system [[H, G'], [G, 0]], the
