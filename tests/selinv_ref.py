@@ -1,7 +1,8 @@
 """References for the selected inversion (cs3_selinv_*): the dense inverse, and a NumPy restatement of the per-front
 recurrence driven by the handle's ordering, supernodes, front structures and factors -- the arithmetic selinv.hip does,
 front by front, so that a wrong entry can be traced to its front.  The restatement is itself held to the dense inverse
-(tests/test_selinv_cpu.py).  Used by tests/test_selinv_cpu.py and tests/test_gpu_selinv.py.
+(tests/test_selinv_cpu.py).  Used by tests/test_selinv_cpu.py and tests/test_gpu_selinv.py, and, with the error measure
+per block of a front (front_block_errors), by tests/test_selinv_edge_cases_cpu.py and tests/test_gpu_selinv_edges.py.
 """
 import numpy as np
 
@@ -81,6 +82,50 @@ def restated_positions(hip, F, Ap, Ai, front):
     entry = np.array([position(int(pinv[Ai[p]]), int(pinv[cols[p]])) for p in range(int(Ap[n]))], dtype=np.int64)
     diag = np.array([position(int(pinv[i]), int(pinv[i])) for i in range(n)], dtype=np.int64)
     return entry, diag, total
+
+
+def front_block_errors(hip, F, Zl, Zu, Zref):
+    """max |Z - Z_ref| / max |Z_ref| over every block of every front ALONE, so that a wrong block cannot hide behind the
+    larger entries of another one.  (Zl, Zu) are F.inverse_on_factors() -- Z at the positions of factors()' L and U, in
+    pivot-order labels, Zu None for Cholesky -- and Zref is the dense inverse in the caller's labels.  The blocks of the
+    front of supernode s with pivots P and update rows C: 'PP' (the stored entries of Z(P, P): the lower triangle from Zl,
+    the upper one from Zu), 'CP' (Z(C, P), from Zl) and 'PC' (Z(P, C), from Zu; absent for Cholesky).
+    -> [(supernode, r, w, block, error)] for the blocks that hold an entry; anything not finite in a block makes it inf."""
+    sn_ptr, _, _, st = fronts(hip, F)
+    n, ns = F.n, len(st)
+    q = F.ordering()["q"]
+    Zp = Zref[np.ix_(q, q)]
+    col2sn = np.repeat(np.arange(ns), np.diff(sn_ptr))
+    Lp, Li, _, Up, Ui, _ = F.factors(values=False)
+    num = {b: np.zeros(ns) for b in ("PP", "CP", "PC")}
+    den = {b: np.zeros(ns) for b in ("PP", "CP", "PC")}
+    parts = [(Zl, Lp, Li, "CP", False)] + ([(Zu, Up, Ui, "PC", True)] if Zu is not None else [])
+    for got, Gp, Gi, off, upper in parts:
+        nz = int(Gp[n])
+        rows, cols = np.asarray(Gi[:nz]), np.repeat(np.arange(n), np.diff(Gp))
+        want = Zp[rows, cols]
+        got = np.asarray(got[:nz], dtype=np.float64)
+        diff = np.where(np.isfinite(got), np.abs(got - want), np.inf)
+        piv = rows if upper else cols                          # the label that is a pivot of the front: min(row, col)
+        assert ((rows <= cols) if upper else (rows >= cols)).all()
+        sn = col2sn[piv]
+        inside = col2sn[rows] == col2sn[cols]
+        for block, mask in (("PP", inside), (off, ~inside)):
+            np.maximum.at(num[block], sn[mask], diff[mask])
+            np.maximum.at(den[block], sn[mask], np.abs(want[mask]))
+    out = []
+    for s in range(ns):
+        r, w = len(st[s]), int(sn_ptr[s + 1] - sn_ptr[s])
+        for block in ("PP", "CP", "PC"):
+            if den[block][s] > 0.0 or num[block][s] > 0.0:
+                out.append((s, r, w, block, float(num[block][s] / den[block][s]) if den[block][s] > 0.0 else np.inf))
+    return out
+
+
+def worst_block(blocks):
+    """The block of front_block_errors() with the largest error, as text."""
+    s, r, w, block, err = max(blocks, key=lambda b: b[4])
+    return "%.3e in Z_%s of front %d (r = %d, w = %d)" % (err, block, s, r, w)
 
 
 def dense_factors(F, b=0):
