@@ -396,7 +396,7 @@ int read_status(cs3_handle h, hipStream_t st)
     CS3_HIP(hipStreamSynchronize(st));
     if (word[3] != 0) {
         // a wait inside the step was given up: a wave of a shared elimination never saw the multipliers of its partner
-        // (eliminate_pair in k_big_step / the shared fronts of the forest).  Whatever was computed behind that point is
+        // (eliminate_parts in k_big_step / the shared fronts of the forest).  Whatever was computed behind that point is
         // not to be used.
         CS3_HIP(hipMemsetAsync(h->D.status + 3, 0, sizeof(int), st));
         h->factored = false;

@@ -109,7 +109,7 @@ __device__ __forceinline__ void first_rejected(bool rej, int col, bool &bad, int
     bad = bad | rej;
 }
 
-// ---- multipliers handed from wave to wave through LDS (eliminate_pair in k_big_step, the shared fronts of forest.hip) ----
+// ---- multipliers handed from wave to wave through LDS (eliminate_parts in k_big_step, the shared fronts of forest.hip) ----
 // The producer stores a vector of multipliers, then the number of pivots handed over so far; the consumer polls that number.
 // LDS operations of one wave complete in order, so no fence sits on the producer's pivot chain (a release fence per pivot
 // measured 350 instead of 275 cycles per pivot); the counter is accessed with relaxed workgroup-scope atomics so that the
@@ -366,7 +366,9 @@ __device__ __forceinline__ int lane_limit(bool ok, int lim)
 
 // What a tile of k_big_step addresses its operands with: the front as bytes, a column in bytes (ld8; as an offset: ldu),
 // the block step [kb, kb + bw) and the previous panel [kp, kp + pw), the tile's rows and columns, the thread's wave (a
-// scalar) and lane indices, and its offsets: entry (l32, h5) of a panel with 32 rows, row l64 of the tile's rows / columns.
+// scalar, 0 .. 7) and lane indices, and its offsets: entry (l32, h5) of a panel with 32 rows (h5 = tid / 32, 0 .. 15), row
+// l64 of the tile's rows / columns.
+constexpr int BIG_THREADS = 512;              // k_big_step: eight waves per workgroup
 struct BigTile {
     char *Fb;
     long long ld8;
@@ -376,44 +378,45 @@ struct BigTile {
 };
 
 // The operand panels of the previous block step, RAW: where an entry does not exist the offset is 0 (a panel's first
-// entry always exists) and the caller masks the value where it uses it.  Entry e = tid + 256 q of a panel is
-// (e % 64, e / 64) = (l64, wu + 4 q) or (e % 32, e / 32) = (l32, h5 + 8 q).
+// entry always exists) and the caller masks the value where it uses it.  Entry e = tid + 512 q of a panel is
+// (e % 64, e / 64) = (l64, wu + 8 q) or (e % 32, e / 32) = (l32, h5 + 16 q).
 // The 64-wide panels of a tile: ra (A: the L panel of the tile's rows) and rb (B: the U panel of its columns; Cholesky:
 // the L panel of its columns).  A block-column tile asks for ra only and a block-row tile for rb only: the other panel of
 // theirs is the diagonal block's (big_diag_panels), entry for entry.
 template <int KIND, bool A, bool B>
-__device__ __forceinline__ void big_tile_panels(const BigTile &t, double (&ra)[8], double (&rb)[8])
+__device__ __forceinline__ void big_tile_panels(const BigTile &t, double (&ra)[4], double (&rb)[4])
 {
-    const char *pa = t.Fb + 8ll * t.row0 + t.kp * t.ld8;       // L(row0 + l64, kp + wu + 4 q)
+    const char *pa = t.Fb + 8ll * t.row0 + t.kp * t.ld8;       // L(row0 + l64, kp + wu + 8 q)
     const char *pb = (KIND == CS3_LU) ? t.Fb + 8ll * t.kp + t.col0 * t.ld8 : t.Fb + 8ll * t.col0 + t.kp * t.ld8;
-    const int lim_b = lane_limit(t.l32 < t.pw, t.ncol - t.h5); // LU: entry (l32, h5 + 8 q) exists iff 8 q < lim_b
+    const int lim_b = lane_limit(t.l32 < t.pw, t.ncol - t.h5); // LU: entry (l32, h5 + 16 q) exists iff 16 q < lim_b
 #pragma unroll
-    for (int q = 0; q < 8; ++q) {
-        const unsigned k_off = t.wu + 4 * q < t.pw ? (unsigned) (t.wu + 4 * q) * t.ldu : 0u;    // (a scalar)
+    for (int q = 0; q < 4; ++q) {
+        const unsigned k_off = t.wu + 8 * q < t.pw ? (unsigned) (t.wu + 8 * q) * t.ldu : 0u;    // (a scalar)
         if (A) ra[q] = load_at(pa, t.o_row + k_off);
-        if (B) rb[q] = load_at(pb, (KIND == CS3_LU) ? (8 * q < lim_b ? t.o_kj + 8 * q * t.ldu : 0u) : t.o_col + k_off);
+        if (B) rb[q] = load_at(pb, (KIND == CS3_LU) ? (16 * q < lim_b ? t.o_kj + 16 * q * t.ldu : 0u) : t.o_col + k_off);
     }
 }
 
-// The 32-wide panels of the diagonal block D = F[kb:ke, kb:ke], for the tiles that need it: rad (L(kb + l32, kp + h5 + 8 q))
-// and rbd (U(kp + l32, kb + h5 + 8 q); Cholesky: rad again)
+// The 32-wide panels of the diagonal block D = F[kb:ke, kb:ke], for the tiles that need it: rad (L(kb + l32, kp + h5 + 16 q))
+// and rbd (U(kp + l32, kb + h5 + 16 q); Cholesky: rad again)
 template <int KIND>
-__device__ __forceinline__ void big_diag_panels(const BigTile &t, double (&rad)[4], double (&rbd)[4])
+__device__ __forceinline__ void big_diag_panels(const BigTile &t, double (&rad)[2], double (&rbd)[2])
 {
     const char *pad = t.Fb + 8ll * t.kb + t.kp * t.ld8;
     const char *pbd = (KIND == CS3_LU) ? t.Fb + 8ll * t.kp + t.kb * t.ld8 : pad;
     const int lim_ad = lane_limit(t.l32 < t.bw, t.pw - t.h5);
     const int lim_bd = (KIND == CS3_LU) ? lane_limit(t.l32 < t.pw, t.bw - t.h5) : lim_ad;
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        rad[q] = load_at(pad, 8 * q < lim_ad ? t.o_kj + 8 * q * t.ldu : 0u);
-        rbd[q] = load_at(pbd, 8 * q < lim_bd ? t.o_kj + 8 * q * t.ldu : 0u);
+    for (int q = 0; q < 2; ++q) {
+        rad[q] = load_at(pad, 16 * q < lim_ad ? t.o_kj + 16 * q * t.ldu : 0u);
+        rbd[q] = load_at(pbd, 16 * q < lim_bd ? t.o_kj + 16 * q * t.ldu : 0u);
     }
 }
 
 // NCB of the tile's accumulators, the column blocks cb0 .. cb0 + NCB - 1 (cb0 a scalar): acc[c][v] = F(row0 + ti,
 // col0 + 16 (cb0 + c) + 4 v + mq), RAW in the same way (o_acc: the thread's entry at cb = v = 0).  A plain trailing tile
-// takes all four, a block-column tile the two that its 32 columns fill, a wave of a block-row tile the two it is dealt.
+// wave takes two: of a plain trailing tile and of a block-row tile the two it is dealt, of a block-column tile the two that
+// the tile's 32 columns fill.
 template <int NCB, class V4>
 __device__ __forceinline__ void big_tile_accumulators(const BigTile &t, int ti, int mq, int cb0, V4 (&acc)[NCB])
 {
@@ -427,7 +430,25 @@ __device__ __forceinline__ void big_tile_accumulators(const BigTile &t, int ti, 
             acc[c][v] = load_at(pc, 16 * c + 4 * v < lim_c ? o_acc + (unsigned) (16 * (cb0 + c) + 4 * v) * t.ldu : 0u);
 }
 
-// ... and of the diagonal block, for a tile that needs it: dacc[v] = F(kb + dr, kb + j0 + 4 v + mq)
+// The two accumulator blocks of a wave of a block-column or block-row tile, whatever its role: acc[c][v] = M(ri, j0 + 16 c +
+// 4 v + mq) of the nr x nc matrix M that starts at pm (all of them scalars but ri) -- the tile for a tile wave, the diagonal
+// block for a D wave, which uses acc[0] alone (acc[1] then holds the entries of D's next sub-block, or its first entry).
+// ONE code path for both roles: with the loads behind a branch on the role, the D waves waited for three of their panel
+// loads before they issued their accumulator loads (a wave's registers were the other role's pending destinations to the
+// compiler's wait counting): not every load of theirs was out before their first wait.
+template <class V4>
+__device__ __forceinline__ void big_wave_accumulators(const BigTile &t, const char *pm, int ri, int nr, int nc, int mq, int j0, V4 (&acc)[2])
+{
+    const unsigned o_acc = 8u * (unsigned) ri + (unsigned) mq * t.ldu;
+    const int lim = lane_limit(ri < nr, nc - mq - j0);         // column j0 + 16 c + 4 v + mq exists iff 16 c + 4 v < lim
+#pragma unroll
+    for (int c = 0; c < 2; ++c)
+#pragma unroll
+        for (int v = 0; v < 4; ++v)
+            acc[c][v] = load_at(pm, 16 * c + 4 * v < lim ? o_acc + (unsigned) (j0 + 16 * c + 4 * v) * t.ldu : 0u);
+}
+
+// ... and of the diagonal block, for the diagonal tile: dacc[v] = F(kb + dr, kb + j0 + 4 v + mq)
 template <class V4>
 __device__ __forceinline__ void big_diag_accumulator(const BigTile &t, int dr, int mq, int j0, V4 &dacc)
 {
@@ -447,31 +468,39 @@ struct BigLds {
 
 // A panel tile of k_big_step (the diagonal tile, a block-column tile: bj == 0, or a block-row tile) up to the point where
 // the updated diagonal block D (identity-padded past bw) and the tile T meet in LDS: the update of the previous panel,
-// for the 16 x 16 blocks that the 32-wide panel uses and no others.  Every kind issues ALL of its loads before its first
-// wait (the kernel's header says why):
-//   diagonal tile (0, 0)  D alone: its two 32-wide panels and one accumulator, 8 MFMAs per wave (it has no tile of its own:
-//                         T is only read for bi > 0 or bj > 0), and the copy-home of the parked block (send_home)
-//   block-column tile     D, and its 32 columns: the L panel of its rows and acc[0 .. 1].  Its U panel IS D's (col0 = kb,
-//                         ncol = bw: Bs would repeat Bd entry for entry), so the tile MFMAs read Bd: 16 + 8 per wave
-//   block-row tile (LU)   D, and its 32 rows: the U panel of its columns and two accumulators per wave -- wave wv takes row
-//                         block wv & 1 (the rows of its D sub-block: ONE B operand feeds both) and the column blocks
-//                         2 (wv >> 1), 2 (wv >> 1) + 1, and writes them to T[col][row] itself.  Its L panel is D's
-//                         (row0 = kb, nrow = bw): Ad.  16 + 8 MFMAs in every wave
+// for the 16 x 16 blocks that the 32-wide panel uses and no others, dealt to eight waves.  All eight load and stage the
+// operand panels (entry tid + 512 q); the accumulators go by role, and the role is a scalar (t.wu): tw = wv & 3 is a
+// wave's place among the four of its role.  Every kind issues ALL of its loads before its first wait (the kernel's header
+// says why):
+//   diagonal tile (0, 0)  D alone: waves 0 .. 3 own its four sub-blocks (tw & 1, tw >> 1), 8 MFMAs each (it has no tile of
+//                         its own: T is only read for bi > 0 or bj > 0); waves 4 .. 7 load and stage, and all eight
+//                         send the parked block home (send_home)
+//   block-column tile     waves 0 .. 3: the tile's 32 columns, row block tw with acc[0 .. 1], 16 MFMAs.  Its U panel IS D's
+//                         (col0 = kb, ncol = bw: Bs would repeat Bd entry for entry), so the tile MFMAs read Bd.  Waves
+//                         4 .. 7: D's four sub-blocks, 8 MFMAs
+//   block-row tile (LU)   waves 0 .. 3: the tile's 32 rows -- wave tw takes row block tw & 1 (ONE B operand feeds both of its
+//                         chains) and the column blocks 2 (tw >> 1), 2 (tw >> 1) + 1, and writes them to T[col][row]
+//                         itself, 16 MFMAs.  Its L panel is D's (row0 = kb, nrow = bw): Ad.  Waves 4 .. 7: D, 8 MFMAs
 // Every entry's sum keeps its terms, their order (k0 upward, the MFMA's own order inside a group of four), its operand
 // roles (A = U, B = -L) and the zero padding past pw whichever wave forms it: the bits are those of the full 64 x 64 tile
-// path that the plain trailing tiles take.  In the block-column and block-row tiles the D chain stands in the k loop beside
-// the two tile chains (three independent accumulators per step), not behind them.  stamp(p): the profiling stamps 0 .. 2.
+// path.  The D chain runs in waves of its own beside the tile chains, not behind them.  stamp(p): the profiling stamps
+// 0 .. 2 (thread 0: a tile wave of the block-column tile, a D wave of the diagonal tile).
 template <int KIND, class Home, class Stamp>
 __device__ __forceinline__ void big_panel_tile(const BigTile &t, const BigLds &s, int tid, bool diag, bool col, Home send_home, Stamp stamp)
 {
     auto &As = s.As; auto &Bs = s.Bs; auto &Ad = s.Ad; auto &Bd = s.Bd; auto &D = s.D; auto &T = s.T;
     const int kb = t.kb, bw = t.bw, pw = t.pw, nrow = t.nrow, ncol = t.ncol;
-    const int wv = tid >> 6, mi = tid & 15, mq = (tid >> 4) & 3;
-    const int ti = 16 * wv + mi;                    // tile row of the block-column tile's accumulators
-    // D: wave wv owns the 16 x 16 sub-block (wv & 1, wv >> 1): dacc[v] = D(dr, dc0 + 4 v)
-    const int dr = 16 * (wv & 1) + mi, dc0 = 16 * (wv >> 1) + mq;
-    double rad[4] = {0.0, 0.0, 0.0, 0.0}, rbd[4] = {0.0, 0.0, 0.0, 0.0};
-    cs3_double4 dacc = {0.0, 0.0, 0.0, 0.0};
+    const int tw = (tid >> 6) & 3, mi = tid & 15, mq = (tid >> 4) & 3;
+    const int twu = t.wu & 3;                       // tw, as a scalar
+    const bool own_d = diag ? t.wu < 4 : t.wu >= 4; // (a scalar) my wave forms a sub-block of D
+    const int ti = 16 * tw + mi;                    // tile row of the block-column tile's accumulators
+    // D: wave tw of its four owns the 16 x 16 sub-block (tw & 1, tw >> 1): dacc[v] = D(dr, dc0 + 4 v)
+    const int dr = 16 * (tw & 1) + mi, dc0 = 16 * (tw >> 1) + mq;
+    double rad[2] = {0.0, 0.0}, rbd[2] = {0.0, 0.0};
+    // a wave's two accumulators; a D wave keeps its sub-block in the first (the loads of both roles are one code path)
+    cs3_double4 acc[2] = {{0.0, 0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}};
+    cs3_double4 &dacc = acc[0];
+    const char *pdiag = t.Fb + 8ll * t.kb + t.kb * t.ld8;
     auto mask_d = [&]() {
 #pragma unroll
         for (int v = 0; v < 4; ++v)
@@ -479,12 +508,17 @@ __device__ __forceinline__ void big_panel_tile(const BigTile &t, const BigLds &s
     };
     auto stage_d = [&]() {
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int e = tid + 256 * q;
+        for (int q = 0; q < 2; ++q) {
+            const int e = tid + BIG_THREADS * q;
             { const int i = e % BIG_NB, k = e / BIG_NB; Ad[k][i] = (k < pw && i < bw) ? -rad[q] : 0.0; }
             if (KIND == CS3_LU) { const int k = e % BIG_NB, j = e / BIG_NB; Bd[k][j] = (k < pw && j < bw) ? rbd[q] : 0.0; }
             else { const int j = e % BIG_NB, k = e / BIG_NB; Bd[k][j] = (k < pw && j < bw) ? rbd[q] : 0.0; }
         }
+    };
+    auto update_d = [&]() {
+#pragma unroll
+        for (int k0 = 0; k0 < BIG_NB; k0 += 4)
+            dacc = __builtin_amdgcn_mfma_f64_16x16x4f64(Bd[k0 + mq][16 * (tw >> 1) + mi], Ad[k0 + mq][dr], dacc, 0, 0, 0);
     };
     auto put_d = [&]() {                            // the updated D, identity-padded past bw
 #pragma unroll
@@ -495,44 +529,41 @@ __device__ __forceinline__ void big_panel_tile(const BigTile &t, const BigLds &s
     };
     if (diag) {                                     // ---- diagonal tile
         if (kb > 0) big_diag_panels<KIND>(t, rad, rbd);
-        big_diag_accumulator(t, dr, mq, 16 * (t.wu >> 1), dacc);
+        if (own_d) big_diag_accumulator(t, dr, mq, 16 * (twu >> 1), dacc);
         __builtin_amdgcn_sched_barrier(0);
         stamp(0);
         send_home();
-        mask_d();
+        if (own_d) mask_d();
         if (kb > 0) stage_d();
         __syncthreads();
         stamp(1);
-        if (kb > 0) {
-#pragma unroll
-            for (int k0 = 0; k0 < BIG_NB; k0 += 4)
-                dacc = __builtin_amdgcn_mfma_f64_16x16x4f64(Bd[k0 + mq][16 * (wv >> 1) + mi], Ad[k0 + mq][dr], dacc, 0, 0, 0);
-        }
+        if (own_d && kb > 0) update_d();
         stamp(2);
-        put_d();
+        if (own_d) put_d();
     } else if (col) {                               // ---- block-column tile: D and T[row][col], 32 columns
-        double ra[8], rb[8];                        // (rb stays unused)
-        cs3_double4 acc[2];
+        double ra[4], rb[4];                        // (rb stays unused)
         if (kb > 0) {
             big_tile_panels<KIND, true, false>(t, ra, rb);
             big_diag_panels<KIND>(t, rad, rbd);
         }
-        big_tile_accumulators<2>(t, ti, mq, 0, acc);
-        big_diag_accumulator(t, dr, mq, 16 * (t.wu >> 1), dacc);
+        big_wave_accumulators(t, own_d ? pdiag : t.Fb + 8ll * t.row0 + t.col0 * t.ld8, own_d ? dr : ti, own_d ? bw : nrow, ncol,
+                              mq, own_d ? 16 * (twu >> 1) : 0, acc);     // (ncol = bw)
         __builtin_amdgcn_sched_barrier(0);
         stamp(0);
+        if (own_d) mask_d();
+        else {
 #pragma unroll
-        for (int cb = 0; cb < 2; ++cb)
+            for (int cb = 0; cb < 2; ++cb)
 #pragma unroll
-            for (int v = 0; v < 4; ++v) {
-                const int j = 16 * cb + mq + 4 * v;
-                if (!(ti < nrow && j < ncol)) acc[cb][v] = 0.0;
-            }
-        mask_d();
+                for (int v = 0; v < 4; ++v) {
+                    const int j = 16 * cb + mq + 4 * v;
+                    if (!(ti < nrow && j < ncol)) acc[cb][v] = 0.0;
+                }
+        }
         if (kb > 0) {
 #pragma unroll
-            for (int q = 0; q < 8; ++q) {
-                const int e = tid + 256 * q;
+            for (int q = 0; q < 4; ++q) {
+                const int e = tid + BIG_THREADS * q;
                 const int i = e % 64, k = e / 64;
                 As[k][i] = (k < pw && i < nrow) ? -ra[q] : 0.0;     // negated: the MFMA accumulates acc += U' (-L)'
             }
@@ -540,69 +571,75 @@ __device__ __forceinline__ void big_panel_tile(const BigTile &t, const BigLds &s
         }
         __syncthreads();
         stamp(1);
-        if (kb > 0) {
+        if (own_d) {
+            if (kb > 0) update_d();
+            put_d();
+        } else {
+            if (kb > 0) {
 #pragma unroll
-            for (int k0 = 0; k0 < BIG_NB; k0 += 4) {
-                const double bl = As[k0 + mq][ti];
-                const double au0 = Bd[k0 + mq][mi], au1 = Bd[k0 + mq][16 + mi];
-                const double aud = Bd[k0 + mq][16 * (wv >> 1) + mi], bld = Ad[k0 + mq][dr];
-                acc[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(au0, bl, acc[0], 0, 0, 0);
-                acc[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(au1, bl, acc[1], 0, 0, 0);
-                dacc = __builtin_amdgcn_mfma_f64_16x16x4f64(aud, bld, dacc, 0, 0, 0);
+                for (int k0 = 0; k0 < BIG_NB; k0 += 4) {
+                    const double bl = As[k0 + mq][ti];
+                    const double au0 = Bd[k0 + mq][mi], au1 = Bd[k0 + mq][16 + mi];
+                    acc[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(au0, bl, acc[0], 0, 0, 0);
+                    acc[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(au1, bl, acc[1], 0, 0, 0);
+                }
             }
+            stamp(2);
+#pragma unroll
+            for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+                for (int v = 0; v < 4; ++v) T[ti][16 * cb + mq + 4 * v] = acc[cb][v];
         }
-        stamp(2);
-        put_d();
-#pragma unroll
-        for (int cb = 0; cb < 2; ++cb)
-#pragma unroll
-            for (int v = 0; v < 4; ++v) T[ti][16 * cb + mq + 4 * v] = acc[cb][v];
     } else if constexpr (KIND == CS3_LU) {          // ---- block-row tile: D and T[col][row], 32 rows
-        const int cb0 = 2 * (t.wu >> 1);            // my column blocks cb0, cb0 + 1; my rows are D's: dr
-        double ra[8], rb[8];                        // (ra stays unused)
-        cs3_double4 acc[2];
+        const int cb0 = 2 * (twu >> 1);             // my column blocks cb0, cb0 + 1; my rows are those of D's sub-block: dr
+        double ra[4], rb[4];                        // (ra stays unused)
         if (kb > 0) {
             big_tile_panels<KIND, false, true>(t, ra, rb);
             big_diag_panels<KIND>(t, rad, rbd);
         }
-        big_tile_accumulators<2>(t, dr, mq, cb0, acc);
-        big_diag_accumulator(t, dr, mq, 16 * (t.wu >> 1), dacc);
+        big_wave_accumulators(t, own_d ? pdiag : t.Fb + 8ll * t.row0 + t.col0 * t.ld8, dr, bw, own_d ? bw : ncol,
+                              mq, 16 * (own_d ? twu >> 1 : cb0), acc);   // (nrow = bw)
         __builtin_amdgcn_sched_barrier(0);
+        if (own_d) mask_d();
+        else {
 #pragma unroll
-        for (int c = 0; c < 2; ++c)
+            for (int c = 0; c < 2; ++c)
 #pragma unroll
-            for (int v = 0; v < 4; ++v) {
-                const int j = 16 * (cb0 + c) + mq + 4 * v;
-                if (!(dr < nrow && j < ncol)) acc[c][v] = 0.0;
-            }
-        mask_d();
+                for (int v = 0; v < 4; ++v) {
+                    const int j = 16 * (cb0 + c) + mq + 4 * v;
+                    if (!(dr < nrow && j < ncol)) acc[c][v] = 0.0;
+                }
+        }
         if (kb > 0) {
 #pragma unroll
-            for (int q = 0; q < 8; ++q) {
-                const int e = tid + 256 * q;
+            for (int q = 0; q < 4; ++q) {
+                const int e = tid + BIG_THREADS * q;
                 const int k = e % BIG_NB, j = e / BIG_NB;
                 Bs[k][j] = (k < pw && j < ncol) ? rb[q] : 0.0;
             }
             stage_d();
         }
         __syncthreads();
-        if (kb > 0) {
+        if (own_d) {
+            if (kb > 0) update_d();
+            put_d();
+        } else {
+            if (kb > 0) {
 #pragma unroll
-            for (int k0 = 0; k0 < BIG_NB; k0 += 4) {
-                const double bl = Ad[k0 + mq][dr];              // -L(kb + dr, k0 + mq): the tile's rows are D's
-                const double au0 = Bs[k0 + mq][16 * cb0 + mi], au1 = Bs[k0 + mq][16 * cb0 + 16 + mi];
-                const double aud = Bd[k0 + mq][16 * (wv >> 1) + mi];
-                acc[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(au0, bl, acc[0], 0, 0, 0);
-                acc[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(au1, bl, acc[1], 0, 0, 0);
-                dacc = __builtin_amdgcn_mfma_f64_16x16x4f64(aud, bl, dacc, 0, 0, 0);
+                for (int k0 = 0; k0 < BIG_NB; k0 += 4) {
+                    const double bl = Ad[k0 + mq][dr];          // -L(kb + dr, k0 + mq): the tile's rows are D's
+                    const double au0 = Bs[k0 + mq][16 * cb0 + mi], au1 = Bs[k0 + mq][16 * cb0 + 16 + mi];
+                    acc[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(au0, bl, acc[0], 0, 0, 0);
+                    acc[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(au1, bl, acc[1], 0, 0, 0);
+                }
             }
+#pragma unroll
+            for (int c = 0; c < 2; ++c)
+#pragma unroll
+                for (int v = 0; v < 4; ++v) T[16 * (cb0 + c) + mq + 4 * v][dr] = acc[c][v];
         }
-        put_d();
-#pragma unroll
-        for (int c = 0; c < 2; ++c)
-#pragma unroll
-            for (int v = 0; v < 4; ++v) T[16 * (cb0 + c) + mq + 4 * v][dr] = acc[c][v];
     }
 }
 
 }  // namespace cs3
+

@@ -398,11 +398,11 @@ front_lds_body(const FrontDesc &d, int first, double *F,
 }
 
 
-constexpr int PAIR_NC = 16;                   // columns per wave of a two-wave elimination (half a 32-pivot block)
+constexpr int SLICE_PARTS = 4, SLICE_NC = 8;  // waves that share the elimination of a 32-pivot block; columns per wave (slice)
 
 // The elimination of eliminate_block (below) on a SLICE of NC columns of the stacked block: d[c] = column c0 + c, whose pivot sits in lane
 // c0 + c (lanes 0..31 are the block's rows, lanes 32..63 the stacked rows).  publish(c, l) receives the multipliers of
-// every pivot as soon as they exist, for the wave that holds the columns to the right (eliminate_pair below).
+// every pivot as soon as they exist, for the waves that hold the columns to the right (eliminate_parts below).
 // npiv (a front instead of a padded block): only pivots < npiv are eliminated -- the other steps run with zero multipliers
 // rather than behind a branch (a wave-uniform branch per pivot and column group cost the lone wave 200 cycles per pivot).
 // SKIP: steps past npiv are skipped behind one wave-uniform branch each (for a slice nobody waits for: the trailing
@@ -460,49 +460,59 @@ __device__ __forceinline__ void eliminate_slice(double (&d)[NC], int c0, bool ke
     }
 }
 
-// A stacked 32-pivot elimination by TWO waves: a lone wave spends 425 cycles per pivot on it, nearly all of them issuing
-// two v_readlane and one FMA per column update.  Wave `part` 0 holds columns 0..15 of the 64 rows, wave 1 columns
-// 16..31.  Wave 0 eliminates its 16 pivots and hands the multipliers of each to wave 1 through LDS (lm[k][lane], then
-// *ready = k + 1: LDS operations of a wave complete in order); wave 1 applies them to its columns one pivot behind,
-// then eliminates pivots 16..31 alone.  Wave 0 never waits for wave 1, so the wait below cannot deadlock; it is bounded
-// anyway, and a wave that gives up raises status[3]: cs3_factor_status reports the step as failed (handover_wait).
-template <int KIND, class Rule>
-__device__ __forceinline__ void eliminate_pair(double (&d)[PAIR_NC], int part, bool keep_unscaled, double *lm_generic, int *ready_generic,
-                                               int *status, int npiv, const Rule &rule, int &hits)
+// A stacked 32-pivot elimination by FOUR waves: a lone wave spends 425 cycles per pivot on it, nearly all of them issuing
+// two v_readlane and one FMA per column update, two waves of 16 columns still 220.  Wave `part` p holds columns 8 p .. 8 p + 7
+// of the 64 rows: it applies the pivots 0 .. 8 p - 1 in order, one hand-over behind their owners, then eliminates its own 8
+// and hands the multipliers of each to the waves on its right through LDS (lm[pivot][lane], then *ready = pivot + 1: LDS
+// operations of a wave complete in order).  ONE counter that only grows: pivot k is published by part k / 8, which has
+// consumed every pivot before k.  The last part publishes nothing (SKIP).  A part waits only for parts on its left, so the
+// wait cannot deadlock; it is bounded anyway, and a wave that gives up raises status[3] (handover_wait).  Every column sees
+// the FMAs it saw in one wave, in the same order.  PART is a template argument: every pivot's lane is an immediate.
+template <int KIND, int PART, class Rule>
+__device__ __forceinline__ void eliminate_part(double (&d)[SLICE_NC], bool keep_unscaled, lds_vdouble_ptr lm, lds_int_ptr ready,
+                                               int *status, bool withhold, int npiv, const Rule &rule, int &hits)
 {
-    constexpr int NC = PAIR_NC;
+    constexpr int NC = SLICE_NC, c0 = NC * PART;                // my first column = the number of pivots on my left
     const int lane = threadIdx.x & 63;
+    bool alive = true;                                          // (a consumer that gave up once does not wait again)
+#pragma unroll
+    for (int k = 0; k < c0; ++k) {                              // (all c0 hand-overs happen, with zeros past npiv)
+        if (alive) alive = handover_wait(ready, k, status, withhold);
+        const double l = lm[k * 64 + lane];                     // zero on and above the pivot row
+        double bc[NC];
+#pragma unroll
+        for (int u = 0; u < NC; ++u) bc[u] = (KIND == CS3_LU) ? bcast_lane(d[u], k) : bcast_lane(l, c0 + u);
+#pragma unroll
+        for (int u = 0; u < NC; ++u) {
+            d[u] -= l * bc[u];
+            keep_here(d[u]);                                    // (or the FMAs sink past the waits that follow: cs3_devfn.hpp)
+        }
+    }
+    if constexpr (PART == SLICE_PARTS - 1)
+        eliminate_slice<KIND, NC, true>(d, c0, keep_unscaled, [](int, double) {}, npiv, rule, hits);
+    else
+        eliminate_slice<KIND, NC>(d, c0, keep_unscaled, [&](int k, double l) {
+            lm[(c0 + k) * 64 + lane] = l;
+            if (lane == 0) handover_publish(ready, c0 + k + 1, withhold);
+        }, npiv, rule, hits);
+}
+
+template <int KIND, class Rule>
+__device__ __forceinline__ void eliminate_parts(double (&d)[SLICE_NC], int part, bool keep_unscaled, double *lm_generic, int *ready_generic,
+                                                int *status, int npiv, const Rule &rule, int &hits)
+{
     // (explicitly LDS: through generic pointers these become flat accesses, and every hand-over waits out a flat store)
     // volatile on both sides instead of fences: the compiler keeps volatile accesses in program order, the LDS performs a
     // wave's operations in order -- a release fence after every hand-over (s_waitcnt lgkmcnt(0)) sat on the pivot chain
     auto lm = (lds_vdouble_ptr) lm_generic;
     auto ready = (lds_int_ptr) ready_generic;
     const bool withhold = g_withhold_handover != 0;
-    if (part == 0) {
-        eliminate_slice<KIND, NC>(d, 0, keep_unscaled, [&](int k, double l) {
-            lm[k * 64 + lane] = l;
-            if (lane == 0) handover_publish(ready, k + 1, withhold);
-        }, npiv, rule, hits);
-        return;
+    switch (part) {                                             // (wave-uniform; SLICE_PARTS cases)
+    case 0: eliminate_part<KIND, 0>(d, keep_unscaled, lm, ready, status, withhold, npiv, rule, hits); break;
+    case 1: eliminate_part<KIND, 1>(d, keep_unscaled, lm, ready, status, withhold, npiv, rule, hits); break;
+    case 2: eliminate_part<KIND, 2>(d, keep_unscaled, lm, ready, status, withhold, npiv, rule, hits); break;
+    default: eliminate_part<KIND, 3>(d, keep_unscaled, lm, ready, status, withhold, npiv, rule, hits); break;
     }
-    bool alive = true;                                          // (a consumer that gave up once does not wait again)
-#pragma unroll
-    for (int k = 0; k < NC; ++k) {                              // (all NC hand-overs happen, with zeros past npiv)
-        if (alive) alive = handover_wait(ready, k, status, withhold);
-        const double l = lm[k * 64 + lane];                     // zero on and above the pivot row
-#pragma unroll
-        for (int j0 = 0; j0 < NC; j0 += 8) {
-            double bc[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) bc[u] = (KIND == CS3_LU) ? bcast_lane(d[j0 + u], k) : bcast_lane(l, NC + j0 + u);
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                if (KIND == CS3_LU) d[j0 + u] -= l * bc[u];
-                else d[j0 + u] -= l * bc[u];
-            }
-        }
-    }
-    eliminate_slice<KIND, NC, true>(d, NC, keep_unscaled, [](int, double) {}, npiv, rule, hits);
 }
 
 // ---------------------------------------------- front owned by ONE wave ----
@@ -729,7 +739,7 @@ k_front_mix(const FrontDesc *__restrict__ fdesc, int first,
 // of BIG_NB pivots a panel launch and a trailing-update launch -- a blocked
 // right-looking LU / Cholesky without pivoting, many workgroups per launch.
 // (BIG_NB = 32 pivots per block-step launch: cs3_device.hpp)
-static_assert(BIG_NB == 2 * PAIR_NC, "eliminate_pair splits a block of BIG_NB pivots in two");
+static_assert(BIG_NB == SLICE_PARTS * SLICE_NC, "eliminate_parts splits a block of BIG_NB pivots in SLICE_PARTS slices");
 
 __global__ void __launch_bounds__(256)
 k_big_gather(const FrontDesc *__restrict__ fdesc, int first, int kind,
@@ -1402,16 +1412,12 @@ k_front_wg(const FrontDesc *__restrict__ fdesc, int first,
 // column of the factor up to block b is final in F, which is what lets the forward sweep of a
 // chunk start while later blocks are still being factorised.
 // Tile index 0 = the panel block [kb, ke); index t >= 1 = 64 rows/columns from ke + 64 (t-1).
-// The three panel tiles, which end the launch, load and multiply only the blocks their 32-wide panel uses: the diagonal
-// tile D alone, a block-column tile two of the four column blocks (with D's U panel as its own), a block-row tile its
-// eight blocks dealt to all four waves (with D's L panel as its own); the D chain runs beside the tile chains.  The
-// comment at the branch on the tile's kind has the details.  Loads per thread: diagonal tile 16 (it was 52 with the full
-// 64 x 64 tile path), block-column and block-row tile 28 (48); MFMAs per wave 8 and 24 (40; block-row tile: 40 in two
-// waves, 8 in the others).  On the root step kb = 64 of the 50k Jacobian the diagonal tile parks its block at 15.2 k cycles
-// instead of 21.3 k and the block-column tile stores at 17.0 k instead of 20.5 k: it now ends the launch, the block-row
-// tile in front of it (16.1 k).  From "D and T meet in LDS" on nothing changed: 6.9 k cycles for the 32 pivots, 1.8 to
-// 2.5 k for the stores and the checks.
-// What a launch costs beside the elimination (220 cycles per pivot, a dependent chain) is what stands in front of and
+// A workgroup is EIGHT waves (512 threads, two workgroups per CU).  The three panel tiles, which end the launch, load and
+// multiply only the blocks their 32-wide panel uses; four waves take the tile's blocks, two each, the other four D's
+// sub-blocks, and all eight load and stage the panels (the comment at the branch on the tile's kind has the details).
+// The 32 pivots are then eliminated in four column slices of 8, one wave per slice and half of the stacked rows
+// (eliminate_parts): about 105 cycles per pivot, the pivot's own chain, where two slices of 16 took 220.
+// What a launch costs beside the elimination (105 cycles per pivot, a dependent chain) is what stands in front of and
 // behind it on the tile that finishes last: the descriptor (one scalar load of its first 64 bytes; four waits on kernel
 // arguments remain around it), the address arithmetic until the loads are out (one uniform base per panel, 32-bit offsets), the
 // one round trip of those loads, and the panel store.  The diagonal tile carries the copy-home on top: its parked
@@ -1420,7 +1426,7 @@ k_front_wg(const FrontDesc *__restrict__ fdesc, int first,
 // not between them: a lane keeps a plain running minimum (first_rejected in cs3_devfn.hpp; no __any, the compiler itself
 // sinks the selects behind the one branch) and calls flag_column once, behind its last store.  Numbers: DESIGN.md, section 7.
 template <int KIND, class Rule>
-__global__ void __launch_bounds__(256)
+__global__ void __launch_bounds__(BIG_THREADS)
 k_big_step(const FrontDesc *__restrict__ fdesc, int first, int kb, double *__restrict__ pool_all,
            long long pool_stride, double *__restrict__ dbuf_all, long long dbuf_stride,
            Rule rule, int *status, int batch, long long *tbuf, int stamp_bi)
@@ -1440,7 +1446,7 @@ k_big_step(const FrontDesc *__restrict__ fdesc, int first, int kb, double *__res
     __shared__ double Bd[BIG_NB][BIG_NB + 1];   // Bd[k][j] = U(kp + k, kb + j)
     __shared__ double D[BIG_NB][BIG_NB + 1];
     __shared__ double T[64][BIG_NB + 1];
-    __shared__ int pair_ready[2];               // eliminate_pair: pivots whose multipliers wave 0 / 1 has handed over
+    __shared__ int pair_ready[2];               // eliminate_parts: pivots of the block handed over so far, per half of the stacked rows
     if (threadIdx.x < 2) pair_ready[threadIdx.x] = 0;           // (two block barriers lie between this and the first use)
     const DescHead d = load_desc_head(fdesc + (first + blockIdx.z / batch));   // grid (tiles, tiles, fronts * batch); ONE fetch
     const int bz = blockIdx.z % batch;
@@ -1468,19 +1474,19 @@ k_big_step(const FrontDesc *__restrict__ fdesc, int first, int kb, double *__res
               __builtin_amdgcn_readfirstlane(tid >> 6), tid & 31, tid >> 5, 0u, 8u * (unsigned) (l64 < nrow ? l64 : 0), 8u * (unsigned) (l64 < ncol ? l64 : 0)};
     t.o_kj = 8u * (unsigned) t.l32 + (unsigned) t.h5 * t.ldu;
     // ---- the diagonal block parked by the previous launch goes home (tile (0, 0); for the last block this is the closing
-    // launch): nobody reads that part of F any more, so the tile requests its four parked entries per thread (entry
-    // tid + 256 q = (l32, h5 + 8 q) of the block) with its other loads and stores them once all of those are out
+    // launch): nobody reads that part of F any more, so the tile requests its two parked entries per thread (entry
+    // tid + 512 q = (l32, h5 + 16 q) of the block) with its other loads and stores them once all of those are out
     const bool home = kb > 0 && bi == 0 && bj == 0;
     const int hblk = kb / BIG_NB - 1, hk0 = hblk * BIG_NB, hcw = min(BIG_NB, w - hk0);
-    double cp[4] = {0.0, 0.0, 0.0, 0.0};
+    double cp[2] = {0.0, 0.0};
 #pragma unroll
-    for (int q = 0; q < 4; ++q)
-        if (home) cp[q] = load_at(reinterpret_cast<const char *>(dbuf + (long long) hblk * (BIG_NB * BIG_NB) + 256 * q), 8u * (unsigned) tid);
+    for (int q = 0; q < 2; ++q)
+        if (home) cp[q] = load_at(reinterpret_cast<const char *>(dbuf + (long long) hblk * (BIG_NB * BIG_NB) + BIG_THREADS * q), 8u * (unsigned) tid);
     auto send_home = [&]() {
 #pragma unroll
-        for (int q = 0; q < 4; ++q)
-            if (t.l32 < hcw && t.h5 + 8 * q < hcw && (KIND == CS3_LU || t.l32 >= t.h5 + 8 * q))
-                store_at(t.Fb + 8ll * hk0 + hk0 * t.ld8, t.o_kj + 8 * q * t.ldu, cp[q]);
+        for (int q = 0; q < 2; ++q)
+            if (t.l32 < hcw && t.h5 + 16 * q < hcw && (KIND == CS3_LU || t.l32 >= t.h5 + 16 * q))
+                store_at(t.Fb + 8ll * hk0 + hk0 * t.ld8, t.o_kj + 16 * q * t.ldu, cp[q]);
     };
     if (!has_panel && (bi == 0 || bj == 0)) { if (home) send_home(); return; }
     // ---- every global load of this tile goes out before anything waits for one: ONE round trip.  The loads are RAW
@@ -1488,48 +1494,41 @@ k_big_step(const FrontDesc *__restrict__ fdesc, int first, int kb, double *__res
     // the select next to the load the compiler waited for the panel operands and stored them to LDS before it issued the
     // loads of the accumulators (two round trips).
     // The tile's kind decides what it loads and multiplies (bi, bj are uniform: one branch per workgroup, in front of
-    // the loads), and every kind issues ALL of its loads before its first wait:
-    //   plain trailing tile   the two 64-wide panels, 64 x 64 accumulators, 32 MFMAs per wave; stores and leaves
-    //   diagonal tile (0, 0)  D alone: its two 32-wide panels and one accumulator, 8 MFMAs per wave (it has no tile of
-    //                         its own: T is only read for bi > 0 or bj > 0)
-    //   block-column tile     D, and its 32 columns: the L panel of its rows and acc[0 .. 1].  Its U panel IS D's (col0 =
-    //                         kb, ncol = bw: Bs would repeat Bd entry for entry), so the tile MFMAs read Bd: 16 + 8 per wave
-    //   block-row tile (LU)   D, and its 32 rows: the U panel of its columns and two accumulators per wave -- wave wv takes
-    //                         row block wv & 1 (the rows of its D sub-block: ONE B operand feeds both) and the column
-    //                         blocks 2 (wv >> 1), 2 (wv >> 1) + 1.  Its L panel is D's (row0 = kb, nrow = bw): Ad.  16 + 8
+    // the loads), and every kind issues ALL of its loads before its first wait.  A plain trailing tile: the two 64-wide
+    // panels (entry tid + 512 q, four of each per thread) and, per wave, one row block with two column blocks of the
+    // 64 x 64 accumulators, 16 MFMAs; stores and leaves.  The three panel tiles: big_panel_tile (cs3_devfn.hpp).
     // Every entry's sum keeps its terms, their order (k0 upward, the MFMA's own order inside a group of four), its operand
     // roles (A = U, B = -L) and the zero padding past pw whichever wave forms it: the bits are those of the full tile.
-    // In the block-column and block-row tiles the D chain stands in the k loop beside the two tile chains (three
-    // independent accumulators per step), not behind them.
     // To be read again in the gfx950 assembly of all three instances after a change here or a compiler change:
-    //   * global loads before a path's first s_waitcnt vmcnt: plain tile 32; block-column and block-row tile 16 + 12
-    //     (Cholesky, whose two D panels are one: 12 + 12); diagonal tile 4 parked entries + 8 + 4 (Cholesky 4 + 4 + 4)
-    //   * v_mfma_f64_16x16x4_f64 of a block-column / block-row tile: 24, as (tile, tile, D) per k step, none behind the others
-    //   * no scratch, 75 528 bytes of LDS, two workgroups per CU (tools/kernel_resources.py)
-    //
+    //   * global loads before a path's first s_waitcnt vmcnt: plain tile 16; block-column and block-row tile 8 + 8 in every
+    //     wave whatever its role (Cholesky 6 + 8); diagonal tile 2 parked entries + 4 + 4 (Cholesky 2 + 2 + 4; waves 4 .. 7: no last 4)
+    //   * v_mfma_f64_16x16x4_f64 of a block-column / block-row tile: 16 in a tile wave, (tile, tile) per k step; 8 in a D wave
+    //   * no scratch, no AGPRs, 75 528 bytes of LDS, two workgroups per CU (tools/kernel_resources.py)
     // my outputs, in the register layout of v_mfma_f64_16x16x4 with the tile transposed (A operand = U
     // panel, B operand = L panel, so that lanes % 16 run along tile ROWS and global accesses stay
-    // coalesced): wave wv owns tile rows [16 wv, 16 wv + 16), acc[cb][v] = F(row0 + 16 wv + mi, col0 + 16 cb + mq + 4 v)
+    // coalesced): wave wv owns tile rows [16 (wv & 3), 16 (wv & 3) + 16) and the column blocks cb0 = 2 (wv >> 2) and cb0 + 1,
+    // acc[c][v] = F(row0 + 16 (wv & 3) + mi, col0 + 16 (cb0 + c) + mq + 4 v)
     const int wv = tid >> 6, mi = tid & 15, mq = (tid >> 4) & 3;
-    const int ti = 16 * wv + mi;
+    const int ti = 16 * (wv & 3) + mi;
     if (!needs_d) {                                 // ---- plain trailing tile (kb > 0)
+        const int cb0 = 2 * (t.wu >> 2);            // (a scalar)
         const unsigned o_acc = 8u * (unsigned) ti + (unsigned) mq * t.ldu;
-        double ra[8], rb[8];
-        double4_t acc[4];
+        double ra[4], rb[4];
+        double4_t acc[2];
         big_tile_panels<KIND, true, true>(t, ra, rb);
-        big_tile_accumulators<4>(t, ti, mq, 0, acc);
+        big_tile_accumulators<2>(t, ti, mq, cb0, acc);
         __builtin_amdgcn_sched_barrier(0);
         // (the masks now)
 #pragma unroll
-        for (int cb = 0; cb < 4; ++cb)
+        for (int c = 0; c < 2; ++c)
 #pragma unroll
             for (int v = 0; v < 4; ++v) {
-                const int j = 16 * cb + mq + 4 * v;
-                if (!(ti < nrow && j < ncol)) acc[cb][v] = 0.0;
+                const int j = 16 * (cb0 + c) + mq + 4 * v;
+                if (!(ti < nrow && j < ncol)) acc[c][v] = 0.0;
             }
 #pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            const int e = tid + 256 * q;
+        for (int q = 0; q < 4; ++q) {
+            const int e = tid + BIG_THREADS * q;
             { const int i = e % 64, k = e / 64; As[e / 64][e % 64] = (k < pw && i < nrow) ? -ra[q] : 0.0; }     // negated: the MFMA accumulates acc += U' (-L)'
             if (KIND == CS3_LU) { const int k = e % BIG_NB, j = e / BIG_NB; Bs[k][j] = (k < pw && j < ncol) ? rb[q] : 0.0; }
             else { const int j = e % 64, k = e / 64; Bs[k][j] = (k < pw && j < ncol) ? rb[q] : 0.0; }
@@ -1539,16 +1538,16 @@ k_big_step(const FrontDesc *__restrict__ fdesc, int first, int kb, double *__res
         for (int k0 = 0; k0 < BIG_NB; k0 += 4) {
             const double bl = As[k0 + mq][ti];                  // B operand: -L(row ti, k0 + mq), lane mi + 16 mq
 #pragma unroll
-            for (int cb = 0; cb < 4; ++cb)                      // A operand: U(k0 + mq, column 16 cb + mi)
-                acc[cb] = __builtin_amdgcn_mfma_f64_16x16x4f64(Bs[k0 + mq][16 * cb + mi], bl, acc[cb], 0, 0, 0);
+            for (int c = 0; c < 2; ++c)                         // A operand: U(k0 + mq, column 16 (cb0 + c) + mi)
+                acc[c] = __builtin_amdgcn_mfma_f64_16x16x4f64(Bs[k0 + mq][16 * (cb0 + c) + mi], bl, acc[c], 0, 0, 0);
         }
 #pragma unroll
-        for (int cb = 0; cb < 4; ++cb)
+        for (int c = 0; c < 2; ++c)
 #pragma unroll
             for (int v = 0; v < 4; ++v) {
-                const int j = 16 * cb + mq + 4 * v;
+                const int j = 16 * (cb0 + c) + mq + 4 * v;
                 if (ti < nrow && j < ncol && (KIND == CS3_LU || row0 + ti >= col0 + j))
-                    store_at(t.Fb + 8ll * row0 + col0 * t.ld8, o_acc + (16 * cb + 4 * v) * t.ldu, acc[cb][v]);
+                    store_at(t.Fb + 8ll * row0 + col0 * t.ld8, o_acc + (unsigned) (16 * (cb0 + c) + 4 * v) * t.ldu, acc[c][v]);
             }
         return;
     }
@@ -1571,14 +1570,15 @@ k_big_step(const FrontDesc *__restrict__ fdesc, int first, int kb, double *__res
     // ---- the updated D and my tile have met in LDS
     __syncthreads();
     CS3_BSTAMP(3);
-    // all four waves carry on: waves 0 and 1 take 32 stacked tile rows each with columns 0..15 of the block, waves 2 and 3
-    // the same rows with columns 16..31 (eliminate_pair).  The multipliers travel through the dead As / Bs buffers.
+    // all eight waves carry on: waves 2 p and 2 p + 1 take 32 stacked tile rows each (half 0 / 1) with columns 8 p .. 8 p + 7
+    // of the block (eliminate_parts).  The multipliers travel through the dead As (half 0) / Bs (half 1) buffers, [24][64] each.
     const int lane = tid & 63, half = (tid >> 6) & 1, part = tid >> 7, li = lane & 31;
     const bool stacked = lane >= 32;
     const bool row_tile = (bi == 0 && bj > 0);      // block-row tile (LU only): eliminate D' with tile columns stacked
     const bool diag_tile = (bi == 0 && bj == 0);
     if (diag_tile && half == 1) return;
-    constexpr int HC = PAIR_NC;
+    constexpr int HC = SLICE_NC;
+    static_assert((BIG_NB - SLICE_NC) * 64 <= BIG_NB * (64 + 1), "the multipliers of a half fit As / Bs");
     const int cbase = HC * part;                    // my first column of the block
     double e[HC];
 #pragma unroll
@@ -1593,7 +1593,7 @@ k_big_step(const FrontDesc *__restrict__ fdesc, int first, int kb, double *__res
     // (perturbation: the steps past bw run with zero multipliers instead of the padding's identity pivots, which a delta
     //  above 1 would replace -- the same factors either way)
     int hits = 0;
-    eliminate_pair<KIND>(e, part, row_tile, (half == 0) ? &As[0][0] : &Bs[0][0], &pair_ready[half], status,
+    eliminate_parts<KIND>(e, part, row_tile, (half == 0) ? &As[0][0] : &Bs[0][0], &pair_ready[half], status,
                          Rule::on ? bw : (1 << 30), rule, hits);
     CS3_BSTAMP(4);
     CS3_BSTAMP_ROW(6);
@@ -1602,7 +1602,7 @@ k_big_step(const FrontDesc *__restrict__ fdesc, int first, int kb, double *__res
     int bad_col = 0;
     if (diag_tile) {                                // park the factored block, check its pivots
         double *db = dbuf + (long long) (kb / BIG_NB) * (BIG_NB * BIG_NB);
-        if (lane == 0) count_perturbed(rule, bz, hits);         // (the parked copy is the stored one: each wave its own 16 pivots)
+        if (lane == 0) count_perturbed(rule, bz, hits);         // (the parked copy is the stored one: each wave its own 8 pivots)
         if (lane < bw) {
             unsigned o_db = 8u * (unsigned) lane;   // (uniform base, one 32-bit offset, the column in the immediate)
             asm("" : "+v"(o_db));
@@ -3951,7 +3951,7 @@ static hipError_t launch_big_block(const DeviceFactor &D, const LaunchGroup &g, 
     // (unreachable with today's memories: such a front alone takes 2^47 bytes)
     if (g.max_r >= (1 << 22)) { set_error("k_big_step: a front of order " + std::to_string(g.max_r) + " is beyond its 32-bit tile offsets"); return hipErrorInvalidValue; }
     with_rule<KIND>(pc, [&](auto rule) {
-        hipLaunchKernelGGL((k_big_step<KIND, decltype(rule)>), dim3(tiles, tiles, g.count * batch), dim3(256), 0, st, D.fdesc,
+        hipLaunchKernelGGL((k_big_step<KIND, decltype(rule)>), dim3(tiles, tiles, g.count * batch), dim3(512), 0, st, D.fdesc,
                            g.first, kb, D.pool_pm, D.pm_stride, D.dbuf, D.dbuf_size, rule, D.status, (int) batch, D.tbuf,
                            D.tbuf_diag ? 0 : 1);
     });
