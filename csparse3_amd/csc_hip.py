@@ -136,6 +136,20 @@ class CplxSelinvLimits(C.Structure):
     _fields_ = [(name, C.c_int64) for name in ("block", "grid_cap")]
 
 
+class PfInfo(C.Structure):
+    """cs3_pf_info: sizes of a power-flow plan and how its rows are summed."""
+    _fields_ = [(name, C.c_int64) for name in ("n", "nnz_y", "npv", "npq", "nref", "nj", "nnz_j", "batch", "y_batch",
+                                               "rows_lane", "rows_wave", "max_row")]
+
+    def __repr__(self):
+        return "PfInfo(%s)" % ", ".join("%s=%d" % (f, getattr(self, f)) for f, _ in self._fields_)
+
+
+class PfLimits(C.Structure):
+    """cs3_pf_limits_t: the constants that shape the launches of the power-flow kernels."""
+    _fields_ = [(name, C.c_int64) for name in ("block", "grid_cap", "wave_row")]
+
+
 class Cs3Error(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("cs3 error %d: %s" % (code, msg))
@@ -365,6 +379,19 @@ def lib():
         L.cs3_cplx_selinv_diag.argtypes = [vp, vp, _f64p]
         L.cs3_cplx_selinv_thevenin.argtypes = [vp, vp, _f64p]
         L.cs3_debug_cplx_selinv_maps.argtypes = [vp, vp] + [C.POINTER(I64)] * 3
+        L.cs3_pf_limits.argtypes = [C.POINTER(PfLimits)]
+        L.cs3_pf_plan_create.argtypes = [I64, _i32p, _i32p, I64, _i32p, I64, _i32p, I64, I64, I64, C.POINTER(vp)]
+        L.cs3_pf_plan_free.argtypes = [vp]
+        L.cs3_pf_handle.argtypes = [vp, C.POINTER(vp)]
+        L.cs3_pf_plan_info.argtypes = [vp, C.POINTER(PfInfo)]
+        L.cs3_pf_plan_pattern.argtypes = [vp, _i32p, _i32p]
+        L.cs3_pf_plan_maps.argtypes = [vp] + [_i32p] * 6
+        L.cs3_pf_mismatch_dev.argtypes = [vp] * 8
+        L.cs3_pf_jacobian_dev.argtypes = [vp] * 6
+        L.cs3_pf_solve_dev.argtypes = [vp, vp, vp, vp, vp, C.c_double, I64, I64, C.c_double, _i32p, _f64p, _i32p, vp]
+        L.cs3_pf_mismatch.argtypes = [vp] + [_f64p] * 6
+        L.cs3_pf_jacobian.argtypes = [vp] + [_f64p] * 4
+        L.cs3_pf_solve.argtypes = [vp, _f64p, _f64p, _f64p, _f64p, C.c_double, I64, I64, C.c_double, _i32p, _f64p, _i32p]
         _lib = L
     return _lib
 
@@ -689,9 +716,21 @@ class Factorization:
         else:
             _check(lib().cs3_analyze(kind, order, n, _pi(Ap), _pi(Ai), _pi(qa), batch, C.byref(self._h)))
 
+    _borrowed = False                 # a handle lent by a plan that owns it (PowerFlowPlan.factorization): never freed here
+
+    @classmethod
+    def _borrow(cls, handle, n, nnz, batch):
+        self = cls.__new__(cls)
+        self._h = C.c_void_p(handle)
+        self._borrowed = True
+        self.kind, self.n, self.nnz, self.batch = CS3_LU, int(n), int(nnz), int(batch)
+        self.matched, self.perturbation, self.ns = False, 0.0, 0
+        return self
+
     def close(self):
         if self._h:
-            lib().cs3_free(self._h)
+            if not self._borrowed:
+                lib().cs3_free(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):
@@ -1584,6 +1623,139 @@ class UnionPlan:
         """[nmat, nnz_union] at union_ptr from the concatenated values at cat_ptr (device addresses), asynchronous on
         `stream`: one launch, no allocation, no synchronisation.  The same bits as values()."""
         _check(lib().cs3_union_values_dev(self._p, C.c_void_p(cat_ptr), C.c_void_p(union_ptr), C.c_void_p(stream)))
+
+
+# ----------------------------------------------------------- AC power flow --
+
+def pf_limits():
+    """The constants that shape the launches of the power-flow kernels (cs3_pf_limits); needs no GPU."""
+    out = PfLimits()
+    _check(lib().cs3_pf_limits(C.byref(out)))
+    return out
+
+
+class PowerFlowPlan:
+    """Newton-Raphson AC power flow on the device (include/csparse3_amd.h, "AC power flow"): from the pattern (Yp, Yi) of
+    a bus admittance matrix of order n and the bus lists pv, pq, the pattern of the Jacobian [[H, N], [M, L]] and the
+    maps the kernels read (host work, no GPU needed), and a batched LU handle on that pattern, owned by the plan and lent
+    out as `factorization`.  batch scenarios advance in lock-step; y_batch is 1 (one Y for all) or batch.
+    Host arrays: Yz complex [y_batch, nnz_y], S complex [batch, n], vm and va float64 [batch, n].  The *_dev forms take
+    device addresses of the same layouts (complex as interleaved doubles)."""
+
+    def __init__(self, n, Yp, Yi, pv, pq, batch=1, y_batch=1, order=ORDER_AMD):
+        self._p = C.c_void_p()
+        self._f = None
+        Yp, Yi, pv, pq = _i32(Yp), _i32(Yi), _i32(pv).reshape(-1), _i32(pq).reshape(-1)
+        _check(lib().cs3_pf_plan_create(n, _pi(Yp), _pi(Yi), pv.size, _pi(pv), pq.size, _pi(pq), batch, y_batch, order,
+                                        C.byref(self._p)))
+        inf = self.info
+        self.n, self.nnz_y, self.nj, self.nnz_j = int(inf.n), int(inf.nnz_y), int(inf.nj), int(inf.nnz_j)
+        self.batch, self.y_batch = int(inf.batch), int(inf.y_batch)
+
+    def close(self):
+        if self._p:
+            if self._f is not None:
+                self._f.close()                          # the lent handle goes with the plan: the borrower is left empty
+            lib().cs3_pf_plan_free(self._p)
+            self._p = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    @property
+    def info(self):
+        out = PfInfo()
+        _check(lib().cs3_pf_plan_info(self._p, C.byref(out)))
+        return out
+
+    @property
+    def factorization(self):
+        """The plan's LU handle on the Jacobian as a Factorization that BORROWS it: everything a handle offers works on
+        the Jacobian of the last factorisation; closing it frees nothing, and closing the plan leaves it empty (every
+        call on it then raises Cs3Error).  Closing the borrower ends that loan only: the next access lends the handle again."""
+        if self._f is None or not self._f._h:
+            h = C.c_void_p()
+            _check(lib().cs3_pf_handle(self._p, C.byref(h)))
+            self._f = Factorization._borrow(h.value, self.nj, self.nnz_j, self.batch)
+        return self._f
+
+    def pattern(self):
+        """-> (Jp int32[nj + 1], Ji int32[nnz_j]) on the host."""
+        Jp = np.empty(self.nj + 1, dtype=np.int32)
+        Ji = np.empty(self.nnz_j, dtype=np.int32)
+        _check(lib().cs3_pf_plan_pattern(self._p, _pi(Jp), _pi(Ji)))
+        return Jp, Ji
+
+    def maps(self):
+        """-> dict(jpos int32[4, nnz_y] (H, N, M, L; -1: none), Rp, Rj, Rpos (Y by rows), upos_a, upos_m int32[n])."""
+        out = dict(jpos=np.empty((4, self.nnz_y), dtype=np.int32), Rp=np.empty(self.n + 1, dtype=np.int32),
+                   Rj=np.empty(self.nnz_y, dtype=np.int32), Rpos=np.empty(self.nnz_y, dtype=np.int32),
+                   upos_a=np.empty(self.n, dtype=np.int32), upos_m=np.empty(self.n, dtype=np.int32))
+        _check(lib().cs3_pf_plan_maps(self._p, *[_pi(out[k]) for k in ("jpos", "Rp", "Rj", "Rpos", "upos_a", "upos_m")]))
+        return out
+
+    def _yz(self, Yz):
+        Yz = _c128(Yz).reshape(-1)
+        assert Yz.size == self.y_batch * self.nnz_y, "Yz must be [y_batch, nnz_y]"
+        return Yz
+
+    def _bn(self, a, dtype):
+        a = np.ascontiguousarray(a, dtype=dtype).reshape(-1)
+        assert a.size == self.batch * self.n, "expected [batch, n]"
+        return a
+
+    def mismatch(self, Yz, S, vm, va):
+        """-> (-F float64[batch, nj] in unknown order, max |F| float64[batch])."""
+        Yz, S, vm, va = self._yz(Yz), self._bn(S, np.complex128), self._bn(vm, np.float64), self._bn(va, np.float64)
+        F = np.empty((self.batch, self.nj)); norm = np.empty(self.batch)
+        _check(lib().cs3_pf_mismatch(self._p, _pc(Yz), _pc(S), _pf(vm), _pf(va), _pf(F), _pf(norm)))
+        return F, norm
+
+    def jacobian(self, Yz, vm, va):
+        """-> Jx float64[batch, nnz_j], the values of pattern()."""
+        Yz, vm, va = self._yz(Yz), self._bn(vm, np.float64), self._bn(va, np.float64)
+        Jx = np.empty((self.batch, self.nnz_j))
+        _check(lib().cs3_pf_jacobian(self._p, _pc(Yz), _pf(vm), _pf(va), _pf(Jx)))
+        return Jx
+
+    def _results(self):
+        return np.zeros(self.batch, dtype=np.int32), np.zeros(self.batch), np.zeros(self.batch, dtype=np.int32)
+
+    def solve(self, Yz, S, vm, va, tol=1e-8, max_iters=20, refactor_every=1, pivot_tol=1e-3):
+        """Newton from (vm, va).  -> (vm, va, dict(iters, norm, flag)); flag 0 converged, 1 out of iterations, 2 not
+        finite.  A rejected pivot raises SingularMatrix."""
+        Yz, S = self._yz(Yz), self._bn(S, np.complex128)
+        vm, va = self._bn(vm, np.float64).copy(), self._bn(va, np.float64).copy()
+        iters, norm, flag = self._results()
+        _check(lib().cs3_pf_solve(self._p, _pc(Yz), _pc(S), _pf(vm), _pf(va), tol, max_iters, refactor_every, pivot_tol,
+                                  _pi(iters), _pf(norm), _pi(flag)))
+        return vm.reshape(self.batch, self.n), va.reshape(self.batch, self.n), dict(iters=iters, norm=norm, flag=flag)
+
+    def mismatch_dev(self, yz_ptr, s_ptr, vm_ptr, va_ptr, f_ptr, norm_ptr=0, stream=0):
+        vp = C.c_void_p
+        _check(lib().cs3_pf_mismatch_dev(self._p, vp(yz_ptr), vp(s_ptr), vp(vm_ptr), vp(va_ptr), vp(f_ptr), vp(norm_ptr), vp(stream)))
+
+    def jacobian_dev(self, yz_ptr, vm_ptr, va_ptr, jx_ptr, stream=0):
+        vp = C.c_void_p
+        _check(lib().cs3_pf_jacobian_dev(self._p, vp(yz_ptr), vp(vm_ptr), vp(va_ptr), vp(jx_ptr), vp(stream)))
+
+    def solve_dev(self, yz_ptr, s_ptr, vm_ptr, va_ptr, tol=1e-8, max_iters=20, refactor_every=1, pivot_tol=1e-3, stream=0):
+        """Newton in place on the device arrays at vm_ptr, va_ptr.  -> dict(iters, norm, flag) (host).  Host-driven: one
+        4-byte read per iteration synchronises `stream`."""
+        vp = C.c_void_p
+        iters, norm, flag = self._results()
+        _check(lib().cs3_pf_solve_dev(self._p, vp(yz_ptr), vp(s_ptr), vp(vm_ptr), vp(va_ptr), tol, max_iters, refactor_every,
+                                      pivot_tol, _pi(iters), _pf(norm), _pi(flag), vp(stream)))
+        return dict(iters=iters, norm=norm, flag=flag)
 
 
 # -------------------------------------------------------- complex matrices --

@@ -350,3 +350,34 @@ def se_case(nbus, nedges, seed, inj_share=0.5, ncrit=2):
     w = 10.0 ** rng.uniform(0.0, 2.0, size=m)
     return (m, nbus, np.cumsum(Hp).astype(np.int32), rows[order].astype(np.int32), vals[order].astype(np.float64), w,
             np.arange(nbr - ncrit, nbr))
+
+
+def pf_planted(n, Ap, Ai, Az, vm, va):
+    """S = V conj(Y V) for V = vm exp(j va): the injections that make (vm, va) a solution of the power flow."""
+    V = vm * np.exp(1j * va)
+    cols = np.repeat(np.arange(n), np.diff(Ap))
+    I = np.zeros(n, dtype=np.complex128)
+    np.add.at(I, Ai, Az * V[cols])
+    return V * np.conj(I)
+
+
+def pf_case(nbus, nedges, seed, npv, spread=0.15):
+    """A power-flow case with a planted solution on ybus(nbus, nedges, seed): voltages vm ~ U(0.97, 1.03) and
+    va ~ U(-spread, spread) with va[0] = 0 from default_rng(seed + 7); injections S = V conj(Y V); pv = sorted
+    choice(1 .. n - 1, npv), pq = the remaining buses, bus 0 the reference.  The flat start is vm = 1 at pq buses, the
+    planted magnitude at pv and reference buses, va = 0.
+    -> dict(n, Yp, Yi, Yz, pv, pq, vm, va, S, vm0, va0)."""
+    n, Ap, Ai, Az = ybus(nbus, nedges, seed)
+    rng = np.random.default_rng(seed + 7)
+    vm = rng.uniform(0.97, 1.03, size=n)
+    va = rng.uniform(-spread, spread, size=n)
+    va[0] = 0.0
+    pv = np.sort(rng.choice(np.arange(1, n), size=npv, replace=False)).astype(np.int32)
+    is_pq = np.ones(n, dtype=bool)
+    is_pq[0] = False
+    is_pq[pv] = False
+    pq = np.flatnonzero(is_pq).astype(np.int32)
+    vm0 = vm.copy()
+    vm0[pq] = 1.0
+    return dict(n=n, Yp=Ap, Yi=Ai, Yz=Az, pv=pv, pq=pq, vm=vm, va=va, S=pf_planted(n, Ap, Ai, Az, vm, va), vm0=vm0,
+                va0=np.zeros(n))

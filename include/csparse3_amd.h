@@ -1290,6 +1290,118 @@ int cs3_cplx_selinv_diag(cs3_cplx p, cs3_handle h, double *d);
 int cs3_cplx_selinv_thevenin(cs3_cplx p, cs3_handle h, double *T);
 int cs3_debug_cplx_selinv_maps(cs3_cplx p, cs3_handle h, int64_t *entry, int64_t *entry_t, int64_t *diag);
 
+/* ---- AC power flow: batched Newton from the bus admittance matrix to the voltages ----
+ * The computation everything above serves ("the real power-flow inner loop"): the two steps between
+ * a bus admittance matrix and the factor + solve chain -- the power mismatch and the values of the Jacobian's four blocks
+ * -- as kernels, and a host driver around them, cs3_factor_solve_dev and cs3_solve_dev.  `batch` injection scenarios of
+ * one network advance in lock-step, one launch chain per iteration (a time series, a Monte-Carlo study).
+ *
+ * Definitions.  Y is n x n complex CSC, (Yp, Yi) int32, values Yz interleaved complex128 ([y_batch][nnz_y][2] doubles).
+ * Rows inside a column may be unsorted; the pattern may be one-sided (Y_ij stored, Y_ji not: a phase shifter) and the
+ * values need not be symmetric; a row stored twice in one column is refused.  Bus types are two int32 lists pv[npv] and
+ * pq[npq]: disjoint, in range, no repeats, in any order; every bus in neither list is a reference bus (several are
+ * allowed).  pvpq = pv ++ pq, nj = npv + 2 npq.  Unknowns x = [theta(pvpq); |V|(pq)] in the order of the lists; equations
+ * F = [Re mis(pvpq); Im mis(pq)] with mis = V o conj(I) - S, I = Y V, V = vm o exp(j va).  A Newton step solves J dx = -F,
+ * then va[pvpq] += dx[:npv + npq], vm[pq] += dx[npv + npq:].  The Jacobian is the polar form with d/d|V| (not |V| d/d|V|);
+ * with Vn = V / |V|:
+ *   i != j:  dS_i/dtheta_j = -j V_i conj(Y_ij V_j),        dS_i/d|V|_j = V_i conj(Y_ij Vn_j)
+ *            dS_i/dtheta_i =  j V_i conj(I_i - Y_ii V_i),  dS_i/d|V|_i = V_i conj(Y_ii Vn_i) + conj(I_i) Vn_i
+ *   H = Re dS/dtheta on [pvpq, pvpq], N = Re dS/d|V| on [pvpq, pq], M = Im dS/dtheta on [pq, pvpq], L = Im dS/d|V| on
+ *   [pq, pq], placed as [[H, N], [M, L]] the way pack_4_by_4 places them (cs3_csc_stack_4_by_4).  One stored entry of Y
+ *   yields at most four entries of J, and J has exactly those: column c of J comes from column pvpq[c] (c < npv + npq) or
+ *   pq[c - npv - npq] of Y and lists its top-block entries in the storage order of that column, then its bottom-block
+ *   entries in the same order.
+ * S [batch][n] complex, vm and va [batch][n].  The entries of S at reference buses, and the imaginary parts at PV buses,
+ * are never read and may hold anything, NaN included.
+ *
+ * cs3_pf_plan_create: host work only, O(nnz_y + n) plus cs3_analyze of the Jacobian; no device is needed until the first
+ *   device call (like union plans).  y_batch is 1 (one Y for all scenarios) or batch (one per scenario); order is
+ *   CS3_ORDER_NATURAL or CS3_ORDER_AMD.  Checked in this order, each failure CS3_ERR_ARG with a message: null pointers;
+ *   a bad pattern, by the checks of cs3_union_plan_create (n outside [0, 2^30), Yp[0] != 0, a decreasing Yp, null Yi with
+ *   entries, a row outside [0, n), 2^29 - 256 entries or more); batch < 1, y_batch neither 1 nor batch, a bad order; a bus
+ *   list of bad length, out of range, with repeats, or not disjoint from the other; npv + npq = 0; a row stored twice in
+ *   a column; a pv or pq bus without a stored diagonal entry.
+ *   It builds the pattern (Jp, Ji); the map jpos[4][nnz_y] (H, N, M, L; struct-of-arrays; -1 where a bus type removes
+ *   the entry); Y by rows -- per row the entries in ascending column with their positions in Yz: no transposed copy of
+ *   values is ever made; and the unknown behind every bus.
+ * cs3_pf_handle: the plan OWNS an ordinary batched LU handle on (Jp, Ji) and lends it out: cs3_set_pivot_perturbation,
+ *   cs3_condest, cs3_slogdet, cs3_selinv_dev, cs3_sens_plan and the rest work on the Jacobian of the last factorisation
+ *   with no new code.  It is freed with the plan: never pass it to cs3_free, never use it after cs3_pf_plan_free.
+ * cs3_pf_plan_info; cs3_pf_plan_pattern: Jp[nj + 1], Ji[nnz_j]; cs3_pf_plan_maps: jpos[4 * nnz_y], Rp[n + 1], Rj[nnz_y],
+ *   Rpos[nnz_y], upos_a[n] (the unknown behind theta_i, -1: none), upos_m[n] (behind |V|_i); any output may be NULL.
+ * cs3_pf_limits: the constants that shape the launches; needs no device.
+ *
+ * Kernels (powerflow.hip).  k_pf_mismatch: one lane per bus row, one wave per row of more than wave_row entries (lane l
+ * sums entries l, l + 64, ... in order, then a fixed butterfly); reference rows are skipped.  It writes -F into the
+ * right-hand side [batch][nj] and I for the next kernel, and per scenario max |F| over the monitored entries by a wave
+ * reduction and an INTEGER atomic max on the bit pattern of the non-negative double -- order-independent, the same bits on
+ * every run; no float atomics.  A NaN orders above infinity there, so "not finite" is that maximum's exponent field all
+ * ones.  k_pf_jacobian: one lane per stored entry of Y, grid-stride past grid_cap workgroups per scenario; up to four
+ * values through jpos into Jx [batch][nnz_j]; a scenario that is no longer active gets the identity (1 at the diagonal
+ * positions of H and L, 0 elsewhere), whose factorisation is harmless.  k_pf_decide: one workgroup per scenario freezes
+ * it when its iteration ends and counts the active scenarios down.  k_pf_update: applies dx to the scenarios still active,
+ * and to none when the handle's status word reports a failed factorisation.
+ *
+ * cs3_pf_solve_dev.  Iteration it = 0, 1, ...: (1) the mismatch; (2) per scenario: not finite -> flag 2; norm <= tol ->
+ * flag 0; it == max_iters -> flag 1; each with iters = it, and each makes the scenario inactive and FROZEN: its right-hand
+ * side is 0 and vm, va are untouched from then on, bit for bit; (3) stop when no scenario is active; (4) when
+ * it % refactor_every == 0 the Jacobian and cs3_factor_solve_dev on the plan's handle with pivot_tol, else cs3_solve_dev on
+ * the held factors (dishonest Newton); (5) the update.  iters, norm (the norm at the iteration where the scenario stopped)
+ * and flag are HOST arrays [batch]; any may be NULL.
+ *   Not converging is not an error: CS3_OK, and flag tells.  vm, va of a scenario flagged 2 are unspecified; the other
+ *   scenarios are unaffected.  A rejected pivot in an active scenario ends the call with CS3_ERR_PIVOT (the handle keeps
+ *   ONE status word per batch; per-member status is not built); vm, va are then as the last completed update left them.
+ *   With cs3_set_pivot_perturbation on the lent handle nothing fails.  max_iters = 0 evaluates the mismatch only.
+ *   HOST INVOLVEMENT: the call is host-driven, as cs3_gmres_dev is.  In every iteration, after step 2, it reads one 4-byte
+ *   "scenarios still active" word and the handle's status word of the factorisation before, which synchronises `stream`.
+ *   It cannot be captured into a graph.
+ *   Checks, in this order, all CS3_ERR_ARG before any device work: null plan or arrays, tol negative or not finite,
+ *   max_iters < 0, refactor_every < 1.  CS3_ERR_HIP without a device.  CS3_ERR_STATE when the handle reports that a
+ *   hand-over between the waves of a shared elimination timed out (as cs3_factor_status does): no update was applied for
+ *   that factorisation, and the factors are not valid.
+ *   ONE CALL AT A TIME PER PLAN: the right-hand side, the Jacobian values, the currents I and the per-scenario state live
+ *   in the plan, so two calls on one plan must not overlap -- not from two host threads, and not on two streams.  The
+ *   same holds for cs3_pf_mismatch_dev and cs3_pf_jacobian_dev, which write the plan's current buffer.
+ * cs3_pf_mismatch_dev: -F in unknown order into F_dev [batch][nj] and max |F| into norm_dev [batch] (may be NULL; 8-byte
+ *   aligned; it is cleared on `stream` first), every scenario active.  cs3_pf_jacobian_dev: Jx_dev [batch][nnz_j] at the
+ *   given voltages (it runs the currents' pass of the mismatch kernel first: two launches).  Both asynchronous; users build
+ *   their own Newton variants (Q-limit switching) around them: mismatch_dev -> jacobian_dev -> cs3_factor_solve_dev on the
+ *   lent handle gives the bits of the driver.
+ * cs3_pf_mismatch, cs3_pf_jacobian, cs3_pf_solve: the host-array forms (the null stream): the same kernels in the same
+ *   order, the same bits.
+ * Not offered: bus-type switching inside the call (a changed pv / pq split is a new plan); fast-decoupled or DC variants;
+ * a rectangular or current-injection formulation; per-member pivot status; a graph-capturable fixed-length form; sharding;
+ * a matched handle for the Jacobian. */
+typedef struct cs3_pf_s *cs3_pf;
+typedef struct cs3_pf_info {
+    int64_t n, nnz_y, npv, npq, nref, nj, nnz_j, batch, y_batch;
+    int64_t rows_lane, rows_wave;  /* non-reference rows of Y summed by one lane / by a wave */
+    int64_t max_row;               /* stored entries of the longest non-reference row */
+} cs3_pf_info;
+typedef struct cs3_pf_limits_t {
+    int64_t block;                 /* threads of a workgroup */
+    int64_t grid_cap;              /* most workgroups per scenario: beyond grid_cap * block rows or entries a lane loops */
+    int64_t wave_row;              /* a row with more stored entries than this is summed by a wave */
+} cs3_pf_limits_t;
+int cs3_pf_limits(cs3_pf_limits_t *out);
+int cs3_pf_plan_create(int64_t n, const int32_t *Yp, const int32_t *Yi, int64_t npv, const int32_t *pv, int64_t npq,
+                       const int32_t *pq, int64_t batch, int64_t y_batch, int64_t order, cs3_pf *out);
+int cs3_pf_plan_free(cs3_pf p);
+int cs3_pf_handle(cs3_pf p, cs3_handle *h);
+int cs3_pf_plan_info(cs3_pf p, cs3_pf_info *info);
+int cs3_pf_plan_pattern(cs3_pf p, int32_t *Jp, int32_t *Ji);
+int cs3_pf_plan_maps(cs3_pf p, int32_t *jpos, int32_t *Rp, int32_t *Rj, int32_t *Rpos, int32_t *upos_a, int32_t *upos_m);
+int cs3_pf_mismatch_dev(cs3_pf p, const double *Yz_dev, const double *S_dev, const double *vm_dev, const double *va_dev,
+                        double *F_dev, double *norm_dev, void *stream);
+int cs3_pf_jacobian_dev(cs3_pf p, const double *Yz_dev, const double *vm_dev, const double *va_dev, double *Jx_dev, void *stream);
+int cs3_pf_solve_dev(cs3_pf p, const double *Yz_dev, const double *S_dev, double *vm_dev, double *va_dev, double tol,
+                     int64_t max_iters, int64_t refactor_every, double pivot_tol, int32_t *iters, double *norm, int32_t *flag,
+                     void *stream);
+int cs3_pf_mismatch(cs3_pf p, const double *Yz, const double *S, const double *vm, const double *va, double *F, double *norm);
+int cs3_pf_jacobian(cs3_pf p, const double *Yz, const double *vm, const double *va, double *Jx);
+int cs3_pf_solve(cs3_pf p, const double *Yz, const double *S, double *vm, double *va, double tol, int64_t max_iters,
+                 int64_t refactor_every, double pivot_tol, int32_t *iters, double *norm, int32_t *flag);
+
 #ifdef __cplusplus
 }
 #endif
