@@ -150,6 +150,20 @@ class PfLimits(C.Structure):
     _fields_ = [(name, C.c_int64) for name in ("block", "grid_cap", "wave_row")]
 
 
+class SeInfo(C.Structure):
+    """cs3_se_info: sizes of a state-estimation plan (kind0 .. kind4: the rows per kind)."""
+    _fields_ = [(name, C.c_int64) for name in ("n", "nnz_y", "nref", "na", "ns", "ne", "m", "nnz_h", "kind0", "kind1", "kind2",
+                                               "kind3", "kind4", "max_row", "max_col", "rows_wave", "cols_wave", "nnz_g")]
+
+    def __repr__(self):
+        return "SeInfo(%s)" % ", ".join("%s=%d" % (f, getattr(self, f)) for f, _ in self._fields_)
+
+
+class SeLimits(C.Structure):
+    """cs3_se_limits_t: the constants that shape the launches of the state-estimation kernels."""
+    _fields_ = [(name, C.c_int64) for name in ("block", "grid_cap", "wave_row", "wave_col")]
+
+
 class Cs3Error(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("cs3 error %d: %s" % (code, msg))
@@ -392,6 +406,25 @@ def lib():
         L.cs3_pf_mismatch.argtypes = [vp] + [_f64p] * 6
         L.cs3_pf_jacobian.argtypes = [vp] + [_f64p] * 4
         L.cs3_pf_solve.argtypes = [vp, _f64p, _f64p, _f64p, _f64p, C.c_double, I64, I64, C.c_double, _i32p, _f64p, _i32p]
+        pi32, pdbl = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+        L.cs3_se_limits.argtypes = [C.POINTER(SeLimits)]
+        L.cs3_se_plan_create.argtypes = [I64, _i32p, _i32p, I64, _i32p, I64, _i32p, _i32p, I64, _i32p, _i32p, I64, C.POINTER(vp)]
+        L.cs3_se_plan_free.argtypes = [vp]
+        L.cs3_se_plan_info.argtypes = [vp, C.POINTER(SeInfo)]
+        L.cs3_se_plan_pattern.argtypes = [vp] + [_i32p] * 4
+        L.cs3_se_plan_maps.argtypes = [vp] + [_i32p] * 3
+        L.cs3_se_handle.argtypes = [vp, C.POINTER(vp)]
+        L.cs3_se_gain_pattern.argtypes = [vp, _i32p, _i32p]
+        L.cs3_se_residuals_dev.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+        L.cs3_se_measure_dev.argtypes = [vp] * 10
+        L.cs3_se_jacobian_dev.argtypes = [vp] * 10
+        L.cs3_se_gradient_dev.argtypes = [vp] * 5
+        L.cs3_se_solve_dev.argtypes = [vp] * 7 + [C.c_double, I64, pi32, pdbl, pdbl, pi32, vp]
+        L.cs3_se_baddata_dev.argtypes = [vp] * 7 + [C.c_double] + [vp] * 5
+        L.cs3_se_measure.argtypes = [vp] + [_f64p] * 8
+        L.cs3_se_jacobian.argtypes = [vp] + [_f64p] * 8
+        L.cs3_se_solve.argtypes = [vp] + [_f64p] * 6 + [C.c_double, I64, pi32, pdbl, pdbl, pi32]
+        L.cs3_se_baddata.argtypes = [vp] + [_f64p] * 6 + [C.c_double] + [_f64p] * 4
         _lib = L
     return _lib
 
@@ -1756,6 +1789,185 @@ class PowerFlowPlan:
         _check(lib().cs3_pf_solve_dev(self._p, vp(yz_ptr), vp(s_ptr), vp(vm_ptr), vp(va_ptr), tol, max_iters, refactor_every,
                                       pivot_tol, _pi(iters), _pf(norm), _pi(flag), vp(stream)))
         return dict(iters=iters, norm=norm, flag=flag)
+
+
+# ---------------------------------------------------- AC state estimation --
+
+def se_limits():
+    """The constants that shape the launches of the state-estimation kernels (cs3_se_limits); needs no GPU."""
+    out = SeLimits()
+    _check(lib().cs3_se_limits(C.byref(out)))
+    return out
+
+
+class StateEstPlan:
+    """Weighted-least-squares AC state estimation on the device (include/csparse3_amd.h, "AC state estimation"): from the
+    pattern (Yp, Yi) of a bus admittance matrix of order n, the reference buses, the branch-end table (end_from, end_to)
+    and the measurement list (kind, where), the pattern of the measurement Jacobian H by rows and in CSC and the tables
+    the kernels read (host work, no GPU needed).  The first solve, bad_data, factorization or gain_pattern() builds the
+    solver: the sparse product H' (W H), a Cholesky handle on its pattern (lent out as `factorization`), the bilinear-form
+    plan of the rows of H.
+    Host arrays: Yz complex [nnz_y], Ye complex [ne, 2] = (yff, yft), z and w float64 [m], vm and va float64 [n].  The
+    *_dev forms take device addresses of the same layouts (complex as interleaved doubles)."""
+
+    def __init__(self, n, Yp, Yi, ref, end_from, end_to, kind, where, order=ORDER_AMD):
+        self._p = C.c_void_p()
+        self._f = None
+        Yp, Yi, ref = _i32(Yp), _i32(Yi), _i32(ref).reshape(-1)
+        ef, et, kind, where = (_i32(a).reshape(-1) for a in (end_from, end_to, kind, where))
+        assert ef.size == et.size and kind.size == where.size
+        _check(lib().cs3_se_plan_create(n, _pi(Yp), _pi(Yi), ref.size, _pi(ref), ef.size, _pi(ef), _pi(et), kind.size, _pi(kind),
+                                        _pi(where), order, C.byref(self._p)))
+        inf = self.info
+        self.n, self.nnz_y, self.ns, self.na, self.ne = int(inf.n), int(inf.nnz_y), int(inf.ns), int(inf.na), int(inf.ne)
+        self.m, self.nnz_h = int(inf.m), int(inf.nnz_h)
+
+    def close(self):
+        if self._p:
+            if self._f is not None:
+                self._f.close()                          # the lent handle goes with the plan: the borrower is left empty
+            lib().cs3_se_plan_free(self._p)
+            self._p = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    @property
+    def info(self):
+        out = SeInfo()
+        _check(lib().cs3_se_plan_info(self._p, C.byref(out)))
+        return out
+
+    @property
+    def factorization(self):
+        """The plan's Cholesky handle on the gain matrix as a Factorization that BORROWS it (the rules of
+        PowerFlowPlan.factorization): condest, slogdet, selinv, quad_plan ... work on the gain matrix of the last
+        factorisation; closing it frees nothing, and closing the plan leaves it empty.  Builds the solver when needed."""
+        if self._f is None or not self._f._h:
+            h = C.c_void_p()
+            _check(lib().cs3_se_handle(self._p, C.byref(h)))
+            self._f = Factorization._borrow(h.value, self.ns, int(self.info.nnz_g), 1)
+            self._f.kind = CS3_CHOLESKY
+        return self._f
+
+    def pattern(self):
+        """-> dict(Hp int32[ns + 1], Hi int32[nnz_h] (CSC), Rp int32[m + 1], Rj int32[nnz_h] (by rows)) on the host."""
+        out = dict(Hp=np.empty(self.ns + 1, dtype=np.int32), Hi=np.empty(self.nnz_h, dtype=np.int32),
+                   Rp=np.empty(self.m + 1, dtype=np.int32), Rj=np.empty(self.nnz_h, dtype=np.int32))
+        _check(lib().cs3_se_plan_pattern(self._p, *[_pi(out[k]) for k in ("Hp", "Hi", "Rp", "Rj")]))
+        return out
+
+    def maps(self):
+        """-> dict(cpos int32[nnz_h] (row-order entry -> CSC position), upos_a int32[n] (-1: reference), upos_m int32[n])."""
+        out = dict(cpos=np.empty(self.nnz_h, dtype=np.int32), upos_a=np.empty(self.n, dtype=np.int32),
+                   upos_m=np.empty(self.n, dtype=np.int32))
+        _check(lib().cs3_se_plan_maps(self._p, *[_pi(out[k]) for k in ("cpos", "upos_a", "upos_m")]))
+        return out
+
+    def gain_pattern(self):
+        """-> (Gp int32[ns + 1], Gi int32[nnz_g]) of G = H' W H, rows in the order of the sparse product.  Needs the GPU."""
+        _check(lib().cs3_se_gain_pattern(self._p, None, None))
+        Gp, Gi = np.empty(self.ns + 1, dtype=np.int32), np.empty(int(self.info.nnz_g), dtype=np.int32)
+        _check(lib().cs3_se_gain_pattern(self._p, _pi(Gp), _pi(Gi)))
+        return Gp, Gi
+
+    def _host(self, Yz, Ye, vm, va, z=None, w=None):
+        Yz, Ye = _c128(Yz).reshape(-1), _c128(Ye).reshape(-1)
+        assert Yz.size == self.nnz_y and Ye.size == 2 * self.ne, "Yz must be [nnz_y], Ye [ne, 2]"
+        vm, va = _f64(vm).reshape(-1), _f64(va).reshape(-1)
+        assert vm.size == self.n and va.size == self.n, "vm and va must be [n]"
+        out = [Yz, Ye, vm, va]
+        for a in (z, w):
+            if a is not None:
+                a = _f64(a).reshape(-1)
+                assert a.size == self.m, "z and w must be [m]"
+            out.append(a)
+        return out
+
+    def measure(self, Yz, Ye, z, w, vm, va):
+        """-> (r float64[m] = z - h(x), J = sum w r^2)."""
+        Yz, Ye, vm, va, z, w = self._host(Yz, Ye, vm, va, z, w)
+        r, J = np.empty(self.m), np.empty(1)
+        _check(lib().cs3_se_measure(self._p, _pc(Yz), _pc(Ye), _pf(z), _pf(w), _pf(vm), _pf(va), _pf(r), _pf(J)))
+        return r, float(J[0])
+
+    def jacobian(self, Yz, Ye, w, vm, va):
+        """-> (Hr, Hc, WHc) float64[nnz_h]: H by rows, in CSC, and w_i H_ij in CSC, on pattern()."""
+        Yz, Ye, vm, va, _, w = self._host(Yz, Ye, vm, va, None, w)
+        Hr, Hc, WHc = (np.empty(self.nnz_h) for _ in range(3))
+        _check(lib().cs3_se_jacobian(self._p, _pc(Yz), _pc(Ye), _pf(w), _pf(vm), _pf(va), _pf(Hr), _pf(Hc), _pf(WHc)))
+        return Hr, Hc, WHc
+
+    @staticmethod
+    def _scalars():
+        return C.c_int32(0), C.c_double(0.0), C.c_double(0.0), C.c_int32(0)
+
+    @staticmethod
+    def _solve_info(iters, step, J, flag):
+        return dict(iters=int(iters.value), step=float(step.value), J=float(J.value), flag=int(flag.value))
+
+    def solve(self, Yz, Ye, z, w, vm, va, tol=1e-8, max_iters=20):
+        """Gauss-Newton from (vm, va).  -> (vm, va, dict(iters, step, J, flag)); flag 0 converged (max |dx| <= tol), 1 out
+        of iterations, 2 a step that is not finite.  An unobservable state raises NotPositiveDefinite."""
+        Yz, Ye, vm, va, z, w = self._host(Yz, Ye, vm, va, z, w)
+        vm, va = vm.copy(), va.copy()
+        iters, step, J, flag = self._scalars()
+        _check(lib().cs3_se_solve(self._p, _pc(Yz), _pc(Ye), _pf(z), _pf(w), _pf(vm), _pf(va), tol, max_iters, C.byref(iters),
+                                  C.byref(step), C.byref(J), C.byref(flag)))
+        return vm, va, self._solve_info(iters, step, J, flag)
+
+    def bad_data(self, Yz, Ye, z, w, vm, va, crit_tol=1e-8):
+        """The largest-normalised-residual test at (vm, va).  -> dict(t, omega, rn float64[m], worst, worst_row, J, critical)."""
+        Yz, Ye, vm, va, z, w = self._host(Yz, Ye, vm, va, z, w)
+        t, omega, rn, s = np.empty(self.m), np.empty(self.m), np.empty(self.m), np.empty(4)
+        _check(lib().cs3_se_baddata(self._p, _pc(Yz), _pc(Ye), _pf(z), _pf(w), _pf(vm), _pf(va), crit_tol, _pf(t), _pf(omega), _pf(rn),
+                                    _pf(s)))
+        return dict(t=t, omega=omega, rn=rn, worst=float(s[0]), worst_row=int(s[1]), J=float(s[2]), critical=int(s[3]))
+
+    def residuals_dev(self):
+        """-> (r_ptr, wr_ptr): device addresses of the plan's r [m] and w r [m] of the last residual pass."""
+        r, wr = C.c_void_p(), C.c_void_p()
+        _check(lib().cs3_se_residuals_dev(self._p, C.byref(r), C.byref(wr)))
+        return r.value, wr.value
+
+    def measure_dev(self, yz_ptr, ye_ptr, z_ptr, w_ptr, vm_ptr, va_ptr, r_ptr=0, j_ptr=0, stream=0):
+        vp = C.c_void_p
+        _check(lib().cs3_se_measure_dev(self._p, vp(yz_ptr), vp(ye_ptr), vp(z_ptr), vp(w_ptr), vp(vm_ptr), vp(va_ptr), vp(r_ptr),
+                                        vp(j_ptr), vp(stream)))
+
+    def jacobian_dev(self, yz_ptr, ye_ptr, w_ptr, vm_ptr, va_ptr, hr_ptr=0, hc_ptr=0, whc_ptr=0, stream=0):
+        vp = C.c_void_p
+        _check(lib().cs3_se_jacobian_dev(self._p, vp(yz_ptr), vp(ye_ptr), vp(w_ptr), vp(vm_ptr), vp(va_ptr), vp(hr_ptr), vp(hc_ptr),
+                                         vp(whc_ptr), vp(stream)))
+
+    def gradient_dev(self, hc_ptr, wr_ptr, g_ptr, stream=0):
+        """g [ns] = H' (w r) from Hc [nnz_h] and w r [m], in the fixed order of k_se_gradient."""
+        vp = C.c_void_p
+        _check(lib().cs3_se_gradient_dev(self._p, vp(hc_ptr), vp(wr_ptr), vp(g_ptr), vp(stream)))
+
+    def solve_dev(self, yz_ptr, ye_ptr, z_ptr, w_ptr, vm_ptr, va_ptr, tol=1e-8, max_iters=20, stream=0):
+        """Gauss-Newton in place on the device arrays at vm_ptr, va_ptr.  -> dict(iters, step, J, flag) (host).
+        Host-driven: one read per iteration synchronises `stream`."""
+        vp = C.c_void_p
+        iters, step, J, flag = self._scalars()
+        _check(lib().cs3_se_solve_dev(self._p, vp(yz_ptr), vp(ye_ptr), vp(z_ptr), vp(w_ptr), vp(vm_ptr), vp(va_ptr), tol, max_iters,
+                                      C.byref(iters), C.byref(step), C.byref(J), C.byref(flag), vp(stream)))
+        return self._solve_info(iters, step, J, flag)
+
+    def bad_data_dev(self, yz_ptr, ye_ptr, z_ptr, w_ptr, vm_ptr, va_ptr, crit_tol, summary_ptr, t_ptr=0, omega_ptr=0, rn_ptr=0,
+                     stream=0):
+        vp = C.c_void_p
+        _check(lib().cs3_se_baddata_dev(self._p, vp(yz_ptr), vp(ye_ptr), vp(z_ptr), vp(w_ptr), vp(vm_ptr), vp(va_ptr), crit_tol,
+                                        vp(t_ptr), vp(omega_ptr), vp(rn_ptr), vp(summary_ptr), vp(stream)))
 
 
 # -------------------------------------------------------- complex matrices --

@@ -162,6 +162,17 @@ def jacobian_config2(seed=118):
     return jacobian_like(nbus=220, nedges=340, n_pv=38, seed=seed)
 
 
+def ybus_branches(nbus, nedges, seed):
+    """The branches (ei, ej) with their series admittances y and the bus shunts behind ybus(nbus, nedges, seed)."""
+    rng = np.random.default_rng(seed)
+    ei, ej = _connected_graph(nbus, nedges, rng)
+    r = rng.uniform(0.001, 0.01, size=len(ei))
+    x = rng.uniform(0.02, 0.1, size=len(ei))
+    y = 1.0 / (r + 1j * x)
+    shunt = rng.uniform(0.0, 0.1, size=nbus) - 1j * rng.uniform(0.05, 0.5, size=nbus)
+    return ei, ej, y, shunt
+
+
 def ybus(nbus, nedges, seed, lossless=False):
     """Complex bus admittance matrix of a random connected network (the graph of jacobian_like): branches with
     r ~ U(0.001, 0.01), x ~ U(0.02, 0.1), y = 1 / (r + jx), and on every bus a shunt g - jb with g ~ U(0, 0.1),
@@ -169,12 +180,7 @@ def ybus(nbus, nedges, seed, lossless=False):
     chords beyond the spanning tree are random, so fill grows quickly with nedges - nbus.  Symmetric, not Hermitian; the diagonal is mostly
     imaginary.  lossless: every real part is +0 -- the diagonal is purely imaginary, as for a network without
     resistance.  -> (n, Ap, Ai, Az) with Az complex128, rows sorted, no duplicates."""
-    rng = np.random.default_rng(seed)
-    ei, ej = _connected_graph(nbus, nedges, rng)
-    r = rng.uniform(0.001, 0.01, size=len(ei))
-    x = rng.uniform(0.02, 0.1, size=len(ei))
-    y = 1.0 / (r + 1j * x)
-    shunt = rng.uniform(0.0, 0.1, size=nbus) - 1j * rng.uniform(0.05, 0.5, size=nbus)
+    ei, ej, y, shunt = ybus_branches(nbus, nedges, seed)
     diag = shunt.copy()
     np.add.at(diag, ei, y)
     np.add.at(diag, ej, y)
@@ -381,3 +387,58 @@ def pf_case(nbus, nedges, seed, npv, spread=0.15):
     vm0[pq] = 1.0
     return dict(n=n, Yp=Ap, Yi=Ai, Yz=Az, pv=pv, pq=pq, vm=vm, va=va, S=pf_planted(n, Ap, Ai, Az, vm, va), vm0=vm0,
                 va0=np.zeros(n))
+
+
+def se_flows(end_from, end_to, Ye, vm, va):
+    """Sf_k = V_f conj(yff V_f + yft V_t) at every branch end, Ye complex [ne, 2] = (yff, yft)."""
+    V = vm * np.exp(1j * va)
+    Ye = np.asarray(Ye, dtype=np.complex128).reshape(-1, 2)
+    return V[end_from] * np.conj(Ye[:, 0] * V[end_from] + Ye[:, 1] * V[end_to])
+
+
+def se_measurements(n, Ap, Ai, Az, end_from, end_to, Ye, kind, where, vm, va):
+    """h(x) of the measurement rows (kind, where) of an AC state estimate: 0 |V|, 1 / 2 Re / Im of the injection
+    V conj(Y V) at a bus, 3 / 4 Re / Im of the flow at a branch end."""
+    S = pf_planted(n, Ap, Ai, Az, vm, va)
+    Sf = se_flows(end_from, end_to, Ye, vm, va) if len(end_from) else np.zeros(0, dtype=np.complex128)
+    kind, where = np.asarray(kind), np.asarray(where)
+    h = np.empty(len(kind))
+    for k, src in ((0, vm), (1, S.real), (2, S.imag), (3, Sf.real), (4, Sf.imag)):
+        h[kind == k] = src[where[kind == k]]
+    return h
+
+
+def se_ac_case(nbus, nedges, seed, noise=0.0, inj_share=0.5, spread=0.15):
+    """An AC state-estimation case with a planted state on ybus(nbus, nedges, seed) and its branch list
+    (ybus_branches).  Branch ends: both ends of every branch, the from-ends first,
+    yff = y, yft = -y (the shunts sit on the diagonal of Y only).  State as in pf_case: vm ~ U(0.97, 1.03),
+    va ~ U(-spread, spread) with va[0] = 0 from default_rng(seed + 7); bus 0 is the reference.  Rows, in this order: the P and
+    Q flow at the from-end of every branch (P, Q interleaved); then per bus in ascending order P and Q of its injection on
+    a share `inj_share` of the buses, a magnitude row on the rest and on bus 0.  w = 10^U(2, 4), z = h(x*) + noise N(0, 1) /
+    sqrt(w).  The flat start is vm = 1, va = 0.
+    -> dict(n, Yp, Yi, Yz, ref, end_from, end_to, Ye, kind, where, z, w, vm, va, vm0, va0)."""
+    n, Ap, Ai, Az = ybus(nbus, nedges, seed)
+    ei, ej, y, _ = ybus_branches(nbus, nedges, seed)
+    nbr = len(ei)
+    end_from = np.concatenate([ei, ej]).astype(np.int32)
+    end_to = np.concatenate([ej, ei]).astype(np.int32)
+    Ye = np.stack([np.concatenate([y, y]), -np.concatenate([y, y])], axis=1).astype(np.complex128)
+    rng = np.random.default_rng(seed + 7)
+    vm = rng.uniform(0.97, 1.03, size=n)
+    va = rng.uniform(-spread, spread, size=n)
+    va[0] = 0.0
+    is_inj = rng.random(n) < inj_share
+    kind, where = [], []
+    for k in range(nbr):
+        kind += [3, 4]; where += [k, k]
+    for b in range(n):
+        if is_inj[b]:
+            kind += [1, 2]; where += [b, b]
+        if not is_inj[b] or b == 0:
+            kind.append(0); where.append(b)
+    kind, where = np.asarray(kind, dtype=np.int32), np.asarray(where, dtype=np.int32)
+    m = len(kind)
+    w = 10.0 ** rng.uniform(2.0, 4.0, size=m)
+    z = se_measurements(n, Ap, Ai, Az, end_from, end_to, Ye, kind, where, vm, va) + noise * rng.standard_normal(m) / np.sqrt(w)
+    return dict(n=n, Yp=Ap, Yi=Ai, Yz=Az, ref=np.zeros(1, dtype=np.int32), end_from=end_from, end_to=end_to, Ye=Ye, kind=kind,
+                where=where, z=z, w=w, vm=vm, va=va, vm0=np.ones(n), va0=np.zeros(n))

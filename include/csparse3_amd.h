@@ -1402,6 +1402,157 @@ int cs3_pf_jacobian(cs3_pf p, const double *Yz, const double *vm, const double *
 int cs3_pf_solve(cs3_pf p, const double *Yz, const double *S, double *vm, double *va, double tol, int64_t max_iters,
                  int64_t refactor_every, double pivot_tol, int32_t *iters, double *norm, int32_t *flag);
 
+/* ---- AC state estimation: weighted least squares, Gauss-Newton from measurements to the voltages ----
+ * The estimator that the power flow, the contingency screens and the Z-bus tools start from: it joins three subsystems
+ * that exist above -- the sparse product on a fixed pattern (the gain matrix G = H' (W H)), a Cholesky handle that factorises
+ * and solves in one graph, and the normalised residuals on the selected inverse -- by the kernels that were missing between
+ * them: the AC measurement functions h(x), the measurement Jacobian H(x), the gradient H' W r and the update.
+ *     minimise J(x) = sum_i w_i (z_i - h_i(x))^2;   an iteration solves  (H' W H) dx = H' W r,  r = z - h(x),  x += dx.
+ *
+ * Network.  Y is n x n complex CSC, (Yp, Yi) int32, values Yz interleaved complex128 ([nnz_y][2] doubles), by the rules of
+ * the power-flow plan: rows inside a column may be unsorted, the pattern may be one-sided, a row stored twice in a column
+ * is refused.
+ * Branch ends.  end_from[ne], end_to[ne] (int32 buses, from != to) with values Ye [ne][2] complex = (yff, yft) as four
+ * doubles: the flow at end k is Sf_k = V_f conj(yff V_f + yft V_t).  The "to" end of a branch is simply another entry
+ * with the buses swapped; ne = 0 is allowed (Ye may then be NULL).
+ * State.  ref[nref], nref >= 1, lists the buses whose angle is fixed.  x = [va(non-reference buses, ascending bus);
+ * vm(all buses, ascending)], ns = 2 n - nref, the first na = n - nref states are the angles.
+ * Measurements.  m rows in the caller's order, kind[m] and where[m] (int32):
+ *     kind 0  |V| at bus where          kind 1  Re S_i, bus where        kind 2  Im S_i, bus where
+ *     kind 3  Re Sf_k, branch end where kind 4  Im Sf_k, branch end where
+ * with S_i = V_i conj((Y V)_i), the power-flow convention.  Rows may repeat (the same quantity measured twice is two rows).
+ * z[m] and the weights w[m] (positive, finite) are values given at solve time.
+ * Derivatives.  Polar form with d/d|V| (not |V| d/d|V|).  Injections: the formulas of the power-flow section.  For an end k
+ * with I_k = yff V_f + yft V_t and Vn = V / |V|:
+ *     dSf/dtheta_f =  j V_f conj(yft V_t)        dSf/d|V|_f = V_f conj(yff Vn_f) + conj(I_k) Vn_f
+ *     dSf/dtheta_t = -j V_f conj(yft V_t)        dSf/d|V|_t = V_f conj(yft Vn_t)
+ * A kind-0 row has the single entry 1.  Entries in the angle column of a reference bus do not exist.
+ * Pattern of H (m x ns), fixed by the plan.  Row i lists its angle entries first, then its magnitude entries; an injection
+ * row in ascending column of row where[i] of Y (the order of Rj below), a flow row `from` before `to`.  The plan holds H by
+ * rows (Rp[m + 1], Rj[nnz_h]: what cs3_quad_plan takes as Ct) and in CSC (Hp[ns + 1], Hi[nnz_h]; inside a column the
+ * entries are in ascending measurement row), with cpos[nnz_h] mapping a row-order entry to its CSC position.
+ *
+ * cs3_se_plan_create: host work only, O(nnz_y + n + ne + nnz_h); needs no device.  order is CS3_ORDER_NATURAL or
+ *   CS3_ORDER_AMD and is used for the gain matrix later.  Checked in this order, each failure CS3_ERR_ARG with a message:
+ *   (1) null pointers; (2) the pattern checks of cs3_pf_plan_create (n outside [0, 2^30), Yp[0] != 0, a decreasing Yp, null
+ *   Yi with entries, a row outside [0, n), 2^29 - 256 entries or more), a bad order, a row stored twice in a column;
+ *   (3) nref < 1, a ref out of range or repeated; (4) a bad ne, an end out of range or with from == to; (5) m < 1 or m > 2^31 - 1; (6) a
+ *   kind outside 0..4; (7) a where out of range for its kind; (8) a kind-1 or kind-2 row at a bus with no stored diagonal
+ *   entry; (9) 2^29 - 256 entries of H or more.
+ *   It builds Y by rows (ascending column, with the position in Yz behind every entry: no transposed values), the two forms
+ *   of H with cpos, per row-order entry the descriptor k_se_jacobian reads (measurement, position in Yz or branch end, which
+ *   derivative, diagonal / from-side or not, the bus of the state), and the lists of rows of Y longer than wave_row and of
+ *   columns of H longer than wave_col.
+ * cs3_se_plan_info: the sizes; nkind[5] the rows per kind; max_row the longest row of Y (the currents are computed at every
+ *   bus); max_col the longest column of H; rows_wave, cols_wave the lengths of the two lists; nnz_g the entries of the gain
+ *   matrix, 0 until the solver has been built.
+ * cs3_se_plan_pattern: Hp[ns + 1], Hi[nnz_h], Rp[m + 1], Rj[nnz_h].  cs3_se_plan_maps: cpos[nnz_h], upos_a[n] (the state
+ *   behind theta_i, -1 at a reference bus), upos_m[n] (behind |V|_i).  Any output may be NULL.
+ * cs3_se_limits: block, grid_cap, wave_row, wave_col; needs no device.
+ *
+ * THE SOLVER is built once, by the first call of cs3_se_solve*, cs3_se_baddata*, cs3_se_handle or cs3_se_gain_pattern
+ * (cs3_spgemm_plan_create needs the device, which is why cs3_se_plan_create does not do it): the cs3_spgemm plan H' (W H)
+ * (transpose_a = 1, both operands on H's CSC pattern), a CS3_CHOLESKY handle on the product's pattern (batch 1, the
+ * plan's order), a cs3_quadplan on that handle from H by rows.  A refusal of the analysis (32-bit pool offsets) comes back
+ * as that call's error with its message; the next such call tries again.
+ * cs3_se_handle lends the Cholesky handle out under the rules of cs3_pf_handle: cs3_condest, cs3_slogdet, cs3_selinv_dev,
+ *   cs3_quad_plan and the rest work on the gain matrix of the last factorisation; it is freed with the plan: never pass it
+ *   to cs3_free, never use it after cs3_se_plan_free.  cs3_se_gain_pattern: Gp[ns + 1], Gi[nnz_g] (rows unsorted: the
+ *   order of cs3_spgemm).
+ *
+ * Kernels (stateest.hip).  k_se_currents: I = Y V for every bus, one lane per row, one wave for a row of more than wave_row
+ *   stored entries (lane l takes entries l, l + 64, ... in order, then a fixed butterfly); it keeps (cos, sin) of every
+ *   bus angle beside the current, so no later kernel evaluates sincos.  The row sums themselves evaluate sincos of the
+ *   column's angle at every stored entry of Y, as k_pf_mismatch does: nnz_y + n calls per pass, not n.  k_se_residual: one lane per measurement: r_i, w_i
+ *   r_i, and per workgroup the partial of sum w_i (r_i r_i) by a fixed tree over rows 256 g + j; k_se_close, one workgroup:
+ *   thread j takes the partials j, j + 256, ... in order, then the same tree -- the scheme of cs3_quad_normres; no atomics,
+ *   the same bits on every run.  k_se_jacobian: one lane per row-order entry of H, grid-stride past grid_cap workgroups; up
+ *   to three stores: Hr[q], Hc[cpos[q]], WHc[cpos[q]] = w_i H_ij (one rounding).  k_se_gradient: one lane per column of H in
+ *   CSC, one wave for a column of more than wave_col entries (strided as above, then lane l += lane l + off, off = 32 .. 1):
+ *   g_j = sum Hc * (w r) in stored order, every product and every sum rounded on its own -- defined to the bit.
+ *   k_se_update: applies dx, records max |dx| by a wave reduction and an INTEGER atomic max on the bit pattern of the
+ *   non-negative double (NaN above infinity; the power flow's device), and applies nothing when the handle's status word
+ *   reports a failed factorisation.
+ *
+ * cs3_se_measure_dev: r = z - h(x) into r_dev [m] and J = sum w r^2 into J_dev [1]; either may be NULL.  Two launches
+ *   (three with J).  It also refreshes the residuals the plan keeps.
+ * cs3_se_jacobian_dev: H by rows into Hr_dev, in CSC into Hc_dev, w_i H_ij in CSC into WHc_dev [nnz_h]; any may be NULL
+ *   (w_dev may be NULL when WHc_dev is).  Two launches.
+ * cs3_se_gradient_dev: g_dev [ns] = H' (w r) from Hc_dev [nnz_h] and wr_dev [m].  One launch.
+ *   These three need only the plan's tables: no spgemm plan and no handle.  All asynchronous on `stream`.
+ * cs3_se_residuals_dev: borrowed device pointers to the plan's r [m] and w r [m] of the last residual pass (cs3_se_measure_dev,
+ *   cs3_se_solve*, cs3_se_baddata*); valid until the plan is freed.
+ * cs3_se_solve_dev.  Iteration it = 0, 1, ... while it < max_iters: (1) currents + residuals; (2) the Jacobian values;
+ *   (3) the gradient g = H' (w o r) into the right-hand side; (4) cs3_spgemm_values_dev; (5) cs3_factor_solve_dev on the
+ *   handle (k = 1, tol 0); (6) the update va[non-ref] += dx[:na], vm += dx[na:] with max |dx|.  Five launches of
+ *   stateest.hip per iteration beside the product's two and the factor + solve graph.  Then the host reads max |dx| and the
+ *   handle's status word -- the ONE synchronisation per iteration, as in cs3_pf_solve_dev, so the call cannot be captured
+ *   into a graph.  iters = it + 1; flag 2 if max |dx| is not finite, else flag 0 if it is <= tol, else flag 1 if iters ==
+ *   max_iters, else the next iteration.  On exit one more residual pass, so that J and the residuals kept in the plan
+ *   belong to the returned state.  max_iters = 0 evaluates r and J only: iters 0, step 0, flag 1, no voltage changes.
+ *   iters, step (the last max |dx|), J and flag are HOST scalars; any may be NULL.
+ *   A non-positive pivot returns CS3_ERR_NOT_SPD: an unobservable state; vm, va are as the last completed update left
+ *   them (k_se_update applied nothing), iters and step are those of the completed iterations (0 and 0 when the first one
+ *   fails), flag is 1 and J is not written.  Any other error return writes none of the four.  Not converging is CS3_OK plus the flag; vm, va after flag 2 are unspecified.
+ *   Checks, in this order, all CS3_ERR_ARG before any device work: null plan or arrays; tol negative or not finite;
+ *   max_iters < 0.  CS3_ERR_HIP without a device.
+ *   ONE CALL AT A TIME PER PLAN: the currents, the residuals, H, G and the right-hand side live in the plan, so two calls on
+ *   one plan must not overlap -- not from two host threads, and not on two streams; cs3_se_measure_dev and
+ *   cs3_se_jacobian_dev, which write the plan's current buffer, included.
+ * cs3_se_baddata_dev, at the given voltages: residuals; Jacobian; gain values; cs3_factor_dev; cs3_selinv_dev;
+ *   cs3_quad_normres_dev with Hr, w, r.  t_dev, omega_dev, rn_dev [m] (any may be NULL) and summary_dev [4] are exactly
+ *   those of cs3_quad_normres_dev.  Asynchronous; the status of the factorisation is deferred (cs3_factor_status on the
+ *   lent handle).
+ * cs3_se_measure, cs3_se_jacobian, cs3_se_solve, cs3_se_baddata: the host-array forms (the null stream): the same kernels
+ *   in the same order, the same bits.  cs3_se_baddata reports a failed factorisation as its return code.
+ * Not offered: batches of snapshots; equality constraints or zero-injection handling other than a large weight;
+ * current-magnitude, PMU or tap measurements; removing a bad row and estimating again inside the call; observability
+ * analysis beyond the failed pivot; an LU or matched handle for G; sharding. */
+typedef struct cs3_se_s *cs3_se;
+typedef struct cs3_se_info {
+    int64_t n, nnz_y, nref, na, ns, ne, m, nnz_h;
+    int64_t nkind[5];              /* rows of kind 0 .. 4 */
+    int64_t max_row;               /* stored entries of the longest row of Y */
+    int64_t max_col;               /* entries of the longest column of H */
+    int64_t rows_wave, cols_wave;  /* rows of Y / columns of H summed by a wave */
+    int64_t nnz_g;                 /* entries of the gain matrix; 0 until the solver has been built */
+} cs3_se_info;
+typedef struct cs3_se_limits_t {
+    int64_t block;                 /* threads of a workgroup */
+    int64_t grid_cap;              /* most workgroups of the entry kernel: beyond grid_cap * block entries a lane loops */
+    int64_t wave_row;              /* a row of Y with more stored entries than this is summed by a wave */
+    int64_t wave_col;              /* a column of H with more entries than this is summed by a wave */
+} cs3_se_limits_t;
+int cs3_se_limits(cs3_se_limits_t *out);
+int cs3_se_plan_create(int64_t n, const int32_t *Yp, const int32_t *Yi, int64_t nref, const int32_t *ref, int64_t ne,
+                       const int32_t *end_from, const int32_t *end_to, int64_t m, const int32_t *kind, const int32_t *where,
+                       int64_t order, cs3_se *out);
+int cs3_se_plan_free(cs3_se p);
+int cs3_se_plan_info(cs3_se p, cs3_se_info *info);
+int cs3_se_plan_pattern(cs3_se p, int32_t *Hp, int32_t *Hi, int32_t *Rp, int32_t *Rj);
+int cs3_se_plan_maps(cs3_se p, int32_t *cpos, int32_t *upos_a, int32_t *upos_m);
+int cs3_se_handle(cs3_se p, cs3_handle *h);
+int cs3_se_gain_pattern(cs3_se p, int32_t *Gp, int32_t *Gi);
+int cs3_se_residuals_dev(cs3_se p, const double **r_dev, const double **wr_dev);
+int cs3_se_measure_dev(cs3_se p, const double *Yz_dev, const double *Ye_dev, const double *z_dev, const double *w_dev,
+                       const double *vm_dev, const double *va_dev, double *r_dev, double *J_dev, void *stream);
+int cs3_se_jacobian_dev(cs3_se p, const double *Yz_dev, const double *Ye_dev, const double *w_dev, const double *vm_dev,
+                        const double *va_dev, double *Hr_dev, double *Hc_dev, double *WHc_dev, void *stream);
+int cs3_se_gradient_dev(cs3_se p, const double *Hc_dev, const double *wr_dev, double *g_dev, void *stream);
+int cs3_se_solve_dev(cs3_se p, const double *Yz_dev, const double *Ye_dev, const double *z_dev, const double *w_dev, double *vm_dev,
+                     double *va_dev, double tol, int64_t max_iters, int32_t *iters, double *step, double *J, int32_t *flag, void *stream);
+int cs3_se_baddata_dev(cs3_se p, const double *Yz_dev, const double *Ye_dev, const double *z_dev, const double *w_dev,
+                       const double *vm_dev, const double *va_dev, double crit_tol, double *t_dev, double *omega_dev, double *rn_dev,
+                       double *summary_dev, void *stream);
+int cs3_se_measure(cs3_se p, const double *Yz, const double *Ye, const double *z, const double *w, const double *vm, const double *va,
+                   double *r, double *J);
+int cs3_se_jacobian(cs3_se p, const double *Yz, const double *Ye, const double *w, const double *vm, const double *va, double *Hr,
+                    double *Hc, double *WHc);
+int cs3_se_solve(cs3_se p, const double *Yz, const double *Ye, const double *z, const double *w, double *vm, double *va, double tol,
+                 int64_t max_iters, int32_t *iters, double *step, double *J, int32_t *flag);
+int cs3_se_baddata(cs3_se p, const double *Yz, const double *Ye, const double *z, const double *w, const double *vm, const double *va,
+                   double crit_tol, double *t, double *omega, double *rn, double *summary);
+
 #ifdef __cplusplus
 }
 #endif
